@@ -7,15 +7,20 @@
            end to end; PCM already resident in HBM when the timed region starts (synthetic clips)
   unit   : one 1025-bin STFT column of one input stem (8 stems x 130 frames = 1040 per clip)
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--config C1|C2|C3|C5]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--config C1|C2|C3|C5] [--full] [--dump-outputs DIR]
 
 With --gpus N > 1 and no WORLD_SIZE in the environment this process starts the N ranks itself
 (`python -m torch.distributed.run --nproc-per-node N ... bench.py`) BEFORE touching the GPU and relays their output; it
 never falls back to one rank.  Launched by torch.distributed.run it is one rank (RANK / LOCAL_RANK / WORLD_SIZE).
 
-Prints ONE JSON line on rank 0, with the `roofline` object of the config's dominant kernel (measured live with HIP
-events on the launch stream), the `cpu_baseline` object (the CPU oracle timed on the host cores, N = 1 only) and
-`pcie_inclusive` (the same steps fed from page-locked host memory through an overlapped copy stream).
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times the K steps and prints the headline (`metric`, `value`,
+`unit`, `higher_is_better`, `dtype`, `ms_per_step` = milliseconds of one timed step) -- nothing else runs on the GPU.
+--full adds everything measured beside the headline: `repeat` (further regions of K steps), the `roofline` object of the
+config's dominant kernel (measured live with HIP events on the launch stream), the `cpu_baseline` object (the CPU oracle
+timed on the host cores, N = 1 only), `pcie_inclusive` (the same steps fed from page-locked host memory through an
+overlapped copy stream) and, with N > 1, `per_rank`, `overlap_ab` and the replica-sync proof.
+--dump-outputs DIR writes what the timed path computed in its last timed step as DIR/<name>.npy (float32 / float64, at
+most 64 MB; a larger output as a fixed, seeded sample): the inputs are seeded, so two builds can be compared output for output.
 Other configs (--config) print the same shape of line for BASELINE.json's other configurations.
 """
 import argparse
@@ -185,6 +190,41 @@ def time_kernel(fn, iters=30, warm=5, graph=False):
     b.record()
     b.synchronize()
     return a.elapsed_time(b) * 1e-3 / iters
+
+
+DUMP_LIMIT_BYTES = 64 << 20          # --dump-outputs: all files together
+DUMP_MAX_ELEMS = 4 << 20             # a larger output is written as a fixed, seeded sample of this many elements
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: {name: tensor} -> out_dir/<name>.npy, float64 kept, everything else as float32.  An array of more than
+    DUMP_MAX_ELEMS elements is written as out_dir/<name>_sample.npy: the flattened array at DUMP_MAX_ELEMS sorted positions
+    drawn with a fixed seed (the same positions for the same size in every run)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    total = 0
+    for name, t in arrays.items():
+        a = t.detach().cpu().numpy()
+        a = np.atleast_1d(a.astype(np.float64 if a.dtype == np.float64 else np.float32))
+        if a.size > DUMP_MAX_ELEMS:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, DUMP_MAX_ELEMS, replace=False))
+            a, name = a.reshape(-1)[idx], name + '_sample'
+        total += a.nbytes
+        if total > DUMP_LIMIT_BYTES:
+            raise RuntimeError('--dump-outputs: more than %d bytes of outputs' % DUMP_LIMIT_BYTES)
+        np.save(os.path.join(out_dir, name + '.npy'), a)
+
+
+def train_outputs(step, model):
+    """What a caller of the timed training step holds after it: the loss, the masked mix and the stems' gains of the step's
+    forward pass, the updated parameters and the BatchNorm running statistics (model order, flattened)."""
+    import torch
+    bufs = [b.detach().reshape(-1).float() for _, b in model.named_buffers() if b.is_floating_point()]
+    out = {'loss': step.loss.reshape(1), 'masked': step.masked, 'gains': torch.cat(step.gains, 1),
+           'params': torch.cat([p.detach().reshape(-1) for p in model.parameters()])}
+    if bufs:
+        out['buffers'] = torch.cat(bufs)
+    return out
 
 
 def build_model(cfg, device, train=True):
@@ -589,25 +629,31 @@ def run_train(name, cfg, args):
     exposed = step.exposed_wait_ms()
     step.measure_exposed = False
     loss = step.loss.item()
+    if rank == 0 and args.dump_outputs:
+        dog.phase('dump outputs')
+        dump_outputs(args.dump_outputs, train_outputs(step, model))
     frames_per_step = step.frames_per_step * world
     value = frames_per_step * args.steps / dt
-    # the same region repeated (diagnostic: run-to-run spread of a 0.1 s region; `value` stays the region above)
-    dog.phase('repeat regions + per-rank clocks')
-    reps = [1e3 * timed(run, args.steps, args.warmup + (r + 1) * args.steps) / args.steps for r in range(args.repeat)]
-    rank_ms = 1e3 * local_time(run, args.steps, 0) / args.steps
-    if world > 1:
-        allr = [None] * world
-        torch.distributed.all_gather_object(allr, (rank_ms, exposed))
-    else:
-        allr = [(rank_ms, exposed)]
+    reps, allr = [], None
+    if args.full:
+        # the same region repeated (diagnostic: run-to-run spread of a 0.1 s region; `value` stays the region above)
+        dog.phase('repeat regions + per-rank clocks')
+        reps = [1e3 * timed(run, args.steps, args.warmup + (r + 1) * args.steps) / args.steps for r in range(args.repeat)]
+        rank_ms = 1e3 * local_time(run, args.steps, 0) / args.steps
+        if world > 1:
+            allr = [None] * world
+            torch.distributed.all_gather_object(allr, (rank_ms, exposed))
+        else:
+            allr = [(rank_ms, exposed)]
     gflop_step = cfg['gflop_fwd'] * 2.98 * B            # fwd+bwd algorithmic FLOPs per rank and step (SURVEY 8d ratio)
     # N > 1, staged step: does overlapping the big bucket's all-reduce with graph A2 PAY?  The strip kernels of A2 are sized 248
     # workgroups for 256 CUs and a kernel that shares their CUs slows them (side-stream weight gradients, every
-    # big kernel 1.3-1.7x longer) -- RCCL's kernels will sit exactly there.  So the same invocation times two more regions over
-    # the SAME three graphs: the all-reduces beside A2 (as `value` was measured) and both started only after A2, each with
-    # HIP events around graph A2.  One SCALE record then says which schedule the node prefers and what the overlap cost A2.
+    # big kernel 1.3-1.7x longer) -- RCCL's kernels will sit exactly there.  So the same invocation (--full) times two more
+    # regions over the SAME three graphs: the all-reduces beside A2 (as `value` was measured) and both started only after A2,
+    # each with HIP events around graph A2.  One SCALE record then says which schedule the node prefers and what the overlap
+    # cost A2.
     overlap_ab = None
-    if three_graphs:
+    if three_graphs and args.full:
         dog.phase('overlap A/B regions')
         ab = {}
         for label, ov in (('overlapped', True), ('serialized', False), ('inline', True)):
@@ -629,8 +675,10 @@ def run_train(name, cfg, args):
                                'enqueued; "inline" runs synchronous all-reduces on the training stream (no stream waits for the '
                                'training stream; exposed_allreduce_wait_ms is then the small bucket\'s whole exchange); '
                                'graph_A2_ms = HIP events around graph A2 per rank (events are recorded in these regions only)')
-    dog.phase('replica sync proof')
-    sync = replica_sync_proof(model, opt, device, dev_index, world)
+    sync = {'replicas_in_sync': None, 'checksums': None, 'devices': None}
+    if args.full:
+        dog.phase('replica sync proof')
+        sync = replica_sync_proof(model, opt, device, dev_index, world)
 
     result = {
         'metric': 'stem-spectrogram-frames/sec (train)', 'value': value, 'unit': 'stem-spectrogram-frames/s',
@@ -655,7 +703,7 @@ def run_train(name, cfg, args):
         srt = sorted(reps)
         result['repeat'] = {'regions': len(reps), 'steps_per_region': args.steps, 'ms_per_step_median': srt[len(srt) // 2],
                             'ms_per_step_min': srt[0], 'ms_per_step_max': srt[-1]}
-    if world > 1:
+    if world > 1 and allr is not None:
         result['per_rank'] = {'ms_per_step_min': min(a[0] for a in allr), 'ms_per_step_max': max(a[0] for a in allr),
                               'ms_per_step': [a[0] for a in allr],
                               # device time between the end of backward (graph A2) and both buckets having arrived: the part of
@@ -669,8 +717,8 @@ def run_train(name, cfg, args):
         dog.phase('breakdown')
         result['breakdown'] = ddp_breakdown(step, device)
     # the same steps fed from page-locked HOST memory (512 clips in pinned host memory): batch k+1 is uploaded on
-    # a copy stream while step k runs.  PCIe-inclusive: reported beside `value`, never as `value`.
-    if not args.no_host_stream:
+    # a copy stream while step k runs.  PCIe-inclusive: reported beside `value`, never as `value` (--full).
+    if args.full and not args.no_host_stream:
         dog.phase('host-streamed region')
         n_host = max(2 * B, min(N_HOST_CLIPS, args.host_clips) // B * B)
         host = torch.empty((n_host, S + 1, n, CHANNELS), dtype=torch.float32, pin_memory=True)
@@ -697,12 +745,13 @@ def run_train(name, cfg, args):
                                                   'pass of its shallow layers' if step.copy_mark is not None else 'end of step k-1'),
                                     'note': 'batch k+1 uploaded from page-locked host memory on a copy stream beside the steps'}
         del host, stager
-    dog.phase('roofline probe / cpu baseline (rank 0)')
-    if rank == 0 and not args.no_roofline:
+    if args.full:
+        dog.phase('roofline probe / cpu baseline (rank 0)')
+    if rank == 0 and args.full and not args.no_roofline:
         result['roofline'] = roofline_object(name, cfg, device, t_frames)
         result['roofline_extra'] = {'whole_step_tflops': gflop_step * 1e9 * args.steps / dt / 1e12,
                                     'whole_step_frac_of_fp32_mfma_peak': gflop_step * 1e9 * args.steps / dt / PEAK_F32_MFMA}
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         result['cpu_baseline'] = cpu_baseline(cfg)
     if rank == 0:
         result['config']['phases_s'] = {h[0]: h[1] for h in dog.history[1:]}
@@ -975,6 +1024,8 @@ def run_inference(name, cfg, args):
         mixer.launch()
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
+    if args.dump_outputs:           # the peak-normalised master and the chunk gains [raw, smoothed] of the last song
+        dump_outputs(args.dump_outputs, {'master': mixer.out, 'gains': mixer.gains})
     t_frames = 1 + chunk // cfg['hop']
     frames = mixer.n_proc * S * t_frames
     result = {
@@ -985,18 +1036,19 @@ def run_inference(name, cfg, args):
         'config': {'workload': cfg['workload'], 'chunks': mixer.n_proc, 'hip_graph': mixer.graph is not None,
                    'savgol_window': mixer.window},
     }
-    # PCIe-inclusive: host arrays in, normalised master out (page-locked double-buffered staging both ways)
-    rng = np.random.default_rng(0)
-    tracks = [(0.1 * rng.standard_normal((CHANNELS, n))).astype(np.float32) for _ in range(S)]
-    mixer.run(tracks)
-    t0 = time.perf_counter()
-    reps = 3
-    for _ in range(reps):
+    # PCIe-inclusive (--full): host arrays in, normalised master out (page-locked double-buffered staging both ways)
+    if args.full:
+        rng = np.random.default_rng(0)
+        tracks = [(0.1 * rng.standard_normal((CHANNELS, n))).astype(np.float32) for _ in range(S)]
         mixer.run(tracks)
-    dth = (time.perf_counter() - t0) / reps
-    result['pcie_inclusive'] = {'ms_per_song': 1e3 * dth, 'value': frames / dth,
-                                'h2d_bytes': float(S * CHANNELS * n * 4), 'd2h_bytes': float(CHANNELS * n * 4)}
-    if not args.no_roofline:
+        t0 = time.perf_counter()
+        reps = 3
+        for _ in range(reps):
+            mixer.run(tracks)
+        dth = (time.perf_counter() - t0) / reps
+        result['pcie_inclusive'] = {'ms_per_song': 1e3 * dth, 'value': frames / dth,
+                                    'h2d_bytes': float(S * CHANNELS * n * 4), 'd2h_bytes': float(CHANNELS * n * 4)}
+    if args.full and not args.no_roofline:
         result['roofline'] = roofline_object(name, cfg, device, t_frames)
         result['roofline_extra'] = {'whole_step_tflops': cfg['gflop_fwd'] * mixer.n_proc * 1e9 * args.steps / dt / 1e12}
     print(json.dumps(result), flush=True)
@@ -1008,18 +1060,24 @@ def main():
     ap.add_argument('--steps', type=int, default=20)
     ap.add_argument('--warmup', type=int, default=3)
     ap.add_argument('--config', choices=sorted(CONFIGS), default='C3')
+    ap.add_argument('--full', action='store_true',
+                    help='also measure what is reported beside the headline: repeat regions, pcie_inclusive, roofline, '
+                         'cpu_baseline; N > 1: per_rank, overlap_ab, the replica-sync proof')
+    ap.add_argument('--dump-outputs', metavar='DIR',
+                    help='write what the timed path computed in its last timed step as DIR/<name>.npy (at most 64 MB)')
     ap.add_argument('--no-graph', action='store_true')
     ap.add_argument('--no-overlap', action='store_true', help='N > 1: one un-overlapped all-reduce of the whole flat buffer')
     ap.add_argument('--reduce-mode', choices=('auto', 'overlapped', 'inline'), default='auto',
                     help='N > 1: all-reduces beside backward on RCCL\'s stream, on the training stream, or whichever is faster here')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--no-roofline', action='store_true')
-    ap.add_argument('--no-host-stream', action='store_true')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='--full without the cpu_baseline object')
+    ap.add_argument('--no-roofline', action='store_true', help='--full without the roofline object')
+    ap.add_argument('--no-host-stream', action='store_true', help='--full without the pcie_inclusive region')
     ap.add_argument('--bind-per-step', action='store_true', help='A/B: re-point the front-end per step instead of the device-side rotation')
     ap.add_argument('--no-copy-mark', action='store_true', help='A/B: the streamed leg\'s uploads start at step ends (no step mark)')
     ap.add_argument('--host-clips', type=int, default=N_HOST_CLIPS)
     ap.add_argument('--breakdown', action='store_true', help='N > 1: add per-phase timings of the step (diagnostic)')
-    ap.add_argument('--repeat', type=int, default=5, help='extra timed regions of --steps steps: median / min / max in the line')
+    ap.add_argument('--repeat', type=int, default=5,
+                    help='--full: extra timed regions of --steps steps, median / min / max in the line')
     ap.add_argument('--via-trainer', action='store_true',
                     help='diagnostic line (never the headline): ms per step of ModelTrainer.fit fed by Dataset.batch_loader')
     ap.add_argument('--ingest', action='store_true',
@@ -1034,6 +1092,10 @@ def main():
     args = ap.parse_args()
     if args.gpus < 1:
         raise SystemExit('--gpus must be >= 1')
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit('--steps must be >= 1 and --warmup >= 0')
+    if args.dump_outputs and (args.via_trainer or args.ingest):
+        raise SystemExit('--dump-outputs: the timed step of --config C1|C2|C3|C5 only, not --via-trainer / --ingest')
     world_env = os.environ.get('WORLD_SIZE')
     if world_env is None and args.gpus > 1:
         sys.exit(spawn_ranks(args, sys.argv[1:]))            # before any GPU call in this process

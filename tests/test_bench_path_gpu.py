@@ -187,3 +187,38 @@ def test_c1_captured_step_matches_oracle(dam_lib):
     _captured_step_matches_oracle('C1', models_ref.RefMixingModelScalar1s, ((0, 0), (5, 1), (7, 0)),
                                   ('conv_b1.batch_norm.running_mean', 'conv_b2.batch_norm.running_var',
                                    'conv_b5.batch_norm.running_var'))
+
+
+def test_plain_bench_run_prints_the_headline_and_dumps_the_last_step(dam_lib, tmp_path):
+    """`python bench.py --steps K --warmup W --dump-outputs DIR` as a fresh process: one JSON line with the headline only (the
+    regions and probes of --full are not run) and the last timed step's outputs -- loss, masked mix, gains, parameters,
+    BatchNorm running statistics -- as float32 .npy files under DIR."""
+    import json
+    import os
+    import subprocess
+    import sys
+    import bench
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK')}
+    out_dir = tmp_path / 'outputs'
+    r = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--steps', '3', '--warmup', '1',
+                        '--dump-outputs', str(out_dir)], env=env, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith('{')]
+    assert len(lines) == 1, r.stdout[-2000:]
+    line = json.loads(lines[0])
+    assert line['metric'] == 'stem-spectrogram-frames/sec (train)' and line['unit'] == 'stem-spectrogram-frames/s'
+    assert line['higher_is_better'] is True and line['dtype'] == 'f32' and line['steps'] == 3 and line['warmup'] == 1
+    assert line['ms_per_step'] > 0 and line['value'] > 0
+    assert not {'repeat', 'roofline', 'cpu_baseline', 'pcie_inclusive', 'per_rank', 'overlap_ab'} & set(line)
+    cfg = bench.CONFIGS['C3']
+    B, S, t = cfg['batch'], cfg['n_stems'], 1 + cfg['sr'] * cfg['seconds'] // cfg['hop']
+    got = {f[:-4]: np.load(out_dir / f) for f in os.listdir(out_dir)}
+    assert set(got) == {'loss', 'masked', 'gains', 'params', 'buffers'}
+    assert all(a.dtype == np.float32 and np.isfinite(a).all() for a in got.values())
+    assert got['masked'].shape == (B, bench.N_FFT // 2 + 1, t) and got['gains'].shape == (B, S)
+    assert got['loss'].shape == (1,) and got['loss'][0] == np.float32(line['config']['final_loss'])
+    with torch.random.fork_rng(devices=[]):          # (build_model seeds torch's generator)
+        model = bench.build_model(cfg, torch.device('cpu'))
+    assert got['params'].size == sum(p.numel() for p in model.parameters())
+    assert sum(a.nbytes for a in got.values()) <= bench.DUMP_LIMIT_BYTES

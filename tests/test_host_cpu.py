@@ -474,3 +474,37 @@ def test_bench_watchdog_names_the_phase_and_exits_nonzero():
         del os.environ['DAM_DIST_TIMEOUT_S']
     assert bench.dist_timeout_s() == 300.0
     assert bench.ProgressWatchdog(0, rank=0).timeout_s == 0          # off: no thread, phase() still records
+
+
+def test_bench_dump_outputs_writes_float_arrays_within_the_limit(tmp_path):
+    """bench.py --dump-outputs: every output as <name>.npy in float32 (float64 kept), an output larger than DUMP_MAX_ELEMS as
+    the same seeded sample of positions in every run, and never more than DUMP_LIMIT_BYTES in all."""
+    import bench
+    big = torch.arange(bench.DUMP_MAX_ELEMS + 10, dtype=torch.float32)
+    arrays = {'loss': torch.tensor(1.5), 'big': big, 'gains': torch.ones((2, 3), dtype=torch.float64), 'count': torch.arange(4)}
+    for d in ('a', 'b'):
+        bench.dump_outputs(str(tmp_path / d), arrays)
+    assert sorted(os.listdir(tmp_path / 'a')) == ['big_sample.npy', 'count.npy', 'gains.npy', 'loss.npy']
+    loss, gains, count = (np.load(tmp_path / 'a' / f) for f in ('loss.npy', 'gains.npy', 'count.npy'))
+    assert loss.dtype == np.float32 and loss.tolist() == [1.5]
+    assert gains.dtype == np.float64 and gains.shape == (2, 3) and count.dtype == np.float32 and count.tolist() == [0, 1, 2, 3]
+    sample = np.load(tmp_path / 'a' / 'big_sample.npy')
+    assert sample.dtype == np.float32 and sample.shape == (bench.DUMP_MAX_ELEMS,)
+    assert np.all(np.diff(sample) > 0) and sample[-1] <= big[-1].item()          # distinct positions of `big`, in order
+    np.testing.assert_array_equal(sample, np.load(tmp_path / 'b' / 'big_sample.npy'))
+    n = bench.DUMP_LIMIT_BYTES // 4 // bench.DUMP_MAX_ELEMS + 1
+    with pytest.raises(RuntimeError, match='more than'):
+        bench.dump_outputs(str(tmp_path / 'c'), {'x%d' % i: torch.zeros(bench.DUMP_MAX_ELEMS) for i in range(n)})
+
+
+def test_bench_rejects_meaningless_step_counts_and_dump_targets():
+    """--steps sets the number of timed steps (at least one); --dump-outputs belongs to the timed step, not to the diagnostic
+    --via-trainer / --ingest lines.  Both are refused before any GPU work."""
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK')}
+    for extra, msg in ((['--steps', '0'], '--steps'), (['--via-trainer', '--dump-outputs', 'out'], '--dump-outputs')):
+        r = subprocess.run([sys.executable, os.path.join(root, 'bench.py')] + extra, env=env, capture_output=True, text=True,
+                           timeout=120)
+        assert r.returncode != 0 and msg in r.stderr and '{' not in r.stdout

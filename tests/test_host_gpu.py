@@ -1,5 +1,6 @@
 """GPU: the drop-in API end to end -- Dataset items, ModelTrainer.fit (against the trajectory, stdout and checkpoint
 names recorded from the reference's own ModelTrainer), the fused Adam, full-song inference."""
+import gc
 import json
 import os
 
@@ -570,7 +571,7 @@ def _bench_two_ranks(backend):
     env.update(HSA_ENABLE_IPC_MODE_LEGACY='0')
     if backend != 'nccl':
         env.update(DAM_DIST_BACKEND=backend)
-    r = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--gpus', '2', '--steps', '3', '--warmup', '1',
+    r = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--gpus', '2', '--steps', '3', '--warmup', '1', '--full',
                         '--no-cpu-baseline', '--no-roofline', '--no-host-stream', '--repeat', '1'],
                        env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
@@ -764,6 +765,9 @@ def test_notebook_loader_cell_with_six_workers_matches_num_workers_0(dam, tmp_pa
     device = torch.device('cuda')
     runs = []
     for workers in (0, 6):
+        # a forked worker inherits this process's uncollected reference cycles; collecting one there runs the destructors of
+        # its captured graphs and events -- HIP calls in a forked child, which crash it.  Collect them here, before forking
+        gc.collect()
         d_train = MultitrackAudioDataset(str(tmp_path), songlist=['A', 'B'], chunk_length=1, sr=sr, seed=321, normalize=False,
                                          compute_features=True, augment_data=augment)
         d_val = MultitrackAudioDataset(str(tmp_path), songlist=['B'], chunk_length=1, sr=sr, seed=321, normalize=False,
@@ -795,6 +799,7 @@ def test_notebook_loader_cell_with_six_workers_matches_num_workers_0(dam, tmp_pa
         assert (trainer._step.gain is not None) == (augment and workers > 0)
         runs.append((per_batch, train_loss, val_loss))
         trainer.close()
+        del trainer._train_batch            # (the wrapper holds the trainer's own bound method: a reference cycle)
     np.testing.assert_allclose(runs[1][0], runs[0][0], rtol=2e-5)
     np.testing.assert_allclose(runs[1][1], runs[0][1], rtol=2e-5)
     np.testing.assert_allclose(runs[1][2], runs[0][2], rtol=2e-5)
@@ -817,6 +822,7 @@ def test_caller_owned_loop_over_worker_batches(dam):
     d = MultitrackAudioDataset.from_arrays(songs, chunk_length=1, sr=sr)
     items = [d[i] for i in range(len(d))]
     loader = DataLoader(d, batch_size=2, shuffle=False, num_workers=2, pin_memory=True)
+    gc.collect()                # no reference cycles of earlier tests for the forked workers to collect (see above)
     device = torch.device('cuda')
     seen = 0
     for batch in loader:

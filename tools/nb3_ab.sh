@@ -7,7 +7,7 @@ tail -2 $out/tests_nb3.log
 for cfg in C2 C1; do
 for v in on off on off; do
   if [ $v = off ]; then export DAM_CONV_NO_NB3=1; else unset DAM_CONV_NO_NB3; fi
-  timeout -k 10 300 python3 bench.py --config $cfg --steps 10 --warmup 3 --no-cpu-baseline --no-roofline --no-host-stream > $out/bench_nb3_$v.json 2> $out/bench_nb3_$v.err
+  timeout -k 10 300 python3 bench.py --full --config $cfg --steps 10 --warmup 3 --no-cpu-baseline --no-roofline --no-host-stream > $out/bench_nb3_$v.json 2> $out/bench_nb3_$v.err
   python3 - $v $cfg <<'P'
 import json, sys
 d = json.load(open("gpurun_out/r5b/bench_nb3_%s.json" % sys.argv[1]))

@@ -10,8 +10,8 @@ for m in gate end; do
   timeout -k 10 200 python3 tools/copy_gate_probe.py $m 8 > $out/copy_gate_probe_$m.txt 2>&1 || { cat $out/copy_gate_probe_$m.txt; exit 1; }
   grep -a "equal\|period\|step  [3-6]" $out/copy_gate_probe_$m.txt
 done
-timeout -k 10 300 python3 bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-roofline > $out/bench_mark.json 2> $out/bench_mark.err
-timeout -k 10 300 python3 bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-roofline --no-copy-mark > $out/bench_nomark.json 2> $out/bench_nomark.err
+timeout -k 10 300 python3 bench.py --full --steps 20 --warmup 3 --no-cpu-baseline --no-roofline > $out/bench_mark.json 2> $out/bench_mark.err
+timeout -k 10 300 python3 bench.py --full --steps 20 --warmup 3 --no-cpu-baseline --no-roofline --no-copy-mark > $out/bench_nomark.json 2> $out/bench_nomark.err
 python3 - <<'P'
 import json
 for f in ("mark", "nomark"):

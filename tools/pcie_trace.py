@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """tools/pcie_trace.py <rocprofv3 csv dir> [steps]: where the host-streamed (`pcie_inclusive`) region of bench.py loses against the
-HBM-resident region.  Reads the kernel trace and the memory-copy trace of ONE bench.py run (resident regions first, the streamed region
+HBM-resident region.  Reads the kernel trace and the memory-copy trace of ONE `bench.py --full` run (resident regions first, the streamed region
 last) and prints, for the last `steps` steps of each kind: the step period (STFT start to STFT start), the kernel time inside a step,
 the kernels that got slower, what copy kernels (blit) ran on the device, and every host-to-device copy's interval against the steps."""
 import csv, glob, re, sys

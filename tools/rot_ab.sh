@@ -6,7 +6,7 @@ timeout -k 10 600 python3 -m pytest tests/test_host_gpu.py tests/test_features_g
 tail -2 $out/tests_rot.log
 for v in rot bind rot bind; do
   extra=""; [ $v = bind ] && extra="--bind-per-step"
-  timeout -k 10 300 python3 bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-roofline $extra > $out/bench_$v.json 2> $out/bench_$v.err
+  timeout -k 10 300 python3 bench.py --full --steps 20 --warmup 3 --no-cpu-baseline --no-roofline $extra > $out/bench_$v.json 2> $out/bench_$v.err
   python3 - $v <<'P'
 import json, sys
 d = json.load(open("gpurun_out/r5b/bench_%s.json" % sys.argv[1]))

@@ -7,7 +7,7 @@ out=${OUT:-gpurun_out/r5/strip_2wg_ab.log}
 for lib in ${LIBS:-default tools/libdam_2wg0.so tools/libdam_2wg3.so default}; do
   echo "== $lib" >> $out
   if [ "$lib" = default ]; then unset DAM_LIB_PATH; else export DAM_LIB_PATH=$PWD/$lib; fi
-  timeout -k 10 200 python bench.py --steps 20 --no-cpu-baseline --no-host-stream 2>/dev/null | python -c "
+  timeout -k 10 200 python bench.py --full --steps 20 --no-cpu-baseline --no-host-stream 2>/dev/null | python -c "
 import json,sys
 for ln in sys.stdin:
     if ln.startswith('{'):

@@ -5,7 +5,7 @@ timeout -k 10 900 python3 -m pytest tests/test_conv_gpu.py tests/test_blocks_gpu
 tail -2 $out/tests_wd.log
 for v in on off on off; do
   if [ $v = off ]; then export DAM_WG_DIRECT_NO_BATCH=1; else unset DAM_WG_DIRECT_NO_BATCH; fi
-  timeout -k 10 300 python3 bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-roofline --no-host-stream > $out/bench_wd_$v.json 2> $out/bench_wd_$v.err
+  timeout -k 10 300 python3 bench.py --full --steps 20 --warmup 3 --no-cpu-baseline --no-roofline --no-host-stream > $out/bench_wd_$v.json 2> $out/bench_wd_$v.err
   python3 - $v <<'P'
 import json, sys
 d = json.load(open("gpurun_out/r5b/bench_wd_%s.json" % sys.argv[1]))

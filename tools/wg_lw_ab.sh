@@ -5,7 +5,7 @@ out=gpurun_out/r5/wg_lw_ab.log
 : > $out
 for cfg in C2 C1 C3; do
   for lw in 1 0 1 0; do
-    DAM_WG_LW=$lw timeout -k 10 300 python bench.py --config $cfg --steps 10 --no-cpu-baseline --no-host-stream --no-roofline 2>/dev/null | python -c "
+    DAM_WG_LW=$lw timeout -k 10 300 python bench.py --full --config $cfg --steps 10 --no-cpu-baseline --no-host-stream --no-roofline 2>/dev/null | python -c "
 import json,sys
 for ln in sys.stdin:
     if ln.startswith('{'):
