@@ -634,6 +634,9 @@ constexpr int FA_THREADS = 256;
 constexpr int FA_U = 4;                 // pixel pieces per thread, stream and register set (two sets: the next batch's loads are
                                         // requested before the current batch is computed and stored)
 
+// grid of the fused launches: at most this many workgroups over all slices
+constexpr int FA_WGS = 512;
+
 struct FaPlan { int cs, nslices, nranges, q, ppi; int64_t ppr; };
 
 // CS: the whole row for thin layers (one 128-byte line per pixel at 32 channels), 16-channel slices above that (64-byte pieces:
@@ -645,9 +648,8 @@ inline FaPlan fa_plan(int64_t P, int C) {
     f.nslices = C / f.cs;
     f.q = f.cs / 4;
     f.ppi = FA_THREADS / f.q;
-    static const int wgs = [] { const char* e = getenv("DAM_BN_FA_WGS"); const int v = e ? atoi(e) : 0; return v > 0 ? v : 512; }();
     int64_t want = P / ((int64_t)f.ppi * FA_U * 2);       // >= two batches of loads per thread
-    const int64_t cap = wgs / f.nslices > 0 ? wgs / f.nslices : 1;
+    const int64_t cap = FA_WGS / f.nslices > 0 ? FA_WGS / f.nslices : 1;
     if (want > cap) want = cap;
     if (want < 1) want = 1;
     f.ppr = cdiv(P, want);
@@ -660,11 +662,11 @@ constexpr int FA_TABLE_BYTES_MAX = 80 * 1024;
 inline bool fa_table_ok(int C, int parts, int rec_floats) { return (int64_t)parts * fa_cs(C) * rec_floats * 4 <= FA_TABLE_BYTES_MAX; }
 // The FORWARD form pays more per record (12 bytes, a divide-free but longer merge, sqrt) and its launches on the full-resolution
 // stages measured 2-3 us SLOWER than finalize + apply (48 KB tables x 512 workgroups = 24 MB of table reads in front of a 35 us
-// stream), the small stages' about equal: it is taken only for tables up to DAM_BN_FUSED_FWD_KB (default 24) KB per workgroup --
+// stream), the small stages' about equal: it is taken only for tables up to FA_FWD_TABLE_KB KB per workgroup --
 // the backward forms win 1.5-2.5 us per launch on every stage and are taken up to FA_TABLE_BYTES_MAX.
+constexpr int FA_FWD_TABLE_KB = 24;
 inline bool fa_fwd_table_ok(int C, int parts) {
-    static const int kb = [] { const char* e = getenv("DAM_BN_FUSED_FWD_KB"); const int v = e ? atoi(e) : -1; return v >= 0 ? v : 24; }();
-    return fa_table_ok(C, parts, 3) && (int64_t)parts * fa_cs(C) * 12 <= (int64_t)kb * 1024;
+    return fa_table_ok(C, parts, 3) && (int64_t)parts * fa_cs(C) * 12 <= (int64_t)FA_FWD_TABLE_KB * 1024;
 }
 
 // Sums NV per-record values over the slice's records: thread (c = tid % CS, i = tid / CS) takes records i, i + TPC, ...; every
@@ -946,10 +948,10 @@ inline bool fa_enabled() {
     return on;
 }
 
-// records a partial pass may leave for a fused consumer: a workgroup's slice table stays <= 64 KB
+// records a partial pass may leave for a fused consumer: a workgroup's slice table stays <= FA_PARTS_KB KB
+constexpr int FA_PARTS_KB = 64;
 inline int fa_max_parts(int C, int rec_floats) {
-    static const int kb = [] { const char* e = getenv("DAM_BN_FA_PARTS_KB"); const int v = e ? atoi(e) : 0; return v >= 16 && v <= 80 ? v : 64; }();   // A/B knob
-    int m = kb * 1024 / (fa_cs(C) * rec_floats * 4);
+    int m = FA_PARTS_KB * 1024 / (fa_cs(C) * rec_floats * 4);
     if (m > BN_MAX_PARTS) m = BN_MAX_PARTS;
     return m < 64 ? 64 : m;
 }

@@ -695,7 +695,7 @@ extern "C" int dam_conv2d_tapgrid_f32(const float* x, int B, int H, int W, int C
         // Too wide for its patch buffers (the strided 16 -> 32 convolution on 1025x130: 131 input columns x 5 rows): the same
         // kernel on 2-4 column ranges of the output, one launch each -- a range is just another output sub-grid of this entry
         // point's geometry (width, output column offset, input column offset).  Not with an epilogue that leaves records.
-        if (nA == 3 && nB == 3 && !in_nchw && !bn_partial && !getenv("DAM_PIPE_NO_COLSPLIT")) {
+        if (nA == 3 && nB == 3 && !in_nchw && !bn_partial) {
             for (int ns = 2; ns <= 4; ++ns) {
                 const int wd0 = (int)cdiv(Wo, ns);
                 if (wd0 < 16) break;
@@ -722,9 +722,8 @@ extern "C" int dam_conv2d_tapgrid_f32(const float* x, int B, int H, int W, int C
     const int64_t npix = (int64_t)Ho * Wo;
     const int nblk = n_out / 16;
     // NB must divide the block count.  Three-block tiles for the 48-channel layers of the scalar models (models/model_scalar_2s.py:
-    // 64-77: the 7x7 data gradient 64 -> 48 ran the one-block tile, every LDS operand feeding ONE MFMA group: 371 us = 0.50 of peak)
-    static const bool no_nb3 = getenv("DAM_CONV_NO_NB3") != nullptr;      // A/B switch
-    int MB = 4, NB = nblk % 4 == 0 ? 4 : (nblk % 3 == 0 && !no_nb3 ? 3 : (nblk % 2 == 0 ? 2 : 1));
+    // 64-77: the 7x7 data gradient 64 -> 48 ran the one-block tile, every LDS operand feeding ONE MFMA group: 371 us = 0.50 of peak; three-block tiles: 312 us, C2 5.267 -> 5.198 ms)
+    int MB = 4, NB = nblk % 4 == 0 ? 4 : (nblk % 3 == 0 ? 3 : (nblk % 2 == 0 ? 2 : 1));
     auto wgs = [&](int mb, int nb) { return cdiv(npix, 64 * mb) * cdiv(nblk, nb) * B; };
     const bool can_split = workspace && out_stride == 1 && Ho == OHt && Wo == OWt && out_off_h == 0 && out_off_w == 0 &&
                            k_chunks >= 4;

@@ -49,13 +49,6 @@ constexpr int PIPE_BUF1 = 32768;                // LDS byte offset of the second
 // weight loads that were just put in flight on purpose).
 #define DAM_PIPE_BARRIER() asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory")
 
-// timing experiments (tools/build_variant.sh): results are wrong with any of these defined
-#ifdef DAM_PIPE_DIAG_W0
-#define DAM_PIPE_WOFF(x) ((x) & 0)              // every weight load hits the same 4 KB
-#else
-#define DAM_PIPE_WOFF(x) (x)
-#endif
-
 // Diagnostic build only (-DDAM_PIPE_STAMPS): the caller's workspace (`stamps`, otherwise unused here) receives s_memtime stamps of phase
 // boundaries, [workgroup][role: wave 0 / first loader wave][64] of (tag << 56 | time); read by tools/pipe_stamps_probe.py.
 #ifdef DAM_PIPE_STAMPS
@@ -101,7 +94,7 @@ __global__ __launch_bounds__(PIPE_THREADS) void conv_pipe_kernel(const ConvGeo g
                                                                  const float* __restrict__ in_shift, float* __restrict__ Y,
                                                                  const float* __restrict__ res, const float* __restrict__ res_mask,
                                                                  float* __restrict__ stamps, float* __restrict__ stats,
-                                                                 const BnBwdEpi bwd, const int stats_acc, const int xcd_aware) {
+                                                                 const BnBwdEpi bwd) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -118,7 +111,7 @@ __global__ __launch_bounds__(PIPE_THREADS) void conv_pipe_kernel(const ConvGeo g
     // XCD-aware unit walk: workgroup b runs on XCD b % 8 and every XCD has its own L2.  Each XCD takes one CONTIGUOUS eighth of the
     // units and its workgroups walk it side by side, so that neighbouring tiles (they share halo rows) and the channel-block groups
     // of one tile meet in ONE L2 (plain stride walk: FETCH_SIZE 2.6 x the input on the 257 x 33 stage, 6 x on 33 x 5).
-    const bool xa = xcd_aware && (gridDim.x & 7) == 0;
+    const bool xa = (gridDim.x & 7) == 0;
     const int G = xa ? (int)gridDim.x >> 3 : (int)gridDim.x;
     const int per_xcd = xa ? (nunits + 7) >> 3 : nunits;
     const int u_lo = xa ? (int)(blockIdx.x & 7) * per_xcd : 0;
@@ -260,7 +253,6 @@ __global__ __launch_bounds__(PIPE_THREADS) void conv_pipe_kernel(const ConvGeo g
             if (!s_live[0]) break;
         }
         DAM_PIPE_BARRIER();                         // the last chunk is consumed
-        if (STATS && stats_acc) DAM_PIPE_BARRIER(); // the compute waves' statistics are in LDS (their merge follows, see below)
 #undef DAM_PIPE_REFILL
 #undef DAM_PIPE_COMMIT
 #undef DAM_PIPE_ROUND_END
@@ -271,12 +263,6 @@ __global__ __launch_bounds__(PIPE_THREADS) void conv_pipe_kernel(const ConvGeo g
     const int j = lane & 15, kq = lane >> 4;
     const int mt = wave & (MT - 1), kh = wave / MT;        // pixel block of the unit, K half (KS == 2)
     const int part_off = PIPE_BUF1 + stage_bytes + (in_scale ? 2 * g.C * 4 : 0) + PIPE_LT * 16;   // behind the loaders' dump zone
-    // stats_acc (one channel-block group per image row of units: every unit of the launch has the SAME channels): the waves'
-    // statistics accumulate over the units this workgroup walks -- in LDS, [wave][channel][k, s1, s2] + [wave] n -- and the
-    // workgroup leaves ONE record per channel at the end instead of one per wave and unit (257 x 33 stage: 512 instead of 4256)
-    const int sacc_off = part_off + (KS == 2 ? 2 * MB * NB * 1024 : 0);
-    float* const sacc = reinterpret_cast<float*>(smem + sacc_off) + wave * (g.N * 3 + 4);
-    bool sacc_first = true;
     // tap constants: packed-weight byte offset of (tap, chunk 0, block 0) and LDS byte offset of the tap inside the patch
     int tapw[9], tapx[9];
 #pragma unroll
@@ -295,11 +281,7 @@ __global__ __launch_bounds__(PIPE_THREADS) void conv_pipe_kernel(const ConvGeo g
     // every request has a whole chunk (1152 clocks) to land.  (Measured: no difference on those stages -- a build whose weight
     // loads all hit one 4 KB block is no faster either, the weights are not what they wait for -- so the two-block tiles, where
     // nine sets cost 48 registers, keep three.)
-#ifdef DAM_PIPE_NO_W9
-    constexpr bool W9 = false;
-#else
     constexpr bool W9 = MB * NB == 1;
-#endif
     constexpr int WSETS = W9 ? 9 : 3;
     v4f acc[MB][NB];
     float4 wa[WSETS][NB], xv[3][MB];
@@ -309,7 +291,7 @@ __global__ __launch_bounds__(PIPE_THREADS) void conv_pipe_kernel(const ConvGeo g
     int sbuf = 0;
 #define DAM_PIPE_W(S_, CPART_, T_)                                                                                         \
     do {                                                                                                                   \
-        const int ws_ = DAM_PIPE_WOFF(tapw[T_] + (CPART_));                                                                \
+        const int ws_ = tapw[T_] + (CPART_);                                                                                \
         _Pragma("unroll") for (int nb = 0; nb < NB; ++nb)                                                                  \
             wa[S_][nb] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(wrsrc, lane16 + nb * 1024, ws_, 0)); \
     } while (0)
@@ -319,16 +301,6 @@ __global__ __launch_bounds__(PIPE_THREADS) void conv_pipe_kernel(const ConvGeo g
         _Pragma("unroll") for (int mb = 0; mb < MB; ++mb)                                                                  \
             xv[S_][mb] = *reinterpret_cast<const float4*>(smem + base_b[mb] + lo_);                                        \
     } while (0)
-#ifdef DAM_PIPE_DIAG_NOMFMA
-#define DAM_PIPE_MFMA2(SW_, SX_)                                                                                           \
-    do {                                                                                                                   \
-        _Pragma("unroll") for (int mb = 0; mb < MB; ++mb)                                                                  \
-            _Pragma("unroll") for (int nb = 0; nb < NB; ++nb) {                                                            \
-                acc[mb][nb].x += wa[SW_][nb].x * xv[SX_][mb].x; acc[mb][nb].y += wa[SW_][nb].y * xv[SX_][mb].y;            \
-                acc[mb][nb].z += wa[SW_][nb].z * xv[SX_][mb].z; acc[mb][nb].w += wa[SW_][nb].w * xv[SX_][mb].w;            \
-            }                                                                                                              \
-    } while (0)
-#else
 #define DAM_PIPE_MFMA2(SW_, SX_)                                                                                           \
     do {                                                                                                                   \
         _Pragma("unroll") for (int mb = 0; mb < MB; ++mb)                                                                  \
@@ -339,7 +311,6 @@ __global__ __launch_bounds__(PIPE_THREADS) void conv_pipe_kernel(const ConvGeo g
                 acc[mb][nb] = __builtin_amdgcn_mfma_f32_16x16x4f32(wa[SW_][nb].w, xv[SX_][mb].w, acc[mb][nb], 0, 0, 0);    \
             }                                                                                                              \
     } while (0)
-#endif
 #define DAM_PIPE_MFMA(S_) DAM_PIPE_MFMA2(S_, S_)
     {
         const int cfirst = (kh * g.NBtot + cur.nb0) * 1024;
@@ -468,8 +439,6 @@ __global__ __launch_bounds__(PIPE_THREADS) void conv_pipe_kernel(const ConvGeo g
                                     (bias ? bias[(cur.nb0 + nb) * 16 + kq * 4 + r] : 0.f);
                 st_k[nb][r] = STATS == 1 ? __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, first), 0x150, 0xF, 0xF, false))
                                     : 0.f;                                     // row_newbcast:0 -- lane 0 of the row
-                // accumulating form: ONE shift per channel for everything this wave sees (its first unit's, kept in LDS)
-                if (STATS == 1 && stats_acc && !sacc_first) st_k[nb][r] = sacc[((cur.nb0 + nb) * 16 + kq * 4 + r) * 3];
                 st_s1[nb][r] = 0.f; st_s2[nb][r] = 0.f;
             }
         // STATS == 2: `res` is the BatchNorm's input x (nothing is added); per channel quad the two affine maps
@@ -547,7 +516,6 @@ __global__ __launch_bounds__(PIPE_THREADS) void conv_pipe_kernel(const ConvGeo g
             const size_t rec = ((size_t)cur.img * g.tiles_m + (cur.p0 / UPX)) * MT + mt;
             float n = st_n;
             DAM_ROW_SUM(n);
-            if (stats_acc && j == 0 && kq == 0) sacc[g.N * 3] = sacc_first ? n : sacc[g.N * 3] + n;
 #pragma unroll
             for (int nb = 0; nb < NB; ++nb)
 #pragma unroll
@@ -556,13 +524,7 @@ __global__ __launch_bounds__(PIPE_THREADS) void conv_pipe_kernel(const ConvGeo g
                     DAM_ROW_SUM(s1);
                     DAM_ROW_SUM(s2);
                     const int ch = (cur.nb0 + nb) * 16 + kq * 4 + r;
-                    if (stats_acc) {            // this wave's own LDS cells: plain read-add-write, fixed order
-                        if (j == 0 && ch < g.N) {
-                            float* o = sacc + ch * 3;
-                            if (sacc_first) { o[0] = st_k[nb][r]; o[1] = s1; o[2] = s2; }
-                            else { o[1] += s1; o[2] += s2; }
-                        }
-                    } else if (STATS == 2) {
+                    if (STATS == 2) {
                         if (j == 0 && ch < g.N) { float* o = stats + (rec * g.N + ch) * 2; o[0] = s1; o[1] = s2; }
                     } else if (j == 0 && ch < g.N) {
                         const float md = n > 0.f ? s1 / n : 0.f;
@@ -571,42 +533,11 @@ __global__ __launch_bounds__(PIPE_THREADS) void conv_pipe_kernel(const ConvGeo g
                     }
                 }
 #undef DAM_ROW_SUM
-            sacc_first = false;
         }
         DAM_PSTAMP(0, 8);
         if (!has_next) break;
         unit += G;
         cur = nxt;
-    }
-    if (STATS && stats_acc) {
-        // every wave's sums are in LDS: one barrier (the loaders join it, see their last line), then the first N lanes of the
-        // workgroup merge the MT waves of a channel in wave order and write the workgroup's record
-        DAM_PIPE_BARRIER();
-        const int c = tid;
-        if (c < g.N) {
-            const float* base = reinterpret_cast<const float*>(smem + sacc_off);
-            const int wstride = g.N * 3 + 4;
-            if (STATS == 2) {
-                float s1 = 0.f, s2 = 0.f;
-                for (int w = 0; w < MT; ++w) { s1 += base[w * wstride + c * 3 + 1]; s2 += base[w * wstride + c * 3 + 2]; }
-                float* o = stats + ((size_t)blockIdx.x * g.N + c) * 2;
-                o[0] = s1; o[1] = s2;
-            } else {
-                float na = 0.f, ma = 0.f, qa = 0.f;          // Chan merge of the waves' (n, mean, M2), fixed order
-                for (int w = 0; w < MT; ++w) {
-                    const float nb_ = base[w * wstride + g.N * 3];
-                    if (nb_ <= 0.f) continue;
-                    const float k_ = base[w * wstride + c * 3], s1 = base[w * wstride + c * 3 + 1], s2 = base[w * wstride + c * 3 + 2];
-                    const float md = s1 / nb_, mb_ = k_ + md, qb = fmaxf(s2 - s1 * md, 0.f);
-                    const float nn = na + nb_, d = mb_ - ma;
-                    ma += d * (nb_ / nn);
-                    qa += qb + d * d * (na * nb_ / nn);
-                    na = nn;
-                }
-                float* o = stats + ((size_t)blockIdx.x * g.N + c) * 3;
-                o[0] = na; o[1] = ma; o[2] = qa;
-            }
-        }
     }
 #undef DAM_PIPE_W
 #undef DAM_PIPE_X
@@ -638,32 +569,23 @@ int launch_pipe(const ConvGeo& g, size_t lds, const float* X, const float* Wp, c
                 const BnBwdEpi& bwd, hipStream_t st) {
     const int nunits = g.tiles_m * (g.N / 16 / NB) * g.B;
     // statistics records: one per (image tile, wave), each unit fills its own channels of it
-    int mode = 0, acc = 0;
+    int mode = 0;
     if (stats) {
         const int64_t parts = (int64_t)g.B * g.tiles_m * (4 / KS);
         mode = bwd.x ? 2 : 1;
-        // one channel-block group per unit row (every unit has all the layer's channels: the 1 x 4 tile of a 64-channel stage):
-        // the workgroups accumulate over their units and leave ONE record each (kernel: stats_acc).  BUILT, PARITY-GREEN, MEASURED
-        // SLOWER, OFF (DAM_PIPE_STATS_ACC=1 turns it on for the A/B): it removes the 257 x 33 stage's five separate statistics /
-        // backward-sums passes (3 x 8.6 + 2 x 11 us), but the 1 x 4 tile's instantiations WITH an epilogue run 61.9 us (forward
-        // statistics, 512 workgroups) and 73.8 us (backward sums: 256 workgroups, the register budget of two per CU is gone)
-        // against 52.6 us without -- C3 step 4.456 -> 4.483 ms on one box (gpurun_out/r4, profiles/r04_pipe_stats_acc_ab.txt)
-        static const bool acc_ok = [] { const char* e = getenv("DAM_PIPE_STATS_ACC"); return e && e[0] == '1'; }();
-        if (acc_ok && g.N == 16 * NB && g.N <= PIPE_THREADS - PIPE_LT) acc = 1;
-        else if (parts > (bwd.x ? BN_BWD_RECORDS_MAX : BN_RECORDS_MAX)) { stats = nullptr; mode = 0; }   // the caller runs the separate pass
+        // (one record per WORKGROUP, accumulated over its units, was measured slower: C3 step 4.456 -> 4.483 ms, the 1 x 4 tile's
+        // launches with an epilogue 61.9 / 73.8 us against 52.6 us without -- profiles/r04_pipe_stats_acc_ab.txt)
+        if (parts > (bwd.x ? BN_BWD_RECORDS_MAX : BN_RECORDS_MAX)) { stats = nullptr; mode = 0; }   // the caller runs the separate pass
         else if (stats_parts) *stats_parts = (int)parts;
     }
     if (bwd.x) res = mode == 2 ? bwd.x : nullptr;               // the sums epilogue reads x through the residual operand
-    if (acc) lds += (size_t)(4 / KS) * (g.N * 3 + 4) * sizeof(float);
     int wgs = mode == 2 ? pipe_slots<MB, NB, PU, 2, KS>(lds) : (mode == 1 ? pipe_slots<MB, NB, PU, 1, KS>(lds) : pipe_slots<MB, NB, PU, 0, KS>(lds));
     if (const char* e = getenv("DAM_PIPE_WGS")) wgs = atoi(e);          // diagnostic
     if (wgs < 1) wgs = 1;
     if (wgs > nunits) wgs = nunits;
-    if (acc && stats_parts) *stats_parts = wgs;
-    static const int xcd_aware = getenv("DAM_PIPE_NO_XCD") ? 0 : 1;      // A/B knob
 #define DAM_PIPE_LAUNCH(S_)                                                                                                 \
     hipLaunchKernelGGL((conv_pipe_kernel<MB, NB, PU, S_, KS>), dim3((unsigned)wgs), dim3(PIPE_THREADS), lds, st, g, nunits, X,  \
-                       reinterpret_cast<const float4*>(Wp), bias, sc, sh, Y, res, res_mask, workspace, stats, bwd, acc, xcd_aware)
+                       reinterpret_cast<const float4*>(Wp), bias, sc, sh, Y, res, res_mask, workspace, stats, bwd)
     if (mode == 2) DAM_PIPE_LAUNCH(2); else if (mode == 1) DAM_PIPE_LAUNCH(1); else DAM_PIPE_LAUNCH(0);
 #undef DAM_PIPE_LAUNCH
     DAM_CHECK_LAUNCH();

@@ -16,7 +16,6 @@
 // merged once at the end (Chan), then the four waves: one record per workgroup -- no pass over c1 / cs.
 #include "dam_common.h"
 #include "dam_bn_fin.h"
-#include <cstdlib>
 
 namespace dam {
 namespace {
@@ -30,7 +29,7 @@ template <int NB, int NCH, bool STATS, int WAVES>
 __global__ __launch_bounds__(64 * WAVES) void conv_s2_pair_kernel(const float* __restrict__ X, unsigned x_bytes, const float4* __restrict__ Wp,
                                                            const float4* __restrict__ Wp2, int Hd, int Wd, int H, int W,
                                                            float* __restrict__ Y, float* __restrict__ Ys, float* __restrict__ P1,
-                                                           float* __restrict__ P2, int total_px, int total_units, int xcd_aware) {
+                                                           float* __restrict__ P2, int total_px, int total_units) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];      // [9 + 1][NCH][NB][64 lanes] float4
     constexpr int Ci = 16 * NCH, Co = 16 * NB;
     static_assert(NCH == 1 || NCH == 2, "the operand sets alternate per chunk (NCH == 2) or per unit (NCH == 1)");
@@ -137,8 +136,8 @@ __global__ __launch_bounds__(64 * WAVES) void conv_s2_pair_kernel(const float* _
     // XCD-aware unit order: workgroup b runs on XCD b % 8 and every XCD has its own L2.  Each XCD takes one CONTIGUOUS eighth of
     // the units, so the rows that neighbouring units share (the taps reach one row up and down) are fetched into ONE L2 instead of
     // up to three; inside an XCD wave-major: the units left over after the last full round go to ONE wave each of different
-    // workgroups (SIMDs).  DAM_S2_NO_XCD=1 (read by the launcher: `xcd_aware`): the plain interleaved order (A/B).
-    const int n_xcd = (xcd_aware && (gridDim.x & 7) == 0) ? 8 : 1;
+    // workgroups (SIMDs).
+    const int n_xcd = (gridDim.x & 7) == 0 ? 8 : 1;
     const int wg_per_xcd = gridDim.x / n_xcd, per_xcd = (total_units + n_xcd - 1) / n_xcd;
     const int u_lo = (blockIdx.x % n_xcd) * per_xcd;
     const int unit_end = u_lo + per_xcd < total_units ? u_lo + per_xcd : total_units;
@@ -285,17 +284,14 @@ int launch_conv_s2_pair(const float* x, const float* wp, const float* wp2, int B
     if (max_per_cu < 1) max_per_cu = 1;
     while (max_per_cu > 1 && (int64_t)cus * max_per_cu > BN_RECORDS_MAX) --max_per_cu;
     if ((int64_t)cus > BN_RECORDS_MAX) return DAM_ERR_UNSUPPORTED;
-    static const int forced = [] { const char* e = getenv("DAM_CS2_PER_CU"); return e ? atoi(e) : 0; }();      // A/B knob
     int per_cu = 1;
     int64_t best = 0;
     for (int n = 1; n <= max_per_cu; ++n) {
         const int64_t cost = cdiv(units, (int64_t)WAVES * cus * n) * n * 100;
         if (n == 1 || cost * 100 <= best * 115) { best = n == 1 ? cost : (cost < best ? cost : best); per_cu = n; }
     }
-    if (forced >= 1 && forced <= max_per_cu) per_cu = forced;
     int64_t wgs = (int64_t)cus * per_cu;
     if (wgs > cdiv(units, WAVES)) wgs = cdiv(units, WAVES);
-    static const int xcd_aware = getenv("DAM_S2_NO_XCD") ? 0 : 1;      // A/B knob
     if (parts_host) *parts_host = stats ? (int)wgs : 0;
     static PerDevice<bool> raised_pd[2];
     bool& raised = raised_pd[stats ? 1 : 0]();
@@ -308,11 +304,11 @@ int launch_conv_s2_pair(const float* x, const float* wp, const float* wp2, int B
     if (stats)
         hipLaunchKernelGGL((conv_s2_pair_kernel<NB, NCH, true, WAVES>), dim3((unsigned)wgs), dim3(64 * WAVES), lds, st, x, (unsigned)xb,
                            reinterpret_cast<const float4*>(wp), reinterpret_cast<const float4*>(wp2), Hd, Wd, H, W, y, ys, p1, p2, (int)px,
-                           (int)units, xcd_aware);
+                           (int)units);
     else
         hipLaunchKernelGGL((conv_s2_pair_kernel<NB, NCH, false, WAVES>), dim3((unsigned)wgs), dim3(64 * WAVES), lds, st, x, (unsigned)xb,
                            reinterpret_cast<const float4*>(wp), reinterpret_cast<const float4*>(wp2), Hd, Wd, H, W, y, ys, p1, p2, (int)px,
-                           (int)units, xcd_aware);
+                           (int)units);
     DAM_CHECK_LAUNCH();
     return DAM_OK;
 }
@@ -325,8 +321,7 @@ int launch_conv_s2_pair(const float* x, const float* wp, const float* wp2, int B
 // block: the ten weight fragments of a chunk are fetched once per workgroup into LDS (two chunk buffers, one barrier per chunk), and
 // the waves' statistics merge through LDS into the workgroup's 16 channels of record blockIdx.x / NB: the NB workgroups of a pixel
 // group fill one record between them.
-// MB: pixel blocks of 16 per wave (1 is what ships; 2 = twice the MFMAs under every round of operand requests, measured slower)
-template <bool STATS, int MB>
+template <bool STATS>
 __global__ __launch_bounds__(256) void conv_s2_pair_stream_kernel(const float* __restrict__ X, unsigned x_bytes, const float4* __restrict__ Wp,
                                                                   const float4* __restrict__ Wp2, int Hd, int Wd, int H, int W, int NCH,
                                                                   int NB, float* __restrict__ Y, float* __restrict__ Ys,
@@ -334,6 +329,9 @@ __global__ __launch_bounds__(256) void conv_s2_pair_stream_kernel(const float* _
     __shared__ float rec[4][2][16][3];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int j = lane & 15, kq = lane >> 4;
+    // MB: pixel blocks of 16 per wave.  Two (twice the MFMAs under every round of operand requests) measured slower on the one layer
+    // with the units for it: 48.9 us against 41.8 on the 64 -> 96 block (230 VGPRs: two waves per SIMD instead of three)
+    constexpr int MB = 1;
     // XCD-aware order: workgroup b runs on XCD b % 8 (round-robin dispatch; every XCD has its own L2) and the NB workgroups of a
     // pixel group read the same x -- dealt b -> (group, block) in plain order they sat on NB different XCDs and FETCH_SIZE was 6.8 x
     // the bytes of x on the 64 -> 96 block.  Here the groups are dealt to the XCDs (group g on XCD g % 8) and an XCD's workgroups
@@ -502,21 +500,16 @@ int launch_conv_s2_pair_stream(const float* x, const float* wp, const float* wp2
                                float* p1, float* p2, int* parts_host, hipStream_t st) {
     const int Hd = (H + 1) / 2, Wd = (W + 1) / 2, NCH = Ci / 16, NB = Co / 16;
     const int64_t px = (int64_t)B * Hd * Wd, xb = (int64_t)B * H * W * Ci * 4;
-    // one pixel block per wave; two (DAM_CS2_STREAM_MB=2: A/B) measured slower on the one layer with the units for it: 48.9 us
-    // against 41.8 on the 64 -> 96 block (230 VGPRs: two waves per SIMD instead of three)
-    static const int mb_forced = [] { const char* e = getenv("DAM_CS2_STREAM_MB"); return e ? atoi(e) : 0; }();
-    const int mb = mb_forced == 2 ? 2 : 1;
-    const int64_t groups = cdiv(px, 64 * mb);
+    const int64_t groups = cdiv(px, 64);             // one pixel block of 16 per wave
     if (px >= (1ll << 26) || xb >= (1ll << 31) || groups * NB >= (1ll << 31) || (int64_t)9 * Ci * Co * 4 >= (1ll << 31)) return DAM_ERR_UNSUPPORTED;
     const bool stats = p1 != nullptr;
-    if (stats && groups > BN_RECORDS_MAX) return DAM_ERR_UNSUPPORTED;      // (one record per group of 64 * mb pixels)
+    if (stats && groups > BN_RECORDS_MAX) return DAM_ERR_UNSUPPORTED;      // (one record per group of 64 pixels)
     if (parts_host) *parts_host = stats ? (int)groups : 0;
     const dim3 grid((unsigned)(cdiv(groups, 8) * 8 * NB)), block(256);        // whole rounds of eight groups (one per XCD)
-#define DAM_CS2S_GO(ST_, MB_)                                                                                                   \
-    hipLaunchKernelGGL((conv_s2_pair_stream_kernel<ST_, MB_>), grid, block, 0, st, x, (unsigned)xb, reinterpret_cast<const float4*>(wp), \
+#define DAM_CS2S_GO(ST_)                                                                                                        \
+    hipLaunchKernelGGL((conv_s2_pair_stream_kernel<ST_>), grid, block, 0, st, x, (unsigned)xb, reinterpret_cast<const float4*>(wp), \
                        reinterpret_cast<const float4*>(wp2), Hd, Wd, H, W, NCH, NB, y, ys, p1, p2, (int)px)
-    if (stats) { if (mb == 2) DAM_CS2S_GO(true, 2); else DAM_CS2S_GO(true, 1); }
-    else { if (mb == 2) DAM_CS2S_GO(false, 2); else DAM_CS2S_GO(false, 1); }
+    if (stats) DAM_CS2S_GO(true); else DAM_CS2S_GO(false);
 #undef DAM_CS2S_GO
     DAM_CHECK_LAUNCH();
     return DAM_OK;
@@ -535,12 +528,9 @@ extern "C" int dam_conv_s2_pair_fwd_f32(const float* x, const float* w_packed, c
     if (partial && !parts_host) return DAM_ERR_BAD_ARG;
     hipStream_t st = (hipStream_t)stream;
     if (Ci == 16 && Co == 32) return launch_conv_s2_pair<2, 1, 4>(x, w_packed, wsc_packed, B, H, W, y, ysc, partial, partial_sc, parts_host, st);
-    static const int w4 = [] { const char* e = getenv("DAM_CS2_WAVES4"); return e ? atoi(e) : 0; }();          // A/B knob
-    if (Ci == 32 && Co == 64 && w4) return launch_conv_s2_pair<4, 2, 4>(x, w_packed, wsc_packed, B, H, W, y, ysc, partial, partial_sc, parts_host, st);
     if (Ci == 32 && Co == 64) return launch_conv_s2_pair<4, 2, 8>(x, w_packed, wsc_packed, B, H, W, y, ysc, partial, partial_sc, parts_host, st);
     // the wide blocks: weight fragments streamed from L2 (an even chunk count: the two register sets alternate)
-    static const int no_stream = getenv("DAM_CS2_NO_STREAM") ? 1 : 0;        // A/B knob
-    if (!no_stream && Ci % 32 == 0 && Co % 16 == 0)
+    if (Ci % 32 == 0 && Co % 16 == 0)
         return launch_conv_s2_pair_stream(x, w_packed, wsc_packed, B, H, W, Ci, Co, y, ysc, partial, partial_sc, parts_host, st);
     return DAM_ERR_UNSUPPORTED;
 }

@@ -142,16 +142,8 @@ __device__ __forceinline__ void rows_commit(unsigned char* smem, const float4 (&
 // pinned between the MFMAs with sched_group_barrier), so what the write-out does is compile time: with EPI == 0, SO = 1 raw
 // store, 2 raw + BatchNorm partial statistics, 3 + bias, max(., floor) [folded inference convolution], 4 as 3 + residual,
 // 5 + residual * (mask > 0); with EPI >= 1 the sums epilogues as above (SO = 1).
-// DAM_STRIP_2WG (experiment, profiles/r05_strip_two_per_cu.txt): the self-overlapped 16-channel forms compiled for FOUR waves per
-// SIMD (<= 128 registers; the second __launch_bounds__ argument is HIP's minimum waves per execution unit) so that two 8-wave
-// workgroups share a CU -- one's prologue, loader stalls and tail under the other's MFMA stream.
-#ifdef DAM_STRIP_2WG
-#define DAM_STRIP_WAVES_PER_EU(SO_, EPI_, NCH_) (((SO_) && (EPI_) <= DAM_STRIP_2WG && (NCH_) == 1) ? 4 : 1)
-#else
-#define DAM_STRIP_WAVES_PER_EU(SO_, EPI_, NCH_) 1
-#endif
 template <int MB, int NB, int NCH, bool T33, bool LW, int EPI, int SO>
-__global__ __launch_bounds__(SO ? 512 : STRIP_THREADS, DAM_STRIP_WAVES_PER_EU(SO, EPI, NCH)) void conv_strip_kernel(const ConvGeo g, const StripGeo sg, const float* __restrict__ X,
+__global__ __launch_bounds__(SO ? 512 : STRIP_THREADS, 1) void conv_strip_kernel(const ConvGeo g, const StripGeo sg, const float* __restrict__ X,
                                                          const float4* __restrict__ Wp, const float* __restrict__ bias,
                                                          float* __restrict__ Y, const float* __restrict__ res,
                                                          const float* __restrict__ res_mask, float* __restrict__ stats,
@@ -224,11 +216,7 @@ __global__ __launch_bounds__(SO ? 512 : STRIP_THREADS, DAM_STRIP_WAVES_PER_EU(SO
     // carried all the pieces -- and all the VALU of a fused input affine (72 instructions per slot on the SIMDs of two compute
     // waves, the other two idle: +8 us per launch).  A loader's unit is then HALF a plane: the even or the odd 1 KB pieces
     // (wave parity), every wave the same 4-5 pieces.
-#ifdef DAM_STRIP_NO_HS          // timing A/B (tools/build_variant.sh)
-    constexpr int HS = 1;
-#else
     constexpr int HS = (NCH == 1 && !LW && SO != 0) ? 2 : 1;
-#endif
     constexpr int KP = (NCH == 1 ? 1 : (LW ? 2 : 3)) * HS;    // units (planes / half planes) per loader wave per tile
     constexpr int GPPF = NCH == 1 ? (LW ? 14 : 9) : (LW ? 7 : 5);  // 1 KB pieces per plane (host: groups_per_plane <= GPPF)
     constexpr int GPP = (GPPF + HS - 1) / HS;                 // ... per unit
@@ -258,42 +246,10 @@ __global__ __launch_bounds__(SO ? 512 : STRIP_THREADS, DAM_STRIP_WAVES_PER_EU(SO
     int ccA[KP], ccB[KP];                            // outside the tensor (zeros are written), -1 = nothing to write; chunk
 #pragma unroll
     for (int k = 0; k < KP; ++k) { dstA[k] = -1; dstB[k] = -1; ccA[k] = 0; ccB[k] = 0; }
-    // TIMING EXPERIMENT ONLY (-DDAM_DIAG_DXHAT=1|2, tools/dxhat_ladder.py; results are wrong): what it would cost this kernel to form
-    // its INPUT operand dc = a * (dy . mask) + b * c + k (BatchNorm backward: the bn_bwd_apply launch folded into the loaders)
-    // itself -- every plane is accompanied by a second plane from another tensor (read through the `bias` pointer: real HBM
-    // traffic); 1 = the loads and one fma per quad, 2 = the full arithmetic with the mask recomputed from the second stream.
-#ifdef DAM_DIAG_DXHAT
-    const __amdgpu_buffer_rsrc_t crsrc = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<float*>(bias) + (size_t)img * g.H * g.W * g.C, 0, g.H * g.W * g.C * 4, 0x00020000);
-    v4f lvcA[KP][GPP], lvcB[KP][GPP];
-#define DAM_SDX_ON 1
-#define DAM_SDX_REQ(LVC_, K_, SOFF_)                                                                                       \
-    _Pragma("unroll") for (int gi = 0; gi < GPP; ++gi)                                                                     \
-        LVC_[K_][gi] = __builtin_bit_cast(v4f, __builtin_amdgcn_raw_buffer_load_b128(crsrc, loffb[gi], SOFF_, 0))
-#if DAM_DIAG_DXHAT == 1
-#define DAM_SDX_COMBINE(LV_, LVC_, K_, GI_) __builtin_elementwise_fma(LVC_[K_][GI_], shq[0], LV_[K_][GI_])
-#else
-#define DAM_SDX_COMBINE(LV_, LVC_, K_, GI_)                                                                                \
-    ([&]() {                                                                                                               \
-        const v4f c_ = LVC_[K_][GI_], dy_ = LV_[K_][GI_];                                                                  \
-        const v4f m_ = __builtin_elementwise_fma(c_, scq[0], shq[0]);                                                      \
-        v4f dz_;                                                                                                           \
-        dz_.x = m_.x > 0.f ? dy_.x : 0.f; dz_.y = m_.y > 0.f ? dy_.y : 0.f;                                                \
-        dz_.z = m_.z > 0.f ? dy_.z : 0.f; dz_.w = m_.w > 0.f ? dy_.w : 0.f;                                                \
-        return __builtin_elementwise_fma(dz_, scq[0], __builtin_elementwise_fma(c_, shq[0], relu_lo4));                    \
-    }())
-#endif
-#else
-#define DAM_SDX_ON 0
-#define DAM_SDX_REQ(LVC_, K_, SOFF_) do { } while (0)
-#define DAM_SDX_COMBINE(LV_, LVC_, K_, GI_) (LV_[K_][GI_])
-#define lvcA lvA
-#define lvcB lvB
-#endif
     const int chs = NCH == 1 ? 0 : 1;
     int loaded_hi;
     { int lo; tile_rows(t_begin, lo, loaded_hi); }
-#define DAM_STRIP_REQUEST(K_, LV_, DST_, CC_, LVC_)                                                                          \
+#define DAM_STRIP_REQUEST(K_, LV_, DST_, CC_)                                                                                \
     do {                                                                                                                   \
         int first_ = 0, planes_ = 0;                                                                                       \
         if ((K_) < n_tiles) {                                                                                              \
@@ -310,7 +266,6 @@ __global__ __launch_bounds__(SO ? 512 : STRIP_THREADS, DAM_STRIP_WAVES_PER_EU(SO
             const int soff_ = ((rowok_ ? ih_ : 0) * g.W * g.C + (used_ ? cc_ : 0) * 16) * 4;                               \
             _Pragma("unroll") for (int gi = 0; gi < GPP; ++gi)                                                             \
                 LV_[k][gi] = __builtin_bit_cast(v4f, __builtin_amdgcn_raw_buffer_load_b128(xrsrc, loffb[gi], soff_, 0));   \
-            DAM_SDX_REQ(LVC_, k, soff_);                                                                                   \
             DST_[k] = used_ ? ((cc_ * CHB + ((ih_ + sg.ring_off) & (sg.NR - 1)) * RB) | (rowok_ ? 0 : 1 << 30)) : -1;     \
             CC_[k] = cc_;                                                                                                  \
         }                                                                                                                  \
@@ -318,8 +273,8 @@ __global__ __launch_bounds__(SO ? 512 : STRIP_THREADS, DAM_STRIP_WAVES_PER_EU(SO
 #define DAM_STRIP_WRITE(ADDR_, DATA_, GI_)                                                                                 \
     asm volatile("s_mov_b64 exec, %2\n\tds_write_b128 %0, %1 offset:%3\n\ts_mov_b64 exec, -1"                              \
                  : : "v"(ADDR_), "v"(DATA_), "s"(cmask[GI_]), "n"((GI_) * 1024 * HS) : "memory")
-#define DAM_STRIP_COMMIT(LV_, DST_, CC_, LVC_) DAM_STRIP_COMMIT_N(KP, LV_, DST_, CC_, LVC_)
-#define DAM_STRIP_COMMIT_N(KPX_, LV_, DST_, CC_, LVC_)                                                                        \
+#define DAM_STRIP_COMMIT(LV_, DST_, CC_) DAM_STRIP_COMMIT_N(KP, LV_, DST_, CC_)
+#define DAM_STRIP_COMMIT_N(KPX_, LV_, DST_, CC_)                                                                              \
     do {                                                                                                                   \
         _Pragma("unroll") for (int k = 0; k < (KPX_); ++k) {                                                                   \
             if (DST_[k] >= 0) {                                                                                            \
@@ -333,11 +288,6 @@ __global__ __launch_bounds__(SO ? 512 : STRIP_THREADS, DAM_STRIP_WAVES_PER_EU(SO
                             v_ = __builtin_elementwise_max(v_, relu_lo4);   /* max(., -inf) when there is no ReLU: no selects */ \
                             DAM_STRIP_WRITE(va_, v_, gi);                                                                  \
                         }                                                                                                  \
-                    } else if (DAM_SDX_ON) {                                                                               \
-                        _Pragma("unroll") for (int gi = 0; gi < GPP; ++gi) {                                               \
-                            const v4f v_ = DAM_SDX_COMBINE(LV_, LVC_, k, gi);                                              \
-                            DAM_STRIP_WRITE(va_, v_, gi);                                                                  \
-                        }                                                                                                  \
                     } else {                                                                                               \
                         _Pragma("unroll") for (int gi = 0; gi < GPP; ++gi) DAM_STRIP_WRITE(va_, LV_[k][gi], gi);           \
                     }                                                                                                      \
@@ -347,13 +297,9 @@ __global__ __launch_bounds__(SO ? 512 : STRIP_THREADS, DAM_STRIP_WAVES_PER_EU(SO
             }                                                                                                              \
         }                                                                                                                  \
     } while (0)
-#ifdef DAM_DIAG_NO_LOAD        // timing experiments only (results are wrong)
-#undef DAM_STRIP_REQUEST
-#define DAM_STRIP_REQUEST(K_, LV_, DST_, CC_, LVC_) do { } while (0)
-#endif
     // SO prologue: the rows of the workgroup's FIRST tile as whole planes too, spread over all NT / 64 waves (plane = wave + k * NT/64)
     constexpr int KP0 = (NCH == 1 ? 1 : 2) * HS;
-#define DAM_STRIP_REQUEST0(LV_, DST_, CC_, LVC_)                                                                             \
+#define DAM_STRIP_REQUEST0(LV_, DST_, CC_)                                                                                   \
     do {                                                                                                                   \
         const int planes_ = (hi0 - lo0 + 1) << chs;                                                                        \
         _Pragma("unroll") for (int k = 0; k < KP0; ++k) {                                                                  \
@@ -364,7 +310,6 @@ __global__ __launch_bounds__(SO ? 512 : STRIP_THREADS, DAM_STRIP_WAVES_PER_EU(SO
             const int soff_ = ((rowok_ ? ih_ : 0) * g.W * g.C + (used_ ? cc_ : 0) * 16) * 4;                               \
             _Pragma("unroll") for (int gi = 0; gi < GPP; ++gi)                                                             \
                 LV_[k][gi] = __builtin_bit_cast(v4f, __builtin_amdgcn_raw_buffer_load_b128(xrsrc, loffb[gi], soff_, 0));   \
-            DAM_SDX_REQ(LVC_, k, soff_);                                                                                   \
             DST_[k] = used_ ? ((cc_ * CHB + ((ih_ + sg.ring_off) & (sg.NR - 1)) * RB) | (rowok_ ? 0 : 1 << 30)) : -1;     \
             CC_[k] = cc_;                                                                                                  \
         }                                                                                                                  \
@@ -394,23 +339,18 @@ __global__ __launch_bounds__(SO ? 512 : STRIP_THREADS, DAM_STRIP_WAVES_PER_EU(SO
     }
     DAM_STAMP(9);
     v4f lv0[SO ? KP0 : 1][SO ? GPP : 1];
-#ifdef DAM_DIAG_DXHAT
-    v4f lvc0[SO ? KP0 : 1][SO ? GPP : 1];
-#else
-#define lvc0 lv0
-#endif
     int dst0[KP0], cc0[KP0];
     if constexpr (SO != 0) {
         // rows of the first tile: whole planes over all waves (the per-piece path of the ping-pong form costs 3.4-5 k cycles
         // of address arithmetic per wave); the loader waves' requests for tiles 1 and 2 follow at once, so that tile 1's rows
         // are there long before slot 0 ends (requested after the prologue, the first barrier waited 1.3-3.4 k cycles for them)
-        DAM_STRIP_REQUEST0(lv0, dst0, cc0, lvc0);
+        DAM_STRIP_REQUEST0(lv0, dst0, cc0);
         if (grp == LGRP) {
 #ifdef DAM_STRIP_ONE_SET       // experiment: ONE register set, the rows of tile s+2 are requested in slot s (one slot ahead, not two)
-            DAM_STRIP_REQUEST(1, lvA, dstA, ccA, lvcA);
+            DAM_STRIP_REQUEST(1, lvA, dstA, ccA);
 #else
-            DAM_STRIP_REQUEST(1, lvB, dstB, ccB, lvcB);
-            DAM_STRIP_REQUEST(2, lvA, dstA, ccA, lvcA);
+            DAM_STRIP_REQUEST(1, lvB, dstB, ccB);
+            DAM_STRIP_REQUEST(2, lvA, dstA, ccA);
 #endif
         }
     } else {
@@ -430,7 +370,7 @@ __global__ __launch_bounds__(SO ? 512 : STRIP_THREADS, DAM_STRIP_WAVES_PER_EU(SO
     __syncthreads();
     DAM_STAMP(2);
     if constexpr (SO != 0) {
-        DAM_STRIP_COMMIT_N(KP0, lv0, dst0, cc0, lvc0);
+        DAM_STRIP_COMMIT_N(KP0, lv0, dst0, cc0);
     } else {
         rows_commit<NCH>(smem, lv, ldst, laff, has_aff, scq, shq, relu_in);
         for (int base = (NT / 64) * STRIP_PU; base < total0; base += (NT / 64) * STRIP_PU) {
@@ -507,21 +447,21 @@ __global__ __launch_bounds__(SO ? 512 : STRIP_THREADS, DAM_STRIP_WAVES_PER_EU(SO
         // a piece costs no VALU instruction at all: buffer_load with scalar base + per-lane offset, ds_write with the
         // piece's column mask in EXEC and an immediate offset.
         if constexpr (SO == 0) {
-            DAM_STRIP_REQUEST(1, lvB, dstB, ccB, lvcB);
-            DAM_STRIP_REQUEST(2, lvA, dstA, ccA, lvcA);
+            DAM_STRIP_REQUEST(1, lvB, dstB, ccB);
+            DAM_STRIP_REQUEST(2, lvA, dstA, ccA);
         }
         // slots come in pairs (n_slots is even) so that no load sits inside a conditional: the compiler then knows that the
         // set being written is the older of the two in flight and waits with vmcnt(pieces of the other set), not vmcnt(0)
 #ifdef DAM_STRIP_ONE_SET
         if constexpr (SO != 0) {
         for (int s = 0; s < n_slots; s += 2) {
-            DAM_STRIP_COMMIT(lvA, dstA, ccA, lvcA);       // tile s+1
-            DAM_STRIP_REQUEST(s + 2, lvA, dstA, ccA, lvcA);
+            DAM_STRIP_COMMIT(lvA, dstA, ccA);       // tile s+1
+            DAM_STRIP_REQUEST(s + 2, lvA, dstA, ccA);
             SO_TABLE(s + 2);
             DAM_STAMP(4);
             asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-            DAM_STRIP_COMMIT(lvA, dstA, ccA, lvcA);       // tile s+2
-            DAM_STRIP_REQUEST(s + 3, lvA, dstA, ccA, lvcA);
+            DAM_STRIP_COMMIT(lvA, dstA, ccA);       // tile s+2
+            DAM_STRIP_REQUEST(s + 3, lvA, dstA, ccA);
             SO_TABLE(s + 3);
             DAM_STAMP(4);
             asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
@@ -530,13 +470,13 @@ __global__ __launch_bounds__(SO ? 512 : STRIP_THREADS, DAM_STRIP_WAVES_PER_EU(SO
 #endif
         {
         for (int s = 0; s < n_slots; s += 2) {
-            DAM_STRIP_COMMIT(lvB, dstB, ccB, lvcB);       // tile s+1
-            DAM_STRIP_REQUEST(s + 3, lvB, dstB, ccB, lvcB);
+            DAM_STRIP_COMMIT(lvB, dstB, ccB);       // tile s+1
+            DAM_STRIP_REQUEST(s + 3, lvB, dstB, ccB);
             if constexpr (SO != 0) SO_TABLE(s + 2);  // read by the compute waves in slot s+1
             DAM_STAMP(4);
             asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-            DAM_STRIP_COMMIT(lvA, dstA, ccA, lvcA);       // tile s+2
-            DAM_STRIP_REQUEST(s + 4, lvA, dstA, ccA, lvcA);
+            DAM_STRIP_COMMIT(lvA, dstA, ccA);       // tile s+2
+            DAM_STRIP_REQUEST(s + 4, lvA, dstA, ccA);
             if constexpr (SO != 0) SO_TABLE(s + 3);
             DAM_STAMP(4);
             asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
@@ -547,14 +487,6 @@ __global__ __launch_bounds__(SO ? 512 : STRIP_THREADS, DAM_STRIP_WAVES_PER_EU(SO
 #undef DAM_STRIP_WRITE
 #undef DAM_STRIP_COMMIT
 #undef DAM_STRIP_COMMIT_N
-#undef DAM_SDX_ON
-#undef DAM_SDX_REQ
-#undef DAM_SDX_COMBINE
-#ifndef DAM_DIAG_DXHAT
-#undef lvcA
-#undef lvcB
-#undef lvc0
-#endif
     }
 
     // BatchNorm partial statistics of this wave's outputs: shifted sums per lane (channels 4*kq..+3 of block nb), kept as
@@ -652,11 +584,7 @@ __global__ __launch_bounds__(SO ? 512 : STRIP_THREADS, DAM_STRIP_WAVES_PER_EU(SO
         if (false) {
         } else if (grp == (s & 1)) {
             // ---------------- MFMA slot of this group: tile s ----------------
-#ifdef DAM_DIAG_NO_MFMA
-            if (false) {
-#else
             if (s < n_tiles) {
-#endif
                 int ohm[MB], owm[MB];                                 // scalars (generic path: decoded in the slot)
                 if constexpr (!T33) {
                     const int p0w = (t_begin + s) * TM + cw * MW;     // scalar: first pixel of this wave
@@ -696,15 +624,12 @@ __global__ __launch_bounds__(SO ? 512 : STRIP_THREADS, DAM_STRIP_WAVES_PER_EU(SO
                     acc[mb][nb] = __builtin_amdgcn_mfma_f32_16x16x4f32(reinterpret_cast<const float*>(&wa[BUF_][nb])[r],  \
                                                                        reinterpret_cast<const float*>(&xv[BUF_][mb])[r], acc[mb][nb], 0, 0, 0); \
     } while (0)
-#ifndef DAM_STRIP_YIELD
-#define DAM_STRIP_YIELD asm volatile("s_nop 15\n\ts_nop 15")
-#endif
 #define DAM_STRIP_ITEM(I_)                                                                                                \
     do {                                                                                                                  \
         if constexpr ((I_) + 1 < NI) DAM_STRIP_LOAD(((I_) + 1 < NI ? (I_) + 1 : 0), ((I_) + 1) & 1);                      \
         __builtin_amdgcn_sched_barrier(0);                                                                                \
         DAM_STRIP_MFMA((I_) & 1);                                                                                         \
-        DAM_STRIP_YIELD;                                                                                                  \
+        asm volatile("s_nop 15\n\ts_nop 15");                                                                         \
         __builtin_amdgcn_sched_barrier(0);                                                                                \
     } while (0)
                     DAM_STRIP_LOAD(0, 0);
@@ -795,11 +720,7 @@ __global__ __launch_bounds__(SO ? 512 : STRIP_THREADS, DAM_STRIP_WAVES_PER_EU(SO
 #pragma unroll
             for (int mb = 0; mb < MB; ++mb) {
                 const int pm = p0w + mb * 16;                    // scalar
-#ifdef DAM_DIAG_NO_WRITEOUT
-                const int nvalid = g.B == 12345 ? HoWo - pm : 0;     // runtime-false: keeps the MFMAs alive
-#else
                 const int nvalid = HoWo - pm;                    // lanes j < nvalid hold pixels of this image
-#endif
                 if (nvalid <= 0) continue;
                 const int oh_m = (int)__umulhi((unsigned)pm, sg.wo_magic), ow_m = pm - oh_m * g.Wo;
                 const int voff = __builtin_amdgcn_readfirstlane(oh_m * oA + ow_m * oB) + (lane_o + wflag[mb] * oD);
@@ -836,9 +757,6 @@ __global__ __launch_bounds__(SO ? 512 : STRIP_THREADS, DAM_STRIP_WAVES_PER_EU(SO
                             }
                         }
                         if (relu_out) v = __builtin_elementwise_max(v, (v4f){0.f, 0.f, 0.f, 0.f});
-#ifdef DAM_DIAG_NO_STORE     // timing experiments only: the write-out's VALU work without its stores
-                        if (g.B == 12345)
-#endif
                         __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(v4i, v), yrsrc, voff + nb * 64, 0, 0);
                         if constexpr (EPI >= 2) {       // v is the gradient reaching relu(bn(x) [+ ..]) of the block input: its two sums
                             const v4f xq = x_pf[mb][nb];
@@ -857,7 +775,7 @@ __global__ __launch_bounds__(SO ? 512 : STRIP_THREADS, DAM_STRIP_WAVES_PER_EU(SO
                             st_s2[nb][0] = __builtin_elementwise_fma(dz.xy, xh.xy, st_s2[nb][0]);
                             st_s2[nb][1] = __builtin_elementwise_fma(dz.zw, xh.zw, st_s2[nb][1]);
                         }
-#if !defined(DAM_STAMPS) && !defined(DAM_DIAG_NO_STATS)
+#ifndef DAM_STAMPS
                         if (stats && !epi_bwd) {
                             if (!st_have) { st_nk[nb][0] = -v.xy; st_nk[nb][1] = -v.zw; }
                             const v2f d0 = v.xy + st_nk[nb][0], d1 = v.zw + st_nk[nb][1];
@@ -872,11 +790,9 @@ __global__ __launch_bounds__(SO ? 512 : STRIP_THREADS, DAM_STRIP_WAVES_PER_EU(SO
                 st_have = true;
             }
             }
-#ifndef DAM_DIAG_NO_GEOM
             if constexpr (T33) {
                 if (s + 1 < n_tiles) DAM_STRIP_GEOM(s + 1);        // this group's next MFMA slot
             }
-#endif
             DAM_STAMP(6);
         }
         // slot boundary: the loaders' rows are in LDS (their ds_writes waited on the loads), the MFMA group's LDS reads
@@ -892,26 +808,6 @@ __global__ __launch_bounds__(SO ? 512 : STRIP_THREADS, DAM_STRIP_WAVES_PER_EU(SO
             constexpr bool ST = EPI == 0 && SO == 2, BIAS = EPI == 0 && (SO == 3 || SO == 4), RADD = EPI == 0 && SO == 4,
                            RMSK = EPI == 0 && SO == 5, NEED_R = EPI != 0 || RADD || RMSK;
             constexpr int NI = 9 * NCH;
-#ifdef DAM_DIAG_SO_FROZEN          // timing experiments only: the fillers see tile 1 in every slot -- their scalar pixel decode
-            constexpr bool SO_FROZEN = true;      // becomes loop invariant (results are wrong)
-#else
-            constexpr bool SO_FROZEN = false;
-#endif
-#ifdef DAM_DIAG_SO_NO_STATS_UNIT   // timing experiments only: no statistics arithmetic in the write-out units
-            constexpr bool SO_NOSTU = true;
-#else
-            constexpr bool SO_NOSTU = false;
-#endif
-#ifdef DAM_SO_LATE_PREFETCH        // A/B build: the write-out operands of a tile requested in one filler at the end of its slot
-            constexpr bool SO_LATE_PF = true;
-#else
-            constexpr bool SO_LATE_PF = false;
-#endif
-#ifdef DAM_DIAG_SO_NOFILL          // timing experiments only: the bare MFMA + operand-read stream (results are wrong)
-            constexpr bool SO_NOFILL = true;
-#else
-            constexpr bool SO_NOFILL = false;
-#endif
             static_assert(NI >= 2 * MB + 1, "one filler per item: MB write-out units, MB geometry units, the operand prefetch");
             v4f accX[2][MB][NB];            // [parity of the tile]: produced in one slot, written out inside the next
             int voffX[2][MB];               // lane part of the output byte offset of pixel block mb (row wrap folded in)
@@ -967,9 +863,6 @@ __global__ __launch_bounds__(SO ? 512 : STRIP_THREADS, DAM_STRIP_WAVES_PER_EU(SO
         _Pragma("unroll") for (int mb = 0; mb < MB; ++mb)                                                                 \
             xv[BUF_][mb] = *reinterpret_cast<const float4*>(smem + (cc_ ? baseX[P_][a_][mb] + CHB : baseX[P_][a_][mb]) + b_ * 64); \
     } while (0)
-#ifdef DAM_DIAG_NO_MFMA        // timing experiments only (results are wrong)
-#define SO_MFMA(P_, I_, BUF_) do { if ((I_) == 0) { _Pragma("unroll") for (int mb = 0; mb < MB; ++mb) _Pragma("unroll") for (int nb = 0; nb < NB; ++nb) accX[P_][mb][nb] = __builtin_bit_cast(v4f, wa[BUF_][nb]) + __builtin_bit_cast(v4f, xv[BUF_][mb]); } } while (0)
-#else
 #define SO_MFMA(P_, I_, BUF_)                                                                                             \
     do {                                                                                                                  \
         _Pragma("unroll") for (int r = 0; r < 4; ++r)                                                                     \
@@ -979,13 +872,12 @@ __global__ __launch_bounds__(SO ? 512 : STRIP_THREADS, DAM_STRIP_WAVES_PER_EU(SO
                         reinterpret_cast<const float*>(&wa[BUF_][nb])[r], reinterpret_cast<const float*>(&xv[BUF_][mb])[r], \
                         ((I_) == 0 && r == 0) ? (v4f){0.f, 0.f, 0.f, 0.f} : accX[P_][mb][nb], 0, 0, 0);                   \
     } while (0)
-#endif
             // operands of the write-out of tile T_ (residual / mask / the BatchNorm's x), requested a slot ahead -- PER PIXEL BLOCK, in the
             // filler that has just written that block of the previous tile out (its operand registers are free from there on).
             // Round 3 requested all of a tile's blocks in ONE filler at item 2 * MB, the slot's last, and consumed them from item 0
             // of the next slot on: ~1 k cycles of lead for loads that take 4-5 k under this load.  PMC (profiles/r04_pmc_strip_epi.txt):
             // SQ_WAIT_ANY 12.4 M wave-cycles per forward launch, 26.4 M with the sums epilogue, 36.3 M with residual + upstream sums --
-            // the compute waves stood in front of their write-out units.  DAM_SO_LATE_PREFETCH keeps the old placement (A/B build).
+            // the compute waves stood in front of their write-out units.
 #define SO_PREFETCH1(P_, MBI_)                                                                                            \
     do {                                                                                                                  \
         if constexpr (NEED_R) {                                                                                           \
@@ -1002,10 +894,6 @@ __global__ __launch_bounds__(SO ? 512 : STRIP_THREADS, DAM_STRIP_WAVES_PER_EU(SO
                     ubpf[MBI_][nb] = (int)__builtin_amdgcn_raw_buffer_load_b8(ubrsrc, (vo_ >> 4) + nb * 4, 0, 0);         \
             }                                                                                                             \
         }                                                                                                                 \
-    } while (0)
-#define SO_PREFETCH(P_)                                                                                                   \
-    do {                                                                                                                  \
-        _Pragma("unroll") for (int mb = 0; mb < MB; ++mb) SO_PREFETCH1(P_, mb);                                           \
     } while (0)
             // write-out of pixel block MBI_ of tile T_ (parity Q_).  PRED_: per-lane validity (the image's last tile only)
 #define SO_UNIT(Q_, T_, MBI_, PRED_)                                                                                      \
@@ -1051,7 +939,7 @@ __global__ __launch_bounds__(SO ? 512 : STRIP_THREADS, DAM_STRIP_WAVES_PER_EU(SO
                     st_s2[nb][0] = __builtin_elementwise_fma(dz.xy, xh.xy, st_s2[nb][0]);                                 \
                     st_s2[nb][1] = __builtin_elementwise_fma(dz.zw, xh.zw, st_s2[nb][1]);                                 \
                 }                                                                                                         \
-                if constexpr (ST && !SO_NOSTU) {                                                                          \
+                if constexpr (ST) {                                                                                       \
                     const v2f d0 = v.xy + st_nk[nb][0], d1 = v.zw + st_nk[nb][1];                                         \
                     st_s1[nb][0] += d0; st_s1[nb][1] += d1;                                                               \
                     st_s2[nb][0] = __builtin_elementwise_fma(d0, d0, st_s2[nb][0]);                                       \
@@ -1067,37 +955,25 @@ __global__ __launch_bounds__(SO ? 512 : STRIP_THREADS, DAM_STRIP_WAVES_PER_EU(SO
     do {                                                                                                                  \
         /* the tile index through an opaque volatile copy: the scalar pixel decode below must stay in THIS item's region */  \
         /* (free-floating, the instruction selector lines all of a slot's decodes up in front of the slot's first MFMA) */ \
-        int sa_ = SO_FROZEN ? 1 : (S_);                                                                                   \
-        if constexpr (!SO_FROZEN) asm volatile("" : "+s"(sa_));                                                           \
-        if constexpr (SO_NOFILL) { }                                                                                      \
-        else if constexpr ((I_) < MB) {                                                                                   \
+        int sa_ = (S_);                                                                                                   \
+        asm volatile("" : "+s"(sa_));                                                                                     \
+        if constexpr ((I_) < MB) {                                                                                        \
             if constexpr (WO_) SO_UNIT(1 - (P_), sa_ - 1, ((I_) < MB ? (I_) : 0), 0);                                     \
             SO_TABREAD(sa_ + 1, ((I_) < MB ? (I_) : 0));                                                                  \
-            if constexpr (!SO_LATE_PF) SO_PREFETCH1(P_, ((I_) < MB ? (I_) : 0));                                          \
+            SO_PREFETCH1(P_, ((I_) < MB ? (I_) : 0));                                                                     \
         } else if constexpr ((I_) < 2 * MB) SO_GEOM(1 - (P_), ((I_) < 2 * MB && (I_) >= MB ? (I_) - MB : 0));             \
-        else if constexpr ((I_) == 2 * MB && SO_LATE_PF) SO_PREFETCH(P_);                                                 \
     } while (0)
             // one MFMA gap = 32 cycles of which the MFMA holds the issue port for 8: room for ~5 four-cycle instructions
-#ifndef DAM_SO_PAT_VALU
-#define DAM_SO_PAT_VALU 3
-#endif
-#ifndef DAM_SO_PAT_SALU
-#define DAM_SO_PAT_SALU 2
-#endif
-#ifdef DAM_SO_NOPATTERN
-#define SO_PATTERN() do { } while (0)
-#else
 #define SO_PATTERN()                                                                                                      \
     do {                                                                                                                  \
         _Pragma("unroll") for (int q_ = 0; q_ < 4 * MB * NB; ++q_) {                                                      \
             __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);                                                            \
             __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);                                                            \
-            __builtin_amdgcn_sched_group_barrier(0x002, DAM_SO_PAT_VALU, 0);                                              \
-            __builtin_amdgcn_sched_group_barrier(0x004, DAM_SO_PAT_SALU, 0);                                              \
+            __builtin_amdgcn_sched_group_barrier(0x002, 3, 0);                                                            \
+            __builtin_amdgcn_sched_group_barrier(0x004, 2, 0);                                                            \
             __builtin_amdgcn_sched_group_barrier(0x030, 1, 0);                                                            \
         }                                                                                                                 \
     } while (0)
-#endif
 #define SO_ITEM(P_, S_, I_, WO_)                                                                                          \
     do {                                                                                                                  \
         if constexpr ((I_) + 1 < NI) SO_LOAD(P_, ((I_) + 1 < NI ? (I_) + 1 : 0), ((I_) + 1) & 1);                         \
@@ -1168,7 +1044,6 @@ __global__ __launch_bounds__(SO ? 512 : STRIP_THREADS, DAM_STRIP_WAVES_PER_EU(SO
 #undef SO_TAG_CHECK
 #undef SO_LOAD
 #undef SO_MFMA
-#undef SO_PREFETCH
 #undef SO_PREFETCH1
 #undef SO_UNIT
 #undef SO_FILL
@@ -1215,11 +1090,7 @@ __global__ __launch_bounds__(SO ? 512 : STRIP_THREADS, DAM_STRIP_WAVES_PER_EU(SO
         }
         return;
     }
-#ifdef DAM_DIAG_SO_NO_STATS_EPI    // timing experiments only: no merge of the statistics at the end
-    if (stats && g.B == 12345) {
-#else
     if (stats) {
-#endif
         // (n, mean, M2) per lane -> Chan merge over the 16 pixel lanes, then over the 4 compute waves through LDS
         float* sm = reinterpret_cast<float*>(smem);        // ring no longer needed: [8 compute waves][NB*16 ch][3]
 #pragma unroll
@@ -1355,12 +1226,6 @@ int conv_strip_try(ConvGeo& g_in, int h_lo, int h_hi, const float* X, const floa
     // the chip: 512 and 384 us per launch where 236 workgroups of 66 tiles / 472 of 66 need 290 / 270.
     int tpw = sg.tiles_m;
     int64_t slots = 256;
-#ifdef DAM_STRIP_2WG
-    // two co-resident workgroups per CU for the instantiations compiled that way (16 channels, self-overlapped, LDS <= 80 KB)
-    if (g.nchunks == 1 && MB == 4 && NB == 1 && g.nA == 3 && g.nB == 3 && g.s == 1 && g.step_w == 1 && !wide && !getenv("DAM_STRIP_PINGPONG") &&
-        (lds + 2048) * 2 <= 160 * 1024 && (bwd.x ? (res ? (bwd.mask_bits ? 3 : 2) : 1) : 0) <= DAM_STRIP_2WG)
-        slots = 512;
-#endif
     {
         const int64_t per_image = cdiv(nblk, NB);
         int64_t best = INT64_MAX;
@@ -1385,10 +1250,9 @@ int conv_strip_try(ConvGeo& g_in, int h_lo, int h_hi, const float* X, const floa
     const bool t33 = g.nA == 3 && g.nB == 3 && g.s == 1 && g.step_w == 1;
 #define DAM_STRIP_ARGS g, sg, lds, X, Wp, bias, Y, (bwd.x && !res ? bwd.x : res), (bwd.x && res ? reinterpret_cast<const float*>(bwd.res_bits) : res_mask), stats, in_scale, in_shift, fin, bwd, st
     // Self-overlapped form (template comment of the kernel) for the 3x3 / stride-1 shapes of the 16- and 32-channel stages at
-    // ordinary row widths; DAM_STRIP_PINGPONG=1 keeps the ping-pong form (A/B switch).  The write-out variant is compile time.
-    static const bool pingpong = getenv("DAM_STRIP_PINGPONG") != nullptr;
+    // ordinary row widths; the ping-pong form takes every other shape.  The write-out variant is compile time.
     const int rows_out_so = std::min(g.Ho, (64 * MB + g.Wo - 2) / g.Wo + 1), rows_tile_so = (rows_out_so - 1) * g.s + sg.RH;
-    if (t33 && !wide && !pingpong && !fin.counter && rows_tile_so * g.nchunks <= 8 * (g.nchunks == 1 ? 1 : 2) &&
+    if (t33 && !wide && !fin.counter && rows_tile_so * g.nchunks <= 8 * (g.nchunks == 1 ? 1 : 2) &&
         ((g.nchunks == 1 && MB == 4 && NB == 1) || (g.nchunks == 2 && MB == 2 && NB == 2))) {
         const bool c16 = g.nchunks == 1;
         lds += 2048;                        // geometry tables: 4 compute waves x 4 buffers x 8 ints x <= 4 pixel blocks

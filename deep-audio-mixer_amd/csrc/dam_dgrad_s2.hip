@@ -21,7 +21,6 @@
 // DESIGN.md section 4.2a has the measurements; profiles/r04_s2_kernels_ab.txt the steps that led here.
 #include "dam_common.h"
 #include "dam_bn_fin.h"
-#include <cstdlib>
 
 namespace dam {
 namespace {
@@ -41,7 +40,7 @@ struct S2Sums {
 template <int NB, int NCH, int MB, bool PAIR, int WAVES, bool SUMS>
 __global__ __launch_bounds__(64 * WAVES) void dgrad_s2_kernel(const float* __restrict__ DC, const float4* __restrict__ Wp,
                                                        const float* __restrict__ DS, const float4* __restrict__ Wp2, int B, int Hd,
-                                                       int Wd, float* __restrict__ DX, int H, int W, int total_px, int total_units, int xcd_aware,
+                                                       int Wd, float* __restrict__ DX, int H, int W, int total_px, int total_units,
                                                        const S2Sums sums) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];      // [9 (+1)][NCH][NB][64 lanes] float4
     constexpr int Co = 16 * NCH, Ci = 16 * NB;
@@ -121,8 +120,8 @@ __global__ __launch_bounds__(64 * WAVES) void dgrad_s2_kernel(const float* __res
     // XCD-aware unit order: workgroup b runs on XCD b % 8 and every XCD has its own L2.  Each XCD takes one CONTIGUOUS eighth of
     // the units, so the rows that neighbouring units share (the taps reach one row up and down) are fetched into ONE L2 instead of
     // up to three; inside an XCD wave-major: the units left over after the last full round go to ONE wave each of different
-    // workgroups (SIMDs).  DAM_S2_NO_XCD=1 (read by the launcher: `xcd_aware`): the plain interleaved order (A/B).
-    const int n_xcd = (xcd_aware && (gridDim.x & 7) == 0) ? 8 : 1;
+    // workgroups (SIMDs).
+    const int n_xcd = (gridDim.x & 7) == 0 ? 8 : 1;
     const int wg_per_xcd = gridDim.x / n_xcd, per_xcd = (total_units + n_xcd - 1) / n_xcd;
     const int u_lo = (blockIdx.x % n_xcd) * per_xcd;
     const int unit_end = u_lo + per_xcd < total_units ? u_lo + per_xcd : total_units;
@@ -288,8 +287,6 @@ int launch_dgrad_s2(const float* dc, const float* wpt, const float* ds, const fl
     int max_per_cu = oc;
     if (max_per_cu > 3) max_per_cu = 3;
     if (WAVES == 8) max_per_cu = 1;
-    static const int xcd_aware = getenv("DAM_S2_NO_XCD") ? 0 : 1;      // A/B knob
-    static const int forced = [] { const char* e = getenv("DAM_S2_PER_CU"); return e ? atoi(e) : 0; }();      // A/B knob
     // Workgroups per CU by makespan: n resident waves per SIMD share its MFMA pipe, so a SIMD's time is (units per wave) * n unit
     // times; more waves hide the operand latency better, which decides when the costs are within ~15 %.
     int per_cu = 1;
@@ -298,7 +295,6 @@ int launch_dgrad_s2(const float* dc, const float* wpt, const float* ds, const fl
         const int64_t cost = cdiv(units, (int64_t)WAVES * cus * n) * n * 100;
         if (n == 1 || cost * 100 <= best * 115) { best = n == 1 ? cost : (cost < best ? cost : best); per_cu = n; }
     }
-    if (forced >= 1 && forced <= max_per_cu) per_cu = forced;
     int64_t wgs = (int64_t)cus * per_cu;
     if (wgs > cdiv(units, WAVES)) wgs = cdiv(units, WAVES);
     if (sums.u && wgs > BN_BWD_RECORDS_MAX) return DAM_ERR_UNSUPPORTED;
@@ -312,7 +308,7 @@ int launch_dgrad_s2(const float* dc, const float* wpt, const float* ds, const fl
         }                                                                                                                         \
         hipLaunchKernelGGL((dgrad_s2_kernel<NB, NCH, MB, PAIR_, WAVES, SUMS_>), dim3((unsigned)wgs), dim3(64 * WAVES), lds, st, dc, \
                            reinterpret_cast<const float4*>(wpt), ds, reinterpret_cast<const float4*>(wpt2), B, Hd, Wd, dx, H, W,      \
-                           (int)px, (int)units, xcd_aware, sums);                                                                 \
+                           (int)px, (int)units, sums);                                                                            \
     } while (0)
     if (ds) { if (sums.u) DAM_S2_GO(true, true); else DAM_S2_GO(true, false); }
     else { if (sums.u) DAM_S2_GO(false, true); else DAM_S2_GO(false, false); }
@@ -329,11 +325,12 @@ int launch_dgrad_s2(const float* dc, const float* wpt, const float* ds, const fl
 // (64 lanes x 16 bytes = one packed 1 KB block per load; every wave with the same channel block reads the same image), the operand
 // loads are the four shifted views of the kernel above, and two register sets keep the next chunk's fifteen loads in flight under the
 // current chunk's 40 * MB MFMAs.  No LDS, no barrier: several workgroups per CU cover each other's waits.
-template <int MB, bool PAIR>
+template <bool PAIR>
 __global__ __launch_bounds__(256) void dgrad_s2_stream_kernel(const float* __restrict__ DC, const float4* __restrict__ Wp,
                                                               const float* __restrict__ DS, const float4* __restrict__ Wp2, int Hd, int Wd,
                                                               float* __restrict__ DX, int H, int W, int total_px, int NCH, int NB,
                                                               int total_units) {
+    constexpr int MB = 2;           // two pixel blocks per wave: the form for a full chip (one block: dgrad_s2_stream_lds_kernel)
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int unit = blockIdx.x * 4 + wave;
     if (unit >= total_units) return;                                   // (no barrier below)
@@ -534,15 +531,14 @@ __global__ __launch_bounds__(256) void dgrad_s2_stream_lds_kernel(const float* _
     }
 }
 
-template <int MB>
 int launch_dgrad_s2_stream(const float* dc, const float* wpt, const float* ds, const float* wpt2, int B, int Hd, int Wd, int Co, int Ci,
                            float* dx, int H, int W, hipStream_t st) {
     const int64_t px = (int64_t)B * Hd * Wd;
     const int NCH = Co / 16, NB = Ci / 16;
+    const int MB = cdiv(px, 16) * NB >= 8 * 1024 ? 2 : 1;                  // two pixel blocks per wave once the chip is full
     const int64_t units = cdiv(px, 16 * MB) * NB;
     if (px >= (1ll << 26) || units >= (1ll << 30)) return DAM_ERR_UNSUPPORTED;
-    static const int no_lds = getenv("DAM_S2_STREAM_NO_LDS") ? 1 : 0;       // A/B knob: every wave loads all its weight fragments
-    if (MB == 1 && !no_lds) {
+    if (MB == 1) {
         const dim3 grid_l((unsigned)(cdiv(cdiv(px, 64), 8) * 8 * NB)), block_l(256);      // whole rounds of eight groups (one per XCD)
         if (ds)
             hipLaunchKernelGGL((dgrad_s2_stream_lds_kernel<true>), grid_l, block_l, 0, st, dc, reinterpret_cast<const float4*>(wpt), ds,
@@ -555,10 +551,10 @@ int launch_dgrad_s2_stream(const float* dc, const float* wpt, const float* ds, c
     }
     const dim3 grid((unsigned)cdiv(units, 4)), block(256);
     if (ds)
-        hipLaunchKernelGGL((dgrad_s2_stream_kernel<MB, true>), grid, block, 0, st, dc, reinterpret_cast<const float4*>(wpt), ds,
+        hipLaunchKernelGGL((dgrad_s2_stream_kernel<true>), grid, block, 0, st, dc, reinterpret_cast<const float4*>(wpt), ds,
                            reinterpret_cast<const float4*>(wpt2), Hd, Wd, dx, H, W, (int)px, NCH, NB, (int)units);
     else
-        hipLaunchKernelGGL((dgrad_s2_stream_kernel<MB, false>), grid, block, 0, st, dc, reinterpret_cast<const float4*>(wpt),
+        hipLaunchKernelGGL((dgrad_s2_stream_kernel<false>), grid, block, 0, st, dc, reinterpret_cast<const float4*>(wpt),
                            (const float*)nullptr, (const float4*)nullptr, Hd, Wd, dx, H, W, (int)px, NCH, NB, (int)units);
     DAM_CHECK_LAUNCH();
     return DAM_OK;
@@ -580,21 +576,12 @@ extern "C" int dam_dgrad_s2_3x3_f32(const float* dy, const float* w_packed_t, co
     if (bn_parts_host) *bn_parts_host = 0;
     // the upstream BatchNorm's backward sums (mask as sign bytes only): taken by the persistent kernels, "not produced" elsewhere
     S2Sums sums{nullptr, nullptr, nullptr, nullptr, nullptr};
-    static const int no_sums = getenv("DAM_S2_NO_SUMS") ? 1 : 0;          // A/B knob
-    if (bn_bwd && bn_bwd->x && bn_bwd->mask_bits && bn_bwd->mean && bn_bwd->invstd && bn_partial && bn_parts_host && !no_sums)
+    if (bn_bwd && bn_bwd->x && bn_bwd->mask_bits && bn_bwd->mean && bn_bwd->invstd && bn_partial && bn_parts_host)
         sums = S2Sums{bn_bwd->x, bn_bwd->mask_bits, bn_bwd->mean, bn_bwd->invstd, bn_partial};
-    static const int mb1 = [] { const char* e = getenv("DAM_S2_MB1"); return e ? atoi(e) : 0; }();           // A/B knob
-    if (Co == 32 && Ci == 16 && !(mb1 & 1)) return launch_dgrad_s2<1, 2, 2, 4>(dy, w_packed_t, dy_pair, w_pair_packed_t, B, Hd, Wd, dx, H, W, sums, bn_parts_host, st);
-    if (Co == 32 && Ci == 16 && (mb1 & 1)) return launch_dgrad_s2<1, 2, 1, 4>(dy, w_packed_t, dy_pair, w_pair_packed_t, B, Hd, Wd, dx, H, W, sums, bn_parts_host, st);
+    if (Co == 32 && Ci == 16) return launch_dgrad_s2<1, 2, 2, 4>(dy, w_packed_t, dy_pair, w_pair_packed_t, B, Hd, Wd, dx, H, W, sums, bn_parts_host, st);
     if (Co == 64 && Ci == 32) return launch_dgrad_s2<2, 4, 1, 8>(dy, w_packed_t, dy_pair, w_pair_packed_t, B, Hd, Wd, dx, H, W, sums, bn_parts_host, st);
     // wider layers: the weight image streams from L2 (even chunk count: the two register sets alternate)
-    static const int no_stream = [] { const char* e = getenv("DAM_S2_NO_STREAM"); return e ? atoi(e) : 0; }();       // A/B knob
-    if (!no_stream && Co % 32 == 0 && Ci % 16 == 0 && (int64_t)9 * Co * Ci * 4 < (1ll << 31)) {
-        const int64_t units1 = cdiv((int64_t)B * Hd * Wd, 16) * (Ci / 16);
-        static const int mb_forced = [] { const char* e = getenv("DAM_S2_STREAM_MB"); return e ? atoi(e) : 0; }();   // A/B knob
-        const bool two = mb_forced ? mb_forced == 2 : units1 >= 8 * 1024;          // two pixel blocks per wave once the chip is full
-        return two ? launch_dgrad_s2_stream<2>(dy, w_packed_t, dy_pair, w_pair_packed_t, B, Hd, Wd, Co, Ci, dx, H, W, st)
-                   : launch_dgrad_s2_stream<1>(dy, w_packed_t, dy_pair, w_pair_packed_t, B, Hd, Wd, Co, Ci, dx, H, W, st);
-    }
+    if (Co % 32 == 0 && Ci % 16 == 0 && (int64_t)9 * Co * Ci * 4 < (1ll << 31))
+        return launch_dgrad_s2_stream(dy, w_packed_t, dy_pair, w_pair_packed_t, B, Hd, Wd, Co, Ci, dx, H, W, st);
     return DAM_ERR_UNSUPPORTED;
 }

@@ -335,11 +335,7 @@ __global__ __launch_bounds__(TF2* WAVE, 4) void stft2048_kernel(
                     const f32x2 wk = __builtin_bit_cast(f32x2, __builtin_amdgcn_raw_buffer_load_b64(trs, lane * 8, (64 * i + 256 * d) * 8, 0));
                     const float2 tt = cmul(make_float2(wk.x, wk.y), o);
                     const float2 xa = cadd(e, tt);
-#ifdef DAM_STFT_DIAG_NO_LOG
-                    db[4 * i + d] = xa.x * xa.x + xa.y * xa.y;
-#else
                     db[4 * i + d] = power_to_db(xa.x * xa.x + xa.y * xa.y, amin2, floor_db);
-#endif
                     mx = fmaxf(mx, fabsf(db[4 * i + d]));
                     if (i == 0 && d == 0 && lane == 0) {          // k = 0: Nyquist bin X[1024] = e - tt
                         const float2 xb = csub(e, tt);
@@ -366,7 +362,6 @@ __global__ __launch_bounds__(TF2* WAVE, 4) void stft2048_kernel(
             if (lane == 0) trow[NCPX] = nyq;
         }
         __syncthreads();
-#ifndef DAM_STFT_DIAG_NO_WRITEOUT
         {   // write-out: (bin, half) -> 4 consecutive frames = one 16-byte piece of out[track][bin][t0 + 4 half ...]
             const int64_t og = track / n_inner;
             const int ig = (int)(track % n_inner);
@@ -389,9 +384,6 @@ __global__ __launch_bounds__(TF2* WAVE, 4) void stft2048_kernel(
                 }
             }
         }
-#else
-        if (tile_i == 0x7fffffff) out[tid] = tile[tid];
-#endif
         __syncthreads();
     }
 }

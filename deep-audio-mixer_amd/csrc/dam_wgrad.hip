@@ -16,7 +16,6 @@
 //     registers; waves are combined through LDS once at the end, the workgroup writes ONE partial slab;
 //   * a second kernel sums the slabs in a fixed order (deterministic, no float atomics) and writes
 //     torch's [O][I][KH][KW] layout.
-#include <cstdlib>
 #include <string.h>
 #include "dam_common.h"
 #include "dam_conv_stage.h"
@@ -66,13 +65,11 @@ namespace {
 typedef float v4f __attribute__((ext_vector_type(4)));
 typedef int v4i __attribute__((ext_vector_type(4)));
 
-// LW (loader waves; experiment of round 5, off by default -- see launch_wgrad_jobs): 512 threads -- waves 0-3 compute exactly as in
-// the plain form, waves 4-7 stage the NEXT tile's X patch and dY pixels into the other of two LDS images while the compute waves run
-// the MFMAs of this one (one barrier per tile).  The plain form stages and computes in turn and relies on a second co-resident
-// workgroup to fill the gaps: its matrix pipe was 58 % busy on the scalar models' 9x9 layer (0.585 of peak) and a 176-pixel tile of
-// the 33 x 5 stage cost 19 us for 5.3 us of MFMAs -- and still beats this form.
-template <int TNB, int TKB, int TA, int TB, bool LW>
-__global__ __launch_bounds__(LW ? 512 : 256) void wgrad_kernel(const WgradGeo g, const WgradJobs jobs) {
+// A workgroup stages and computes in turn and relies on a second co-resident workgroup to fill the gaps (its matrix pipe was 58 %
+// busy on the scalar models' 9x9 layer).  Loader waves staging the next tile beside the MFMAs measured slower still: C2 5.28 ->
+// 5.52 ms, C1 3.71 -> 3.86 ms (profiles/r05_wgrad_loader_waves_ab.txt).
+template <int TNB, int TKB, int TA, int TB>
+__global__ __launch_bounds__(256) void wgrad_kernel(const WgradGeo g, const WgradJobs jobs) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_all[];
     const float* __restrict__ X = jobs.X[blockIdx.z];
     const float* __restrict__ dY = jobs.dY[blockIdx.z];
@@ -80,9 +77,8 @@ __global__ __launch_bounds__(LW ? 512 : 256) void wgrad_kernel(const WgradGeo g,
     const float* __restrict__ in_shift = jobs.sh[blockIdx.z];
     float* __restrict__ partial = jobs.partial[blockIdx.z];
     constexpr int NBLK = TNB * TKB * TA * TB;
-    const int tid = threadIdx.x & 255, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6) & 3;          // index inside the role
-    const bool loader = LW && __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 8) != 0;
+    const int tid = threadIdx.x & 255, lane = tid & 63;          // (the masks are no-ops at 256 threads; they steer register allocation)
+    const int wave = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6) & 3;
     const int j = lane & 15, kq = lane >> 4;
     int xt = blockIdx.x;
     const int tg = xt % g.tap_groups; xt /= g.tap_groups;
@@ -92,14 +88,13 @@ __global__ __launch_bounds__(LW ? 512 : 256) void wgrad_kernel(const WgradGeo g,
     const int HoWo = g.Ho * g.Wo;
     const int chunk_bytes = g.PR * g.PWT * 64;
     const int TMW = g.TMW, WP = g.TMW >> 2;   // pixels per wave
-    const int img_bytes = TKB * chunk_bytes + TNB * TMW * 64;      // one LDS image: [TKB chunks of the X patch][TNB][TMW][16] floats of dY
 
     PatchGeo pg;
     pg.H = g.H; pg.W = g.W; pg.C = g.C; pg.s = g.s; pg.c0 = g.c0; pg.PR = g.PR; pg.PWin = g.PWin; pg.PWs = g.PWs;
     pg.PWT = g.PWT; pg.in_nchw = g.in_nchw; pg.relu_in = jobs.relu_in[blockIdx.z];
 
     const size_t img_elems = (size_t)g.H * g.W * g.C;
-    // stage tile `tile` into the LDS image at `smem` (all 256 threads of the staging role)
+    // stage tile `tile` into the LDS image at `smem` (all 256 threads)
     auto stage_tile = [&](int tile, unsigned char* smem) {
         unsigned char* dy_s = smem + TKB * chunk_bytes;
         const int img = tile / g.tiles_m;
@@ -130,22 +125,6 @@ __global__ __launch_bounds__(LW ? 512 : 256) void wgrad_kernel(const WgradGeo g,
             }
         }
     };
-    if constexpr (LW) {
-        // ---- loader waves: their own loop with the SAME number of barriers as the compute waves' path below (one after the first
-        //      image, one per tile, five in the cross-wave reduction); the accumulators do not exist on this path
-        if (loader) {
-            int tile = blockIdx.y;
-            if (tile < g.total_tiles) stage_tile(tile, smem_all);
-            __syncthreads();
-            for (int k = 0; tile < g.total_tiles; tile += g.nsplit, ++k) {
-                if (tile + g.nsplit < g.total_tiles) stage_tile(tile + g.nsplit, smem_all + ((k + 1) & 1) * img_bytes);
-                __syncthreads();
-            }
-#pragma unroll
-            for (int i = 0; i < 5; ++i) __syncthreads();
-            return;
-        }
-    }
     v4f acc[NBLK];
 #pragma unroll
     for (int i = 0; i < NBLK; ++i) acc[i] = (v4f){0.f, 0.f, 0.f, 0.f};
@@ -169,46 +148,11 @@ __global__ __launch_bounds__(LW ? 512 : 256) void wgrad_kernel(const WgradGeo g,
         // this wave's WP pixels, 4 per MFMA step; lane group kq owns pixel 4*t + kq.  Two operand sets: the TNB + TA*TB*TKB
         // ds_read_b32 of step t + 1 are requested before the MFMAs of step t (one wave per SIMD here -- 80-odd KB of LDS per
         // workgroup -- so nothing else hides the LDS latency: the single-set loop ran the 9x9 / 64 -> 128 layer of the scalar
-        // models at 0.41 of the matrix peak; DAM_WG_NO_PIPELINE keeps it for the A/B)
+        // models at 0.41 of the matrix peak)
         int p = p0 + wave * WP + kq;
         int pc = p < HoWo ? p : HoWo - 1;
         int oh = pc / g.Wo, ow = pc - oh * g.Wo;
         const int nsteps = WP >> 2;
-#ifdef DAM_WG_NO_PIPELINE
-        for (int t = 0; t < nsteps; ++t) {
-            const int pl = wave * WP + 4 * t + kq;
-            float av[TNB];
-#pragma unroll
-            for (int nb = 0; nb < TNB; ++nb)
-                av[nb] = *reinterpret_cast<const float*>(dy_s + ((nb * TMW + pl) * 16 + j) * 4);
-            const int base = (((oh - oh_first) * g.s) * g.PWT + ow) * 64 + j * 4;
-#pragma unroll
-            for (int ta = 0; ta < TA; ++ta) {
-                const int roff = ta * g.step_h;                 // relative to the first staged row (tap row a0)
-#pragma unroll
-                for (int tb = 0; tb < TB; ++tb) {
-                    const int coff = g.off_w + tb * g.step_w - g.c0;
-                    const int slotoff = g.s == 1 ? coff : (coff & 1) * g.PWs + (coff >> 1);
-                    const int toff = (roff * g.PWT + slotoff) * 64;
-#pragma unroll
-                    for (int kb = 0; kb < TKB; ++kb) {
-                        const float bv = *reinterpret_cast<const float*>(smem + kb * chunk_bytes + base + toff);
-#pragma unroll
-                        for (int nb = 0; nb < TNB; ++nb) {
-                            const int idx = ((nb * TKB + kb) * TA + ta) * TB + tb;
-                            acc[idx] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[nb], bv, acc[idx], 0, 0, 0);
-                        }
-                    }
-                }
-            }
-            // advance this lane's pixel by 4 (clamped pixels past the image end carry dY == 0)
-            p += 4;
-            if (p < HoWo) {
-                ow += 4;
-                while (ow >= g.Wo) { ow -= g.Wo; ++oh; }
-            }
-        }
-#else
         float av[2][TNB], bv[2][TA * TB * TKB];
 #define DAM_WG_LOAD(BUF_, T_)                                                                                               \
     do {                                                                                                                  \
@@ -252,28 +196,18 @@ __global__ __launch_bounds__(LW ? 512 : 256) void wgrad_kernel(const WgradGeo g,
         if (t < nsteps) DAM_WG_MFMA(0);
 #undef DAM_WG_LOAD
 #undef DAM_WG_MFMA
-#endif
     };
-    if constexpr (LW) {
-        int tile = blockIdx.y;
-        __syncthreads();                                  // the loaders have staged the first tile
-        for (int k = 0; tile < g.total_tiles; tile += g.nsplit, ++k) {
-            compute_tile(tile, smem_all + (k & 1) * img_bytes);
-            __syncthreads();                              // image k & 1 may be refilled; image (k + 1) & 1 is complete
-        }
-    } else {
-        for (int tile = blockIdx.y; tile < g.total_tiles; tile += g.nsplit) {
-            __syncthreads();
-            stage_tile(tile, smem_all);
-            __syncthreads();
-            compute_tile(tile, smem_all);
-        }
+    for (int tile = blockIdx.y; tile < g.total_tiles; tile += g.nsplit) {
+        __syncthreads();
+        stage_tile(tile, smem_all);
+        __syncthreads();
+        compute_tile(tile, smem_all);
     }
 
     // combine the 4 waves through LDS (sequential adds: fixed order), then one slab per workgroup
     __syncthreads();
     float* red = reinterpret_cast<float*>(smem_all);
-    for (int w = 0; w < 4; ++w) {       // (five barriers from here to the end: the loader waves' path counts them)
+    for (int w = 0; w < 4; ++w) {
         if (wave == w) {
 #pragma unroll
             for (int i = 0; i < NBLK; ++i) {
@@ -419,7 +353,7 @@ int reduce_submit(void* queue, const float* partial, float* dw, int nsplit, int 
     if (nsplit >= 64) {
         j.sl = 32;
         j.blocks = (int)(cdiv(per_split4, 8) < 4096 ? cdiv(per_split4, 8) : 4096);
-    } else if (per_split4 >= 8192 && !getenv("DAM_REDUCE_NO_SL1")) {
+    } else if (per_split4 >= 8192) {
         // few big slabs (the thick stages): one element per thread, the splits added in order by that thread (4 chains, all
         // loads in flight) -- no LDS step at all; the 32 x 8 shape spent its time in one-load-then-barrier rounds
         j.sl = 1;
@@ -580,42 +514,11 @@ __global__ __launch_bounds__(256 + 64 * NL) void wgrad_rows_kernel(const RowsGeo
         }
         v4f lv[KP][GPP];
         int dst[KP];               // scalar: LDS byte offset of the plane | 1 << 30 (row outside the image: zeros), -1 = none
-        int aff[KP], aff2[KP];     // scalar: chunk index kb of an X plane that gets the input affine, -1 otherwise
+        int aff[KP], aff2[KP];     // scalar: chunk index kb of an X plane that gets the input affine, -1 other X, -2 dY
         const int rowstride = g.W * g.C * 4;
-        // TIMING EXPERIMENT ONLY (-DDAM_DIAG_DXHAT=1|2, tools/dxhat_ladder.py; results are wrong): what it would cost this kernel to
-        // form its dY operand dc = a * (dy . mask) + b * c + k (BatchNorm backward, the bn_bwd_apply launch folded into the
-        // loaders) itself: every dY plane is accompanied by a second plane from a THIRD tensor (read through the slab workspace
-        // pointer at +128 MB: real HBM traffic, no aliasing with X or dY); 1 = the loads and one fma, 2 = the full arithmetic
-        // with the mask recomputed from the second stream.
-#ifdef DAM_DIAG_DXHAT
-        const __amdgpu_buffer_rsrc_t crsrc = __builtin_amdgcn_make_buffer_rsrc(
-            const_cast<float*>(partial) + (size_t)(32u << 20) + (size_t)img * g.H * g.W * g.C, 0, img_bytes, 0x00020000);
-        v4f lvc_a[KP][GPP], lvc_b[KP][GPP], lvc_c[(2 * TKB + NL - 1) / NL][GPP];
-#define DAM_DXHAT_ON 1
-#define DAM_DXHAT_REQ(LVC_, K_, SOFF_)                                                                                      \
-    _Pragma("unroll") for (int gi = 0; gi < GPP; ++gi)                                                                     \
-        LVC_[K_][gi] = __builtin_bit_cast(v4f, __builtin_amdgcn_raw_buffer_load_b128(crsrc, loffb[gi], SOFF_, 0))
-#if DAM_DIAG_DXHAT == 1
-#define DAM_DXHAT_COMBINE(LV_, LVC_, K_, GI_) __builtin_elementwise_fma(LVC_[K_][GI_], shq[0], LV_[K_][GI_])
-#else
-#define DAM_DXHAT_COMBINE(LV_, LVC_, K_, GI_)                                                                              \
-    ([&]() {                                                                                                               \
-        const v4f c_ = LVC_[K_][GI_], dy_ = LV_[K_][GI_];                                                    \
-        const v4f m_ = __builtin_elementwise_fma(c_, scq[0], shq[0]);                                                      \
-        v4f dz_;                                                                                                           \
-        dz_.x = m_.x > 0.f ? dy_.x : 0.f; dz_.y = m_.y > 0.f ? dy_.y : 0.f;                                                \
-        dz_.z = m_.z > 0.f ? dy_.z : 0.f; dz_.w = m_.w > 0.f ? dy_.w : 0.f;                                                \
-        return __builtin_elementwise_fma(dz_, scq[0], __builtin_elementwise_fma(c_, shq[0], relu_lo4));                    \
-    }())
-#endif
-#else
-#define DAM_DXHAT_ON 0
-#define DAM_DXHAT_REQ(LVC_, K_, SOFF_) do { } while (0)
-#define DAM_DXHAT_COMBINE(LV_, LVC_, K_, GI_) (LV_[K_][GI_])
-#endif
         // X rows xr0 .. xr0+nx-1 (in-channel chunks of this tile) then dY rows dr0 .. dr0+nd-1 (out-channel blocks), one
         // plane = one (row, 16 channels); loader wave cwl takes planes cwl, cwl+4, ...  Loads are unconditional (clamped).
-#define DAM_RW_REQUEST(XR0_, NX_, DR0_, ND_, LV_, DST_, KP_, AFF_, LVC_)                                                                               \
+#define DAM_RW_REQUEST(XR0_, NX_, DR0_, ND_, LV_, DST_, KP_, AFF_)                                                  \
     do {                                                                                                                   \
         _Pragma("unroll") for (int k = 0; k < KP_; ++k) {                                                                  \
             const int pl_ = cwl + NL * k;                                                                          \
@@ -638,7 +541,6 @@ __global__ __launch_bounds__(256 + 64 * NL) void wgrad_rows_kernel(const RowsGeo
             } else {                                                                                                       \
                 _Pragma("unroll") for (int gi = 0; gi < GPP; ++gi)                                                         \
                     LV_[k][gi] = __builtin_bit_cast(v4f, __builtin_amdgcn_raw_buffer_load_b128(drsrc, loffb[gi], soff_, 0)); \
-                DAM_DXHAT_REQ(LVC_, k, soff_);                                                                             \
             }                                                                                                              \
             DST_[k] = need_ ? (ldsoff_ | (inimg_ ? 0 : 1 << 30)) : -1;                                                     \
             AFF_[k] = (isx_ && has_aff) ? c_ : (isx_ ? -1 : -2);                                                           \
@@ -647,7 +549,7 @@ __global__ __launch_bounds__(256 + 64 * NL) void wgrad_rows_kernel(const RowsGeo
 #define DAM_RW_WRITE(ADDR_, DATA_, GI_)                                                                                    \
     asm volatile("s_mov_b64 exec, %2\n\tds_write_b128 %0, %1 offset:%3\n\ts_mov_b64 exec, -1"                              \
                  : : "v"(ADDR_), "v"(DATA_), "s"(cmask[GI_]), "n"((GI_) * 1024) : "memory")
-#define DAM_RW_COMMIT(LV_, DST_, KP_, AFF_, LVC_)                                                                              \
+#define DAM_RW_COMMIT(LV_, DST_, KP_, AFF_)                                                                         \
     do {                                                                                                                   \
         _Pragma("unroll") for (int k = 0; k < KP_; ++k) {                                                                  \
             if (DST_[k] >= 0) {                                                                                            \
@@ -662,11 +564,6 @@ __global__ __launch_bounds__(256 + 64 * NL) void wgrad_rows_kernel(const RowsGeo
                         v_ = __builtin_elementwise_max(v_, relu_lo4);       /* -inf without ReLU: no selects */             \
                         DAM_RW_WRITE(va_, v_, gi);                                                                         \
                     }                                                                                                      \
-                } else if (DAM_DXHAT_ON && AFF_[k] == -2) {                                                                \
-                    _Pragma("unroll") for (int gi = 0; gi < GPP; ++gi) {                                                   \
-                        v4f v_ = DAM_DXHAT_COMBINE(LV_, LVC_, k, gi);                                                          \
-                        DAM_RW_WRITE(va_, v_, gi);                                                                         \
-                    }                                                                                                      \
                 } else {                                                                                                   \
                     _Pragma("unroll") for (int gi = 0; gi < GPP; ++gi) DAM_RW_WRITE(va_, LV_[k][gi], gi);                  \
                 }                                                                                                          \
@@ -678,13 +575,13 @@ __global__ __launch_bounds__(256 + 64 * NL) void wgrad_rows_kernel(const RowsGeo
         v4f lvb[KPB][GPP], lv2[KP][GPP];
         int dstb[KPB], dst2[KP], affb[KPB];
         DAM_WSTAMP(9);                                                         // setup done
-        DAM_RW_REQUEST(r_begin - 1, RPS, r_begin, RPS, lv, dst, KP, aff, lvc_a);
-        DAM_RW_REQUEST(r_begin + RPS - 1, 2, r_begin, 0, lvb, dstb, KPB, affb, lvc_c);
+        DAM_RW_REQUEST(r_begin - 1, RPS, r_begin, RPS, lv, dst, KP, aff);
+        DAM_RW_REQUEST(r_begin + RPS - 1, 2, r_begin, 0, lvb, dstb, KPB, affb);
         DAM_WSTAMP(10);                                                        // first rows requested
         DAM_RW_ZERO();
         DAM_WSTAMP(11);                                                        // padding cells cleared
-        DAM_RW_COMMIT(lv, dst, KP, aff, lvc_a);
-        DAM_RW_COMMIT(lvb, dstb, KPB, affb, lvc_c);
+        DAM_RW_COMMIT(lv, dst, KP, aff);
+        DAM_RW_COMMIT(lvb, dstb, KPB, affb);
         DAM_WSTAMP(12);                                                        // first rows written (their loads have landed)
         // the compute waves start slot 0 HERE; the requests for slots 1 and 2 follow (in front of this barrier they held the
         // first MFMA back by 5-8 k clocks: with three slots of rows wanted by 256 CUs at once the request queue backs up)
@@ -693,18 +590,18 @@ __global__ __launch_bounds__(256 + 64 * NL) void wgrad_rows_kernel(const RowsGeo
         // adds (X rows r_begin+RPS(s+1)+1 .. +RPS, dY rows r_begin+RPS(s+1) .. +RPS-1; requested during slot s-1) and
         // requests those of slot s+3.  Two register sets alternate; slots come in pairs so that no load sits inside a
         // conditional.
-#define DAM_RW_SLOT(T_, LV_, DST_, AFF_, LVC_) DAM_RW_REQUEST(r_begin + RPS * (T_) + 1, RPS, r_begin + RPS * (T_), RPS, LV_, DST_, KP, AFF_, LVC_)
+#define DAM_RW_SLOT(T_, LV_, DST_, AFF_) DAM_RW_REQUEST(r_begin + RPS * (T_) + 1, RPS, r_begin + RPS * (T_), RPS, LV_, DST_, KP, AFF_)
         DAM_WSTAMP(2);
-        DAM_RW_SLOT(1, lv, dst, aff, lvc_a);
-        DAM_RW_SLOT(2, lv2, dst2, aff2, lvc_b);
+        DAM_RW_SLOT(1, lv, dst, aff);
+        DAM_RW_SLOT(2, lv2, dst2, aff2);
         for (int s = 0; s < n_slots2; s += 2) {
-            DAM_RW_COMMIT(lv, dst, KP, aff, lvc_a);
-            DAM_RW_SLOT(s + 3, lv, dst, aff, lvc_a);
+            DAM_RW_COMMIT(lv, dst, KP, aff);
+            DAM_RW_SLOT(s + 3, lv, dst, aff);
             DAM_WSTAMP(5);
             asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
             DAM_WSTAMP(7);
-            DAM_RW_COMMIT(lv2, dst2, KP, aff2, lvc_b);
-            DAM_RW_SLOT(s + 4, lv2, dst2, aff2, lvc_b);
+            DAM_RW_COMMIT(lv2, dst2, KP, aff2);
+            DAM_RW_SLOT(s + 4, lv2, dst2, aff2);
             DAM_WSTAMP(5);
             asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
             DAM_WSTAMP(7);
@@ -713,14 +610,6 @@ __global__ __launch_bounds__(256 + 64 * NL) void wgrad_rows_kernel(const RowsGeo
 #undef DAM_RW_REQUEST
 #undef DAM_RW_WRITE
 #undef DAM_RW_COMMIT
-#undef DAM_DXHAT_ON
-#undef DAM_DXHAT_REQ
-#undef DAM_DXHAT_COMBINE
-#ifndef DAM_DIAG_DXHAT
-#undef lvc_a
-#undef lvc_b
-#undef lvc_c
-#endif
     } else {
         // ================================ compute waves ================================
         const int cw = wave;
@@ -729,26 +618,17 @@ __global__ __launch_bounds__(256 + 64 * NL) void wgrad_rows_kernel(const RowsGeo
         asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");       // rows of slot 0 are in LDS, padding cleared
         DAM_WSTAMP(2);
         // operand reads of step t + 1 against the MFMAs of step t: one read behind each of the first MFMAs (as a burst in front
-        // of them -- build flag DAM_WGR_NO_INTERLEAVE, scheduling barriers only -- the launch is 1.3-1.6 us slower: the pipe drains
-        // while seven reads issue)
-#ifndef DAM_WGR_IL_STRIDE
-#define DAM_WGR_IL_STRIDE (NL == 4 ? 2 : 1)   /* MFMAs between two operand reads: 2 measured -1.1 us on the four-loader 129x17 kernel, +0.5 us on the others */
-#endif
-#ifndef DAM_WGR_NO_INTERLEAVE
-#define DAM_RW_SCHED_A() do { } while (0)
-#define DAM_RW_SCHED_B()                                                                                                   \
+        // of them the launch is 1.3-1.6 us slower: the pipe drains while seven reads issue).  MFMAs between two operand reads:
+        // 2 measured -1.1 us on the four-loader 129x17 kernel, +0.5 us on the others
+#define DAM_RW_SCHED()                                                                                                     \
     do {                                                                                                                   \
         _Pragma("unroll") for (int i_ = 0; i_ < 8; ++i_) {                                                                 \
-            __builtin_amdgcn_sched_group_barrier(0x008, DAM_WGR_IL_STRIDE, 0);                                             \
+            __builtin_amdgcn_sched_group_barrier(0x008, NL == 4 ? 2 : 1, 0);                                               \
             __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);                                                             \
         }                                                                                                                  \
         __builtin_amdgcn_sched_group_barrier(0x008, 9 * TNB * TKB, 0);                                                     \
         __builtin_amdgcn_sched_barrier(0);                                                                                 \
     } while (0)
-#else
-#define DAM_RW_SCHED_A() __builtin_amdgcn_sched_barrier(0)
-#define DAM_RW_SCHED_B() __builtin_amdgcn_sched_barrier(0)
-#endif
         // one (row, first cell, step stride) assignment of this wave for the slot: F = 1 a whole row part (the steady state),
         // F = 4 / 2 every fourth / second MFMA step of the one / two rows of a strip's last slot
 #define DAM_RW_LOAD(T_, BUF_)                                                                                              \
@@ -775,14 +655,13 @@ __global__ __launch_bounds__(256 + 64 * NL) void wgrad_rows_kernel(const RowsGeo
         _Pragma("unroll") for (int t = 0; t < NS_; ++t) {                                                                  \
             if ((F_) > 1 && (SUB_) + (F_) * t >= STEPS) break;                /* (scalar; last step of the split form only) */ \
             if (t + 1 < NS_) DAM_RW_LOAD((F_) * (t + 1), (t + 1) & 1);                                                     \
-            DAM_RW_SCHED_A();                                                                                              \
             _Pragma("unroll") for (int nb = 0; nb < TNB; ++nb)                                                             \
                 _Pragma("unroll") for (int kb = 0; kb < TKB; ++kb)                                                         \
                     _Pragma("unroll") for (int tap = 0; tap < 9; ++tap) {                                                  \
                         const int idx = (nb * TKB + kb) * 9 + tap;                                                         \
                         acc[idx] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[t & 1][nb], bv[t & 1][kb][tap], acc[idx], 0, 0, 0); \
                     }                                                                                                      \
-            DAM_RW_SCHED_B();                                                                                              \
+            DAM_RW_SCHED();                                                                                                \
         }                                                                                                                  \
     } while (0)
         for (int s = 0; s < n_slots2; ++s) {
@@ -803,8 +682,7 @@ __global__ __launch_bounds__(256 + 64 * NL) void wgrad_rows_kernel(const RowsGeo
     }
 #undef DAM_RW_ROW
 #undef DAM_RW_LOAD
-#undef DAM_RW_SCHED_A
-#undef DAM_RW_SCHED_B
+#undef DAM_RW_SCHED
 
     // combine the 4 compute waves through LDS (sequential adds: fixed order), one slab per workgroup
     __syncthreads();
@@ -864,11 +742,10 @@ int launch_wgrad_rows(int B, int H, int W, int C, const float* X, const float* d
     // launch: 96 channels on 8 images gave 288 workgroups on 256 CUs, 63 us).  One workgroup per CU when whole strips per
     // image fill >= 80 % of the CUs that way; otherwise size for two co-resident workgroups per CU (the register file
     // holds two of these 8-wave workgroups, the narrow stages' rings leave the LDS for both): 432 workgroups, 50 us.
-    // Measured both ways (DAM_WGR_PERCU=1|2): where one per CU already fills the chip, two cost 15 % (more slabs, shared pipe).
+    // Measured both ways: where one per CU already fills the chip, two cost 15 % (more slabs, shared pipe).
     auto strips = [&](int per_cu) { const int w = 256 * per_cu / (nx * B); return w > 0 ? w : 1; };
     int spi = strips(1);
     if (nx * B * spi < 205 && lds * 2 <= 160 * 1024) spi = strips(2);
-    if (const char* e = getenv("DAM_WGR_PERCU")) spi = strips(atoi(e) == 2 && lds * 2 <= 160 * 1024 ? 2 : 1);      // diagnostic
     if (spi > (int)cdiv(H, RPS)) spi = (int)cdiv(H, RPS);
     if (spi > H) spi = H;
     for (;; --spi) {                              // (rows in spi nearly equal parts, see the kernel)
@@ -1074,21 +951,8 @@ __global__ __launch_bounds__(RW_THREADS) void wgrad_rows_s2_kernel(const RowsS2G
         const int lane_b = kq * 64 + j * 4;       // lane group kq owns cell 4t + kq of step t, lane j channel j of the cell
         DAM_RW_ZERO();
         asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");       // rows of slot 0 are in LDS
-#ifdef DAM_WGR_S2_INTERLEAVE                     /* as in wgrad_rows_kernel; here measured SLOWER (42.0 -> 43.6, 40.3 -> 42.2, 46.2 -> 47.0 us): off */
-#define DAM_RW2_SCHED_A() do { } while (0)
-#define DAM_RW2_SCHED_B()                                                                                                  \
-    do {                                                                                                                   \
-        _Pragma("unroll") for (int i_ = 0; i_ < 8; ++i_) {                                                                 \
-            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);                                                             \
-            __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);                                                             \
-        }                                                                                                                  \
-        __builtin_amdgcn_sched_group_barrier(0x008, 9 * TNB, 0);                                                           \
-        __builtin_amdgcn_sched_barrier(0);                                                                                 \
-    } while (0)
-#else
-#define DAM_RW2_SCHED_A() __builtin_amdgcn_sched_barrier(0)
-#define DAM_RW2_SCHED_B() __builtin_amdgcn_sched_barrier(0)
-#endif
+        // (the operand reads interleaved with the MFMAs as in wgrad_rows_kernel measured SLOWER here: 42.0 -> 43.6, 40.3 -> 42.2,
+        // 46.2 -> 47.0 us)
         // column taps: odd-plane cell ow, even-plane cell ow, odd-plane cell ow + 1
 #define DAM_RW2_LOAD(T_, BUF_)                                                                                             \
     do {                                                                                                                   \
@@ -1113,11 +977,11 @@ __global__ __launch_bounds__(RW_THREADS) void wgrad_rows_s2_kernel(const RowsS2G
         _Pragma("unroll") for (int t = 0; t < NS_; ++t) {                                                                  \
             if ((F_) > 1 && (SUB_) + (F_) * t >= STEPS) break;                                                             \
             if (t + 1 < NS_) DAM_RW2_LOAD((F_) * (t + 1), (t + 1) & 1);                                                    \
-            DAM_RW2_SCHED_A();                                                                                             \
+            __builtin_amdgcn_sched_barrier(0);                                                                             \
             _Pragma("unroll") for (int nb = 0; nb < TNB; ++nb)                                                             \
                 _Pragma("unroll") for (int tap = 0; tap < 9; ++tap)                                                        \
                     acc[nb * 9 + tap] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[t & 1][nb], bv[t & 1][tap], acc[nb * 9 + tap], 0, 0, 0); \
-            DAM_RW2_SCHED_B();                                                                                             \
+            __builtin_amdgcn_sched_barrier(0);                                                                             \
         }                                                                                                                  \
     } while (0)
         for (int s = 0; s < n_slots2; ++s) {
@@ -1133,8 +997,6 @@ __global__ __launch_bounds__(RW_THREADS) void wgrad_rows_s2_kernel(const RowsS2G
     }
 #undef DAM_RW2_ROW
 #undef DAM_RW2_LOAD
-#undef DAM_RW2_SCHED_A
-#undef DAM_RW2_SCHED_B
 #undef DAM_RW_ZERO
 
     // combine the 4 compute waves through LDS (sequential adds: fixed order), one slab per workgroup
@@ -1366,8 +1228,7 @@ int launch_wgrad_direct(int B, int H, int W, int C, int Ho, int Wo, int N, int s
     if ((int64_t)nsplit * nx * NBLK * 256 > ws_floats) return DAM_ERR_WORKSPACE;
     WgradQueue* q = static_cast<WgradQueue*>(queue);
     if (q && q->magic != WGRAD_QUEUE_MAGIC) return DAM_ERR_BAD_ARG;
-    static const bool no_batch = getenv("DAM_WG_DIRECT_NO_BATCH") != nullptr;      // A/B switch
-    if (q && q->batching && !no_batch) {
+    if (q && q->batching) {
         // record instead of launching: launches of this instantiation wait for each other until the queue is flushed (the caller
         // keeps X, dY and the slabs valid until then: the batching contract of include/dam_hip.h)
         PendingDirect& p = q->pend_direct;
@@ -1396,15 +1257,7 @@ int launch_wgrad_jobs(WgradGeo g, const WgradJobs& jobs, int njobs, int64_t ws_f
                       const int* k_real, void* queue, hipStream_t st) {
     constexpr int NBLK = TNB * TKB * TA * TB;
     const int nx = g.tiles_n * g.tiles_k * g.tap_groups;
-    size_t lds0 = (size_t)TKB * g.PR * g.PWT * 64 + (size_t)TNB * g.TMW * 64;
-    // Loader-wave form (two LDS images, one 8-wave workgroup per CU) where two images fit.  MEASURED SLOWER than two plain
-    // workgroups per CU (profiles/r05_wgrad_loader_waves_ab.txt: C2 5.28 -> 5.52 ms, C1 3.71 -> 3.86, C3 +8 us): one MFMA wave per
-    // SIMD beside a VALU-heavy staging wave hides LDS operand latency worse than two MFMA waves taking turns.  OFF by default;
-    // DAM_WG_LW=1 enables it for the big-tile instantiations, 2 for all (A/B).
-    static const int lw_env = [] { const char* e = getenv("DAM_WG_LW"); return e ? atoi(e) : 0; }();
-    // (default: the big-tile instantiations only -- 2x2 / 3x2 channel blocks hold 144+ accumulator registers, so at most two of
-    //  their plain workgroups share a CU; the one-block tiles run up to five waves per SIMD and overlap by themselves)
-    const bool lw_fits = lw_env != 0 && (TNB * TKB >= 4 || lw_env == 2) && 2 * lds0 <= 160 * 1024 && 2 * lds0 >= (size_t)NBLK * 1024;
+    size_t lds = (size_t)TKB * g.PR * g.PWT * 64 + (size_t)TNB * g.TMW * 64;
     auto split_for = [&](int64_t slots, double fixed) {
         // Pixel split by MAKESPAN: every CU works through ceil(workgroups / slots) workgroups of ceil(total_tiles / nsplit) tiles
         // each (co-resident workgroups share the matrix pipe, so it is the count per CU that matters).  The first rule -- at least
@@ -1424,48 +1277,25 @@ int launch_wgrad_jobs(WgradGeo g, const WgradJobs& jobs, int njobs, int64_t ws_f
         }
         return ns_best;
     };
-    int nsplit;
-    bool lw = false;
-    static const bool old_rule = getenv("DAM_WG_NSPLIT_OLD") != nullptr;
-    if (old_rule) {                          // DAM_WG_NSPLIT_OLD: the first rule (A/B)
-        nsplit = (int)cdiv(512, (int64_t)nx * njobs);
-        if (nsplit > g.total_tiles) nsplit = g.total_tiles;
-        if (nsplit < 1) nsplit = 1;
-    } else {
-        // slots: two workgroups per CU where the LDS holds two (the small-patch layers: their staging phases overlap each
-        // other -- 256 workgroups of two tiles measured slower than 512 of one on the 33 x 5 stage), one otherwise
-        if (lds0 < (size_t)NBLK * 1024) lds0 = (size_t)NBLK * 1024;
-        static const int slots_forced = [] { const char* e = getenv("DAM_WG_SLOTS"); return e ? atoi(e) : 0; }();      // A/B knob
-        const int64_t slots = slots_forced ? slots_forced : (lds0 * 2 <= 160 * 1024 ? 512 : 256);
-        nsplit = split_for(slots, 1.0);
-        if (lw_fits) {
-            // the loader-wave form is one workgroup per CU and pays its staging only for the FIRST tile: worth it when a
-            // workgroup has several tiles to stream (lw_env 2 forces it)
-            const int ns_lw = split_for(256, 1.0);
-            if (cdiv(g.total_tiles, ns_lw) >= 2 || lw_env == 2) { lw = true; nsplit = ns_lw; }
-        }
-    }
+    // slots: two workgroups per CU where the LDS holds two (the small-patch layers: their staging phases overlap each
+    // other -- 256 workgroups of two tiles measured slower than 512 of one on the 33 x 5 stage), one otherwise
+    if (lds < (size_t)NBLK * 1024) lds = (size_t)NBLK * 1024;
+    int nsplit = split_for(lds * 2 <= 160 * 1024 ? 512 : 256, 1.0);
     while (nsplit > 1 && (int64_t)nsplit * nx * NBLK * 256 > ws_floats) --nsplit;
     if ((int64_t)nsplit * nx * NBLK * 256 > ws_floats) return DAM_ERR_WORKSPACE;
     g.nsplit = nsplit;
-    size_t lds = (size_t)TKB * g.PR * g.PWT * 64 + (size_t)TNB * g.TMW * 64;
-    if (lw) lds *= 2;
-    if (lds < (size_t)NBLK * 1024) lds = (size_t)NBLK * 1024;
     if (lds > 160 * 1024) return DAM_ERR_UNSUPPORTED;
     if (lds > 64 * 1024) {
-        static PerDevice<bool> raised_pd[2];
-        bool& raised = raised_pd[lw ? 1 : 0]();
+        static PerDevice<bool> raised_pd;
+        bool& raised = raised_pd();
         if (!raised) {
-            const void* fn = lw ? reinterpret_cast<const void*>(&wgrad_kernel<TNB, TKB, TA, TB, true>)
-                                : reinterpret_cast<const void*>(&wgrad_kernel<TNB, TKB, TA, TB, false>);
-            if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) return DAM_ERR_LAUNCH;
+            if (hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_kernel<TNB, TKB, TA, TB>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                    160 * 1024) != hipSuccess)
+                return DAM_ERR_LAUNCH;
             raised = true;
         }
     }
-    if (lw)
-        hipLaunchKernelGGL((wgrad_kernel<TNB, TKB, TA, TB, true>), dim3(nx, nsplit, njobs), dim3(512), lds, st, g, jobs);
-    else
-        hipLaunchKernelGGL((wgrad_kernel<TNB, TKB, TA, TB, false>), dim3(nx, nsplit, njobs), dim3(256), lds, st, g, jobs);
+    hipLaunchKernelGGL((wgrad_kernel<TNB, TKB, TA, TB>), dim3(nx, nsplit, njobs), dim3(256), lds, st, g, jobs);
     DAM_CHECK_LAUNCH();
     for (int i = 0; i < njobs; ++i) {
         const int rc = reduce_submit(queue, jobs.partial[i], dw[i], g.nsplit, nx, TNB, TKB, TA, TB, n_real[i], k_real[i], g.KH, g.KW,
@@ -1594,7 +1424,7 @@ extern "C" int dam_conv2d_wgrad_f32(const float* x, int B, int H, int W, int C, 
         else if (W > 80) rc = DAM_WGR(2, 1, 14, 1, 7, 2);
         else if (W > 48) { rc = DAM_WGR(2, 1, 17, 2, 5); if (rc == DAM_ERR_UNSUPPORTED) rc = DAM_WGR(2, 1, 14, 2, 4); }
         else if (W > 20) rc = DAM_WGR(2, 1, 9, 2, 3);
-        else if (W > 12) rc = getenv("DAM_WGR_NL8") ? DAM_WGR(2, 1, 5, 2, 2) : DAM_WGR(2, 1, 5, 3, 2, 1, 4);   // 17-pixel rows (129x17 stage), four loader waves
+        else if (W > 12) rc = DAM_WGR(2, 1, 5, 3, 2, 1, 4);   // 17-pixel rows (129x17 stage), four loader waves
         else if (W > 6) rc = DAM_WGR(2, 1, 3, 2, 1);        // 9-pixel rows (65x9 stage): 40.8 -> 32.1 us; narrower: tile kernel
 #undef DAM_WGR
         if (rc != DAM_ERR_UNSUPPORTED) return rc;
@@ -1609,7 +1439,7 @@ extern "C" int dam_conv2d_wgrad_f32(const float* x, int B, int H, int W, int C, 
     }
     // strided 3x3 (the first convolution of a down-sampling block): measured 61/62/58 us against 80/78/67 us for the tile
     // kernel; for stride-1 narrow rows (17 pixels, 96 channels) it is slower (117 vs 60 us: nine L2 reads per element)
-    if (kh == 3 && kw == 3 && !in_nchw && !in_scale && stride == 2 && pad == 1 && dil == 1 && !getenv("DAM_WGR_S2_DIRECT")) {
+    if (kh == 3 && kw == 3 && !in_nchw && !in_scale && stride == 2 && pad == 1 && dil == 1) {
         // <TN, steps, planes per loader wave, pieces per X plane, per dY plane, row parts>: the down-sampling convolutions of
         // the ResNet stages at 130 frames (65-, 33- and 17-pixel output rows) and at the reference's native 216 (54, 27)
 #define DAM_WGR2(...) launch_wgrad_rows_s2<__VA_ARGS__>(B, H, W, C, Ho, Wo, n_chan, x, dy, workspace, workspace_floats, dw, n_out, k_real, reduce_queue, st)
@@ -1643,7 +1473,7 @@ extern "C" int dam_conv2d_wgrad_f32(const float* x, int B, int H, int W, int C, 
         // pixels per tile: the image in equal parts of at most tmw_max pixels, rounded up to the 16 a step of the four waves takes
         // (165 pixels of the 33 x 5 stage in a 256-pixel tile were 16 MFMA steps per wave for 10.3 of work: 176 -> 11)
         const int64_t npix_ = (int64_t)Ho * Wo, parts_ = cdiv(npix_, tmw_max);
-        const int tmw = getenv("DAM_WG_FIXED_TILE") ? tmw_max : (int)(cdiv(cdiv(npix_, parts_), 16) * 16);
+        const int tmw = (int)(cdiv(cdiv(npix_, parts_), 16) * 16);
         int rows_out = (tmw + Wo - 2) / Wo + 1;
         if (rows_out > Ho) rows_out = Ho;
         g.TMW = tmw;
@@ -1657,11 +1487,10 @@ extern "C" int dam_conv2d_wgrad_f32(const float* x, int B, int H, int W, int C, 
     g.in_nchw = in_nchw; g.relu_in = relu_in;
     // tile choice: 2x2 channel blocks when both sides have them and LDS allows two workgroups per CU.  48 OUTPUT channels (three blocks:
     // the scalar models' 5x5 / 32 -> 48 layer) take a three-block tile on that side instead of two tiles of two with the fourth block
-    // empty (a quarter of the MFMAs on zeros): 167 -> 115 us; DAM_WG_NO_T3 keeps 2x2 (A/B).  The same on the INPUT side (7x7 / 48 -> 64
+    // empty (a quarter of the MFMAs on zeros): 167 -> 115 us.  The same on the INPUT side (7x7 / 48 -> 64
     // as a 1x3 tile) measured 476 us against 463: 22 LDS reads per 21 MFMAs; a 2x3 tile needs 273 VGPRs.  Not instantiated.
-    static const bool no_t3 = getenv("DAM_WG_NO_T3") != nullptr;
     int tnb = 2, tkb = 2;
-    if (!no_t3 && kh == 5 && kw == 5 && g.nblk == 3 && g.nchunks % 2 == 0) { tnb = 3; tkb = 2; }
+    if (kh == 5 && kw == 5 && g.nblk == 3 && g.nchunks % 2 == 0) { tnb = 3; tkb = 2; }
     bool small = g.nchunks == 1 || g.nblk == 1;
     set_tile(256);
     if (!small && lds_bytes(tnb, tkb) > 72 * 1024) {

@@ -24,8 +24,6 @@ stay between them, on RCCL's own stream, so that the big bucket travels while th
 The cut uses autograd itself: stage 1 is torch.autograd.grad(loss, late parameters + [boundary activation]), stage 2
 torch.autograd.backward(boundary activation, its gradient, inputs=early parameters).
 """
-import os
-
 import torch
 
 from . import distributed, features, layers, ops
@@ -166,12 +164,11 @@ class TrainStep:
         else:
             tap = []
             loss, self.masked, self.gains = self.model.forward_mse(self.x, self.gt, tap=tap)
-            if tap and tap[0].requires_grad and os.environ.get('DAM_COPY_MARK_AT', 'boundary') == 'boundary':
+            if tap and tap[0].requires_grad:
                 tap[0].register_hook(self._mark_hook)       # runs when backward reaches the boundary activation
             else:
                 self._record_mark()                         # a model without a boundary: behind the forward pass
         loss.backward(self._unit_seed if loss.dim() == 0 else None)      # (no ones_like fill, no seed multiply: layers.UNIT_SEED)
-        ops.side_stream_join(self.device)
         ops.wgrad_flush(self.device)                # every weight gradient's slab reduction, one launch
         # the loss tensor itself is the step's output: inside a captured graph its address is fixed (the graph's pool keeps it
         # while this reference lives), so no copy launch into a separate buffer
@@ -185,7 +182,6 @@ class TrainStep:
         tap = []
         loss, self.masked, self.gains = self.model.forward_mse(self.x, self.gt, tap=tap)
         grads, dmid = distributed.backward_late(loss, self.opt.bucket_params(1), tap[0])
-        ops.side_stream_join(self.device)
         ops.wgrad_flush(self.device)                # bucket 1 is complete
         self.loss.copy_(loss.detach())
         self.opt.gather_grads(1, grads=grads)
@@ -214,7 +210,6 @@ class TrainStep:
         if self.copy_mark is not None:
             self._record_mark()
         distributed.backward_early(mid, dmid, self.opt.bucket_params(0))
-        ops.side_stream_join(self.device)
         ops.wgrad_flush(self.device)
         self.opt.gather_grads(0)
 

@@ -85,12 +85,10 @@ class ConvSpec:
     def wgrad(self, x, dy, in_affine=None, out=None):
         aff = {} if in_affine is None else dict(in_scale=in_affine[0], in_shift=in_affine[1], relu_in=True)
         # out given = written in place into the optimizer's gradient bucket: a leaf of the backward pass, nothing reads it
-        # before the optimizer, so its slab reduction joins the one launch of ops.wgrad_flush()
-        call = lambda: ops.conv2d_wgrad(x, dy, self.cout, self.k, self.k, self.stride, self.pad, self.dil,
-                                        in_nchw=self.in_nchw, out=out, defer=out is not None, **aff)
-        if out is None:
-            return call()
-        return ops.side_stream_run(call, (x, dy) + (tuple(in_affine) if in_affine is not None else ()), x.device)
+        # before the optimizer, so its slab reduction joins the one launch of ops.wgrad_flush().  (On a second stream beside
+        # the backward chain it measured slower: C3 5.57 -> 5.96 ms, profiles/r02_side_stream_trace_summary.txt)
+        return ops.conv2d_wgrad(x, dy, self.cout, self.k, self.k, self.stride, self.pad, self.dil,
+                                in_nchw=self.in_nchw, out=out, defer=out is not None, **aff)
 
     def dgrad(self, dy, w, hw, **kw):
         return ops.conv2d_dgrad(dy, self.packed(w, transpose=True), self.cin, hw[0], hw[1], self.k, self.k,
@@ -113,8 +111,7 @@ class _Nhwc16Spec(ConvSpec):
 
     def wgrad(self, x, dy, in_affine=None, out=None):
         # only the real input planes are written ([cout, cin, 3, 3] = conv1.weight's shape): the zero-padded ones drop out
-        call = lambda: ops.conv2d_wgrad(x, dy, self.cout, 3, 3, 1, 1, 1, out=out, c_real=self.parent.cin, defer=out is not None)
-        return call() if out is None else ops.side_stream_run(call, (x, dy), x.device)
+        return ops.conv2d_wgrad(x, dy, self.cout, 3, 3, 1, 1, 1, out=out, c_real=self.parent.cin, defer=out is not None)
 
 
 class WeightPacker:
@@ -316,7 +313,7 @@ class BasicBlockFn(torch.autograd.Function):
             # (no statistics from these two launches: the pair pass below is one launch sequence for both tensors, a
             # fused epilogue on conv1 alone would leave the shortcut's statistics a pass of their own)
             one = None
-            if (ops.CONV_S2_PAIR and training and blk.spec1.k == 3 and blk.spec1.stride == 2 and blk.spec1.pad == 1
+            if (training and blk.spec1.k == 3 and blk.spec1.stride == 2 and blk.spec1.pad == 1
                     and blk.spec1.dil == 1 and blk.spec_sc.k == 1 and blk.spec_sc.stride == 2 and blk.spec_sc.pad == 0
                     and not blk.spec1.in_nchw):
                 # both convolutions and both statistics passes from one read of x (thin stages; None: not such a layer)
@@ -388,7 +385,7 @@ class BasicBlockFn(torch.autograd.Function):
         first = (keep(dw1, s_w1), keep(dg1, s_g1), keep(db1, s_b1), keep(dw2, s_w2), keep(dg2, s_g2), keep(db2, s_b2))
         if ctx.has_sc:
             dws = blk.spec_sc.wgrad(x, dcs, out=wview(s_ws, wsc))
-            if (ops.PAIR_1X1 and blk.spec1.k == 3 and blk.spec1.stride == 2 and blk.spec1.pad == 1 and blk.spec1.dil == 1
+            if (blk.spec1.k == 3 and blk.spec1.stride == 2 and blk.spec1.pad == 1 and blk.spec1.dil == 1
                     and blk.spec_sc.k == 1 and blk.spec_sc.stride == 2 and blk.spec_sc.pad == 0):      # (the forward's gate)
                 # the shortcut's whole data gradient and the centre tap of conv1's land on the same (even, even) pixels: one launch
                 up = ctx.upstream

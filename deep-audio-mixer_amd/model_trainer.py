@@ -35,7 +35,6 @@ import warnings
 
 import torch
 
-_COPY_MARK = os.environ.get('DAM_TRAINER_COPY_MARK', '1') != '0'     # A/B switch: uploads timed by the step mark
 _LOG_EVERY = 10                                   # model_trainer.py:39
 _CKPT_PATTERN = 'mixmodel_{}_1s_{:04d}_{:.4f}.pt'  # model_trainer.py:64
 
@@ -198,10 +197,10 @@ class ModelTrainer:
             B, K, n, ch = pcm.clips.shape
             step = TrainStep(model, opt, K - 1, n, ch, B, pcm.n_fft, pcm.hop, use_graph=True, device=pcm.clips.device,
                              pcm_dtype=pcm.clips.dtype, track_gains=pcm.gain is not None, normalize=pcm.normalize,
-                             copy_mark=_COPY_MARK)
+                             copy_mark=True)
         else:
             B, S, F, T = feats.shape
-            step = TrainStep(model, opt, S, batch=B, feature_shape=(F, T), use_graph=True, device=feats.device, copy_mark=_COPY_MARK)
+            step = TrainStep(model, opt, S, batch=B, feature_shape=(F, T), use_graph=True, device=feats.device, copy_mark=True)
         keep = [t.clone() for t in (opt._flat, opt._exp_avg, opt._exp_avg_sq, opt._step)]
         bufs = [(b, b.clone()) for b in model.buffers()]
         training = model.training

@@ -59,15 +59,6 @@ FUSED_FINALIZE = os.environ.get('DAM_BN_FUSED_FIN', '1') != '0'
 # strided 3x3 data gradients of the thin stages as one launch (dam_dgrad_s2_3x3_f32); DAM_NO_DGRAD_S2=1: the parity-class launches (A/B)
 DGRAD_S2 = not os.environ.get('DAM_NO_DGRAD_S2')
 dgrad_s2_launches = 0        # launches dam_dgrad_s2_3x3_f32 accepted (tests check that a shape took the one-launch form)
-# shortcut data gradient riding in conv1's single-tap class launch (dam_conv1x1_pair_f32); DAM_NO_PAIR_1X1=1: two launches (A/B)
-PAIR_1X1 = not os.environ.get('DAM_NO_PAIR_1X1')
-
-
-# a down-sampling block's conv1 + shortcut convolution + both statistics passes as one launch (dam_conv_s2_pair_fwd_f32);
-# DAM_NO_CONV_S2_PAIR=1: the separate launches (A/B)
-CONV_S2_PAIR = not os.environ.get('DAM_NO_CONV_S2_PAIR')
-
-
 # BatchNorm-backward sums from the data-gradient epilogue (include/dam_hip.h: dam_bn_bwd_sums); DAM_NO_DGRAD_SUMS=1 keeps the
 # separate pass over dy and x (A/B switch)
 DGRAD_BN_SUMS = not os.environ.get('DAM_NO_DGRAD_SUMS')
@@ -162,7 +153,7 @@ def _dgrad_axis(parity, pad, dil, k, stride):
 
 
 def conv2d_dgrad(dy, wpt, n_in, H, W, kh, kw, stride=1, pad=0, dil=1, res=None, res_mask=None, accumulate_into=None,
-                 bn_bwd=None, res_mask_bits=None, _diag_bias=None, pair_1x1=None, _s2_sums=None):
+                 bn_bwd=None, res_mask_bits=None, pair_1x1=None, _s2_sums=None):
     """dy: NHWC [B,Ho,Wo,Cout]; wpt packed with transpose=True.  Returns dx NHWC [B,H,W,n_in16]
     (+ res * (res_mask > 0) if given).  With accumulate_into=dx0 the result is added to dx0 in place.
     bn_bwd=(x, save_mean, save_invstd, mask_scale, mask_shift[, mask_bits]) (stride 1; 3x3 / stride 2 / pad 1 with the mask_bits
@@ -205,8 +196,7 @@ def conv2d_dgrad(dy, wpt, n_in, H, W, kh, kw, stride=1, pad=0, dil=1, res=None, 
         rec = torch.empty(_lib.lib().dam_bn_workspace_floats(n16), dtype=torch.float32, device=dy.device)
         epi = _lib.BnBwdSums(_lib.ptr(xb), _lib.ptr(mean), _lib.ptr(invstd), _lib.ptr(msc), _lib.ptr(msh), _lib.ptr(res_mask_bits),
                              _lib.ptr(up_bits))
-        # (_diag_bias: timing builds only -- tools/dxhat_ladder.py hands the kernel a second input stream through the bias pointer)
-        parts = _tapgrid(dy, B, Ho, Wo, Co, False, wpt, Co // 16, n16, _diag_bias, None, None, False, dx, H, W, H, W, 1, 0, 0, 1,
+        parts = _tapgrid(dy, B, Ho, Wo, Co, False, wpt, Co // 16, n16, None, None, None, False, dx, H, W, H, W, 1, 0, 0, 1,
                          kh, kw, pad, -dil, pad, -dil, 0, kw, 1, res, res_mask, bn_partial=rec, bn_bwd=epi)
         return dx, ((rec, parts) if parts > 0 else None)
     _f32c(dy, 'dy'), _f32c(res, 'res'), _f32c(res_mask, 'res_mask')
@@ -312,60 +302,10 @@ def _grow(table, key, device, floats):
 
 
 def _workspace(device, floats):
-    """One grow-only scratch buffer per device and stream role (split-K slabs, weight-gradient slabs, reduction scratch of
-    the heads / mask-sum); all users of one buffer are ordered on one stream -- launches made inside side_stream_run()
-    get their own.  A buffer that has to grow is never freed: hipGraphs captured earlier keep replaying into the old one
-    (the launches recorded there were sized for it)."""
-    key = (device.type, device.index, 'side') if _side_active else (device.type, device.index)
-    return _grow(_workspaces, key, device, floats)
-
-
-# -- side stream for the leaves of the backward pass ------------------------------------------------------------------------
-# A weight gradient is a leaf: nothing in the backward chain (BatchNorm backward -> data gradient -> next layer) waits for it,
-# so it can run on a second stream beside the chain (under hipGraph capture: a parallel branch of the graph).  MEASURED, C3
-# ResNet18 step: 5.57 ms on one stream, 5.96 ms with the weight gradients on the side stream -- the kernels do overlap
-# (profiles/r02_side_stream_trace_summary.txt) but the big ones are one-workgroup-per-CU persistent kernels with 60-150 KB
-# of LDS: two of them cannot share a CU, so each runs 1.3-1.7 x longer (conv_strip 66 -> 85-92 us, wgrad_rows 54 -> 79-96 us)
-# and the sum grows.  Hence OFF by default; DAM_SIDE_STREAM=1 turns it on for the A/B.  Only gradients written in place into a
-# caller-owned buffer (Adam's flat gradient bucket) take it: the consumer joins with side_stream_join() before it reads them.
-SIDE_STREAM = bool(os.environ.get('DAM_SIDE_STREAM'))
-_side_active = False
-_side_streams = {}
-_side_dirty = set()
-
-
-def side_stream_run(fn, reads, device):
-    """Runs fn() (kernel launches only) on the device's side stream, ordered after everything issued so far on the current
-    stream.  `reads`: the tensors those launches read -- their memory is not handed out again before the side stream is done."""
-    global _side_active
-    if not SIDE_STREAM or device.type != 'cuda' or _side_active:
-        return fn()
-    key = (device.type, device.index)
-    side = _side_streams.get(key)
-    if side is None:
-        side = _side_streams[key] = torch.cuda.Stream(device=device)
-    side.wait_stream(torch.cuda.current_stream(device))
-    _side_active = True
-    try:
-        with torch.cuda.stream(side):
-            out = fn()
-    finally:
-        _side_active = False
-    for t in reads:
-        if t is not None:
-            t.record_stream(side)
-    _side_dirty.add(key)
-    return out
-
-
-def side_stream_join(device=None):
-    """The current stream waits for everything side_stream_run() has issued (call before reading its results, and before
-    the end of a hipGraph capture that contains such launches)."""
-    for key in list(_side_dirty):
-        if device is not None and key != (device.type, device.index):
-            continue
-        torch.cuda.current_stream(torch.device(*key)).wait_stream(_side_streams[key])
-        _side_dirty.discard(key)
+    """One grow-only scratch buffer per device (split-K slabs, weight-gradient slabs, reduction scratch of
+    the heads / mask-sum); all users of one buffer are ordered on one stream.  A buffer that has to grow is never freed:
+    hipGraphs captured earlier keep replaying into the old one (the launches recorded there were sized for it)."""
+    return _grow(_workspaces, (device.type, device.index), device, floats)
 
 
 # Parameters and BatchNorm running statistics are updated IN PLACE by kernels of this library (the fused Adam launch, the
@@ -380,8 +320,9 @@ def params_changed():
     PARAM_EPOCH += 1
 
 
-# The equal weight gradients of a deep stage as one launch (include/dam_hip.h: dam_wgrad_queue_set_batching); DAM_WGRAD_BATCH=0: A/B
-WGRAD_BATCH = os.environ.get('DAM_WGRAD_BATCH', '1') != '0'
+# The equal weight gradients of a deep stage as one launch (include/dam_hip.h: dam_wgrad_queue_set_batching): every queue asks
+# for it.  A constant, not a switch (the unbatched A/B lost); tests read it as their precondition.
+WGRAD_BATCH = True
 _wgrad_queues = {}      # device -> [ctypes buffer of the library's queue, calls recorded since the last flush]
 
 
@@ -392,8 +333,7 @@ def _wgrad_queue(device):
         L = _lib.lib()
         buf = ctypes.create_string_buffer(int(L.dam_wgrad_queue_bytes()))
         _lib.check(L.dam_wgrad_queue_init(ctypes.addressof(buf)), 'dam_wgrad_queue_init')
-        if WGRAD_BATCH:
-            _lib.check(L.dam_wgrad_queue_set_batching(ctypes.addressof(buf), 1), 'dam_wgrad_queue_set_batching')
+        _lib.check(L.dam_wgrad_queue_set_batching(ctypes.addressof(buf), int(WGRAD_BATCH)), 'dam_wgrad_queue_set_batching')
         # [the library's queue, calls recorded since the last flush, tensors those calls read (kept alive until the flush: with
         #  batching a recorded call's slab kernel may not have been launched yet)]
         q = _wgrad_queues[key] = [buf, 0, []]

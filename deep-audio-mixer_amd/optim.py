@@ -142,7 +142,6 @@ class Adam(torch.optim.Optimizer):
         """One launch: every p.grad (or the given list of gradient tensors, bucket order) -> its slice of the flat
         buffer (missing grads count as zero).  bucket=None: all parameters."""
         if self._flat.is_cuda:
-            ops.side_stream_join(self._flat.device)
             ops.wgrad_flush(self._flat.device)            # slab reductions of the in-place weight gradients
         lo, hi = (0, len(self._params)) if bucket is None else self._bucket_params[bucket]
         views, srcs = [], []
@@ -165,7 +164,6 @@ class Adam(torch.optim.Optimizer):
         """Sum one bucket (default: the whole flat buffer) over the data-parallel group (RCCL all-reduce over xGMI);
         the 1/world average is folded into the Adam launch.  Returns the work handle when async_op."""
         if self._flat.is_cuda:
-            ops.side_stream_join(self._flat.device)
             ops.wgrad_flush(self._flat.device)
         if self.world_size > 1:
             t = self._grad if bucket is None else self.bucket_view(bucket)
@@ -185,7 +183,6 @@ class Adam(torch.optim.Optimizer):
     def launch_update(self):
         """The Adam launch alone (gradients already in the flat buffer, already reduced)."""
         if self._flat.is_cuda:
-            ops.side_stream_join(self._flat.device)
             ops.wgrad_flush(self._flat.device)
         ops.params_changed()
         h = self._hyper_tuple()
