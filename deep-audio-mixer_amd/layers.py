@@ -624,6 +624,13 @@ class MixingNet(nn.Module):
             raise RuntimeError('expected scalar type Float but found %s' % str(x.dtype).replace('torch.', '').capitalize())
         return x.contiguous()
 
+    @staticmethod
+    def _refuse_input_grad(x):
+        """No gradient reaches x: the heads' Functions return none for the masked sum's x and the stem's data
+        gradient is not written in x's NCHW layout -- so an x that asks for one is refused instead of left with a wrong .grad."""
+        if x.requires_grad and torch.is_grad_enabled():
+            raise RuntimeError('input gradients are not supported: x requires grad (detach it, or run under torch.no_grad())')
+
     def conv_pairs(self):
         """(ConvSpec, weight, needs_dgrad) of every convolution of the trunk; overridden by the models."""
         return []
@@ -639,6 +646,7 @@ class MixingNet(nn.Module):
 
     def forward(self, x):
         x = self._check_input(x)
+        self._refuse_input_grad(x)
         self._pack_weights()
         masked, g = self._heads(self.trunk(x), x)
         return masked, tuple(g[:, s:s + 1] for s in range(self.n_stems))
@@ -656,6 +664,7 @@ class MixingNet(nn.Module):
         """Fused fast path for criterion == nn.MSELoss(): returns (loss, masked, gains tuple); masked and the
         gains are detached outputs, loss carries the gradient.  tap: see trunk()."""
         x = self._check_input(x)
+        self._refuse_input_grad(x)
         self._pack_weights()
         loss, masked, g = self._heads.forward_mse(self.trunk(x) if tap is None else self.trunk(x, tap), x, gt)
         return loss, masked, tuple(g[:, s:s + 1] for s in range(self.n_stems))

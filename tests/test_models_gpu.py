@@ -207,6 +207,25 @@ def test_wrong_inputs_fail_loudly(dam):
         m(torch.zeros(1, 4, 1025, 130, device='cuda'))
 
 
+@pytest.mark.parametrize('name,shape', [('resnet18', (2, 4, 257, 64)), ('scalar1s', (2, 4, 257, 87)), ('scalar2s', (2, 4, 257, 93))])
+def test_input_gradient_is_refused(dam, name, shape):
+    """No gradient flows to x: an x that asks for one is refused by forward and forward_mse, so a wrong x.grad
+    cannot happen.  Without autograd, or with x detached, the same input runs."""
+    ctor, _ = dam[name]
+    m = ctor(n_stems=shape[1], input_shape=shape[2:]).cuda().train()
+    x, gt = (torch.from_numpy(a).cuda() for a in model_input(*shape, seed=1))
+    xg = x.clone().requires_grad_(True)
+    with pytest.raises(RuntimeError, match='input gradients are not supported'):
+        m(xg)
+    with pytest.raises(RuntimeError, match='input gradients are not supported'):
+        m.forward_mse(xg, gt)
+    assert xg.grad is None
+    with torch.no_grad():
+        masked, _ = m(xg)
+    assert masked.shape == gt.shape
+    m.forward_mse(xg.detach(), gt)[0].backward()
+
+
 def test_dropout_kernel_statistics(dam_lib):
     """ConvBlock2d dropout (training mode only): keep-rate, 1/(1-p) scaling, fresh mask per call, backward uses the
     forward's mask, eval mode is the identity."""
