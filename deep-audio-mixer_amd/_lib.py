@@ -12,7 +12,7 @@ LIB_PATH = os.environ.get('DAM_LIB_PATH') or os.path.join(_HERE, 'libdam_hip.so'
 # include/dam_hip.h: bumped whenever a C signature changes (together with dam_abi_version() in csrc/dam_api.hip and
 # DAM_ABI_VERSION in the header).  libdam_hip.so is git-ignored and travels prebuilt: a stale one would read device pointers
 # as streams, so lib() refuses it instead of launching.
-EXPECTED_ABI = 15
+EXPECTED_ABI = 16
 
 _STATUS = {0: 'DAM_OK', -1: 'DAM_ERR_BAD_ARG', -2: 'DAM_ERR_UNSUPPORTED', -3: 'DAM_ERR_LAUNCH',
            -4: 'DAM_ERR_WORKSPACE'}
@@ -79,6 +79,7 @@ SIGNATURES = {
     'dam_masksum_bwd_f32': (c_i, [c_p, c_p, c_i, c_i, c_i64, c_p, c_p, c_p]),
     'dam_masksum_mse_f32': (c_i, [c_p, c_p, c_p, c_i, c_i, c_i64, c_p, c_p, c_p, c_p, c_p]),
     'dam_adam_l2_step_f32': (c_i, [c_p, c_p, c_p, c_p, c_i64, c_p, c_p, c_f, c_f, c_f, c_f, c_f, c_f, c_p, c_p]),
+    'dam_digest64_u32': (c_i, [c_p, c_i64, c_i64, c_i, c_i, c_p, c_p]),
     'dam_gains_smooth': (c_i, [c_p, c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_p]),
     'dam_gain_ramp_apply': (c_i, [c_p, c_i, c_p, c_i64, c_i64, c_i64, c_i, c_p, c_i, c_p]),
     'dam_mixdown_workspace_elems': (c_i64, [c_i64]),

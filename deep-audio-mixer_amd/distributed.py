@@ -4,8 +4,9 @@ RCCL over xGMI on ROCm; "gloo" on CPU for tests).
 The reference is single-device; the semantics defined here are: clips (chunks) are sharded
 rank-strided over the replicas, BatchNorm statistics stay local to a replica, gradients are summed over ranks
 in ONE flat bucket (12.6 MB for ResNet18: a single all-reduce, sized for xGMI's per-link bandwidth rather than
-many small ones) and divided by the world size, rank 0 logs and writes checkpoints.  An N-GPU step therefore equals
-a reference step over N micro-batches with averaged gradients.
+many small ones; engine.TrainStep's staged step cuts it in two) and divided by the world size, rank 0 logs and writes
+checkpoints.  An N-GPU step therefore equals a reference step over N micro-batches with averaged gradients.
+model_trainer.ModelTrainer.fit implements these semantics for every optimizer and criterion ("N GPUs").
 """
 import os
 
@@ -51,6 +52,74 @@ class DistributedChunkSampler(Sampler):
 
     def __len__(self):
         return len(self.indices)
+
+
+def world_size(group=None):
+    """Size of the process group; 1 when torch.distributed is not initialised."""
+    return dist.get_world_size(group) if dist.is_available() and dist.is_initialized() else 1
+
+
+def _wire(t, group=None):
+    """Where a small host-side collective travels: RCCL takes device tensors only, gloo carries CPU tensors itself."""
+    return t.cuda() if dist.get_backend(group) == 'nccl' else t
+
+
+def all_reduce_max_min(values, group=None):
+    """Maximum and minimum over ranks of a list of int64 values, in ONE collective (MAX of [v, ~v]: ~ reverses the order of
+    int64 without overflow).  Returns (max list, min list), identical on every rank."""
+    n = len(values)
+    t = torch.tensor(list(values) + [~int(v) for v in values], dtype=torch.int64)
+    w = _wire(t, group)
+    dist.all_reduce(w, op=dist.ReduceOp.MAX, group=group)
+    t = w.cpu().tolist()
+    return t[:n], [~v for v in t[n:]]
+
+
+def check_equal_lengths(loader, what, group=None):
+    """Every rank must run the same number of batches, or a rank would wait forever in the next collective.  One small
+    collective compares len(loader) over ranks; on a mismatch, or a loader without __len__ on any rank, EVERY rank raises
+    ValueError (before its first batch).  Returns the length."""
+    try:
+        n = len(loader)
+    except TypeError:
+        n = -1
+    (hi,), (lo,) = all_reduce_max_min([n], group)
+    if lo < 0:
+        raise ValueError('%s: a loader without __len__ on at least one of %d ranks -- data-parallel training needs loaders of '
+                         'a known, equal length (DataLoader(..., sampler=DistributedChunkSampler(len(dataset))))'
+                         % (what, world_size(group)))
+    if hi != lo:
+        raise ValueError('%s: the ranks have between %d and %d batches -- data-parallel training needs loaders of equal length '
+                         '(DistributedChunkSampler drops the last len(dataset) %% world items for that)' % (what, lo, hi))
+    return n
+
+
+def all_gather_floats(values, group=None):
+    """[rank][i] table of every rank's float64 values (one collective); identical on every rank, so a sum taken over it in
+    rank order is bit-identical everywhere."""
+    t = _wire(torch.tensor([float(v) for v in values], dtype=torch.float64), group)
+    parts = [torch.empty_like(t) for _ in range(world_size(group))]
+    dist.all_gather(parts, t, group=group)
+    return [p.cpu().tolist() for p in parts]
+
+
+def broadcast_tensors(tensors, src=0, group=None):
+    """Rank `src`'s values of the given tensors everywhere, one broadcast per dtype (the tensors are packed into one flat
+    buffer, staged through host memory for gloo)."""
+    if world_size(group) == 1:
+        return
+    by_dtype = {}
+    for t in tensors:
+        by_dtype.setdefault(t.dtype, []).append(t)
+    for ts in by_dtype.values():
+        flat = torch.cat([t.detach().reshape(-1) for t in ts])
+        wire = flat if dist.get_backend(group) == 'nccl' else flat.cpu()
+        dist.broadcast(wire, src, group=group)
+        off = 0
+        for t in ts:
+            k = t.numel()
+            t.data.copy_(wire[off:off + k].view(t.shape))
+            off += k
 
 
 def broadcast_module(module, src=0, group=None):
@@ -110,6 +179,10 @@ class GradBucket:
     def start_all_reduce(self):
         """Asynchronous SUM over the group; returns the work handle (None on a single rank)."""
         if dist.is_initialized() and dist.get_world_size(self.group) > 1:
+            if self.flat.is_cuda and dist.get_backend(self.group) == 'gloo':
+                # gloo stages a CUDA tensor on its own and stalls for seconds while the producing stream is busy
+                # (optim._HostStagedAllReduce); once that stream is idle the exchange takes milliseconds
+                torch.cuda.current_stream(self.flat.device).synchronize()
             return dist.all_reduce(self.flat, op=dist.ReduceOp.SUM, group=self.group, async_op=True)
         return None
 

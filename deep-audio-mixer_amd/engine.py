@@ -216,30 +216,34 @@ class TrainStep:
     def _update(self):
         self.opt.launch_update()
 
-    def _eager(self):
+    def _eager(self, exchange=True):
         first = not self._slots_checked and not torch.cuda.is_current_stream_capturing()
         if first:
             self.opt._grad.view(torch.int32).fill_(self._SENTINEL)
-        self._eager_body(self._check_slots_written if first else None)
+        self._eager_body(self._check_slots_written if first else None, exchange)
 
-    def _eager_body(self, check=None):
+    def _eager_body(self, check=None, exchange=True):
         """check (first eager step only): called when backward has filled the whole bucket and nothing has consumed it yet
-        -- the staged form then starts both all-reduces after it instead of overlapping the first with stage 2."""
+        -- the staged form then starts both all-reduces after it instead of overlapping the first with stage 2.
+        exchange=False: no all-reduce at all (the local gradients are applied; see capture())."""
         if self.staged:
             self._stage1()
-            w1 = self.opt.all_reduce_grads(1, async_op=True) if check is None else None
+            w1 = self.opt.all_reduce_grads(1, async_op=True) if check is None and exchange else None
             self._stage2()
             if check is not None:
                 check()
-                w1 = self.opt.all_reduce_grads(1, async_op=True)
-            w0 = self.opt.all_reduce_grads(0, async_op=True)
-            w1.wait()
-            w0.wait()
+            if exchange:
+                if w1 is None:
+                    w1 = self.opt.all_reduce_grads(1, async_op=True)
+                w0 = self.opt.all_reduce_grads(0, async_op=True)
+                w1.wait()
+                w0.wait()
         else:
             self._fwd_bwd()
             if check is not None:
                 check()
-            self.opt.all_reduce_grads()
+            if exchange:
+                self.opt.all_reduce_grads()
         self._update()
 
     # -- public ---------------------------------------------------------------------------------
@@ -310,14 +314,17 @@ class TrainStep:
                 self.gain.copy_(gain.reshape(self.gain.shape), non_blocking=True)
         self._point_at(clips)
 
-    def capture(self, warmup=3):
-        """Eager warm-up on a side stream (sizes every workspace), then capture."""
+    def capture(self, warmup=3, exchange=True):
+        """Eager warm-up on a side stream (sizes every workspace), then capture.  exchange=False: the warm-up steps run
+        no all-reduce -- for a caller that rolls them back (model_trainer.ModelTrainer._capture): a rank that captures then
+        issues exactly the collectives of a rank that runs the same batch eagerly, and ranks that capture at different
+        batches stay aligned.  Capturing itself never exchanges (the all-reduces sit between the replayed graphs)."""
         self.opt.sync_hyper()
         s = torch.cuda.Stream(device=self.device)
         s.wait_stream(torch.cuda.current_stream(self.device))
         with torch.cuda.stream(s):
             for _ in range(warmup):
-                self._eager()
+                self._eager(exchange)
         torch.cuda.current_stream(self.device).wait_stream(s)
         torch.cuda.synchronize(self.device)
         if not self.use_graph:

@@ -23,17 +23,39 @@ What is different underneath:
   * ``DataLoader(dataset, batch_size, num_workers=6, pin_memory=True)`` over this package's MultitrackAudioDataset (training.ipynb
     cell 6 as written) yields HostPcmBatch objects -- decoded clips in page-locked host memory, no GPU work in the workers;
     they are uploaded on a copy stream into alternating device slots (``_upload``) and bound to the same PCM-fed captured step;
-  * loaders without ``__len__`` (generators such as ``MultitrackAudioDataset.iter_batches``) are accepted: the epoch mean
-    is taken over the batches seen;
+  * loaders without ``__len__`` (generators such as ``MultitrackAudioDataset.iter_batches``) are accepted on a single
+    process: the epoch mean is taken over the batches seen;
   * like the reference, the trainer never switches the model between train and eval mode: validation runs
     under ``torch.no_grad()`` with whatever mode the caller left the model in;
-  * under ``torch.distributed`` only rank 0 prints and saves.
+  * data parallel: under an initialised default process group of W > 1 ranks (one process per GPU, ``distributed.py``)
+    every rank runs the same fit() on its own shard and the replicas train as ONE model --
+      - gradients are averaged over ranks in every configuration: the fused Adam (own, or the adopted torch.optim.Adam, built
+        with ``world_size=W``) all-reduces its flat buckets and folds 1/W into its launch; any other optimizer or criterion,
+        and ``graph=False``, average ``.grad`` through a ``distributed.GradBucket`` before ``optimizer.step()``.  An
+        ``optim.Adam`` whose ``world_size`` is not W is refused (ValueError);
+      - at the start of every fit() rank 0 broadcasts parameters, buffers and the fused optimizer's state (moments, step
+        count): replicas built from different seeds, or a checkpoint loaded on rank 0 only, start as one;
+      - every train / validation epoch first compares ``len(loader)`` over ranks: unequal lengths, or a loader without
+        ``__len__``, make EVERY rank raise ValueError before its first batch (a rank short of batches would otherwise wait
+        forever in a collective);
+      - a batch issues the same collectives in the same order whether it runs eagerly, captures the step or replays it
+        (the deep bucket, then the shallow one; the rolled-back capture warm-up exchanges nothing), so ranks may take
+        different paths for the same batch;
+      - the per-batch progress lines are rank 0's local losses; the epoch means fit() returns are means over ALL ranks'
+        batches, identical on every rank; rank 0 prints the epoch lines and writes the checkpoint, named by that global
+        train mean;
+      - BatchNorm running statistics stay local to each replica (distributed.py); rank 0's are the ones saved;
+      - after every training epoch the replicas compare a 64-bit digest of their parameters (``ops.digest64``, one read of
+        the parameters and one tiny collective): if they differ, every rank raises RuntimeError before anything is saved.
+    At W = 1 (or without a process group) none of this runs: only rank 0 -- the one process -- prints and saves.
 """
 import os
 import time
 import warnings
 
 import torch
+
+from . import distributed
 
 _LOG_EVERY = 10                                   # model_trainer.py:39
 _CKPT_PATTERN = 'mixmodel_{}_1s_{:04d}_{:.4f}.pt'  # model_trainer.py:64
@@ -44,7 +66,7 @@ def _rank0():
     return not (dist.is_available() and dist.is_initialized()) or dist.get_rank() == 0
 
 
-def _adopt_torch_adam(optimizer):
+def _adopt_torch_adam(optimizer, world_size=1):
     """training.ipynb cell 11 hands ModelTrainer a ``torch.optim.Adam(model.parameters(), weight_decay=1e-5)``.  Returns
     (this package's fused Adam over the same parameters, None) when that optimizer is one the fused launch reproduces --
     exactly torch.optim.Adam, one parameter group, L2 weight decay, no amsgrad / maximize / tensor lr, float32 CUDA
@@ -53,7 +75,8 @@ def _adopt_torch_adam(optimizer):
         built on the caller's object reaches the fused launch (optim.Adam.sync_hyper reads the dict every step);
       * the caller's per-parameter ``exp_avg`` / ``exp_avg_sq`` become views of the fused optimizer's flat buffers (after
         its existing state has been loaded into them), so ``optimizer.state_dict()`` is always current; the per-parameter
-        step counts are written back at the end of every fit() and by close()."""
+        step counts are written back at the end of every fit() and by close().
+    world_size > 1: the fused optimizer sums its gradient buckets over the default process group and averages (1/world)."""
     from .optim import Adam
     if type(optimizer) is not torch.optim.Adam:
         return None, 'the optimizer is %s, not torch.optim.Adam or this package\'s optim.Adam' % type(optimizer).__name__
@@ -70,7 +93,8 @@ def _adopt_torch_adam(optimizer):
         return None, 'parameters that are not float32 CUDA tensors'
     try:
         saved = optimizer.state_dict() if optimizer.state else None
-        new = Adam(g['params'], lr=g['lr'], betas=g['betas'], eps=g['eps'], weight_decay=g['weight_decay'])
+        new = Adam(g['params'], lr=g['lr'], betas=g['betas'], eps=g['eps'], weight_decay=g['weight_decay'],
+                   world_size=world_size)
         if saved is not None:
             new.load_state_dict(saved)
     except (ValueError, RuntimeError) as e:
@@ -92,12 +116,19 @@ class ModelTrainer:
         fusable = type(criterion) is torch.nn.MSELoss and criterion.reduction == 'mean'
         self._fused = fusable and hasattr(model, 'forward_mse')
         from .optim import Adam
+        self._world = distributed.world_size()
+        if self._world > 1 and isinstance(optimizer, Adam) and optimizer.world_size != self._world:
+            raise ValueError('ModelTrainer: optim.Adam(world_size=%d) under a process group of %d ranks -- its gradients '
+                             'would not be averaged over the group; construct it with world_size=%d (or pass a '
+                             'torch.optim.Adam, which is adopted with the right one)'
+                             % (optimizer.world_size, self._world, self._world))
+        self._grad_bucket = None                      # W > 1, optimizers other than this package's Adam: distributed.GradBucket
         self._adopted_from = None
         why = None
         if not self._fused:
             why = 'the criterion is not nn.MSELoss() on a model of this package'
         elif bool(graph) and not isinstance(optimizer, Adam):
-            fused_opt, why = _adopt_torch_adam(optimizer)
+            fused_opt, why = _adopt_torch_adam(optimizer, self._world)
             if fused_opt is not None:
                 self._adopted_from, self.optimizer = optimizer, fused_opt
                 self._push_adopted_state()
@@ -114,6 +145,15 @@ class ModelTrainer:
         # of a run does not depend on which batches happened to be captured.  close() gives the model back to plain autograd.
         if self._fused and isinstance(self.optimizer, Adam):
             self.optimizer.bind_grad_slots()
+        # W > 1: the fused optimizer's flat gradient buffer is cut into the buckets of engine.TrainStep's staged step from the
+        # start, so that an eager optimizer.step() all-reduces the same two buckets in the same order as a replay (optim.Adam.step)
+        self._staged = False
+        if self._world > 1 and isinstance(self.optimizer, Adam) and hasattr(model, 'ddp_late_parameters'):
+            late = model.ddp_late_parameters()
+            params = self.optimizer._params
+            if late and [id(p) for p in params[-len(late):]] == [id(p) for p in late]:
+                self.optimizer.set_bucket_boundaries([late[0]])
+                self._staged = True
         self.graph_steps = self.eager_steps = 0       # diagnostic: how the training batches were run
         # diagnostic: where the HOST spent a training epoch's wall time (seconds, summed over fit()): waiting for the loader,
         # enqueuing the batch's work, waiting for the previous batch's loss; 'epoch_start' = the part of 'loader' before an epoch's
@@ -197,10 +237,11 @@ class ModelTrainer:
             B, K, n, ch = pcm.clips.shape
             step = TrainStep(model, opt, K - 1, n, ch, B, pcm.n_fft, pcm.hop, use_graph=True, device=pcm.clips.device,
                              pcm_dtype=pcm.clips.dtype, track_gains=pcm.gain is not None, normalize=pcm.normalize,
-                             copy_mark=True)
+                             copy_mark=True, overlap=self._staged)
         else:
             B, S, F, T = feats.shape
-            step = TrainStep(model, opt, S, batch=B, feature_shape=(F, T), use_graph=True, device=feats.device, copy_mark=True)
+            step = TrainStep(model, opt, S, batch=B, feature_shape=(F, T), use_graph=True, device=feats.device, copy_mark=True,
+                             overlap=self._staged)
         keep = [t.clone() for t in (opt._flat, opt._exp_avg, opt._exp_avg_sq, opt._step)]
         bufs = [(b, b.clone()) for b in model.buffers()]
         training = model.training
@@ -209,7 +250,9 @@ class ModelTrainer:
                 step.bind_clips(pcm.clips, pcm.gain)
             else:
                 step.load_features(feats, target)
-            step.capture(warmup=1)
+            # W > 1: the warm-up is rolled back below, so it exchanges nothing -- this batch's only collectives are those of
+            # the replay that follows, exactly what another rank running the same batch eagerly issues (optim.Adam.step)
+            step.capture(warmup=1, exchange=self._world == 1)
         except BaseException:
             step.close()
             raise
@@ -282,6 +325,7 @@ class ModelTrainer:
         return self._train_device_batch(batch)
 
     def _train_device_batch(self, batch):
+        from .optim import Adam
         pcm = batch if hasattr(batch, 'clips') else None       # data.dataset.PcmBatch: uploaded PCM, front-end not run yet
         if pcm is not None:
             feats = target = None
@@ -309,8 +353,21 @@ class ModelTrainer:
         self.optimizer.zero_grad()
         loss = self._batch_loss(pcm.features() if pcm is not None else (feats, target))
         loss.backward()
-        self.optimizer.step()
+        if self._world > 1 and not isinstance(self.optimizer, Adam):
+            if self._grad_bucket is None:
+                self._grad_bucket = distributed.GradBucket(self._optimizer_params())
+            self._grad_bucket.all_reduce_mean()      # .grad = mean over ranks
+        self.optimizer.step()                        # (this package's Adam all-reduces its own buckets)
         return loss
+
+    def _optimizer_params(self):
+        seen, out = set(), []
+        for g in self.optimizer.param_groups:
+            for p in g['params']:
+                if id(p) not in seen:
+                    seen.add(id(p))
+                    out.append(p)
+        return out
 
     def close(self):
         """Drops the captured step and gives the model's parameters back to ordinary autograd (.grad tensors); an adopted
@@ -346,6 +403,8 @@ class ModelTrainer:
         enqueued, so the host's work for the next batch (loader, copies, launch) runs beside the device's work on this one.
         Same numbers, same lines on stdout, same returned mean; the host never runs more than one batch ahead."""
         total, quiet = 0.0, not _rank0()
+        if self._world > 1:
+            distributed.check_equal_lengths(loader, 'train_loader' if train else 'val_loader')
         n = len(loader) if hasattr(loader, '__len__') else None
         on_gpu = torch.device(self.device).type == 'cuda'
         if on_gpu and getattr(self, '_loss_host', None) is None:
@@ -399,6 +458,7 @@ class ModelTrainer:
             t0 = clock()
         while pending:
             flush()
+        self._epoch_sums = (total, n if n is not None else step)      # (sum of batch losses, batch count): fit()'s global mean
         return total / (n if n is not None else step)
 
     def _train_epoch(self, train_loader):
@@ -408,17 +468,77 @@ class ModelTrainer:
         with torch.no_grad():
             return self._run(val_loader, False)
 
+    # ---- data parallel (W > 1 ranks)
+    def _broadcast_replica(self):
+        """Rank 0's parameters, buffers and fused optimizer state (flat moments, step count) on every rank."""
+        from . import ops
+        from .optim import Adam
+        model, opt = self.model, self.optimizer
+        tensors = list(model.buffers())
+        if isinstance(opt, Adam):
+            own = {id(p) for p in opt._params}
+            tensors += [opt._flat, opt._exp_avg, opt._exp_avg_sq, opt._step]       # (the parameters are views of _flat)
+            tensors += [p for p in model.parameters() if id(p) not in own]
+        else:
+            tensors += list(model.parameters())
+        distributed.broadcast_tensors(tensors, src=0)
+        ops.params_changed()
+
+    def _parameter_digest(self):
+        """ops.digest64 over the trained parameters (the fused optimizer's flat buffer, or every parameter in turn): a CUDA int64."""
+        from . import ops
+        from .optim import Adam
+        if isinstance(self.optimizer, Adam):
+            return ops.digest64(self.optimizer._flat)
+        out, base = None, 0
+        for p in self._optimizer_params():
+            t = p.detach().contiguous().reshape(-1)
+            if t.element_size() != 4:
+                t = t.view(torch.uint8).view(torch.int32)
+            out = ops.digest64(t, out=out, index_base=base, accumulate=out is not None)
+            base += t.numel()
+        return out
+
+    def _check_replicas(self, epoch):
+        """After a training epoch: every rank must hold bit-identical parameters; else every rank raises."""
+        d = int(self._parameter_digest().item())
+        (hi,), (lo,) = distributed.all_reduce_max_min([d])
+        if hi != lo:
+            raise RuntimeError('ModelTrainer: after training epoch %d the %d data-parallel replicas hold different parameters '
+                               '(64-bit digests from %016x to %016x); nothing of this epoch is saved'
+                               % (epoch, self._world, lo & 0xFFFFFFFFFFFFFFFF, hi & 0xFFFFFFFFFFFFFFFF))
+
+    def _global_means(self, train_sums, val_sums):
+        """(train mean, val mean) over every rank's batches, from one all-gather; identical on every rank."""
+        rows = distributed.all_gather_floats(list(train_sums) + list(val_sums))
+        t = [sum(r[i] for r in rows) for i in range(4)]
+        return t[0] / t[1], t[2] / t[3]
+
     def fit(self, train_loader, val_loader, start_epoch, num_epochs):
         history = {'train': [], 'val': []}
         talk = _rank0()
         self._pull_adopted_step()
+        if self._world > 1:
+            self._broadcast_replica()
         for epoch in range(start_epoch, start_epoch + num_epochs):
             if talk:
                 print('Epoch {}/{}'.format(epoch, num_epochs - 1))
-            history['train'].append(self._train_epoch(train_loader))
-            if talk:
-                print('Epoch {} train loss: {:.4f}'.format(epoch, history['train'][-1]))
-            history['val'].append(self._validate_epoch(val_loader))
+            if self._world > 1:
+                # same lines as below, printed once the global means are known (one collective after validation)
+                self._train_epoch(train_loader)
+                train_sums = self._epoch_sums
+                self._check_replicas(epoch)
+                self._validate_epoch(val_loader)
+                tl, vl = self._global_means(train_sums, self._epoch_sums)
+                history['train'].append(tl)
+                history['val'].append(vl)
+                if talk:
+                    print('Epoch {} train loss: {:.4f}'.format(epoch, tl))
+            else:
+                history['train'].append(self._train_epoch(train_loader))
+                if talk:
+                    print('Epoch {} train loss: {:.4f}'.format(epoch, history['train'][-1]))
+                history['val'].append(self._validate_epoch(val_loader))
             if talk:
                 print('Epoch {} val loss: {:.4f}'.format(epoch, history['val'][-1]))
                 print('-' * 50)

@@ -693,6 +693,23 @@ def adam_l2_step(params, grads, exp_avg, exp_avg_sq, step, derived, lr, beta1, b
                                                _lib.ptr(hyper), _lib.stream()), 'dam_adam_l2_step_f32')
 
 
+def digest64(t, out=None, index_base=0, accumulate=False, max_blocks=0):
+    """Order-independent 64-bit digest of the bit patterns of a contiguous CUDA tensor of 4-byte elements
+    (include/dam_hip.h: dam_digest64_u32).  Returns ``out``: a CUDA int64 tensor of one element (the uint64 digest's bits),
+    added to when ``accumulate`` -- digest a tensor list piece by piece with index_base = the running element count."""
+    _lib.require_cuda(t, out)
+    if t.element_size() != 4 or not t.is_contiguous():
+        raise ValueError('digest64: a contiguous tensor of 4-byte elements expected (got %s, contiguous=%s)'
+                         % (t.dtype, t.is_contiguous()))
+    if out is None:
+        out = torch.empty(1, dtype=torch.int64, device=t.device)
+    elif out.dtype != torch.int64 or out.numel() != 1 or not out.is_contiguous():
+        raise ValueError('digest64: out must be a contiguous int64 tensor of one element')
+    _lib.check(_lib.lib().dam_digest64_u32(_lib.ptr(t) if t.numel() else None, t.numel(), int(index_base), int(max_blocks),
+                                           int(bool(accumulate)), _lib.ptr(out), _lib.stream()), 'dam_digest64_u32')
+    return out
+
+
 # ----------------------------------------------------------------------------- inference tail
 def _audio_kind(t, what):
     if t.dtype not in (torch.float32, torch.float64):

@@ -197,7 +197,10 @@ class Adam(torch.optim.Optimizer):
                 loss = closure()
         self.sync_hyper()
         self.gather_grads()
-        self.all_reduce_grads()
+        # bucket by bucket, the LAST one first: the collective sequence of engine.TrainStep's staged graphs (deep bucket, then
+        # shallow one), so that ranks may mix eager and replayed steps; with one bucket this is the whole flat buffer
+        for b in reversed(range(self.n_buckets)):
+            self.all_reduce_grads(b)
         self.launch_update()
         return loss
 

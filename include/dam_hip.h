@@ -56,7 +56,7 @@ struct dam_bn_bwd_sums; /* defined in the BatchNorm section */
 /* Library / build identification ("gfx950").  DAM_ABI_VERSION is bumped whenever a signature below changes; a binding
  * compares dam_abi_version() of the library it loaded with the version it was written against and refuses a stale one
  * (deep-audio-mixer_amd/_lib.py: EXPECTED_ABI). */
-#define DAM_ABI_VERSION 15
+#define DAM_ABI_VERSION 16
 const char* dam_arch(void);
 int dam_abi_version(void);
 
@@ -464,6 +464,17 @@ int dam_masksum_mse_f32(const float* x, const float* gains, const float* gt, int
 int dam_adam_l2_step_f32(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, int64_t n,
                          int64_t* step, float* derived2, float lr, float beta1, float beta2, float eps,
                          float weight_decay, float grad_scale, const float* hyper_dev, void* stream);
+
+/* Replica digest (ABI 16).  The reference trains on one device; the data-parallel ModelTrainer (model_trainer.py) checks
+ * after every training epoch that its replicas still hold bit-identical parameters by comparing this digest over ranks.
+ *   *out (+)= sum over i in [0, n) of mix64(x[i] + (index_base + i) * 0x9E3779B97F4A7C15)   (modulo 2^64)
+ * x: n 32-bit words (any 4-byte type, read as bit patterns: NaN payloads and -0.0 count as distinct); mix64 = splitmix64's
+ * finaliser.  The sum is order-independent: the result does not depend on the launch geometry, and a buffer digested in
+ * pieces (accumulate = 1, each piece with its index_base) equals the one-launch digest.  accumulate = 0 zeroes *out first.
+ * max_blocks: 0 = the library's choice, else an upper bound on the grid (tests vary it).  out: device uint64, 8-byte
+ * aligned, written with a global atomic. */
+int dam_digest64_u32(const uint32_t* x, int64_t n, int64_t index_base, int max_blocks, int accumulate, uint64_t* out,
+                     void* stream);
 
 /* ---------------------------------------------------------------------------------
  * Full-song inference tail (BASELINE config C5), all on the device so that the whole of
