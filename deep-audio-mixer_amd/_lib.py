@@ -12,7 +12,7 @@ LIB_PATH = os.environ.get('DAM_LIB_PATH') or os.path.join(_HERE, 'libdam_hip.so'
 # include/dam_hip.h: bumped whenever a C signature changes (together with dam_abi_version() in csrc/dam_api.hip and
 # DAM_ABI_VERSION in the header).  libdam_hip.so is git-ignored and travels prebuilt: a stale one would read device pointers
 # as streams, so lib() refuses it instead of launching.
-EXPECTED_ABI = 16
+EXPECTED_ABI = 17
 
 _STATUS = {0: 'DAM_OK', -1: 'DAM_ERR_BAD_ARG', -2: 'DAM_ERR_UNSUPPORTED', -3: 'DAM_ERR_LAUNCH',
            -4: 'DAM_ERR_WORKSPACE'}
@@ -35,6 +35,11 @@ SIGNATURES = {
     'dam_stft_logmag_f32': (c_i, [c_p, c_i, c_i64, c_i64, c_i, c_i64, c_p, c_p, c_p, c_i, c_i, c_f, c_i, c_p, c_p]),
     'dam_stft_logmag_strided_f32': (c_i, [c_p, c_i, c_i64, c_i64, c_i64, c_i64, c_i64, c_i, c_i64, c_i64, c_p, c_p, c_p,
                                           c_i, c_i, c_f, c_i, c_p, c_p, c_i, c_p]),
+    'dam_stft_complex_f32': (c_i, [c_p, c_i, c_i64, c_i64, c_i, c_i64, c_i64, c_i64, c_p, c_p, c_p, c_i, c_i, c_p, c_p]),
+    'dam_stft_complex_strided_f32': (c_i, [c_p, c_i, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_i, c_i64, c_i64,
+                                           c_p, c_p, c_p, c_i, c_i, c_p, c_p]),
+    'dam_istft_workspace_bytes': (c_i64, [c_i64, c_i64, c_i, c_i, c_i64]),
+    'dam_istft_f32': (c_i, [c_p, c_p, c_i64, c_i64, c_i, c_i, c_i64, c_p, c_p, c_p, c_p, c_i64, c_p]),
     'dam_augment_gains_f32': (c_i, [ctypes.c_uint64, c_p, c_i64, c_i, c_i, c_f, c_f, c_p, c_p]),
     'dam_conv_packed_weight_count': (c_i64, [c_i, c_i, c_i, c_i]),
     'dam_conv_pack_weights_f32': (c_i, [c_p, c_i, c_i, c_i, c_i, c_i, c_p, c_p]),

@@ -9,6 +9,7 @@
 // workgroup = 8 waves = 8 consecutive frames of one track, whose dB values are transposed through LDS into the reference
 // layout out[track][bin][frame].  Details at stft2048_kernel below; other window sizes: stft_generic_kernel.
 #include "dam_common.h"
+#include "dam_fft_lds.h"
 
 namespace dam {
 namespace {
@@ -464,6 +465,47 @@ __global__ __launch_bounds__(256) void stft_generic_kernel(
     }
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// The front-end up to, but not including, |.| -> dB: the complex bins of torch.stft(return_complex=True), interleaved (re, im).
+// The reference needs them for the PHASES of a mix (experiments.ipynb cells 44 and 50: librosa.stft of the stems' sum, kept to
+// re-synthesise the predicted magnitudes in cell 53).  n_sum tracks, sum_stride apart, are added at load the way the channel
+// mean is formed at load, so "the STFT of the stems' sum" is one launch over the planar song.  One workgroup = one frame, any
+// power-of-two window, the scheme of stft_generic_kernel (not tuned: a listening path, not a training path).
+template <typename PCM, int CH, bool PLANAR>
+__global__ __launch_bounds__(FFT_THREADS) void stft_complex_kernel(
+    const PCM* __restrict__ pcm, int64_t n_samples, int64_t outer_stride, int n_inner, int64_t inner_stride, int n_sum,
+    int64_t sum_stride, int64_t cs, const float* __restrict__ window, const float2* __restrict__ tw /* W_nfft^k */,
+    const float* __restrict__ gain, int n_fft, int hop, int n_frames, float2* __restrict__ out) {
+    extern __shared__ __attribute__((aligned(16))) float2 buf[];      // [2][M]
+    const int tid = threadIdx.x;
+    const int M = n_fft >> 1;
+    const int64_t track = blockIdx.y;
+    const int t = blockIdx.x;
+    const PCM* trk = pcm + (track / n_inner) * outer_stride + (track % n_inner) * inner_stride;
+    const float g = (gain ? gain[track] : 1.0f) * pcm_traits<PCM>::scale;
+    const int64_t p0 = (int64_t)t * hop - M;
+    for (int n = tid; n < M; n += FFT_THREADS) {
+        const int64_t a = reflect(p0 + 2 * n, n_samples), b = reflect(p0 + 2 * n + 1, n_samples);
+        float xa = 0.f, xb = 0.f;
+        for (int s = 0; s < n_sum; ++s) {
+            xa += mono_at<PCM, CH, PLANAR>(trk + s * sum_stride, cs, a);
+            xb += mono_at<PCM, CH, PLANAR>(trk + s * sum_stride, cs, b);
+        }
+        buf[n] = make_float2(xa * (window[2 * n] * g), xb * (window[2 * n + 1] * g));
+    }
+    __syncthreads();
+    const float2* x = lds_fft_radix2<false>(buf, buf + M, M, n_fft, tw, tid);
+    float2* o = out + (track * (int64_t)(M + 1)) * n_frames + t;
+    for (int k = tid; k <= M; k += FFT_THREADS) {
+        const float2 zk = x[k & (M - 1)], zn = x[(M - k) & (M - 1)];
+        const float2 e = make_float2(0.5f * (zk.x + zn.x), 0.5f * (zk.y - zn.y));
+        const float2 od = make_float2(0.5f * (zk.y + zn.y), -0.5f * (zk.x - zn.x));
+        float2 xk = cadd(e, cmul(tw[k & (n_fft - 1)], od));
+        if (k == 0 || k == M) xk.y = 0.f;             // DC and Nyquist of a real signal
+        o[(int64_t)k * n_frames] = xk;
+    }
+}
+
 }  // namespace
 }  // namespace dam
 
@@ -595,4 +637,78 @@ extern "C" int dam_stft_logmag_f32(const void* pcm, int pcm_dtype, int64_t n_tra
                                    void* stream) {
     return dam_stft_logmag_strided_f32(pcm, pcm_dtype, n_tracks, pcm_track_stride, 1, 0, n_samples, channels, channels, 1,
                                        window, twiddles, gain, n_fft, hop, amin, normalize, out, nullptr, 0, stream);
+}
+
+extern "C" int dam_stft_complex_strided_f32(const void* pcm, int pcm_dtype, int64_t n_outer, int64_t outer_stride,
+                                            int64_t n_inner, int64_t inner_stride, int64_t n_sum, int64_t sum_stride,
+                                            int64_t n_samples, int channels, int64_t sample_stride, int64_t channel_stride,
+                                            const float* window, const float* twiddles, const float* gain, int n_fft, int hop,
+                                            float* out, void* stream) {
+    using namespace dam;
+    if (n_outer <= 0 || n_inner <= 0 || n_sum <= 0 || n_samples <= 0 || n_fft <= 0 || hop <= 0) return DAM_ERR_BAD_ARG;
+    if (n_fft < 64 || n_fft > 16384 || (n_fft & (n_fft - 1))) return DAM_ERR_UNSUPPORTED;
+    if (n_samples <= n_fft / 2) return DAM_ERR_BAD_ARG;   // reflect padding needs N > n_fft/2 (torch.stft raises too)
+    if (channels != 1 && channels != 2) return DAM_ERR_UNSUPPORTED;
+    if (pcm_dtype != DAM_PCM_F32 && pcm_dtype != DAM_PCM_F64 && pcm_dtype != DAM_PCM_S16 && pcm_dtype != DAM_PCM_S32)
+        return DAM_ERR_UNSUPPORTED;
+    const int64_t n_tracks = n_outer * n_inner;
+    const int64_t n_frames = 1 + n_samples / hop;
+    if (n_tracks > 65535 || n_inner > 0x7fffffff || n_sum > 0x7fffffff || n_frames > 0x7fffffff / 2) return DAM_ERR_UNSUPPORTED;
+    bool planar;
+    if (channels == 1) {
+        if (sample_stride != 1) return DAM_ERR_UNSUPPORTED;
+        planar = false;
+    } else if (sample_stride == channels && channel_stride == 1) {
+        planar = false;
+    } else if (sample_stride == 1 && channel_stride >= n_samples) {
+        planar = true;
+    } else {
+        return DAM_ERR_UNSUPPORTED;
+    }
+    const bool integer = pcm_dtype == DAM_PCM_S16 || pcm_dtype == DAM_PCM_S32;
+    if (integer && planar) return DAM_ERR_UNSUPPORTED;     // integer PCM is what a WAV decoder hands over: interleaved
+    if (!pcm || !window || !twiddles || !out) return DAM_ERR_BAD_ARG;
+    const dim3 grid((unsigned)n_frames, (unsigned)n_tracks);
+    const size_t lds = (size_t)n_fft * sizeof(float2);        // two buffers of n_fft/2 complex points
+#define DAM_STFT_COMPLEX(T, C, P)                                                                                     \
+    do {                                                                                                              \
+        if (lds > 48 * 1024) {                                     /* 8192 / 16384-point windows: raise the kernel's LDS limit once */ \
+            static PerDevice<bool> raised_pd; bool& raised = raised_pd();\
+            if (!raised) {                                                                                            \
+                if (hipFuncSetAttribute(reinterpret_cast<const void*>(&stft_complex_kernel<T, C, P>),                 \
+                                        hipFuncAttributeMaxDynamicSharedMemorySize, 132 * 1024) != hipSuccess)        \
+                    return DAM_ERR_LAUNCH;                                                                            \
+                raised = true;                                                                                        \
+            }                                                                                                         \
+        }                                                                                                             \
+        hipLaunchKernelGGL((stft_complex_kernel<T, C, P>), grid, dim3(FFT_THREADS), lds, (hipStream_t)stream, (const T*)pcm, \
+                           n_samples, outer_stride, (int)n_inner, inner_stride, (int)n_sum, sum_stride, channel_stride, window, \
+                           reinterpret_cast<const float2*>(twiddles), gain, n_fft, hop, (int)n_frames,                \
+                           reinterpret_cast<float2*>(out));                                                           \
+    } while (0)
+    if (pcm_dtype == DAM_PCM_F32) {
+        if (channels == 1) DAM_STFT_COMPLEX(float, 1, false);
+        else if (planar) DAM_STFT_COMPLEX(float, 2, true);
+        else DAM_STFT_COMPLEX(float, 2, false);
+    } else if (pcm_dtype == DAM_PCM_S16) {
+        if (channels == 1) DAM_STFT_COMPLEX(int16_t, 1, false);
+        else DAM_STFT_COMPLEX(int16_t, 2, false);
+    } else if (pcm_dtype == DAM_PCM_S32) {
+        if (channels == 1) DAM_STFT_COMPLEX(int32_t, 1, false);
+        else DAM_STFT_COMPLEX(int32_t, 2, false);
+    } else {
+        if (channels == 1) DAM_STFT_COMPLEX(double, 1, false);
+        else if (planar) DAM_STFT_COMPLEX(double, 2, true);
+        else DAM_STFT_COMPLEX(double, 2, false);
+    }
+#undef DAM_STFT_COMPLEX
+    DAM_CHECK_LAUNCH();
+    return DAM_OK;
+}
+
+extern "C" int dam_stft_complex_f32(const void* pcm, int pcm_dtype, int64_t n_tracks, int64_t n_samples, int channels,
+                                    int64_t pcm_track_stride, int64_t n_sum, int64_t sum_stride, const float* window,
+                                    const float* twiddles, const float* gain, int n_fft, int hop, float* out, void* stream) {
+    return dam_stft_complex_strided_f32(pcm, pcm_dtype, n_tracks, pcm_track_stride, 1, 0, n_sum, sum_stride, n_samples,
+                                        channels, channels, 1, window, twiddles, gain, n_fft, hop, out, stream);
 }

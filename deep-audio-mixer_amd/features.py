@@ -1,10 +1,12 @@
-"""GPU feature front-end: batched STFT -> |.| -> dB through ``dam_stft_logmag_f32``.
+"""GPU feature front-end: batched STFT -> |.| -> dB through ``dam_stft_logmag_f32``, and the complex pair
+``stft`` / ``istft`` (``dam_stft_complex_f32`` / ``dam_istft_f32``) that turns a spectrogram back into audio.
 
 Mirrors the arithmetic of the reference's ``MultitrackAudioDataset.compute_features``
 (data/dataset.py:132-162) with ``_stereo_to_mono`` (:181-183) and ``_augment_audio``
 (:164-168) fused in, for all tracks of a batch in one launch.
 """
 import ctypes
+import numbers
 
 import numpy as np
 import torch
@@ -96,6 +98,127 @@ def stft_logmag_song_chunks(pcm, n_chunks, chunk_samples, n_fft=2048, hop=1024, 
                                                 S, ch * n, chunk_samples, ch, 1, n, _lib.ptr(win), _lib.ptr(tw), None,
                                                 n_fft, hop, AMIN, 0, _lib.ptr(out), None, 0, _lib.stream())
     _lib.check(st, 'dam_stft_logmag_strided_f32')
+    return out
+
+
+def _check_n_fft(n_fft, hop, n_samples=None):
+    if not isinstance(n_fft, numbers.Integral) or not isinstance(hop, numbers.Integral):
+        raise TypeError('n_fft and hop must be integers')
+    if n_fft < 64 or n_fft > 16384 or n_fft & (n_fft - 1):
+        raise ValueError('n_fft must be a power of two from 64 to 16384')
+    if hop < 1:
+        raise ValueError('hop must be positive')
+    if n_samples is not None and n_samples <= n_fft // 2:
+        raise ValueError('reflect padding needs more than n_fft / 2 samples (got %d)' % n_samples)      # torch.stft raises too
+
+
+def _complex_out(out, shape, device):
+    """-> (complex64 tensor to return, its float32 [..., 2] view the kernel writes)"""
+    if out is None:
+        out = torch.empty(shape, dtype=torch.complex64, device=device)
+    elif out.dtype == torch.float32 and tuple(out.shape) == shape + (2,) and out.is_contiguous():
+        return torch.view_as_complex(out), out
+    elif out.dtype != torch.complex64 or tuple(out.shape) != shape or not out.is_contiguous():
+        raise ValueError('bad out tensor')
+    return out, torch.view_as_real(out)
+
+
+def stft(pcm, n_fft=2048, hop=1024, gain=None, out=None):
+    """The front-end of ``stft_logmag`` without |.| -> dB: pcm as there ([n_tracks, n_samples(, channels)], float32 /
+    float64 / int16 / int32, channels averaged at load, optional per-track gain).  Returns complex64
+    [n_tracks, n_fft/2+1, T] = torch.stft(mono * gain, n_fft, hop, window=hann, center=True, return_complex=True)."""
+    _lib.require_cuda(pcm, gain, out)
+    if pcm.dim() == 2:
+        pcm = pcm.unsqueeze(-1)
+    if pcm.dim() != 3:
+        raise ValueError('pcm must be [tracks, samples(, channels)]')
+    code = _pcm_code(pcm)
+    pcm = pcm.contiguous()
+    n_tracks, n, ch = pcm.shape
+    _check_n_fft(n_fft, hop, n)
+    n_fft, hop = int(n_fft), int(hop)
+    if ch not in (1, 2) or n_tracks < 1:
+        raise ValueError('pcm needs at least one track of 1 or 2 channels')
+    win, tw = _get_tables(pcm.device, n_fft)
+    out, out_f = _complex_out(out, (n_tracks, n_fft // 2 + 1, num_frames(n, hop)), pcm.device)
+    if gain is not None:
+        gain = gain.to(device=pcm.device, dtype=torch.float32).contiguous()
+        if gain.numel() != n_tracks:
+            raise ValueError('gain must have one entry per track')
+    st = _lib.lib().dam_stft_complex_f32(_lib.ptr(pcm), code, n_tracks, n, ch, n * ch, 1, 0, _lib.ptr(win), _lib.ptr(tw),
+                                         _lib.ptr(gain), n_fft, hop, _lib.ptr(out_f), _lib.stream())
+    _lib.check(st, 'dam_stft_complex_f32')
+    return out
+
+
+def stft_song_chunks_sum(pcm, n_chunks, chunk_samples, n_fft=2048, hop=1024, out=None):
+    """pcm: CUDA [S, channels, n] planar, as ``stft_logmag_song_chunks`` takes it -> complex64 [n_chunks, n_fft/2+1, T]:
+    the STFT of the SUM of the stems' channel means over each of chunks 0..n_chunks-1 (experiments.ipynb cell 50: the
+    phases of the summed stems).  The stems are added at load; the song is read in place."""
+    _lib.require_cuda(pcm, out)
+    if pcm.dim() != 3:
+        raise ValueError('pcm must be a float32/float64 [stems, channels, samples] tensor')
+    _check_n_fft(n_fft, hop, chunk_samples)
+    n_fft, hop = int(n_fft), int(hop)
+    code = _pcm_code(pcm, planar=True)
+    pcm = pcm.contiguous()
+    S, ch, n = pcm.shape
+    if n_chunks < 1 or S < 1 or ch not in (1, 2):
+        raise ValueError('pcm needs at least one stem of 1 or 2 channels, and n_chunks must be positive')
+    if n_chunks * chunk_samples > n:
+        raise ValueError('the song is shorter than n_chunks chunks')
+    win, tw = _get_tables(pcm.device, n_fft)
+    out, out_f = _complex_out(out, (n_chunks, n_fft // 2 + 1, num_frames(chunk_samples, hop)), pcm.device)
+    st = _lib.lib().dam_stft_complex_strided_f32(_lib.ptr(pcm), code, n_chunks, chunk_samples, 1, 0, S, ch * n, chunk_samples,
+                                                 ch, 1, n, _lib.ptr(win), _lib.ptr(tw), None, n_fft, hop, _lib.ptr(out_f),
+                                                 _lib.stream())
+    _lib.check(st, 'dam_stft_complex_strided_f32')
+    return out
+
+
+def istft(spec, hop=1024, length=None, mag_db=None, out=None):
+    """spec: CUDA complex64 [n_tracks, n_fft/2+1, T] (or its float32 [..., 2] view) -> float32 [n_tracks, length] =
+    torch.istft(spec, n_fft, hop, window=hann, center=True, length=length); length=None means hop * (T - 1) as in torch.
+    mag_db: optional float32 [n_tracks, n_fft/2+1, T]; the spectrum inverted is then 10 ** (0.05 * mag_db) on the phase
+    of ``spec`` ((1, 0) where ``spec`` is 0) -- experiments.ipynb cell 53, ``db_to_amplitude(masked) * phases``.
+    n_fft is taken from the number of bins; hop must not exceed n_fft / 2.  A ``length`` beyond hop * (T - 1) is accepted
+    where torch raises: up to the last frame's reach, hop * (T - 1) + n_fft / 2, the samples are covered by the falling
+    half of the last frame alone, its sample divided by the window (ill-conditioned as the window goes to 0); past it they are 0."""
+    _lib.require_cuda(spec, mag_db, out)
+    if spec.dtype == torch.complex64:
+        spec_f = torch.view_as_real(spec.contiguous())
+    elif spec.dtype == torch.float32 and spec.dim() >= 1 and spec.shape[-1] == 2:
+        spec_f = spec.contiguous()
+    else:
+        raise TypeError('spec must be complex64 or a float32 [..., 2] view')
+    if spec_f.dim() == 3:
+        spec_f = spec_f.unsqueeze(0)
+    if spec_f.dim() != 4:
+        raise ValueError('spec must be [tracks, bins, frames]')
+    n_tracks, bins, t, _ = spec_f.shape
+    n_fft = 2 * (bins - 1)
+    _check_n_fft(n_fft, hop)
+    if hop > n_fft // 2:
+        raise ValueError('hop must not exceed n_fft / 2 (the squared-window envelope would vanish)')
+    if length is None:
+        length = hop * (t - 1)
+    if not isinstance(length, numbers.Integral):
+        raise TypeError('length must be an integer')
+    hop, length = int(hop), int(length)
+    if length < 1 or t < 1 or n_tracks < 1:
+        raise ValueError('nothing to invert: length, frames and tracks must be positive')
+    if mag_db is not None:
+        if mag_db.dtype != torch.float32 or tuple(mag_db.shape[-2:]) != (bins, t) or mag_db.numel() != n_tracks * bins * t:
+            raise ValueError('mag_db must be a float32 tensor of the shape of spec')
+        mag_db = mag_db.contiguous()
+    win, tw = _get_tables(spec_f.device, n_fft)
+    if out is None:
+        out = torch.empty((n_tracks, length), dtype=torch.float32, device=spec_f.device)
+    elif tuple(out.shape) != (n_tracks, length) or out.dtype != torch.float32 or not out.is_contiguous():
+        raise ValueError('bad out tensor')
+    st = _lib.lib().dam_istft_f32(_lib.ptr(spec_f), _lib.ptr(mag_db), n_tracks, t, n_fft, hop, length, _lib.ptr(win),
+                                  _lib.ptr(tw), _lib.ptr(out), None, 0, _lib.stream())
+    _lib.check(st, 'dam_istft_f32')
     return out
 
 

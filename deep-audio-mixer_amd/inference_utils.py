@@ -9,8 +9,10 @@ Everything between the PCM upload and the result download stays on the device an
 hipGraph (``SongMixer``): strided STFT front-end over all chunks of all stems straight out of the planar song
 (dam_stft_logmag_strided_f32) -> model forward of the whole chunk batch -> 10 ** (0.5 g) and the Savitzky-Golay
 smoothing (dam_gains_smooth) -> sample-rate gain ramp x audio (dam_gain_ramp_apply), or for ``mix_song_to_master`` the
-fused stem sum + peak normalisation (dam_mixdown_peak_normalize).  The host sees the song once on the way in (page-locked
-double-buffered staging, staging.PinnedPipe) and the result once on the way out.
+fused stem sum + peak normalisation (dam_mixdown_peak_normalize).  ``mix_song_spectral`` renders in the spectral domain
+instead (experiments.ipynb cells 44-53): the model's predicted dB spectrogram ``masked`` on the phases of the stems' sum
+(dam_stft_complex_strided_f32), inverted by dam_istft_f32 -- the same graph with a different tail.  The host sees the
+song once on the way in (page-locked double-buffered staging, staging.PinnedPipe) and the result once on the way out.
 
 The model is applied as the reference applies it -- whatever ``model.training`` is, never toggled here:
 in eval mode all chunks run as one batch inside the graph; in training mode BatchNorm uses per-call batch statistics
@@ -59,8 +61,8 @@ class SongMixer:
     chunk length, output kind).  ``run(tracks)`` uploads, replays, downloads."""
 
     def __init__(self, model, n_stems, channels, n_samples, dtype, chunk_samples, kind, normalize=True,
-                 out_dtype=torch.float64, use_graph=True):
-        if kind not in ('stems', 'master'):
+                 out_dtype=torch.float64, use_graph=True, hop_length=1024):
+        if kind not in ('stems', 'master', 'spectral'):
             raise ValueError(kind)
         self.model, self.kind, self.normalize = model, kind, normalize
         self.dev = next(model.parameters()).device
@@ -69,16 +71,23 @@ class SongMixer:
         self.n_proc = self.num_chunks - 1
         if self.n_proc < 1:
             raise ValueError('the song must hold at least two chunks')
+        self.hop = hop_length
         self.window = _savgol_window(self.num_chunks)
-        if self.window <= SAVGOL_POLYORDER or self.window > self.n_proc:
+        # (the spectral kind smooths nothing: a song of two chunks is valid there)
+        if kind != 'spectral' and (self.window <= SAVGOL_POLYORDER or self.window > self.n_proc):
             # scipy.signal.savgol_filter raises for these at inference_utils.py:140
             raise ValueError('polyorder must be less than window_length and window_length must not exceed the number '
                              'of gains (window %d, %d gains)' % (self.window, self.n_proc))
         dev = self.dev
         self.pcm = torch.empty((n_stems, channels, n_samples), dtype=dtype, device=dev)
-        t = features.num_frames(chunk_samples, 1024)
+        t = features.num_frames(chunk_samples, hop_length)
         self.feats = torch.empty((self.n_proc * n_stems, 1025, t), dtype=torch.float32, device=dev)
-        if kind == 'stems':
+        if kind == 'spectral':
+            self.spec = torch.empty((self.n_proc, 1025, t), dtype=torch.complex64, device=dev)     # phase source
+            self.masked = None                                                                       # set by every launch
+            self.out = torch.empty((self.n_proc, chunk_samples), dtype=torch.float32, device=dev)
+            self.ws = None
+        elif kind == 'stems':
             self.out = torch.empty((n_stems, channels, n_samples), dtype=out_dtype, device=dev)
             self.ws = None
         else:
@@ -89,8 +98,24 @@ class SongMixer:
         self.use_graph = use_graph
         self._key = None
 
+    def _body_spectral(self):
+        """experiments.ipynb cells 44-53 for every chunk: masked = model(dB features of the stems)[0], the phases of the STFT
+        of the stems' sum, istft(db_to_amplitude(masked) * phases).  Each chunk is its own centred STFT, so the chunks are
+        independent tracks of one batched launch."""
+        feats = features.stft_logmag_song_chunks(self.pcm, self.n_proc, self.chunk, 2048, self.hop, out=self.feats)
+        feats = feats.view(self.n_proc, self.n_stems, feats.shape[1], feats.shape[2])
+        if self.model.training:
+            self.masked = torch.cat([self.model(feats[i:i + 1])[0] for i in range(self.n_proc)], 0)
+        else:
+            self.masked = self.model(feats)[0]            # (captured: the graph's own static output)
+        features.stft_song_chunks_sum(self.pcm, self.n_proc, self.chunk, 2048, self.hop, out=self.spec)
+        features.istft(self.spec, self.hop, self.chunk, mag_db=self.masked, out=self.out)
+
     def _body(self):
-        g = predict_chunk_gains(self.model, self.pcm, self.n_stems, self.num_chunks, self.chunk, feats=self.feats)
+        if self.kind == 'spectral':
+            return self._body_spectral()
+        g = predict_chunk_gains(self.model, self.pcm, self.n_stems, self.num_chunks, self.chunk, hop_length=self.hop,
+                                feats=self.feats)
         _, smooth = ops.gains_smooth(g, self.window, SAVGOL_POLYORDER, out=self.gains)
         if self.kind == 'stems':
             ops.gain_ramp_apply(self.pcm, smooth, out=self.out)
@@ -132,23 +157,25 @@ class SongMixer:
             pipe.upload(self.pcm[i], a)
         self.launch()
         out = pipe.download(self.out)
+        if self.kind == 'spectral':
+            return out.reshape(-1), pipe.download(self.masked)
         return out, self.gains.cpu().numpy()
 
 
 _mixers = {}
 
 
-def _mixer(model, stems, loaded_tracks, chunk_length, sr, kind, normalize, out_dtype):
+def _mixer(model, stems, loaded_tracks, chunk_length, sr, kind, normalize, out_dtype, hop_length=1024):
     first = np.asarray(loaded_tracks[stems[0]])
     if first.ndim != 2:
         raise ValueError('loaded_tracks[track] must be [channels, n] arrays')
     ch, n = first.shape
     dt = torch.float32 if first.dtype == np.float32 else torch.float64
-    key = (id(model), len(stems), ch, n, dt, chunk_length * sr, kind, bool(normalize), out_dtype)
+    key = (id(model), len(stems), ch, n, dt, chunk_length * sr, kind, bool(normalize), out_dtype, hop_length)
     m = _mixers.get(key)
     if m is None:
         _mixers.clear()                        # one geometry at a time: a song's buffers are hundreds of MB
-        m = SongMixer(model, len(stems), ch, n, dt, chunk_length * sr, kind, normalize, out_dtype)
+        m = SongMixer(model, len(stems), ch, n, dt, chunk_length * sr, kind, normalize, out_dtype, hop_length=hop_length)
         _mixers[key] = m
     np_dt = np.float32 if dt == torch.float32 else np.float64
     return m, [np.asarray(loaded_tracks[t], dtype=np_dt) for t in stems]
@@ -175,3 +202,16 @@ def mix_song_to_master(dataset, model, loaded_tracks: dict, chunk_length=1, sr=4
     out, gains = m.run(arrays)
     raw_gains = {t: [float(v) for v in gains[0, i]] for i, t in enumerate(stems)}
     return out, raw_gains, {t: list(gains[1, i]) for i, t in enumerate(stems)}
+
+
+def mix_song_spectral(dataset, model, loaded_tracks: dict, chunk_length=1, sr=44100, hop_length=1024, dtype=np.float32):
+    """Spectral-domain rendering of a whole song, experiments.ipynb cells 44-53 chunk by chunk, chunked exactly as
+    mix_song_smooth chunks it (chunks 0 .. num_chunks-2).  Per chunk: dB features of every stem's channel mean ->
+    ``masked = model(features)[0]``, the predicted mix spectrogram in dB; the phases are those of the STFT of the sum of
+    the stems' channel means over the same chunk; chunk audio = istft(10 ** (masked / 20) * phases, length=chunk samples).
+    Returns (audio ndarray [n_proc * chunk_length * sr] mono of ``dtype``, masked_db ndarray [n_proc, 1025, T] float32).
+    Nothing is peak-normalised (the cells do not): ``masked`` is unbounded, and so is the output."""
+    stems = [t for t in dataset.get_tracklist() if t != 'mix']
+    m, arrays = _mixer(model, stems, loaded_tracks, chunk_length, sr, 'spectral', False, torch.float32, hop_length)
+    audio, masked = m.run(arrays)
+    return audio.astype(dtype, copy=False), masked

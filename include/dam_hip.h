@@ -56,7 +56,7 @@ struct dam_bn_bwd_sums; /* defined in the BatchNorm section */
 /* Library / build identification ("gfx950").  DAM_ABI_VERSION is bumped whenever a signature below changes; a binding
  * compares dam_abi_version() of the library it loaded with the version it was written against and refuses a stale one
  * (deep-audio-mixer_amd/_lib.py: EXPECTED_ABI). */
-#define DAM_ABI_VERSION 16
+#define DAM_ABI_VERSION 17
 const char* dam_arch(void);
 int dam_abi_version(void);
 
@@ -146,6 +146,48 @@ int dam_stft_logmag_strided_f32(const void* pcm, int pcm_dtype, int64_t n_outer,
                                 int64_t channel_stride, const float* window, const float* twiddles, const float* gain,
                                 int n_fft, int hop, float amin, int normalize, float* out, float* out_tail, int n_tail,
                                 void* stream);
+
+/* Complex spectra and their inverse (ABI 17).  The reference listens to a prediction in experiments.ipynb: cell 44 takes
+ * librosa.stft of every stem, cell 50 the stft of the stems' sum and keeps its PHASES, cell 53 re-synthesises
+ * librosa.istft(db_to_amplitude(masked) * phases, hop_length=512) from the predicted dB spectrogram `masked`
+ * (the quantity data/dataset.py:145-149 computes with torch.stft and every model here is trained on).
+ *
+ * dam_stft_complex_f32: the front-end above up to, but not including, |.| -> dB:
+ *   out[track][f][t] = (re, im) float32 = torch.stft(sum_s mean_c pcm[track + s][:, c] * gain[track], n_fft, hop,
+ *   window=w, center=True, return_complex=True).  PCM conventions as dam_stft_logmag_f32 (dtypes, 1 or 2 channels averaged
+ *   at load, optional gain, float32 Hann table, the twiddle table).  n_sum >= 1 tracks, sum_stride elements apart, are
+ *   ADDED at load (float32, ascending s): the "STFT of the stems' sum" of cell 50 without a torch kernel for the sum.
+ *   dam_stft_complex_strided_f32 addresses tracks like dam_stft_logmag_strided_f32 (for all chunks of a planar song:
+ *   outer = chunk, n_inner = 1, n_sum = stems).  out: [n_tracks][n_fft/2+1][T] float2, T = 1 + n_samples/hop; the
+ *   imaginary parts of the DC and Nyquist bins are 0.  n_fft: a power of two from 64 to 16384, hop >= 1; every size runs
+ *   the one-workgroup-per-frame kernel.
+ *
+ * dam_istft_f32: torch.istft(spec, n_fft, hop, window=w, center=True, normalized=False, onesided=True, length=length):
+ *   out[track][n] = (sum_t w[j] irfft(X[track][:, t])[j]) / (sum_t w[j]^2),  j = n + n_fft/2 - t*hop in [0, n_fft),
+ *   0 <= n < length; samples no frame covers (envelope <= 1e-11, torch's threshold) are 0.
+ *   spec   : [n_tracks][n_fft/2+1][n_frames] float2 (re, im)
+ *   mag_db : optional [n_tracks][n_fft/2+1][n_frames] float32; the bin used is then 10^(0.05 mag_db) * spec/|spec|, the phase
+ *            of spec ((1, 0) where spec == 0): cell 53 without a phase tensor.  The imaginary parts of the DC and Nyquist
+ *            bins are ignored, as irfft ignores them.
+ *   window, twiddles : the tables the forward uses (synthesis window = analysis window)
+ *   out    : [n_tracks][length] float32
+ *   workspace : dam_istft_workspace_bytes(...) bytes (0 today: may be nullptr), DAM_ERR_WORKSPACE if smaller.
+ * Accepted: n_fft a power of two from 64 to 16384 and 1 <= hop <= n_fft/2 (for Hann the envelope is then >= 0.5 on every
+ * covered sample); anything else is DAM_ERR_UNSUPPORTED before the device is touched -- torch raises for a vanishing
+ * envelope, this refuses the geometries where one can occur.  Deterministic: every sample is the sum of its covering
+ * frames in frame order (a gather, no atomics), identical bits between runs and batch sizes.  Enqueued on `stream`,
+ * no synchronisation, no allocation, capturable. */
+int dam_stft_complex_f32(const void* pcm, int pcm_dtype, int64_t n_tracks, int64_t n_samples, int channels,
+                         int64_t pcm_track_stride, int64_t n_sum, int64_t sum_stride, const float* window,
+                         const float* twiddles, const float* gain, int n_fft, int hop, float* out, void* stream);
+int dam_stft_complex_strided_f32(const void* pcm, int pcm_dtype, int64_t n_outer, int64_t outer_stride, int64_t n_inner,
+                                 int64_t inner_stride, int64_t n_sum, int64_t sum_stride, int64_t n_samples, int channels,
+                                 int64_t sample_stride, int64_t channel_stride, const float* window, const float* twiddles,
+                                 const float* gain, int n_fft, int hop, float* out, void* stream);
+int64_t dam_istft_workspace_bytes(int64_t n_tracks, int64_t n_frames, int n_fft, int hop, int64_t length);
+int dam_istft_f32(const float* spec, const float* mag_db, int64_t n_tracks, int64_t n_frames, int n_fft, int hop,
+                  int64_t length, const float* window, const float* twiddles, float* out, void* workspace,
+                  int64_t workspace_bytes, void* stream);
 
 /* The augmentation draw of data/dataset.py:164-168,198-199 (one uniform gain per track of an item, the mix included)
  * made on the device and reproducibly: gains[i][k] = lo + (hi - lo) * u(seed, item_i, k), u in [0, 1) a counter-based
