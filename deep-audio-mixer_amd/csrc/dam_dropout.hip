@@ -1,9 +1,13 @@
 // dam_dropout.hip -- inverted dropout for the scalar models' ConvBlock2d (models/model_scalar_1s.py:177,187-188,
 // models/model_scalar_2s.py:35,45-46: nn.Dropout(p) applied only while self.training).
 //
-// torch's Philox stream cannot be reproduced bit for bit outside torch, so parity here is distributional: every element
-// is kept with probability 1-p and scaled by 1/(1-p).  The mask is a pure function of (seed, call offset, element
-// index) -- a counter-based generator, nothing is stored: the backward pass regenerates it from the saved offset.
+// torch's Philox stream cannot be reproduced bit for bit outside torch, so parity with the REFERENCE is distributional:
+// every element is kept with probability 1-p and scaled by 1/(1-p).  The mask is a pure function of (seed, call offset,
+// element index) -- a counter-based generator, nothing is stored: the backward pass regenerates it from the saved offset.
+//   base = seed * 0xD1342543DE82EF95 + offset;  r_i = high 32 bits of the splitmix64 finaliser of (base + i);
+//   keep_i = r_i >= (unsigned)(p * 2^32);  y_i = keep_i ? x_i * (1.0f / (1.0f - p)) : 0        (all wrap-around uint64)
+// oracle/dropout_ref.py restates exactly this on the host, so the float64 oracle applies the same mask and dropout-on
+// training is compared like everything else (tests/test_dropout_gpu.py: bit for bit).
 // The call offset lives on the DEVICE (dam_dropout_tick advances it), so captured hipGraphs draw fresh masks on replay.
 #include "dam_common.h"
 

@@ -290,6 +290,7 @@ class DropoutFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, p):
+        ops.dropout_check(x.numel(), p)         # a call the kernel would refuse must not advance the counter
         snap = ops.dropout_tick(x.device, x.numel())
         ctx.p, ctx.seed = p, torch.initial_seed()
         ctx.save_for_backward(snap)

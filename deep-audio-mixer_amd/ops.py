@@ -788,13 +788,37 @@ def mixdown_peak_normalize(audio, gains, normalize=True, out=None, out_dtype=Non
 _dropout_counters = {}
 
 
-def dropout_tick(device, n):
-    """Snapshots and advances the per-device dropout call counter; returns the snapshot tensor (int64[1])."""
-    key = (device.type, device.index)
+def _dropout_counter(device):
+    device = torch.device(device)
+    key = (device.type, torch.cuda.current_device() if device.index is None else device.index)
     if key not in _dropout_counters:
         _dropout_counters[key] = torch.zeros(1, dtype=torch.int64, device=device)
+    return _dropout_counters[key]
+
+
+def dropout_counter(device):
+    """The per-device dropout call counter as a Python int (synchronises): the offset the next dropout call will use."""
+    return int(_dropout_counter(device).item())
+
+
+def set_dropout_counter(device, value):
+    """Sets the per-device dropout call counter (in stream order): resuming a run at a known offset, and the tests."""
+    _dropout_counter(device).fill_(int(value))
+
+
+def dropout_check(n, p):
+    """The argument checks of dam_dropout_apply_f32, for callers that must know BEFORE they advance the counter."""
+    if n <= 0 or n % 4:
+        raise ValueError('dropout: the element count must be a positive multiple of 4, got %d' % n)
+    if not 0.0 <= p < 1.0:
+        raise ValueError('dropout: p must lie in [0, 1), got %r' % (p,))
+
+
+def dropout_tick(device, n):
+    """Snapshots and advances the per-device dropout call counter; returns the snapshot tensor (int64[1])."""
+    counter = _dropout_counter(device)
     snap = torch.empty(1, dtype=torch.int64, device=device)
-    _lib.check(_lib.lib().dam_dropout_tick(_lib.ptr(_dropout_counters[key]), n, _lib.ptr(snap), _lib.stream()), 'dam_dropout_tick')
+    _lib.check(_lib.lib().dam_dropout_tick(_lib.ptr(counter), n, _lib.ptr(snap), _lib.stream()), 'dam_dropout_tick')
     return snap
 
 

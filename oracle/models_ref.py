@@ -94,18 +94,28 @@ class RefResNet18(_Heads):
 
 class RefConvBlock2d(nn.Module):
     """models/model_scalar_1s.py:151-190: valid conv(+bias) -> BN(eps 1e-3, momentum .9)
-    -> ReLU -> Dropout only while training."""
+    -> ReLU -> Dropout only while training.
+
+    keep_mask (None: torch draws the mask, as in the reference): a bool tensor of the block's output shape (NCHW) given
+    from outside -- oracle/dropout_ref.py restates the product's generator -- applied as y * keep * 1/(1-p) in y's dtype."""
 
     def __init__(self, cin, cout, k, stride=1, dilation=1, dropout_p=-1.0):
         super().__init__()
         self.conv = nn.Conv2d(cin, cout, k, stride, 0, dilation)
         self.batch_norm = nn.BatchNorm2d(cout, momentum=0.90, eps=0.001)
         self.dropout_p = dropout_p
+        self.keep_mask = None
 
     def forward(self, x):
         y = F.relu(self.batch_norm(self.conv(x)))
         if self.training and self.dropout_p != -1:
-            y = F.dropout(y, self.dropout_p, True)
+            if self.keep_mask is None:
+                y = F.dropout(y, self.dropout_p, True)
+            else:
+                if self.keep_mask.shape != y.shape or self.keep_mask.dtype != torch.bool:
+                    raise ValueError('keep_mask: bool %s expected, got %s %s'
+                                     % (tuple(y.shape), self.keep_mask.dtype, tuple(self.keep_mask.shape)))
+                y = y * self.keep_mask.to(y.dtype) * (y.new_ones(()) / (1 - y.new_tensor(self.dropout_p)))
         return y
 
 
@@ -117,6 +127,23 @@ def scalar_trunk_hw(f, t, first_dilation):
         s, d = (2, first_dilation) if i == 0 else (1, 1)
         f, t = conv_out(f, k, s, d), conv_out(t, k, s, d)
     return f, t
+
+
+def scalar_block_shapes(batch, f, t, first_dilation):
+    """[B, Ho, Wo, C] of the five blocks' outputs (the layout the product's dropout kernel indexes)."""
+    out = []
+    for i, (w, k, _) in enumerate(SCALAR_BLOCKS):
+        s, d = (2, first_dilation) if i == 0 else (1, 1)
+        f, t = conv_out(f, k, s, d), conv_out(t, k, s, d)
+        out.append((batch, f, t, w))
+    return out
+
+
+def set_keep_masks(model, masks):
+    """Hands the five blocks of a scalar model their dropout masks (bool NCHW tensors; None: back to torch's own draw)."""
+    for i in range(1, 6):
+        getattr(model, 'conv_b%d' % i).keep_mask = None if masks is None else masks[i - 1]
+    return model
 
 
 class _RefScalar(_Heads):

@@ -9,13 +9,20 @@ the oracle step by step).  A free-running comparison is meaningless after the fi
 a fresh network are chaotic at the 1e-2 level -- measured on the oracle itself, float32 against float64 from identical
 weights and clips: loss 3e-7 / 2.7e-3 / 2.7e-2 apart at steps 1 / 2 / 3, gains 4e-6 / 1.8e-2 / 6e-2 (tools/ note in DESIGN.md
 section 2).  Step by step, everything is deterministic and tight: forward at north_star's 1e-4, the optimizer at float32
-rounding; gradients at the whole-model tolerance (ReLU decision flips, see tests/test_blocks_gpu.py for the tight check)."""
+rounding; gradients at the whole-model tolerance (ReLU decision flips, see tests/test_blocks_gpu.py for the tight check).
+
+C1 and C2 (the scalar models) are pinned twice: with dropout stripped, and AS BUILT -- bench.build_model returns them in
+train() mode with dropout on, and that is what bench.py times.  The device's dropout mask is a pure function of
+(torch.initial_seed(), the device-side call counter, element index); oracle/dropout_ref.py restates it on the host, so in
+the `_with_dropout` tests the oracle applies the SAME masks, at the offset the counter had before each replay, and every
+threshold is the dropout-off one.  They also assert that a replay advances the counter exactly as an eager step does, that
+block 1's output is exactly zero wherever the host mask drops, and that the three replays' block-1 masks differ."""
 import numpy as np
 import pytest
 import torch
 
 from _inputs import feature_error
-from oracle import features_ref, models_ref
+from oracle import dropout_ref, features_ref, models_ref
 
 pytestmark = pytest.mark.gpu
 
@@ -41,8 +48,8 @@ def _ref_named_flat(model, flat, opt):
 
 
 def _no_dropout(m):
-    """Dropout (scalar models, training mode) has its own counter-based generator on the device: it cannot match torch's
-    Philox stream and is tested distributionally (tests/test_models_gpu.py); the step-by-step comparison runs without it."""
+    """The dropout-off form of the comparison (the `_with_dropout` tests run the models as built, the oracle applying the
+    host restatement of the device's masks)."""
     for mod in m.modules():
         if hasattr(mod, 'dropout_p'):
             mod.dropout_p = -1          # oracle blocks
@@ -51,7 +58,7 @@ def _no_dropout(m):
     return m
 
 
-def _captured_step_matches_oracle(cfg_name, ref_ctor, feature_pairs, bn_keys, expect_descent=False):
+def _captured_step_matches_oracle(cfg_name, ref_ctor, feature_pairs, bn_keys, expect_descent=False, dropout=False):
     import bench
     from deep_audio_mixer_amd.engine import TrainStep
     from deep_audio_mixer_amd.optim import Adam
@@ -59,7 +66,16 @@ def _captured_step_matches_oracle(cfg_name, ref_ctor, feature_pairs, bn_keys, ex
     S, Bsz, hop = cfg['n_stems'], cfg['batch'], cfg['hop']
     n = cfg['sr'] * cfg['seconds']
     device = torch.device('cuda', 0)
-    model = _no_dropout(bench.build_model(cfg, device))
+    strip = (lambda m: m) if dropout else _no_dropout
+    model = strip(bench.build_model(cfg, device))
+    assert model.training
+    b1_out = {}
+    if dropout:
+        from deep_audio_mixer_amd import ops
+        assert [getattr(model, 'conv_b%d' % i).dropout.p for i in range(1, 6)] == [0.2, 0.2, 0.2, 0.2, 0.3]
+        # block 1's output of the captured forward stays referenced, so the graph's pool does not hand its memory to a later
+        # allocation and it can be read after every replay (no launch is added to the step)
+        model.conv_b1.register_forward_hook(lambda mod, inp, out: b1_out.__setitem__('out', out.detach()))
     state0 = _ref_state(model)
     lr, wd, b1, b2, eps = 1e-3, 1e-5, 0.9, 0.999, 1e-8
     opt = Adam(model.parameters(), weight_decay=wd)
@@ -67,15 +83,27 @@ def _captured_step_matches_oracle(cfg_name, ref_ctor, feature_pairs, bn_keys, ex
     clips = bench.synth_clips(n_steps * Bsz, S, n, device, 1234)
     step = TrainStep(model, opt, S, n, bench.CHANNELS, Bsz, bench.N_FFT, hop, use_graph=True)
     step.load_clips(clips[:Bsz])
+    F_, T_ = bench.N_FFT // 2 + 1, 1 + n // hop
+    if dropout:
+        shapes = models_ref.scalar_block_shapes(Bsz, F_, T_, ref_ctor.first_dilation)
+        per_step = sum(int(np.prod(sh)) for sh in shapes)
+        c_before = ops.dropout_counter(device)
     step.capture(warmup=2)
     assert step._graphs is not None and len(step._graphs) == 1            # one hipGraph holds the whole step
+    if dropout:
+        # two eager warm-up steps drew per_step counters each; capturing draws nothing
+        assert ops.dropout_counter(device) == c_before + 2 * per_step
+        assert tuple(b1_out['out'].shape) == shapes[0]
+        drop_seed = torch.initial_seed()            # (bench.build_model seeds torch; the captured launches carry this seed)
+        ps = [b[2] for b in models_ref.SCALAR_BLOCKS]
+        b1_masks = []
     # rewind to the initial replica (capture's eager warm-up steps moved parameters, moments and running statistics)
     model.load_state_dict({k: v.to(device) for k, v in state0.items()})
     opt._exp_avg.zero_(), opt._exp_avg_sq.zero_(), opt._step.zero_()
 
     torch.set_num_threads(16)
-    ref = _no_dropout(ref_ctor(n_stems=S, input_shape=(bench.N_FFT // 2 + 1, 1 + n // hop))).double().train()
-    ref32 = _no_dropout(ref_ctor(n_stems=S, input_shape=(bench.N_FFT // 2 + 1, 1 + n // hop))).train()
+    ref = strip(ref_ctor(n_stems=S, input_shape=(F_, T_))).double().train()
+    ref32 = strip(ref_ctor(n_stems=S, input_shape=(F_, T_))).train()
     host = clips.cpu().numpy()
     rel = lambda a, b: float(np.abs(a - b).max() / (np.abs(b).max() + 1e-30))
     losses = []
@@ -83,8 +111,20 @@ def _captured_step_matches_oracle(cfg_name, ref_ctor, feature_pairs, bn_keys, ex
         before = _ref_state(model)
         p0, m0, v0 = opt._flat.double().cpu(), opt._exp_avg.double().cpu(), opt._exp_avg_sq.double().cpu()
         step.bind_clips(clips[k * Bsz:(k + 1) * Bsz])
+        if dropout:
+            c0 = ops.dropout_counter(device)
+            assert torch.initial_seed() == drop_seed
         loss = step().item()
         torch.cuda.synchronize()
+        if dropout:
+            # the replay advanced the device counter exactly as an eager step does, and drew the masks of ITS offset
+            assert ops.dropout_counter(device) == c0 + per_step, (k, c0, ops.dropout_counter(device), per_step)
+            masks, _ = dropout_ref.block_keep_masks(drop_seed, c0, shapes, ps)
+            masks = [torch.from_numpy(m) for m in masks]
+            models_ref.set_keep_masks(ref, masks), models_ref.set_keep_masks(ref32, masks)
+            out1 = b1_out['out'].permute(0, 3, 1, 2).cpu()
+            assert bool((out1[~masks[0]] == 0).all()), 'replay %d: block 1 kept an element the host mask drops' % k
+            b1_masks.append((out1 != 0, masks[0]))
         gains = torch.cat(step.gains, 1).cpu().numpy().astype(np.float64)
         masked = step.masked[:, ::41, ::7].cpu().numpy().astype(np.float64)
         g_dev = opt._grad.double().cpu()
@@ -162,6 +202,13 @@ def _captured_step_matches_oracle(cfg_name, ref_ctor, feature_pairs, bn_keys, ex
         print('step %d: loss %.6f (oracle %.6f, rel %.1e) gains %.1e masked %.1e | worst grad tensor %.1e | adam max err %.1e'
               % (k, loss, loss_r.item(), e_loss, e_gain, e_mask, worst, e_adam))
         losses.append(loss)
+    if dropout:
+        for i in range(3):
+            for j in range(3):
+                if i != j:
+                    # replay i's block-1 mask is not replay j's: device against device, host against host, device against host
+                    assert not torch.equal(b1_masks[i][0], b1_masks[j][0]) and not torch.equal(b1_masks[i][1], b1_masks[j][1])
+                    assert bool(b1_masks[i][0][~b1_masks[j][1]].any()), (i, j)
     if expect_descent:
         assert losses[-1] < losses[0]                                    # and it trains
 
@@ -187,6 +234,22 @@ def test_c1_captured_step_matches_oracle(dam_lib):
     _captured_step_matches_oracle('C1', models_ref.RefMixingModelScalar1s, ((0, 0), (5, 1), (7, 0)),
                                   ('conv_b1.batch_norm.running_mean', 'conv_b2.batch_norm.running_var',
                                    'conv_b5.batch_norm.running_var'))
+
+
+def test_c2_captured_step_matches_oracle_with_dropout(dam_lib):
+    """C2 exactly as bench.py times it: `bench.build_model(C2)` untouched (train mode, dropout 0.2 x 4 / 0.3 ON), captured,
+    three replays from the device's state; the float64 oracle applies the host restatement of the device's masks at the
+    offset the counter had before each replay.  Thresholds of the dropout-off test."""
+    _captured_step_matches_oracle('C2', models_ref.RefMixingModelScalar2s, ((0, 0), (2, 1), (3, 3)),
+                                  ('conv_b1.batch_norm.running_mean', 'conv_b1.batch_norm.running_var',
+                                   'conv_b3.batch_norm.running_var', 'conv_b5.batch_norm.running_mean'), dropout=True)
+
+
+def test_c1_captured_step_matches_oracle_with_dropout(dam_lib):
+    """C1 exactly as bench.py times it (model_scalar_1s, 2 stems, 1 s @ 16 kHz, hop 256, batch 8, dropout ON)."""
+    _captured_step_matches_oracle('C1', models_ref.RefMixingModelScalar1s, ((0, 0), (5, 1), (7, 0)),
+                                  ('conv_b1.batch_norm.running_mean', 'conv_b2.batch_norm.running_var',
+                                   'conv_b5.batch_norm.running_var'), dropout=True)
 
 
 def test_plain_bench_run_prints_the_headline_and_dumps_the_last_step(dam_lib, tmp_path):

@@ -16,7 +16,7 @@ import numpy as np
 import pytest
 import torch
 
-from oracle import models_ref
+from oracle import dropout_ref, models_ref
 
 pytestmark = pytest.mark.gpu
 B = 8
@@ -265,16 +265,24 @@ SCALAR_BLOCKS = [  # name, cin, cout, k, stride, dilation, input H, W, NCHW inpu
     ('conv_b5', 64, 128, 9, 1, 1, 497, 49, False)]
 
 
-@pytest.mark.parametrize('name,cin,cout,k,stride,dil,H,W,nchw', SCALAR_BLOCKS, ids=[b[0] for b in SCALAR_BLOCKS])
-@pytest.mark.parametrize('slotted', [False, True], ids=['grad', 'slots'])
-def test_conv_block2d_c2_batch4(dam, name, cin, cout, k, stride, dil, H, W, nchw, slotted):
-    """models/model_scalar_2s.py:9-47 / model_scalar_1s.py:151-190 (valid convolution with bias -> BatchNorm eps 1e-3,
-    momentum 0.9 -> ReLU; dropout off) at C2's five block shapes and batch 4: forward, dx, dW, dbias, dgamma, dbeta within
-    2e-5 of the float64 oracle block that takes the device's ReLU decisions (same construction as the BasicBlock tests)."""
+def _conv_block2d_case(dam, name, cin, cout, k, stride, dil, H, W, nchw, slotted, dropout):
+    """One ConvBlock2d against the float64 oracle block.  dropout: the block is built with its dropout_p of the model
+    (models/_scalar.py BLOCKS) and the oracle applies the HOST restatement of the device's mask (oracle/dropout_ref.py) at
+    the offset the device counter had before the forward.  The device's output then says `ReLU decision AND keep`; the keep
+    part is NOT taken from it: the output must be exactly zero wherever the host mask drops, and the ReLU decisions are
+    compared with the oracle's over the kept elements (a dropped element's decision reaches nothing).  Tolerances are
+    those of the dropout-off case: one exact mask and one float32 multiply add no value-dependent decision."""
     layers, ops = dam
     Bs = 4
     gen = torch.Generator().manual_seed(70 + [b[0] for b in SCALAR_BLOCKS].index(name))
-    blk = _randomize(layers.ConvBlock2d(cin, cout, k, stride=stride, dilation=dil, dropout_p=-1.0, in_nchw=nchw), gen)
+    idx = [b[0] for b in SCALAR_BLOCKS].index(name)
+    p_drop = -1.0
+    if dropout:
+        from deep_audio_mixer_amd.models._scalar import BLOCKS as MODEL_BLOCKS
+        assert MODEL_BLOCKS[idx][:2] == (cout, k)
+        p_drop = MODEL_BLOCKS[idx][2]
+        assert p_drop == (0.3 if idx == 4 else 0.2)
+    blk = _randomize(layers.ConvBlock2d(cin, cout, k, stride=stride, dilation=dil, dropout_p=p_drop, in_nchw=nchw), gen)
     with torch.no_grad():
         blk.conv.bias.copy_(0.1 * torch.randn(blk.conv.bias.shape, generator=gen))
     ref = models_ref.RefConvBlock2d(cin, cout, k, stride, dil, -1.0).double().train()
@@ -294,14 +302,30 @@ def test_conv_block2d_c2_batch4(dam, name, cin, cout, k, stride, dil, H, W, nchw
     if slotted:
         _bind_slots(params)
     xc = x.cuda().requires_grad_(not nchw)
+    if dropout:
+        torch.manual_seed(2 ** 32 + 1234 + idx)
+        seed, c0 = torch.initial_seed(), ops.dropout_counter(xc.device)
     out = blk(xc)
     assert tuple(out.shape) == (Bs, Ho, Wo, n16)
     mask = (out[..., :cout] > 0).permute(0, 3, 1, 2).cpu()
     out.backward(dout.cuda())
     ops.wgrad_flush()
     torch.cuda.synchronize()
-    a_r, v = models_ref.stem_forward_masked(ref.conv, ref.batch_norm, x_ref, mask)
-    flips = _check_masks(name, v, mask)
+    if dropout:
+        assert ops.dropout_counter(xc.device) == c0 + out.numel()         # one call, forward only
+        keep = dropout_ref.keep_mask(seed, c0, out.numel(), p_drop).reshape(Bs, Ho, Wo, n16)[..., :cout]
+        keep = torch.from_numpy(np.ascontiguousarray(keep.transpose(0, 3, 1, 2)))
+        dropped = _nchw(out[..., :cout])[~keep]
+        assert dropped.numel() > 0 and bool((dropped == 0).all()), 'a dropped element is not zero'
+        # mask == ReLU decision AND keep from here on (mask is False wherever keep is, by the assertion above)
+        a_r, v = models_ref.stem_forward_masked(ref.conv, ref.batch_norm, x_ref, mask)
+        a_r = a_r * (1.0 / (1.0 - p_drop))
+        flips = _check_masks(name, v[keep], mask[keep])
+        kept_rate = float(keep.double().mean())
+        assert abs(kept_rate - (1 - p_drop)) <= 5 * (p_drop * (1 - p_drop) / keep.numel()) ** 0.5
+    else:
+        a_r, v = models_ref.stem_forward_masked(ref.conv, ref.batch_norm, x_ref, mask)
+        flips = _check_masks(name, v, mask)
     a_r.backward(dout[..., :cout].permute(0, 3, 1, 2).double())
     e_out = _rel(_nchw(out[..., :cout]), a_r.detach())
     assert e_out <= TOL, ('forward', e_out)
@@ -317,8 +341,26 @@ def test_conv_block2d_c2_batch4(dam, name, cin, cout, k, stride, dil, H, W, nchw
             continue
         pairs.append((n_, g, q.grad))
     bad = _compare_grads(pairs, report)
-    print('%s B=%d: forward %.1e, %d rounding-level ReLU decisions taken from the device; worst gradient %s'
-          % (name, Bs, e_out, flips, max(report, key=lambda r: r[1])))
+    print('%s B=%d%s: forward %.1e, %d rounding-level ReLU decisions taken from the device; worst gradient %s'
+          % (name, Bs, ' dropout %.1f' % p_drop if dropout else '', e_out, flips, max(report, key=lambda r: r[1])))
     np.testing.assert_allclose(blk.batch_norm.running_var.cpu().numpy(), ref.batch_norm.running_var.numpy(), rtol=1e-5)
     np.testing.assert_allclose(blk.batch_norm.running_mean.cpu().numpy(), ref.batch_norm.running_mean.numpy(), rtol=1e-5, atol=1e-6)
     assert not bad, bad
+
+
+@pytest.mark.parametrize('name,cin,cout,k,stride,dil,H,W,nchw', SCALAR_BLOCKS, ids=[b[0] for b in SCALAR_BLOCKS])
+@pytest.mark.parametrize('slotted', [False, True], ids=['grad', 'slots'])
+def test_conv_block2d_c2_batch4(dam, name, cin, cout, k, stride, dil, H, W, nchw, slotted):
+    """models/model_scalar_2s.py:9-47 / model_scalar_1s.py:151-190 (valid convolution with bias -> BatchNorm eps 1e-3,
+    momentum 0.9 -> ReLU; dropout off) at C2's five block shapes and batch 4: forward, dx, dW, dbias, dgamma, dbeta within
+    2e-5 of the float64 oracle block that takes the device's ReLU decisions (same construction as the BasicBlock tests)."""
+    _conv_block2d_case(dam, name, cin, cout, k, stride, dil, H, W, nchw, slotted, dropout=False)
+
+
+@pytest.mark.parametrize('name,cin,cout,k,stride,dil,H,W,nchw', SCALAR_BLOCKS, ids=[b[0] for b in SCALAR_BLOCKS])
+@pytest.mark.parametrize('slotted', [False, True], ids=['grad', 'slots'])
+def test_conv_block2d_c2_batch4_dropout(dam, name, cin, cout, k, stride, dil, H, W, nchw, slotted):
+    """The same five blocks with dropout ON as the models build them (p = 0.2 x 4, 0.3): the oracle applies the host
+    restatement of the device's mask; forward, dx, dW, dbias, dgamma, dbeta, running statistics at the dropout-off
+    tolerances (2e-5 of the tensor norm)."""
+    _conv_block2d_case(dam, name, cin, cout, k, stride, dil, H, W, nchw, slotted, dropout=True)

@@ -177,6 +177,31 @@ def test_gradients_tight_when_no_relu_flips(dam, name, shape):
     assert not bad, bad[:5]
 
 
+@pytest.mark.parametrize('name,shape', [('scalar1s', (2, 4, 257, 87)), ('scalar2s', (2, 4, 257, 93))])
+def test_gradients_tight_with_dropout_on(dam, name, shape):
+    """The rule of test_gradients_tight_when_no_relu_flips with dropout ON, as bench.py's C1 / C2 and ModelTrainer.fit run
+    the scalar models: the device's masks are a pure function of (torch.initial_seed(), call counter, element index), which
+    oracle/dropout_ref.py restates on the host, so the float32 and float64 oracles apply the SAME masks
+    (_model_check.best_over_seeds(dropout=True)).  Gains 1e-4, loss 2e-4 per seed; every parameter tensor's best agreement
+    over four seeds within max(3 x the CPU float32 oracle's own distance, 2e-5); the counter advances by the five block
+    outputs' element counts per step."""
+    import _model_check
+    ctor, ref_ctor = dam[name]
+    torch.manual_seed(2 ** 63 + 4321)                  # torch.initial_seed() of an unseeded process can be this large
+
+    def loss_dev(model, x, gt):
+        loss, _, gains = model.forward_mse(x, gt)
+        return loss, torch.cat(gains, 1)
+
+    def loss_ref(ref, x, gt):
+        masked, gains = ref(x)
+        return torch.nn.functional.mse_loss(masked, gt), torch.cat(gains, 1)
+
+    best = _model_check.best_over_seeds(ctor, ref_ctor, shape, loss_dev, loss_ref, dropout=True)
+    print('%s dropout on: worst best-over-seeds gradient error %.1e' % (name, max(best.values())))
+    torch.manual_seed(0)
+
+
 def test_forward_mse_equals_unfused(dam):
     ctor, _ = dam['resnet18']
     torch.manual_seed(0)
