@@ -17,7 +17,6 @@
 //     dx = c1*dz + c2*x + c3 with per-channel constants.
 #include <cstdlib>
 #include "dam_common.h"
-#include "dam_bn_fin.h"
 
 namespace dam {
 namespace {
@@ -51,7 +50,7 @@ inline BnLaunch bn_plan(int64_t P, int C, int max_parts = BN_MAX_PARTS) {
 
 // gridDim.y == 2: a second tensor of the same shape (x2 -> partial2) in the same launch (dam_bn_stats_pair_f32).
 __global__ void bn_stats_partial_kernel(const float* __restrict__ x, int64_t P, int C, int Q, int R, int64_t ppb,
-                                        float* __restrict__ partial /* [parts][C][3] */, const BnFinArgs fin,
+                                        float* __restrict__ partial /* [parts][C][3] */,
                                         const float* __restrict__ x2, float* __restrict__ partial2) {
     extern __shared__ __attribute__((aligned(16))) float sm[];    // [R][C][3]
     if (blockIdx.y) { x = x2; partial = partial2; }
@@ -119,11 +118,6 @@ __global__ void bn_stats_partial_kernel(const float* __restrict__ x, int64_t P, 
             float* out = partial + ((size_t)blockIdx.x * C + c) * 3;
             store_sc1(out, a[0]); store_sc1(out + 1, a[1]); store_sc1(out + 2, a[2]);
         }
-    }
-    if (fin.counter) {      // the last workgroup to arrive merges all records (dam_bn_fin.h): no finalize launch
-        __shared__ unsigned ticket;
-        if (block_arrive_last(fin.counter, gridDim.x, &ticket))
-            bn_stats_finalize_block(partial, (int)gridDim.x, C, fin, reinterpret_cast<double*>(sm), threadIdx.x, blockDim.x);
     }
 }
 
@@ -233,55 +227,6 @@ __global__ void bn_apply_kernel(const float* __restrict__ x, int64_t nquads, int
     }
 }
 
-struct BnBwdFin {
-    double count;
-    const float* gamma; const float* mean; const float* invstd;
-    int training;
-    float* dgamma; float* dbeta; float* coef;      // coef [3][C]
-    unsigned* counter;                             // null: separate finalize launch
-};
-
-// dgamma / dbeta and the three per-channel constants of the apply pass from the partial sums [parts][C][2].
-// Thread layout as bn_stats_finalize_block: channel = t % W, slice = t / W; scratch >= nthreads * 2 doubles.
-__device__ __forceinline__ void bn_bwd_finalize_block(const float* partial, int parts, int C, const BnBwdFin& f,
-                                                      double* scratch, int tid, int nthreads) {
-    const int W = C < nthreads ? C : nthreads, S = nthreads / W;
-    for (int c0 = 0; c0 < C; c0 += nthreads) {
-        const int c = c0 + tid % W, sl = tid / W;
-        double s1 = 0, s2 = 0;
-        if (c < C && sl < S) {
-            constexpr int U = 8;            // eight records in flight per thread (see bn_stats_finalize_block)
-            for (int p0 = sl; p0 < parts; p0 += S * U) {
-                float ra[U], rb[U];
-#pragma unroll
-                for (int u = 0; u < U; ++u) {
-                    const int p = p0 + u * S;
-                    const float* o = partial + ((size_t)(p < parts ? p : sl) * C + c) * 2;
-                    ra[u] = load_sc1(o); rb[u] = load_sc1(o + 1);
-                }
-#pragma unroll
-                for (int u = 0; u < U; ++u)
-                    if (p0 + u * S < parts) { s1 += (double)ra[u]; s2 += (double)rb[u]; }
-            }
-        }
-        scratch[tid * 2] = s1; scratch[tid * 2 + 1] = s2;
-        __syncthreads();
-        if (sl == 0 && c < C) {
-            for (int s = 1; s < S; ++s) { s1 += scratch[(size_t)(tid + s * W) * 2]; s2 += scratch[(size_t)(tid + s * W) * 2 + 1]; }
-            f.dbeta[c] = (float)s1;
-            f.dgamma[c] = (float)s2;
-            const double g = (double)f.gamma[c] * f.invstd[c];
-            double c2 = 0, c3 = 0;
-            if (f.training) {
-                c2 = -g * f.invstd[c] * s2 / f.count;
-                c3 = -g * s1 / f.count - c2 * f.mean[c];
-            }
-            f.coef[c] = (float)g; f.coef[C + c] = (float)c2; f.coef[2 * C + c] = (float)c3;
-        }
-        __syncthreads();
-    }
-}
-
 // partial[blk][c] = (sum dz, sum dz*xhat)
 __device__ __forceinline__ float4 sign_quad(unsigned b) {       // sign byte -> (1 or 0) x 4
     return make_float4((float)(b & 1u), (float)((b >> 1) & 1u), (float)((b >> 2) & 1u), (float)((b >> 3) & 1u));
@@ -295,7 +240,7 @@ __global__ void bn_bwd_partial_kernel(const float* __restrict__ dy, const float*
                                       const float* __restrict__ x, int64_t P, int C, int Q, int R, int64_t ppb,
                                       const float* __restrict__ mean, const float* __restrict__ invstd,
                                       const float* __restrict__ mscale, const float* __restrict__ mshift,
-                                      float* __restrict__ partial /* [parts][C][2] */, const BnBwdFin fin) {
+                                      float* __restrict__ partial /* [parts][C][2] */) {
     extern __shared__ __attribute__((aligned(16))) float sm[];    // [R][C][2]
     const int cq = threadIdx.x % Q, pr = threadIdx.x / Q;
     const int64_t lo = blockIdx.x * ppb, hi = (lo + ppb < P) ? lo + ppb : P;
@@ -354,11 +299,6 @@ __global__ void bn_bwd_partial_kernel(const float* __restrict__ dy, const float*
             store_sc1(partial + ((size_t)blockIdx.x * C + c) * 2, sm[(size_t)c * 2]);
             store_sc1(partial + ((size_t)blockIdx.x * C + c) * 2 + 1, sm[(size_t)c * 2 + 1]);
         }
-    }
-    if (fin.counter) {      // the last workgroup to arrive finalizes (dam_bn_fin.h)
-        __shared__ unsigned ticket;
-        if (block_arrive_last(fin.counter, gridDim.x, &ticket))
-            bn_bwd_finalize_block(partial, (int)gridDim.x, C, fin, reinterpret_cast<double*>(sm), threadIdx.x, blockDim.x);
     }
 }
 
@@ -970,7 +910,7 @@ extern "C" int dam_bn_stats_partial_f32(const float* x, int64_t n_pixels, int C,
     if (C % 16 || C > 1024) return DAM_ERR_UNSUPPORTED;
     const BnLaunch l = bn_plan(n_pixels, C, fa_max_parts(C, 3));
     hipLaunchKernelGGL(bn_stats_partial_kernel, dim3(l.parts), dim3(l.threads), (size_t)l.r * C * 3 * sizeof(float), (hipStream_t)stream,
-                       x, n_pixels, C, l.q, l.r, l.ppb, workspace, BnFinArgs{}, (const float*)nullptr, (float*)nullptr);
+                       x, n_pixels, C, l.q, l.r, l.ppb, workspace, (const float*)nullptr, (float*)nullptr);
     DAM_CHECK_LAUNCH();
     *parts_host = l.parts;
     return DAM_OK;
@@ -996,7 +936,7 @@ extern "C" int dam_bn_finalize_apply_f32(const float* partial, int parts, int C,
     }
     const FaPlan f = fa_plan(n_pixels, C);
     const BnFinArgs a{fin->gamma, fin->beta, fin->running_mean, fin->running_var, (long long*)fin->num_batches_tracked, fin->momentum,
-                      fin->eps, fin->save_mean, fin->save_invstd, fin->scale, fin->shift, nullptr};
+                      fin->eps, fin->save_mean, fin->save_invstd, fin->scale, fin->shift};
     hipLaunchKernelGGL(bn_fin_apply_kernel, dim3(f.nranges, f.nslices), dim3(FA_THREADS), 0, st, partial, parts, C, f.cs, a, x,
                        n_pixels, f.ppr, res, res_scale, res_shift, relu, y, sign_bits);
     DAM_CHECK_LAUNCH();
@@ -1006,23 +946,19 @@ extern "C" int dam_bn_finalize_apply_f32(const float* partial, int parts, int C,
 extern "C" int dam_bn_stats_f32(const float* x, int64_t n_pixels, int C, const float* gamma, const float* beta,
                                 float* running_mean, float* running_var, int64_t* num_batches_tracked,
                                 float momentum, float eps, float* save_mean, float* save_invstd, float* scale,
-                                float* shift, float* workspace, uint32_t* counter, void* stream) {
+                                float* shift, float* workspace, void* stream) {
     if (!x || !gamma || !beta || !save_mean || !save_invstd || !scale || !shift || !workspace || n_pixels <= 0)
         return DAM_ERR_BAD_ARG;
     if (C % 16 || C > 1024) return DAM_ERR_UNSUPPORTED;
     const BnLaunch l = bn_plan(n_pixels, C);
     hipStream_t st = (hipStream_t)stream;
-    const BnFinArgs fin{gamma, beta, running_mean, running_var, (long long*)num_batches_tracked, momentum, eps,
-                        save_mean, save_invstd, scale, shift, counter};
     hipLaunchKernelGGL(bn_stats_partial_kernel, dim3(l.parts), dim3(l.threads), (size_t)l.r * C * 3 * sizeof(float), st,
-                       x, n_pixels, C, l.q, l.r, l.ppb, workspace, fin, (const float*)nullptr, (float*)nullptr);
+                       x, n_pixels, C, l.q, l.r, l.ppb, workspace, (const float*)nullptr, (float*)nullptr);
     DAM_CHECK_LAUNCH();
-    if (!counter) {
-        hipLaunchKernelGGL(bn_stats_finalize_kernel, dim3(C), dim3(64), 0, st, workspace, l.parts, C,
-                           gamma, beta, running_mean, running_var, (long long*)num_batches_tracked, momentum, eps,
-                           save_mean, save_invstd, scale, shift, BnFinArgs{}, (const float*)nullptr);
-        DAM_CHECK_LAUNCH();
-    }
+    hipLaunchKernelGGL(bn_stats_finalize_kernel, dim3(C), dim3(64), 0, st, workspace, l.parts, C,
+                       gamma, beta, running_mean, running_var, (long long*)num_batches_tracked, momentum, eps,
+                       save_mean, save_invstd, scale, shift, BnFinArgs{}, (const float*)nullptr);
+    DAM_CHECK_LAUNCH();
     return DAM_OK;
 }
 
@@ -1039,10 +975,10 @@ extern "C" int dam_bn_stats_pair_f32(const float* x_a, const float* x_b, int64_t
     hipStream_t st = (hipStream_t)stream;
     float* ws_b = workspace + (size_t)BN_RECORDS_MAX * C * 3;
     hipLaunchKernelGGL(bn_stats_partial_kernel, dim3(l.parts, 2), dim3(l.threads), (size_t)l.r * C * 3 * sizeof(float), st, x_a,
-                       n_pixels, C, l.q, l.r, l.ppb, workspace, BnFinArgs{}, x_b, ws_b);
+                       n_pixels, C, l.q, l.r, l.ppb, workspace, x_b, ws_b);
     DAM_CHECK_LAUNCH();
     const BnFinArgs fb{b->gamma, b->beta, b->running_mean, b->running_var, (long long*)b->num_batches_tracked, b->momentum,
-                       b->eps, b->save_mean, b->save_invstd, b->scale, b->shift, nullptr};
+                       b->eps, b->save_mean, b->save_invstd, b->scale, b->shift};
     hipLaunchKernelGGL(bn_stats_finalize_kernel, dim3(C, 2), dim3(64), 0, st, workspace, l.parts, C, a->gamma, a->beta,
                        a->running_mean, a->running_var, (long long*)a->num_batches_tracked, a->momentum, a->eps, a->save_mean,
                        a->save_invstd, a->scale, a->shift, fb, (const float*)ws_b);
@@ -1070,7 +1006,7 @@ extern "C" int dam_bn_finalize_pair_f32(const float* partial_a, const float* par
         !b->save_mean || !b->save_invstd || !b->scale || !b->shift)
         return DAM_ERR_BAD_ARG;
     const BnFinArgs fb{b->gamma, b->beta, b->running_mean, b->running_var, (long long*)b->num_batches_tracked, b->momentum,
-                       b->eps, b->save_mean, b->save_invstd, b->scale, b->shift, nullptr};
+                       b->eps, b->save_mean, b->save_invstd, b->scale, b->shift};
     hipLaunchKernelGGL(bn_stats_finalize_kernel, dim3(C, 2), dim3(64), 0, (hipStream_t)stream, partial_a, parts, C, a->gamma, a->beta,
                        a->running_mean, a->running_var, (long long*)a->num_batches_tracked, a->momentum, a->eps, a->save_mean,
                        a->save_invstd, a->scale, a->shift, fb, partial_b);
@@ -1105,26 +1041,24 @@ extern "C" int dam_bn_apply_f32(const float* x, int64_t n_pixels, int C, const f
 extern "C" int dam_bn_backward_f32(const float* dy, const float* y_mask, const float* x, int64_t n_pixels, int C,
                                    const float* gamma, const float* save_mean, const float* save_invstd, int training,
                                    const float* mask_scale, const float* mask_shift, const uint8_t* mask_bits, float* dx,
-                                   float* dgamma, float* dbeta, float* workspace, int partials_given, uint32_t* counter,
-                                   void* stream) {
+                                   float* dgamma, float* dbeta, float* workspace, int partials_given, void* stream) {
     if (!dy || !x || !gamma || !save_mean || !save_invstd || !dx || !dgamma || !dbeta || !workspace || n_pixels <= 0)
         return DAM_ERR_BAD_ARG;
     if ((mask_scale != nullptr) != (mask_shift != nullptr) || (y_mask && mask_scale) || (mask_bits && (y_mask || mask_scale)))
         return DAM_ERR_BAD_ARG;
     if (mask_bits) y_mask = reinterpret_cast<const float*>(mask_bits);       // MASK == 3 reads it as bytes
     if (C % 16 || C > 1024) return DAM_ERR_UNSUPPORTED;
-    const bool fused = fa_enabled() && !counter;
+    const bool fused = fa_enabled();
     BnLaunch l = bn_plan(n_pixels, C, fused ? fa_max_parts(C, 2) : BN_MAX_PARTS);
     if (partials_given < 0 || partials_given > BN_MAX_PARTS) return DAM_ERR_BAD_ARG;
-    if (partials_given) { l.parts = partials_given; counter = nullptr; }       // records from a data-gradient epilogue
+    if (partials_given) l.parts = partials_given;       // records from a data-gradient epilogue
     const bool fuse_now = fused && fa_table_ok(C, l.parts, 2);
     hipStream_t st = (hipStream_t)stream;
     float* coef = workspace + (size_t)BN_MAX_PARTS * C * 2;    // workspace holds [parts][C][2] then [3][C]
     const int mask = mask_bits ? 3 : (y_mask ? 1 : (mask_scale ? 2 : 0));
-    const BnBwdFin fin{(double)n_pixels, gamma, save_mean, save_invstd, training, dgamma, dbeta, coef, counter};
 #define DAM_BN_PARTIAL(M_)                                                                                                   \
     hipLaunchKernelGGL(bn_bwd_partial_kernel<M_>, dim3(l.parts), dim3(l.threads), (size_t)l.r * C * 2 * sizeof(float), st, dy, \
-                       y_mask, x, n_pixels, C, l.q, l.r, l.ppb, save_mean, save_invstd, mask_scale, mask_shift, workspace, fin)
+                       y_mask, x, n_pixels, C, l.q, l.r, l.ppb, save_mean, save_invstd, mask_scale, mask_shift, workspace)
     if (partials_given) { }
     else if (mask == 1) DAM_BN_PARTIAL(1); else if (mask == 2) DAM_BN_PARTIAL(2); else if (mask == 3) DAM_BN_PARTIAL(3); else DAM_BN_PARTIAL(0);
 #undef DAM_BN_PARTIAL
@@ -1140,11 +1074,9 @@ extern "C" int dam_bn_backward_f32(const float* dy, const float* y_mask, const f
         DAM_CHECK_LAUNCH();
         return DAM_OK;
     }
-    if (!counter) {
-        hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3(C), dim3(64), 0, st, workspace, l.parts, C,
-                           (double)n_pixels, gamma, save_mean, save_invstd, training, dgamma, dbeta, coef);
-        DAM_CHECK_LAUNCH();
-    }
+    hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3(C), dim3(64), 0, st, workspace, l.parts, C,
+                       (double)n_pixels, gamma, save_mean, save_invstd, training, dgamma, dbeta, coef);
+    DAM_CHECK_LAUNCH();
     const int64_t nq = n_pixels * (C / 4);
 #define DAM_BN_APPLY(M_)                                                                                                     \
     hipLaunchKernelGGL(bn_bwd_apply_kernel<M_>, dim3(elt_blocks(nq)), dim3(256), 0, st, dy, y_mask, x, nq, C / 4, C, coef,   \

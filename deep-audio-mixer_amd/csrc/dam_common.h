@@ -58,6 +58,30 @@ __device__ __forceinline__ float wave_sum64(float v) {
 
 static inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
+// Records [parts][C][3] a statistics producer may emit (the size dam_bn_workspace_floats() provides for): the BatchNorm
+// kernels' own passes use up to 1024, the loader-wave convolution up to one per (workgroup or tile, wave).
+constexpr int BN_RECORDS_MAX = 2048;
+constexpr int BN_BWD_RECORDS_MAX = 1024;      // records [..][C][2] that dam_bn_backward_f32 takes as partials_given
+
+struct BnFinArgs {            // device pointers; the launch-side mirror of dam_bn_fin (include/dam_hip.h)
+    const float* gamma;
+    const float* beta;
+    float* running_mean;      // may be null
+    float* running_var;
+    long long* num_batches;   // may be null
+    float momentum, eps;
+    float* save_mean;
+    float* save_invstd;
+    float* scale;
+    float* shift;
+};
+
+// Store of one BatchNorm record word: write-through (agent-scope relaxed atomic, `sc1`).  Plain stores in the strip kernel
+// changed the C3 training step's result on the device (loss after one step 889.05 -> 893.63), so every record site keeps this.
+__device__ __forceinline__ void store_sc1(float* p, float v) {
+    __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
 // Launch-side caches.  A kernel's raised LDS limit (hipFuncSetAttribute), the CU count and an occupancy answer belong to ONE
 // device: a process that drives a second GPU must not reuse what it learnt on the first.  PerDevice<T> is a zero-initialised
 // slot per device ordinal, read through the calling thread's current device.

@@ -25,7 +25,6 @@
 #include "dam_common.h"
 #include "dam_conv_geo.h"
 #include "dam_conv_stage.h"
-#include "dam_bn_fin.h"
 
 namespace dam {
 
@@ -613,26 +612,18 @@ extern "C" int dam_conv2d_tapgrid_f32(const float* x, int B, int H, int W, int C
                                       int out_stride, int out_off_h, int out_off_w, int in_stride, int nA, int nB,
                                       int off_h, int step_h, int off_w, int step_w, int wt_base, int wt_sa, int wt_sb,
                                       const float* res, const float* res_mask, float* bn_partial, int* bn_parts_host,
-                                      const dam_bn_fin* bn_fin, const dam_bn_bwd_sums* bn_bwd, float* workspace,
-                                      int64_t workspace_floats, void* batch, void* stream) {
+                                      const dam_bn_bwd_sums* bn_bwd, float* workspace, int64_t workspace_floats,
+                                      void* batch, void* stream) {
     using namespace dam;
     if (bn_parts_host) *bn_parts_host = 0;
     BnBwdEpi bwd{};
     if (bn_bwd && bn_bwd->x) {
-        if (!bn_partial || !bn_parts_host || bn_fin || !bn_bwd->mean || !bn_bwd->invstd) return DAM_ERR_BAD_ARG;
+        if (!bn_partial || !bn_parts_host || !bn_bwd->mean || !bn_bwd->invstd) return DAM_ERR_BAD_ARG;
         if (bn_bwd->mask_bits ? (bn_bwd->mask_scale || bn_bwd->mask_shift || !res) : (!bn_bwd->mask_scale || !bn_bwd->mask_shift))
             return DAM_ERR_BAD_ARG;
         if (res && (!bn_bwd->res_mask_bits || !res_mask)) return DAM_ERR_BAD_ARG;      // bytes for the kernels that can, floats for the rest
         bwd = BnBwdEpi{bn_bwd->x, bn_bwd->mean, bn_bwd->invstd, bn_bwd->mask_scale, bn_bwd->mask_shift, bn_bwd->res_mask_bits,
                        bn_bwd->mask_bits};
-    }
-    BnFinArgs fin{};
-    if (bn_fin && bn_partial) {
-        if (!bn_fin->gamma || !bn_fin->beta || !bn_fin->save_mean || !bn_fin->save_invstd || !bn_fin->scale || !bn_fin->shift ||
-            !bn_fin->counter) return DAM_ERR_BAD_ARG;
-        fin = BnFinArgs{bn_fin->gamma, bn_fin->beta, bn_fin->running_mean, bn_fin->running_var,
-                        (long long*)bn_fin->num_batches_tracked, bn_fin->momentum, bn_fin->eps, bn_fin->save_mean,
-                        bn_fin->save_invstd, bn_fin->scale, bn_fin->shift, bn_fin->counter};
     }
     if (!x || !w_packed || !y || B <= 0 || H <= 0 || W <= 0 || C <= 0 || Ho <= 0 || Wo <= 0 || nA <= 0 || nB <= 0)
         return DAM_ERR_BAD_ARG;
@@ -671,14 +662,14 @@ extern "C" int dam_conv2d_tapgrid_f32(const float* x, int B, int H, int W, int C
     if (!in_nchw) {
         int parts = 0;
         const int rc = conv_strip_try(g, h_lo, h_hi, x, w_packed, bias, y, res, res_mask, bn_partial, &parts,
-                                      fin.counter ? &fin : nullptr, in_scale, in_shift, bwd, st);
+                                      in_scale, in_shift, bwd, st);
         if (rc == DAM_OK) {
             if (bn_partial && bn_parts_host) *bn_parts_host = parts;
             return DAM_OK;
         }
         if (rc != DAM_ERR_UNSUPPORTED) return rc;
         if (bn_partial) {       // maybe only the statistics did not fit: retry without them
-            const int rc2 = conv_strip_try(g, h_lo, h_hi, x, w_packed, bias, y, res, res_mask, nullptr, nullptr, nullptr, in_scale, in_shift,
+            const int rc2 = conv_strip_try(g, h_lo, h_hi, x, w_packed, bias, y, res, res_mask, nullptr, nullptr, in_scale, in_shift,
                                            BnBwdEpi{}, st);
             if (rc2 == DAM_OK) return DAM_OK;
             if (rc2 != DAM_ERR_UNSUPPORTED) return rc2;
@@ -689,7 +680,7 @@ extern "C" int dam_conv2d_tapgrid_f32(const float* x, int B, int H, int W, int C
     if (!getenv("DAM_NO_PIPE")) {
         int parts = 0;
         const int rc = conv_pipe_try(g, h_hi - h_lo, x, w_packed, bias, in_scale, in_shift, y, res, res_mask, workspace,
-                                     (fin.counter || (bwd.x && res)) ? nullptr : bn_partial, &parts, (bwd.x && res) ? BnBwdEpi{} : bwd, st);
+                                     (bwd.x && res) ? nullptr : bn_partial, &parts, (bwd.x && res) ? BnBwdEpi{} : bwd, st);
         if (rc == DAM_OK && bn_partial && bn_parts_host) *bn_parts_host = parts;
         if (rc != DAM_ERR_UNSUPPORTED) return rc;
         // Too wide for its patch buffers (the strided 16 -> 32 convolution on 1025x130: 131 input columns x 5 rows): the same

@@ -27,7 +27,6 @@
 #include "dam_common.h"
 #include "dam_conv_geo.h"
 #include "dam_conv_stage.h"
-#include "dam_bn_fin.h"
 
 namespace dam {
 namespace {

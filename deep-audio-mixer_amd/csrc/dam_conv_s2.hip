@@ -15,7 +15,6 @@
 // keeps shifted sums (pivot = its first value) of the 4 * NB channels it owns across all its units, the sixteen pixel lanes are
 // merged once at the end (Chan), then the four waves: one record per workgroup -- no pass over c1 / cs.
 #include "dam_common.h"
-#include "dam_bn_fin.h"
 
 namespace dam {
 namespace {

@@ -25,7 +25,6 @@
 #include <cstdint>
 #include "dam_common.h"
 #include "dam_conv_geo.h"
-#include "dam_bn_fin.h"
 
 namespace dam {
 namespace {
@@ -148,7 +147,7 @@ __global__ __launch_bounds__(SO ? 512 : STRIP_THREADS, 1) void conv_strip_kernel
                                                          float* __restrict__ Y, const float* __restrict__ res,
                                                          const float* __restrict__ res_mask, float* __restrict__ stats,
                                                          const float* __restrict__ in_scale, const float* __restrict__ in_shift,
-                                                         const BnFinArgs fin, const BnBwdEpi bwd) {
+                                                         const BnBwdEpi bwd) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);     // wave-uniform: role tests and loader arithmetic on the scalar ALU
@@ -1137,12 +1136,6 @@ __global__ __launch_bounds__(SO ? 512 : STRIP_THREADS, 1) void conv_strip_kernel
                 store_sc1(o, n); store_sc1(o + 1, mean); store_sc1(o + 2, m2);
             }
         }
-        if (fin.counter) {      // the last workgroup to arrive merges all records (dam_bn_fin.h): no finalize launch
-            unsigned* ticket = reinterpret_cast<unsigned*>(smem + 16 * 1024);
-            const unsigned total = gridDim.x * gridDim.z;       // statistics launches have gridDim.y == 1 (host check)
-            if (block_arrive_last(fin.counter, total, ticket))
-                bn_stats_finalize_block(stats, (int)total, g.N, fin, reinterpret_cast<double*>(smem + 32 * 1024), tid, NT);
-        }
     }
 }
 
@@ -1152,7 +1145,7 @@ __global__ __launch_bounds__(SO ? 512 : STRIP_THREADS, 1) void conv_strip_kernel
 template <int MB, int NB, int NCH, bool T33, bool LW = false, int EPI = 0, int SO = 0>
 static int launch_strip(ConvGeo& g, StripGeo& sg, size_t lds, const float* X, const float* Wp, const float* bias, float* Y,
                         const float* res, const float* res_mask, float* stats, const float* in_scale, const float* in_shift,
-                        const BnFinArgs& fin, const BnBwdEpi& bwd, hipStream_t st) {
+                        const BnBwdEpi& bwd, hipStream_t st) {
     if (lds > 64 * 1024) {
         static PerDevice<bool> raised_pd; bool& raised = raised_pd();
         if (!raised) {
@@ -1164,16 +1157,14 @@ static int launch_strip(ConvGeo& g, StripGeo& sg, size_t lds, const float* X, co
     }
     dim3 grid((unsigned)sg.strips, (unsigned)cdiv(g.N / 16, NB), (unsigned)g.B);
     hipLaunchKernelGGL((conv_strip_kernel<MB, NB, NCH, T33, LW, EPI, SO>), grid, dim3(SO ? 512 : STRIP_THREADS), lds, st, g, sg, X, reinterpret_cast<const float4*>(Wp), bias,
-                       Y, res, res_mask, stats, in_scale, in_shift, fin, bwd);
+                       Y, res, res_mask, stats, in_scale, in_shift, bwd);
     DAM_CHECK_LAUNCH();
     return DAM_OK;
 }
 
 int conv_strip_try(ConvGeo& g_in, int h_lo, int h_hi, const float* X, const float* Wp, const float* bias, float* Y,
-                   const float* res, const float* res_mask, float* stats, int* stats_parts, const BnFinArgs* fin_in,
+                   const float* res, const float* res_mask, float* stats, int* stats_parts,
                    const float* in_scale, const float* in_shift, const BnBwdEpi& bwd, hipStream_t st) {
-    BnFinArgs fin{};
-    if (fin_in && stats && !bwd.x) fin = *fin_in;
     if (bwd.x && !stats) return DAM_ERR_BAD_ARG;
     if (bwd.x && res && !bwd.res_bits) return DAM_ERR_UNSUPPORTED;     // with a residual the sums need its mask as sign bytes
     ConvGeo g = g_in;                 // the caller's copy stays as it is for the tile kernel
@@ -1245,14 +1236,13 @@ int conv_strip_try(ConvGeo& g_in, int h_lo, int h_hi, const float* X, const floa
     if (stats_parts) *stats_parts = sg.strips * g.B;
     if (stats && (int64_t)sg.strips * g.B > 1024) return DAM_ERR_UNSUPPORTED;
     if (lds < (size_t)8 * NB * 16 * 3 * sizeof(float)) lds = (size_t)8 * NB * 16 * 3 * sizeof(float);
-    if (fin.counter && lds < (size_t)32 * 1024 + STRIP_THREADS * 3 * sizeof(double)) lds = (size_t)32 * 1024 + STRIP_THREADS * 3 * sizeof(double);
     // 3x3 taps, stride 1, unit column step: compile-time item grid with immediate operand offsets
     const bool t33 = g.nA == 3 && g.nB == 3 && g.s == 1 && g.step_w == 1;
-#define DAM_STRIP_ARGS g, sg, lds, X, Wp, bias, Y, (bwd.x && !res ? bwd.x : res), (bwd.x && res ? reinterpret_cast<const float*>(bwd.res_bits) : res_mask), stats, in_scale, in_shift, fin, bwd, st
+#define DAM_STRIP_ARGS g, sg, lds, X, Wp, bias, Y, (bwd.x && !res ? bwd.x : res), (bwd.x && res ? reinterpret_cast<const float*>(bwd.res_bits) : res_mask), stats, in_scale, in_shift, bwd, st
     // Self-overlapped form (template comment of the kernel) for the 3x3 / stride-1 shapes of the 16- and 32-channel stages at
     // ordinary row widths; the ping-pong form takes every other shape.  The write-out variant is compile time.
     const int rows_out_so = std::min(g.Ho, (64 * MB + g.Wo - 2) / g.Wo + 1), rows_tile_so = (rows_out_so - 1) * g.s + sg.RH;
-    if (t33 && !wide && !fin.counter && rows_tile_so * g.nchunks <= 8 * (g.nchunks == 1 ? 1 : 2) &&
+    if (t33 && !wide && rows_tile_so * g.nchunks <= 8 * (g.nchunks == 1 ? 1 : 2) &&
         ((g.nchunks == 1 && MB == 4 && NB == 1) || (g.nchunks == 2 && MB == 2 && NB == 2))) {
         const bool c16 = g.nchunks == 1;
         lds += 2048;                        // geometry tables: 4 compute waves x 4 buffers x 8 ints x <= 4 pixel blocks

@@ -20,7 +20,6 @@
 //                           fragments go straight from L2 into the MFMA operand.
 // DESIGN.md section 4.2a has the measurements; profiles/r04_s2_kernels_ab.txt the steps that led here.
 #include "dam_common.h"
-#include "dam_bn_fin.h"
 
 namespace dam {
 namespace {

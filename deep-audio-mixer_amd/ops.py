@@ -2,7 +2,6 @@
 torch's caching allocator, launch on the current torch stream.  No arithmetic happens here and
 there is no CPU fallback."""
 import ctypes
-
 import os
 
 import torch
@@ -43,14 +42,6 @@ def pack_weights_multi(desc, n_tensors, max_total):
                'dam_conv_pack_weights_multi_f32')
 
 
-_counters = {}
-# "The last workgroup finalizes" (csrc/dam_bn_fin.h) is implemented, tested and OFF: measured on the ResNet18 step it is
-# slower than the separate finalize launches it replaces (5.83 -> 6.09 ms per step; the strip convolution 66 -> 72 us per
-# launch): the last workgroup's returning atomic + its fetch of the records that the sc1 stores pushed out of L2 cost more
-# than a 1.5-2 us kernel boundary.  Kernel boundaries are the cheap synchronisation on this part.
-INKERNEL_FINALIZE = False
-
-
 # Finalize inside the elementwise consumer (dam_bn_finalize_apply_f32; the backward entry points do the same internally):
 # DAM_BN_FUSED_FIN=0 keeps the separate finalize launches (A/B switch; the library reads the same variable)
 FUSED_FINALIZE = os.environ.get('DAM_BN_FUSED_FIN', '1') != '0'
@@ -64,29 +55,16 @@ dgrad_s2_launches = 0        # launches dam_dgrad_s2_3x3_f32 accepted (tests che
 DGRAD_BN_SUMS = not os.environ.get('DAM_NO_DGRAD_SUMS')
 
 
-def arrival_counter(device):
-    """The zero-initialised device word of the "last workgroup finalizes" hand-off (include/dam_hip.h: dam_bn_fin): one per
-    device -- every launch that uses it returns it to zero and all of them are ordered on the current stream.  None while
-    the hand-off is switched off (two-launch form)."""
-    if not INKERNEL_FINALIZE:
-        return None
-    key = (device.type, device.index)
-    if key not in _counters:
-        _counters[key] = torch.zeros(4, dtype=torch.int32, device=device)
-    return _counters[key]
-
-
-def _bn_fin_struct(bn, out4, device):
+def _bn_fin_struct(bn, out4):
     """bn = (gamma, beta, running_mean, running_var, num_batches_tracked, momentum, eps); out4: [4, C] result rows."""
     gamma, beta, rm, rv, nbt, mom, eps = bn
     return _lib.BnFin(_lib.ptr(gamma), _lib.ptr(beta), _lib.ptr(rm), _lib.ptr(rv), _lib.ptr(nbt), float(mom), float(eps),
-                      _lib.ptr(out4[0]), _lib.ptr(out4[1]), _lib.ptr(out4[2]), _lib.ptr(out4[3]),
-                      _lib.ptr(arrival_counter(device)))
+                      _lib.ptr(out4[0]), _lib.ptr(out4[1]), _lib.ptr(out4[2]), _lib.ptr(out4[3]))
 
 
 def _tapgrid(x, B, H, W, C, in_nchw, wp, k_chunks, n_out, bias, in_scale, in_shift, relu_in, y, OHt, OWt, Ho, Wo,
              out_stride, oo_h, oo_w, in_stride, nA, nB, off_h, step_h, off_w, step_w, wt_base, wt_sa, wt_sb,
-             res=None, res_mask=None, bn_partial=None, bn_fin=None, relu_out=False, batch=None, bn_bwd=None):
+             res=None, res_mask=None, bn_partial=None, relu_out=False, batch=None, bn_bwd=None):
     parts = ctypes.c_int(0)
     # split-K scratch: the host code only splits when no tile shape gives 400 workgroups, i.e. for outputs below
     # 400 * 64 px * 64 ch = 1.64 M floats, and then at most 8 ways (dam_conv.hip) -- never more than 13.1 M floats
@@ -97,7 +75,7 @@ def _tapgrid(x, B, H, W, C, in_nchw, wp, k_chunks, n_out, bias, in_scale, in_shi
         out_stride,
         oo_h, oo_w, in_stride, nA, nB, off_h, step_h, off_w, step_w, wt_base, wt_sa, wt_sb, _lib.ptr(res),
         _lib.ptr(res_mask), _lib.ptr(bn_partial), ctypes.byref(parts) if bn_partial is not None else None,
-        ctypes.byref(bn_fin) if bn_fin is not None else None, ctypes.byref(bn_bwd) if bn_bwd is not None else None,
+        ctypes.byref(bn_bwd) if bn_bwd is not None else None,
         _lib.ptr(ws), ws.numel(),
         ctypes.addressof(batch) if batch is not None else None, _lib.stream())
     _lib.check(st, 'dam_conv2d_tapgrid_f32')
@@ -123,17 +101,12 @@ def conv2d_fwd(x, wp, n_out, kh, kw, stride=1, pad=0, dil=1, bias=None, in_scale
     if Ho <= 0 or Wo <= 0:
         raise ValueError('convolution output would be empty')
     y = torch.empty((B, Ho, Wo, n16), dtype=torch.float32, device=x.device)
-    out4 = fin = None
-    if bn is not None and bn_partial is not None and INKERNEL_FINALIZE:
-        # in-kernel finalize: the launch's last workgroup merges the partial records into (mean, invstd, scale, shift)
-        out4 = torch.empty((4, n16), dtype=torch.float32, device=x.device)
-        fin = _bn_fin_struct(bn, out4, x.device)
     parts = _tapgrid(x, B, H, W, C, in_nchw, wp, k_chunks, n16, bias, in_scale, in_shift, relu_in, y, Ho, Wo, Ho, Wo,
-                     1, 0, 0, stride, kh, kw, -pad, dil, -pad, dil, 0, kw, 1, res=res, bn_partial=bn_partial, bn_fin=fin,
+                     1, 0, 0, stride, kh, kw, -pad, dil, -pad, dil, 0, kw, 1, res=res, bn_partial=bn_partial,
                      relu_out=relu_out)
     if bn is not None and bn_partial is not None:
-        if parts > 0 and fin is None and finalize:      # two-launch form: merge the records with the finalize kernel
-            out4 = bn_finalize(bn_partial, parts, *bn)
+        # two-launch form: merge the records with the finalize kernel
+        out4 = bn_finalize(bn_partial, parts, *bn) if parts > 0 and finalize else None
         return y, parts, out4    # parts == 0: no statistics from this launch (out4 is then unset); finalize=False: the caller
         #                          hands (bn_partial, parts) to bn_finalize_apply
     if bn_partial is not None:
@@ -426,7 +399,7 @@ def bn_stats(x, gamma, beta, running_mean, running_var, num_batches_tracked, mom
     _lib.check(_lib.lib().dam_bn_stats_f32(_lib.ptr(x), P, C, _lib.ptr(gamma), _lib.ptr(beta), _lib.ptr(running_mean),
                                            _lib.ptr(running_var), _lib.ptr(num_batches_tracked), float(momentum), float(eps),
                                            _lib.ptr(out[0]), _lib.ptr(out[1]), _lib.ptr(out[2]), _lib.ptr(out[3]),
-                                           _lib.ptr(ws), _lib.ptr(arrival_counter(x.device)), _lib.stream()), 'dam_bn_stats_f32')
+                                           _lib.ptr(ws), _lib.stream()), 'dam_bn_stats_f32')
     return out[0], out[1], out[2], out[3]
 
 
@@ -447,7 +420,7 @@ def bn_finalize_apply(partial, parts, bn, x, relu=True, res=None, res_scale=None
     _lib.require_cuda(partial, x)
     C = x.shape[-1]
     out4 = torch.empty((4, C), dtype=torch.float32, device=x.device)
-    fin = _bn_fin_struct(bn, out4, x.device)
+    fin = _bn_fin_struct(bn, out4)
     y = torch.empty_like(x)
     bits = torch.empty(x.shape[:-1] + (C // 4,), dtype=torch.uint8, device=x.device) if sign_bits else None
     _lib.check(_lib.lib().dam_bn_finalize_apply_f32(_lib.ptr(partial), int(parts), C, ctypes.byref(fin), _lib.ptr(x), x.numel() // C,
@@ -471,7 +444,7 @@ def bn_stats_pair(xa, bn_a, xb, bn_b):
     C = xa.shape[-1]
     L = _lib.lib()
     outs = [torch.empty((4, C), dtype=torch.float32, device=xa.device) for _ in range(2)]
-    fa, fb = _bn_fin_struct(bn_a, outs[0], xa.device), _bn_fin_struct(bn_b, outs[1], xa.device)
+    fa, fb = _bn_fin_struct(bn_a, outs[0]), _bn_fin_struct(bn_b, outs[1])
     ws = _workspace(xa.device, 2 * L.dam_bn_workspace_floats(C))
     _lib.check(L.dam_bn_stats_pair_f32(_lib.ptr(xa), _lib.ptr(xb), xa.numel() // C, C, ctypes.byref(fa), ctypes.byref(fb),
                                        _lib.ptr(ws), _lib.stream()), 'dam_bn_stats_pair_f32')
@@ -507,7 +480,7 @@ def bn_finalize_pair(partial_a, partial_b, parts, bn_a, bn_b):
     Returns two (save_mean, save_invstd, scale, shift) tuples."""
     C = bn_a[0].numel()
     outs = [torch.empty((4, C), dtype=torch.float32, device=partial_a.device) for _ in range(2)]
-    fa, fb = _bn_fin_struct(bn_a, outs[0], partial_a.device), _bn_fin_struct(bn_b, outs[1], partial_a.device)
+    fa, fb = _bn_fin_struct(bn_a, outs[0]), _bn_fin_struct(bn_b, outs[1])
     _lib.check(_lib.lib().dam_bn_finalize_pair_f32(_lib.ptr(partial_a), _lib.ptr(partial_b), parts, C, ctypes.byref(fa),
                                                    ctypes.byref(fb), _lib.stream()), 'dam_bn_finalize_pair_f32')
     return tuple(outs[0]), tuple(outs[1])
@@ -594,8 +567,7 @@ def bn_backward(dy, y_mask, x, gamma, save_mean, save_invstd, training=True, mas
                                               _lib.ptr(save_mean), _lib.ptr(save_invstd), 1 if training else 0,
                                               _lib.ptr(mask_affine[0]) if mask_affine else None,
                                               _lib.ptr(mask_affine[1]) if mask_affine else None, _lib.ptr(mask_bits), _lib.ptr(dx),
-                                              _lib.ptr(dgamma), _lib.ptr(dbeta), _lib.ptr(ws), given,
-                                              _lib.ptr(arrival_counter(x.device)), _lib.stream()),
+                                              _lib.ptr(dgamma), _lib.ptr(dbeta), _lib.ptr(ws), given, _lib.stream()),
                'dam_bn_backward_f32')
     return dx, dgamma, dbeta
 

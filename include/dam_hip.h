@@ -50,13 +50,12 @@ typedef enum dam_pcm_dtype { DAM_PCM_F32 = 0, DAM_PCM_F64 = 1, DAM_PCM_S16 = 2, 
  * staging buffers of an uploader -- with NO launch between the replays: re-pointing the DAM_PCM_INDIRECT word was a 4.8 us fill
  * launch behind an 8 us gap per step (profiles/r05_C3_step_timeline.txt, the last line).  n >= 1, counter + offset >= 0. */
 #define DAM_PCM_ROTATE 0x200
-struct dam_bn_fin;      /* defined in the BatchNorm section */
 struct dam_bn_bwd_sums; /* defined in the BatchNorm section */
 
 /* Library / build identification ("gfx950").  DAM_ABI_VERSION is bumped whenever a signature below changes; a binding
  * compares dam_abi_version() of the library it loaded with the version it was written against and refuses a stale one
  * (deep-audio-mixer_amd/_lib.py: EXPECTED_ABI). */
-#define DAM_ABI_VERSION 17
+#define DAM_ABI_VERSION 18
 const char* dam_arch(void);
 int dam_abi_version(void);
 
@@ -232,9 +231,8 @@ int dam_conv_pack_weights_multi_f32(const int64_t* desc_dev, int n_tensors, int6
  * bn_partial (optional, >= dam_bn_workspace_floats(n_out) floats): if the launch can also produce the BatchNorm
  * partial statistics of y (records (n, mean, M2) per workgroup and channel) it does so and stores the record count
  * in *bn_parts_host (a HOST int); 0 there means "not produced" and the caller runs dam_bn_stats_f32 instead.
- * Feed the records to dam_bn_finalize_f32 -- or pass bn_fin (see dam_bn_fin below): the launch's last workgroup then
- * merges them itself and writes save_mean / save_invstd / scale / shift (+ running statistics), no finalize launch.
- * bn_bwd (optional, see dam_bn_bwd_sums below; excludes bn_fin, needs bn_partial; with res only if res_mask_bits is set there): the launch is a data gradient whose
+ * Feed the records to dam_bn_finalize_f32 or dam_bn_finalize_apply_f32.
+ * bn_bwd (optional, see dam_bn_bwd_sums below; needs bn_partial; with res only if res_mask_bits is set there): the launch is a data gradient whose
  * output dy feeds the backward pass of y = relu(bn(x)); if it can, it also writes that pass's two per-channel sums as records
  * [*bn_parts_host][n_out][2] into bn_partial (then hand them to dam_bn_backward_f32 as partials_given); 0 records = not produced.
  * workspace (optional): scratch for split-K over the input channels (used for small-spatial, wide layers; at most
@@ -245,8 +243,8 @@ int dam_conv2d_tapgrid_f32(const float* x, int B, int H, int W, int C, int in_nc
                            int out_stride, int out_off_h, int out_off_w, int in_stride, int nA, int nB,
                            int off_h, int step_h, int off_w, int step_w, int wt_base, int wt_sa, int wt_sb,
                            const float* res, const float* res_mask, float* bn_partial, int* bn_parts_host,
-                           const struct dam_bn_fin* bn_fin, const struct dam_bn_bwd_sums* bn_bwd, float* workspace,
-                           int64_t workspace_floats, void* batch, void* stream);
+                           const struct dam_bn_bwd_sums* bn_bwd, float* workspace, int64_t workspace_floats,
+                           void* batch, void* stream);
 
 /* Two single-tap operators into the same output pixels in ONE launch:
  *   y[b, oh*out_stride+out_off_h, ow*out_stride+out_off_w, :] = W1p[tap1] . x1[b, oh, ow, :] + W2p[tap2] . x2[b, oh, ow, :]
@@ -352,17 +350,11 @@ int dam_strip_diag_counters(uint32_t* out2_host, int reset);
  * --------------------------------------------------------------------------------- */
 int64_t dam_bn_workspace_floats(int C);
 
-/* "The last workgroup finalizes": the kernels that produce per-workgroup partial records (BatchNorm statistics from a
- * convolution epilogue or from dam_bn_stats_f32, the two sums of dam_bn_backward_f32) can merge them themselves in the
- * workgroup that happens to finish last, instead of a separate 5-7 us finalize launch.  That needs one device word:
- * `counter` -- ZERO-INITIALISED by the caller, returned to zero by every launch, shared only by launches that are
- * ordered on one stream.  counter == NULL keeps the two-launch form. */
-typedef struct dam_bn_fin {       /* host struct of device pointers: what dam_bn_finalize_f32 takes, for an in-kernel finalize */
+typedef struct dam_bn_fin {       /* host struct of device pointers: what dam_bn_finalize_f32 takes, for the pair and finalize-apply entry points */
     const float* gamma; const float* beta;
     float* running_mean; float* running_var; int64_t* num_batches_tracked;    /* may be NULL */
     float momentum, eps;
     float* save_mean; float* save_invstd; float* scale; float* shift;
-    uint32_t* counter;
 } dam_bn_fin;
 
 /* BatchNorm-backward sums from a data-gradient epilogue (dam_conv2d_tapgrid_f32's bn_bwd): the backward pass of
@@ -390,11 +382,11 @@ typedef struct dam_bn_bwd_sums {
 int dam_bn_stats_f32(const float* x, int64_t n_pixels, int C, const float* gamma, const float* beta,
                      float* running_mean, float* running_var, int64_t* num_batches_tracked,
                      float momentum, float eps, float* save_mean, float* save_invstd, float* scale,
-                     float* shift, float* workspace, uint32_t* counter, void* stream);
+                     float* shift, float* workspace, void* stream);
 
 /* dam_bn_stats_f32 for TWO tensors of one shape in one partial + one finalize launch (a residual block's conv1 output and its
  * shortcut convolution's output, models/model_resnet.py:17-21,24-26: two independent BatchNorms that become ready together).
- * a, b: the parameters / outputs of each (struct dam_bn_fin below; `counter` is ignored); workspace:
+ * a, b: the parameters / outputs of each (struct dam_bn_fin above); workspace:
  * 2 * dam_bn_workspace_floats(C) floats. */
 int dam_bn_stats_pair_f32(const float* x_a, const float* x_b, int64_t n_pixels, int C, const struct dam_bn_fin* a,
                           const struct dam_bn_fin* b, float* workspace, void* stream);
@@ -407,7 +399,7 @@ int dam_bn_finalize_f32(const float* partial, int parts, int C, const float* gam
                         float* shift, void* stream);
 
 /* dam_bn_finalize_f32 for the two BatchNorms of a pair in one launch (records of equal count and channel number, e.g. from
- * dam_conv_s2_pair_fwd_f32).  a, b: struct dam_bn_fin (`counter` is ignored). */
+ * dam_conv_s2_pair_fwd_f32).  a, b: struct dam_bn_fin. */
 int dam_bn_finalize_pair_f32(const float* partial_a, const float* partial_b, int parts, int C, const struct dam_bn_fin* a,
                              const struct dam_bn_fin* b, void* stream);
 
@@ -419,7 +411,7 @@ int dam_bn_stats_partial_f32(const float* x, int64_t n_pixels, int C, float* wor
  * and ConvBlock2d's relu(bn(conv(x))), models/model_resnet.py:97, models/model_scalar_1s.py:184-186): every workgroup merges the
  * records of the 16 or 32 channels it applies in its prologue -- no finalize launch (4.6-5 us each, whatever it does).
  * fin: the BatchNorm's parameters and outputs as dam_bn_finalize_f32 takes them (all four outputs and the running statistics
- * are written; `counter` is ignored); the remaining arguments as dam_bn_apply_f32.  DAM_BN_FUSED_FIN=0 in the environment
+ * are written); the remaining arguments as dam_bn_apply_f32.  DAM_BN_FUSED_FIN=0 in the environment
  * makes this (and the backward entry points below) run the separate launches instead (A/B switch). */
 int dam_bn_finalize_apply_f32(const float* partial, int parts, int C, const struct dam_bn_fin* fin, const float* x,
                               int64_t n_pixels, const float* res, const float* res_scale, const float* res_shift, int relu,
@@ -447,7 +439,7 @@ int dam_bn_apply_f32(const float* x, int64_t n_pixels, int C, const float* scale
 int dam_bn_backward_f32(const float* dy, const float* y_mask, const float* x, int64_t n_pixels, int C,
                         const float* gamma, const float* save_mean, const float* save_invstd, int training,
                         const float* mask_scale, const float* mask_shift, const uint8_t* mask_bits, float* dx,
-                        float* dgamma, float* dbeta, float* workspace, int partials_given, uint32_t* counter, void* stream);
+                        float* dgamma, float* dbeta, float* workspace, int partials_given, void* stream);
 
 /* The same for TWO BatchNorms that share dy and the mask (exactly one of y_mask / mask_bits) -- a residual block's bn2 and the BatchNorm of its shortcut
  * convolution, both fed by the gradient of relu(bn2(..) + bn_sc(..)) (models/model_resnet.py:23-28): dy and the mask are
