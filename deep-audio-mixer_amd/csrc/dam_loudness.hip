@@ -217,3 +217,292 @@ extern "C" int dam_loudness_block_energy(const void* x, int x_is_f64, int64_t n_
     DAM_CHECK_LAUNCH();
     return DAM_OK;
 }
+
+// =====================================================================================================================
+// Batched form: every (track, channel) row of a batch in one set of launches, block energies without the y^2 image, the
+// gating and the loudness-normalisation gain on the device.  Nothing below synchronises with the host.
+//
+//   bounds  the 2 n_blocks block bounds lo_j / hi_j merged into one sorted list bnd[] (stable: a lo before an equal hi); the
+//           samples between two consecutive bounds form a SEGMENT, and block j is the segments pos_lo[j]+1 .. pos_hi[j]
+//   pass 1  as above, one wave per 64 consecutive chunks of a row; the wave stages 64 samples of each of its chunks through
+//           LDS (one coalesced row of 64 consecutive samples per load instruction; the loads of the next tile are in
+//           flight while the lanes filter the current one).  The optional gain ramp is applied as the sample leaves LDS:
+//           (double)x * gains[track][min(n / (n_samples / n_gains), n_gains-1)], the product dam_gain_ramp_apply stores.
+//   scan    kw_scan_kernel, one workgroup per row
+//   pass 2  the same walk from the true entry state; the lane sums y^2 per (segment, chunk) PIECE and stores piece
+//           (segment k, chunk c) at piece[row][k + c] -- k and c both grow with the sample index, so k + c is distinct for
+//           every non-empty piece -- 8 bytes per piece instead of 8 bytes per sample
+//   blocks  z[row][j] = (sum of the pieces of block j, ascending sample order, one thread) / block_len
+// No atomics; a row's launch geometry depends on n_samples alone, so its result does not depend on the rest of the batch.
+namespace dam {
+namespace {
+
+constexpr int KW_TILE = 64;                       // samples of every chunk staged per step
+constexpr int KW_ROWS = 64;                       // chunks per wave (one per lane)
+constexpr int64_t KW_NEVER = INT64_MAX;
+
+struct KwBatchGeo {
+    int64_t n_samples, n_chunks;
+    int64_t track_stride, sample_stride, channel_stride;      // elements
+    int channels, n_gains;
+    int n_bounds;                                             // 2 * n_blocks
+    int64_t piece_stride;                                     // n_bounds + n_chunks + 1
+};
+
+// bnd[pos] of every lo_j / hi_j in the stable merge of the two nondecreasing sequences.  pos < 2 n_blocks for any input.
+__global__ __launch_bounds__(256) void kw_bounds_merge_kernel(const int64_t* __restrict__ lo, const int64_t* __restrict__ hi,
+                                                              int n_blocks, int64_t* __restrict__ bnd,
+                                                              int* __restrict__ pos_lo, int* __restrict__ pos_hi) {
+    const int j = blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= n_blocks) return;
+    const int64_t l = lo[j], h = hi[j];
+    int a = 0, b = n_blocks;                      // number of hi values <  lo_j
+    while (a < b) { const int m = (a + b) >> 1; if (hi[m] < l) a = m + 1; else b = m; }
+    const int pl = j + a;
+    a = 0; b = n_blocks;                          // number of lo values <= hi_j
+    while (a < b) { const int m = (a + b) >> 1; if (lo[m] <= h) a = m + 1; else b = m; }
+    const int ph = j + a;
+    bnd[pl] = l; bnd[ph] = h;
+    pos_lo[j] = pl; pos_hi[j] = ph;
+}
+
+template <typename T, int PASS>
+__global__ __launch_bounds__(64) void kw_batch_chunk_kernel(const T* __restrict__ x, KwBatchGeo g, KwCoef k,
+                                                            const double* __restrict__ gains /* [tracks][n_gains] or null */,
+                                                            const int64_t* __restrict__ bnd,
+                                                            double* __restrict__ state /* [row][n_chunks][4] */,
+                                                            double* __restrict__ piece /* [row][piece_stride] */) {
+    __shared__ T tile[KW_ROWS][KW_TILE + 1];      // +1: lane c walks row c, consecutive rows fall on consecutive banks
+    const int lane = threadIdx.x;
+    const int row = blockIdx.y, track = row / g.channels, ch = row - track * g.channels;
+    const int64_t c0 = (int64_t)blockIdx.x * KW_ROWS, c = c0 + lane;
+    const T* xr = x + track * g.track_stride + ch * g.channel_stride;
+    const bool live = c < g.n_chunks;
+    const int64_t lo = c * KW_CHUNK, hi = live ? (lo + KW_CHUNK < g.n_samples ? lo + KW_CHUNK : g.n_samples) : lo;
+
+    double s[4] = {0.0, 0.0, 0.0, 0.0};
+    double* st = state + ((int64_t)row * g.n_chunks + c) * 4;
+    if (PASS == 2 && live) { s[0] = st[0]; s[1] = st[1]; s[2] = st[2]; s[3] = st[3]; }
+
+    // gain ramp: gain index of sample n is min(n / gseg, n_gains - 1); followed incrementally, one division per crossing
+    const int64_t gseg = gains ? g.n_samples / g.n_gains : 1;
+    const double* gr = gains ? gains + (int64_t)track * g.n_gains : nullptr;
+    double gain = 1.0;
+    int64_t gnext = gains ? lo : KW_NEVER;        // first sample refreshes it
+
+    // pass 2: current segment kseg = #{bounds <= n}, the next bound, and the running sum of the piece
+    int kseg = 0;
+    int64_t bnext = KW_NEVER;
+    double acc = 0.0;
+    double* pr = piece + (int64_t)row * g.piece_stride + c;
+    if (PASS == 2 && live) {
+        int a = 0, b = g.n_bounds;
+        while (a < b) { const int m = (a + b) >> 1; if (bnd[m] <= lo) a = m + 1; else b = m; }
+        kseg = a;
+        bnext = kseg < g.n_bounds ? bnd[kseg] : KW_NEVER;
+    }
+
+    // sample (c0 + r) * KW_CHUNK + t * KW_TILE + lane of the row, 0 outside the signal (a chunk past the last one starts
+    // at or after n_samples, so the one comparison covers both)
+    T next[KW_ROWS];
+    const int64_t rstep = (int64_t)KW_CHUNK * g.sample_stride;
+    auto fetch = [&](int t) {
+        const int64_t n0 = c0 * KW_CHUNK + t * KW_TILE + lane;
+        const T* p = xr + n0 * g.sample_stride;
+#pragma unroll
+        for (int r = 0; r < KW_ROWS; ++r)
+            next[r] = n0 + (int64_t)r * KW_CHUNK < g.n_samples ? p[r * rstep] : (T)0;
+    };
+    fetch(0);
+    for (int t = 0; t < KW_CHUNK / KW_TILE; ++t) {
+        __syncthreads();                           // the previous tile has been consumed
+#pragma unroll
+        for (int r = 0; r < KW_ROWS; ++r) tile[r][lane] = next[r];
+        __syncthreads();
+        if (t + 1 < KW_CHUNK / KW_TILE) fetch(t + 1);
+        const int64_t base = lo + (int64_t)t * KW_TILE;
+        const int cnt = hi - base >= KW_TILE ? KW_TILE : (hi > base ? (int)(hi - base) : 0);
+        for (int i = 0; i < cnt; ++i) {
+            const int64_t n = base + i;
+            if (n >= gnext) {
+                int64_t gi = n / gseg;
+                if (gi >= g.n_gains - 1) { gi = g.n_gains - 1; gnext = KW_NEVER; } else gnext = (gi + 1) * gseg;
+                gain = gr[gi];
+            }
+            const double y = kw_step(k, (double)tile[lane][i] * gain, s);
+            if (PASS == 2) {
+                if (n >= bnext) {                  // sample n opens a later segment: the open piece is complete
+                    pr[kseg] = acc;
+                    acc = 0.0;
+                    do { ++kseg; bnext = kseg < g.n_bounds ? bnd[kseg] : KW_NEVER; } while (bnext <= n);
+                }
+                acc += y * y;
+            }
+        }
+    }
+    if (live) {
+        if (PASS == 1) { st[0] = s[0]; st[1] = s[1]; st[2] = s[2]; st[3] = s[3]; }
+        else pr[kseg] = acc;                      // (hi > lo for every live chunk: the open piece holds a sample)
+    }
+}
+
+// z[row][j]: the pieces of block j in ascending sample order.  Segment k holds the samples [bnd[k-1], bnd[k]).
+__global__ __launch_bounds__(256) void kw_batch_block_sum_kernel(const double* __restrict__ piece, KwBatchGeo g,
+                                                                 const int64_t* __restrict__ bnd, const int* __restrict__ pos_lo,
+                                                                 const int* __restrict__ pos_hi, int n_blocks, double inv_len,
+                                                                 double* __restrict__ z) {
+    const int j = blockIdx.x * blockDim.x + threadIdx.x, row = blockIdx.y;
+    if (j >= n_blocks) return;
+    const double* pr = piece + (int64_t)row * g.piece_stride;
+    double sum = 0.0;
+    for (int kk = pos_lo[j] + 1; kk <= pos_hi[j]; ++kk) {
+        int64_t a = bnd[kk - 1], b = bnd[kk] < g.n_samples ? bnd[kk] : g.n_samples;
+        if (a < 0) a = 0;
+        if (a >= b) continue;
+        for (int64_t c = a / KW_CHUNK; c <= (b - 1) / KW_CHUNK; ++c) sum += pr[kk + c];
+    }
+    z[(int64_t)row * n_blocks + j] = sum * inv_len;
+}
+
+// Two-stage gating of one track per workgroup, loudness.gated_loudness: l_j = -0.691 + 10 log10(sum_i G_i z[i][j]);
+// stage 1 keeps l_j >= -70, Gamma_r = loudness of the stage-1 channel means - 10; stage 2 keeps l_j > Gamma_r and l_j > -70;
+// an empty stage-1 set makes Gamma_r NaN (0/0) and so stage 2 empty, an empty stage-2 set gives log10(0) = -inf.
+// Fixed-order sums: thread t takes blocks t, t + 256, ..., then a tree over the 256 partials.
+__device__ __forceinline__ double kw_block_loudness(const double* __restrict__ z, int channels, int n_blocks, int j) {
+    const double G[5] = {1.0, 1.0, 1.0, 1.41, 1.41};
+    double w = 0.0;
+    for (int i = 0; i < channels; ++i) w += G[i] * z[(int64_t)i * n_blocks + j];
+    return -0.691 + 10.0 * log10(w);
+}
+
+__global__ __launch_bounds__(256) void kw_gate_kernel(const double* __restrict__ z_all, int channels, int n_blocks,
+                                                      double* __restrict__ lufs) {
+    __shared__ double red[6][256];                 // five channel sums and the count
+    __shared__ double gamma_r;
+    const double G[5] = {1.0, 1.0, 1.0, 1.41, 1.41};
+    const int t = threadIdx.x;
+    const double* z = z_all + (int64_t)blockIdx.x * channels * n_blocks;
+    for (int stage = 0; stage < 2; ++stage) {
+        double sum[5] = {0.0, 0.0, 0.0, 0.0, 0.0}, cnt = 0.0;
+        const double gr = stage ? gamma_r : 0.0;
+        for (int j = t; j < n_blocks; j += 256) {
+            const double l = kw_block_loudness(z, channels, n_blocks, j);
+            const bool keep = stage ? (l > gr && l > -70.0) : (l >= -70.0);
+            if (keep) {
+                for (int i = 0; i < channels; ++i) sum[i] += z[(int64_t)i * n_blocks + j];
+                cnt += 1.0;
+            }
+        }
+        for (int i = 0; i < 5; ++i) red[i][t] = sum[i];
+        red[5][t] = cnt;
+        __syncthreads();
+        for (int w = 128; w >= 1; w >>= 1) {
+            if (t < w) for (int i = 0; i < 6; ++i) red[i][t] += red[i][t + w];
+            __syncthreads();
+        }
+        if (t == 0) {
+            double w = 0.0;
+            for (int i = 0; i < channels; ++i) {
+                double m = red[i][0] / red[5][0];                       // mean of an empty set: 0/0 = NaN
+                if (stage && m != m) m = 0.0;                           // np.nan_to_num
+                w += G[i] * m;
+            }
+            const double l = -0.691 + 10.0 * log10(w);
+            if (stage) lufs[blockIdx.x] = l; else gamma_r = l - 10.0;
+        }
+        __syncthreads();
+    }
+}
+
+__global__ __launch_bounds__(256) void kw_target_gains_kernel(const double* __restrict__ lufs, const double* __restrict__ target,
+                                                              int n, double* __restrict__ gains) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) gains[i] = pow(10.0, (target[i] - lufs[i]) / 20.0);
+}
+
+struct KwBatchWs { double* state; double* piece; int64_t* bnd; int* pos_lo; int* pos_hi; int64_t bytes; };
+static KwBatchWs kw_batch_ws(void* base, int64_t rows, int64_t n_chunks, int n_blocks) {
+    KwBatchWs w;
+    const int64_t piece_stride = 2 * (int64_t)n_blocks + n_chunks + 1;
+    w.state = reinterpret_cast<double*>(base);
+    w.piece = w.state + rows * n_chunks * 4;
+    w.bnd = reinterpret_cast<int64_t*>(w.piece + rows * piece_stride);
+    w.pos_lo = reinterpret_cast<int*>(w.bnd + 2 * (int64_t)n_blocks);
+    w.pos_hi = w.pos_lo + n_blocks;
+    w.bytes = (rows * n_chunks * 4 + rows * piece_stride + 2 * (int64_t)n_blocks) * 8 + 2 * (int64_t)n_blocks * 4;
+    return w;
+}
+
+}  // namespace
+}  // namespace dam
+
+extern "C" int64_t dam_loudness_batch_workspace_bytes(int n_tracks, int64_t n_samples, int channels, int n_blocks) {
+    if (n_tracks <= 0 || n_samples <= 0 || channels <= 0 || n_blocks <= 0) return 0;
+    return dam::kw_batch_ws(nullptr, (int64_t)n_tracks * channels, dam::cdiv(n_samples, dam::KW_CHUNK), n_blocks).bytes;
+}
+
+extern "C" int dam_loudness_block_energy_batch(const void* x, int x_is_f64, int n_tracks, int64_t n_samples, int channels,
+                                               int64_t track_stride, int64_t sample_stride, int64_t channel_stride,
+                                               const double* gains, int n_gains, const double* coef12_host,
+                                               const int64_t* blk_lo, const int64_t* blk_hi, int n_blocks, double block_len,
+                                               double* z, void* workspace, void* stream) {
+    using namespace dam;
+    if (!x || !coef12_host || !blk_lo || !blk_hi || !z || !workspace) return DAM_ERR_BAD_ARG;
+    if (n_tracks <= 0 || n_samples <= 0 || channels <= 0 || n_blocks <= 0 || !(block_len > 0.0)) return DAM_ERR_BAD_ARG;
+    if (gains && (n_gains <= 0 || n_gains > n_samples)) return DAM_ERR_BAD_ARG;
+    const int64_t rows = (int64_t)n_tracks * channels;
+    if (rows > 65535 || n_blocks > (1 << 29)) return DAM_ERR_UNSUPPORTED;
+    KwCoef k;
+    for (int s = 0; s < 2; ++s) {
+        if (coef12_host[s * 6 + 3] != 1.0) return DAM_ERR_BAD_ARG;        // normalised sections only
+        for (int i = 0; i < 3; ++i) k.b[s][i] = coef12_host[s * 6 + i];
+        k.a[s][0] = coef12_host[s * 6 + 4]; k.a[s][1] = coef12_host[s * 6 + 5];
+    }
+    hipStream_t st = (hipStream_t)stream;
+    KwBatchGeo g;
+    g.n_samples = n_samples; g.n_chunks = cdiv(n_samples, KW_CHUNK);
+    g.track_stride = track_stride; g.sample_stride = sample_stride; g.channel_stride = channel_stride;
+    g.channels = channels; g.n_gains = gains ? n_gains : 1;
+    g.n_bounds = 2 * n_blocks;
+    g.piece_stride = (int64_t)g.n_bounds + g.n_chunks + 1;
+    const KwBatchWs w = kw_batch_ws(workspace, rows, g.n_chunks, n_blocks);
+    const dim3 bgrid((unsigned)cdiv(n_blocks, 256));
+    hipLaunchKernelGGL(kw_bounds_merge_kernel, bgrid, dim3(256), 0, st, blk_lo, blk_hi, n_blocks, w.bnd, w.pos_lo, w.pos_hi);
+    DAM_CHECK_LAUNCH();
+    const dim3 grid((unsigned)cdiv(g.n_chunks, KW_ROWS), (unsigned)rows);
+#define DAM_KW_PASS(P)                                                                                                   \
+    if (x_is_f64)                                                                                                        \
+        hipLaunchKernelGGL((kw_batch_chunk_kernel<double, P>), grid, dim3(64), 0, st, reinterpret_cast<const double*>(x), g, k, \
+                           gains, w.bnd, w.state, w.piece);                                                              \
+    else                                                                                                                 \
+        hipLaunchKernelGGL((kw_batch_chunk_kernel<float, P>), grid, dim3(64), 0, st, reinterpret_cast<const float*>(x), g, k,   \
+                           gains, w.bnd, w.state, w.piece)
+    DAM_KW_PASS(1);
+    DAM_CHECK_LAUNCH();
+    hipLaunchKernelGGL(kw_scan_kernel, dim3((unsigned)rows), dim3(256), 0, st, k, KW_CHUNK, g.n_chunks, w.state);
+    DAM_CHECK_LAUNCH();
+    DAM_KW_PASS(2);
+#undef DAM_KW_PASS
+    DAM_CHECK_LAUNCH();
+    hipLaunchKernelGGL(kw_batch_block_sum_kernel, dim3((unsigned)cdiv(n_blocks, 256), (unsigned)rows), dim3(256), 0, st, w.piece,
+                       g, w.bnd, w.pos_lo, w.pos_hi, n_blocks, 1.0 / block_len, z);
+    DAM_CHECK_LAUNCH();
+    return DAM_OK;
+}
+
+extern "C" int dam_loudness_gate(const double* z, int n_tracks, int channels, int n_blocks, double* lufs, void* stream) {
+    using namespace dam;
+    if (!z || !lufs || n_tracks <= 0 || channels <= 0 || channels > 5 || n_blocks <= 0) return DAM_ERR_BAD_ARG;
+    hipLaunchKernelGGL(kw_gate_kernel, dim3((unsigned)n_tracks), dim3(256), 0, (hipStream_t)stream, z, channels, n_blocks, lufs);
+    DAM_CHECK_LAUNCH();
+    return DAM_OK;
+}
+
+extern "C" int dam_loudness_target_gains(const double* lufs, const double* target, int n, double* gains, void* stream) {
+    using namespace dam;
+    if (!lufs || !target || !gains || n <= 0) return DAM_ERR_BAD_ARG;
+    hipLaunchKernelGGL(kw_target_gains_kernel, dim3((unsigned)cdiv(n, 256)), dim3(256), 0, (hipStream_t)stream, lufs, target, n,
+                       gains);
+    DAM_CHECK_LAUNCH();
+    return DAM_OK;
+}

@@ -1,23 +1,43 @@
-"""Loudness evaluation of a mix against a reference mix -- the numeric core of the reference's evaluation.py:20-75
-(``LoudnessEvaluator``): per-stem BS.1770 loudness relative to the stems' mean, and the mean absolute difference of two
-such profiles (the paper's "loudness error").  Same method names and argument meaning; the meter is the HIP one
-(loudness.Meter), stems stay on the device.  The reference's spreadsheet / WAV export and its experiment driver
-(evaluation.py:77-end: openpyxl, soundfile, MUSDB loaders) are callers of this and are not part of the path.
+"""Loudness evaluation of a mix against a reference mix -- the reference's evaluation.py:20-145 (``LoudnessEvaluator``):
+per-stem BS.1770 loudness relative to the stems' mean, the mean absolute difference of two such profiles (the paper's
+"loudness error"), and the whole-song comparison built on them (``process_song`` / ``process_songlist``: plain sum,
+loudness-normalisation baseline, the model's mix and random mixes against a reference mix).  Same method names and
+argument meaning; the meter is the HIP one (loudness.Meter), stems stay on the device.
+
+The whole-song path uploads a song's stems once and never writes a scaled copy of them: the loudnorm and random variants
+are constant gains, the model's mix is a gain ramp, and the batched meter applies either as it loads the samples
+(Meter.integrated_loudness_batch(gains=...)); the mix variant is the 'loudness' kind of inference_utils.SongMixer, one
+hipGraph from PCM to the four LUFS values.  The reference's spreadsheet / WAV export (openpyxl, soundfile) stays out:
+``process_songlist`` returns the rows and the means instead of writing ./stats.xlsx.
 """
+import os
 from collections import OrderedDict
 from statistics import mean
 
 import numpy as np
 import torch
 
+from . import inference_utils, staging
 from .loudness import Meter, normalize_loudness
+from .models.baselines.mean_loudness_model import MeanLoudnessModel
+from .models.baselines.random_model import RandomModel
 
 
 class LoudnessEvaluator:
-    def __init__(self, sr=44100, keys=('bass', 'drums', 'vocals', 'other')):
+    def __init__(self, sr=44100, keys=('bass', 'drums', 'vocals', 'other'), *, dataset=None, d_mean_loudness=None,
+                 mix_model=None, seed=None):
+        """``LoudnessEvaluator(sr, keys)`` measures profiles; the whole-song methods also need what the reference's
+        constructor takes (evaluation.py:22-30): the dataset (its tracklist names the stems the model mixes), the training
+        set's mean loudness per stem and the mixing model.  ``seed`` seeds numpy's global generator, as there."""
+        if seed:
+            np.random.seed(seed)
         self.sr = sr
         self.meter = Meter(sr)
         self.keys = tuple(keys)
+        self.d = dataset
+        self.mix_model = mix_model
+        self.mean_loudness_model = MeanLoudnessModel(d_mean_loudness, sr) if d_mean_loudness is not None else None
+        self.random_model = RandomModel()
 
     def evaluate_loudness(self, tracks: dict) -> list:
         """evaluation.py:39-46: loudness of every stem ([channels, samples] each) minus the mean over the stems."""
@@ -48,3 +68,83 @@ class LoudnessEvaluator:
         if reference_dict:
             return loudness_dict, self._calculate_diff_between_loudness_dicts(loudness_dict, reference_dict)
         return loudness_dict, None
+
+    # ---- batched device form and the whole-song comparison (evaluation.py:77-145)
+    def evaluate_loudness_batch(self, stems, gains=None) -> list:
+        """evaluate_loudness in one batched measurement.  stems: CUDA [stems, channels, n] in ``keys`` order, or
+        {name: CUDA [channels, n]} (stacked: one device copy); gains: optional CUDA float64 [stems] or [stems, n_gains],
+        the stems are then measured as ``stem * gain ramp`` without that product being written.  The [stems] loudness
+        values come to the host in one copy."""
+        pcm = stems if torch.is_tensor(stems) else torch.stack([stems[name] for name in self.keys])
+        lufs = self.meter.integrated_loudness_batch(pcm.transpose(1, 2), gains=gains)
+        return self._profile(lufs.cpu().tolist())
+
+    @staticmethod
+    def _profile(per_track_loudness):
+        avg_loudness = mean(per_track_loudness)
+        return [l - avg_loudness for l in per_track_loudness]
+
+    def _upload(self, tracks):
+        first = np.asarray(tracks[self.keys[0]])
+        np_dt = np.float32 if first.dtype == np.float32 else np.float64
+        pcm = torch.empty((len(self.keys),) + first.shape, dtype=torch.float32 if np_dt == np.float32 else torch.float64,
+                          device=inference_utils.device)
+        pipe = staging.pipe_for(pcm.device)
+        for i, name in enumerate(self.keys):
+            pipe.upload(pcm[i], np.asarray(tracks[name], dtype=np_dt))
+        return pcm
+
+    def process_song_tracks(self, loaded_tracks: dict, reference_tracks: dict, song_name: str, n_random_samples: int = 5,
+                            chunk_length: int = 2) -> dict:
+        """evaluation.py:77-116 on stems already in memory ({name: ndarray [channels, n]} each): the loudness profile of
+        ``reference_tracks`` against the profiles of ``loaded_tracks`` summed as they are ('sum_error'), normalised to the
+        training set's mean loudness ('loudnorm_error'), mixed by the model ('mix_error') and scaled by random gains
+        ('random_error', the mean over n_random_samples draws, drawn in the reference's order).  Returns the reference's
+        stats dict plus 'smooth_gains' {name: list}, the gains the mix variant used."""
+        if self.d is None or self.mix_model is None or self.mean_loudness_model is None:
+            raise ValueError('process_song needs the dataset, d_mean_loudness and mix_model constructor arguments')
+        stems = [t for t in self.d.get_tracklist() if t != 'mix']
+        if tuple(stems) != self.keys or self.keys != self.random_model.tracklist:
+            raise ValueError('the dataset tracklist and the evaluator keys must both be %s' % (self.random_model.tracklist,))
+        stats = {'song_name': song_name}
+        reference = OrderedDict(zip(self.keys, self.evaluate_loudness_batch(self._upload(reference_tracks))))
+
+        def error(profile):
+            return self._calculate_diff_between_loudness_dicts(OrderedDict(zip(self.keys, profile)), reference)
+
+        # mixed by the model: the song is uploaded here, once -- the other variants read the mixer's PCM buffer
+        mixer, arrays = inference_utils._mixer(self.mix_model, stems, loaded_tracks, chunk_length, self.sr, 'loudness', False,
+                                               torch.float64)
+        mix_lufs, gains = mixer.run(arrays)
+        pcm = mixer.pcm
+        lufs = self.meter.integrated_loudness_batch(pcm.transpose(1, 2))
+        stats['sum_error'] = error(self._profile(lufs.cpu().tolist()))
+        # each multitrack is normalized to the mean loudness of the corresponding track from train set
+        stats['loudnorm_error'] = error(self.evaluate_loudness_batch(pcm, self.mean_loudness_model.device_gains(pcm, lufs)))
+        stats['mix_error'] = error(self._profile([float(v) for v in mix_lufs]))
+        random_errors = []
+        for exp_i in range(n_random_samples):
+            drawn = self.random_model.draw()
+            g = torch.tensor([drawn[name] for name in self.keys], dtype=torch.float64, device=pcm.device)
+            random_errors.append(error(self.evaluate_loudness_batch(pcm, g)))
+        stats['random_error'] = mean(random_errors)
+        stats['smooth_gains'] = {name: list(gains[1, i]) for i, name in enumerate(self.keys)}
+        return stats
+
+    def process_song(self, base_dir: str, song_name: str, n_random_samples: int = 5, chunk_length: int = 2) -> dict:
+        """evaluation.py:77-116: the reference mix from ``base_dir/manual_gain_mixes``, the stems from ``base_dir/test``."""
+        from .data.dataset_utils import load_tracks_musdb18
+        reference_tracks = load_tracks_musdb18(os.path.join(base_dir, 'manual_gain_mixes'), song_name, tracklist=self.keys,
+                                               sr=self.sr)
+        loaded_tracks = load_tracks_musdb18(os.path.join(base_dir, 'test'), song_name, tracklist=self.keys, sr=self.sr)
+        return self.process_song_tracks(loaded_tracks, reference_tracks, song_name, n_random_samples, chunk_length)
+
+    def process_songlist(self, base_dir, songlist, n_random_samples: int = 5, chunk_length: int = 2):
+        """evaluation.py:118-144 without the spreadsheet: (rows, means) -- one stats dict per song and the mean of every
+        error over the songs (the sheet's last row)."""
+        keys = ['sum_error', 'random_error', 'loudnorm_error', 'mix_error']
+        rows = []
+        for i, song_name in enumerate(songlist):
+            print('{}/{}: {}'.format(i + 1, len(songlist), song_name))
+            rows.append(self.process_song(base_dir, song_name, n_random_samples, chunk_length))
+        return rows, {key: mean(row[key] for row in rows) for key in keys}

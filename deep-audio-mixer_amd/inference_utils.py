@@ -9,7 +9,10 @@ Everything between the PCM upload and the result download stays on the device an
 hipGraph (``SongMixer``): strided STFT front-end over all chunks of all stems straight out of the planar song
 (dam_stft_logmag_strided_f32) -> model forward of the whole chunk batch -> 10 ** (0.5 g) and the Savitzky-Golay
 smoothing (dam_gains_smooth) -> sample-rate gain ramp x audio (dam_gain_ramp_apply), or for ``mix_song_to_master`` the
-fused stem sum + peak normalisation (dam_mixdown_peak_normalize).  ``mix_song_spectral`` renders in the spectral domain
+fused stem sum + peak normalisation (dam_mixdown_peak_normalize) or, with ``normalize='loudness'``, the stem sum brought to
+a target BS.1770 loudness; ``mix_song_loudness`` ends in the batched meter instead (the per-stem loudness of the mixed
+stems, dam_loudness_block_energy_batch with the gain ramp applied at load: the mixed stems are never written).
+``mix_song_spectral`` renders in the spectral domain
 instead (experiments.ipynb cells 44-53): the model's predicted dB spectrogram ``masked`` on the phases of the stems' sum
 (dam_stft_complex_strided_f32), inverted by dam_istft_f32 -- the same graph with a different tail.  The host sees the
 song once on the way in (page-locked double-buffered staging, staging.PinnedPipe) and the result once on the way out.
@@ -21,7 +24,7 @@ in eval mode all chunks run as one batch inside the graph; in training mode Batc
 import numpy as np
 import torch
 
-from . import features, ops, staging
+from . import features, loudness, ops, staging
 
 device = torch.device('cuda' if torch.cuda.is_available() else 'cpu')      # inference_utils.py:9
 
@@ -61,9 +64,11 @@ class SongMixer:
     chunk length, output kind).  ``run(tracks)`` uploads, replays, downloads."""
 
     def __init__(self, model, n_stems, channels, n_samples, dtype, chunk_samples, kind, normalize=True,
-                 out_dtype=torch.float64, use_graph=True, hop_length=1024):
-        if kind not in ('stems', 'master', 'spectral'):
+                 out_dtype=torch.float64, use_graph=True, hop_length=1024, sr=44100, target_lufs=-20.0):
+        if kind not in ('stems', 'master', 'spectral', 'loudness'):
             raise ValueError(kind)
+        if normalize not in (True, False, 'loudness'):
+            raise ValueError("normalize must be True, False or 'loudness'")
         self.model, self.kind, self.normalize = model, kind, normalize
         self.dev = next(model.parameters()).device
         self.n_stems, self.channels, self.n, self.chunk = n_stems, channels, n_samples, chunk_samples
@@ -90,9 +95,21 @@ class SongMixer:
         elif kind == 'stems':
             self.out = torch.empty((n_stems, channels, n_samples), dtype=out_dtype, device=dev)
             self.ws = None
+        elif kind == 'loudness':
+            self.meter = loudness.Meter(sr)
+            self.out = torch.empty(n_stems, dtype=torch.float64, device=dev)                       # LUFS of every mixed stem
+            self.ws = None
         else:
             self.out = torch.empty((channels, n_samples), dtype=out_dtype, device=dev)
-            self.ws = torch.empty(ops._lib.lib().dam_mixdown_workspace_elems(channels), dtype=out_dtype, device=dev)
+            if normalize == 'loudness':
+                # evaluation.py:59-66: the float64 stem sum is measured and scaled; only the result takes out_dtype
+                self.meter = loudness.Meter(sr)
+                self.mix = torch.empty((channels, n_samples), dtype=torch.float64, device=dev)
+                self.target = torch.full((1,), float(target_lufs), dtype=torch.float64, device=dev)
+                self.lufs = torch.empty(1, dtype=torch.float64, device=dev)
+                self.master_gain = torch.empty(1, dtype=torch.float64, device=dev)
+            mix_dtype = torch.float64 if normalize == 'loudness' else out_dtype
+            self.ws = torch.empty(ops._lib.lib().dam_mixdown_workspace_elems(channels), dtype=mix_dtype, device=dev)
         self.gains = torch.empty((2, n_stems, self.n_proc), dtype=torch.float64, device=dev)     # [raw amplitude, smoothed]
         self.graph = None
         self.use_graph = use_graph
@@ -119,6 +136,13 @@ class SongMixer:
         _, smooth = ops.gains_smooth(g, self.window, SAVGOL_POLYORDER, out=self.gains)
         if self.kind == 'stems':
             ops.gain_ramp_apply(self.pcm, smooth, out=self.out)
+        elif self.kind == 'loudness':
+            self.meter.integrated_loudness_batch(self.pcm.transpose(1, 2), gains=smooth, out=self.out)
+        elif self.normalize == 'loudness':
+            ops.mixdown_peak_normalize(self.pcm, smooth, normalize=False, out=self.mix, workspace=self.ws)
+            self.meter.integrated_loudness_batch(self.mix.t().unsqueeze(0), out=self.lufs)
+            loudness.target_gains_device(self.lufs, self.target, out=self.master_gain)
+            ops.gain_ramp_apply(self.mix, self.master_gain, out=self.out)
         else:
             ops.mixdown_peak_normalize(self.pcm, smooth, normalize=self.normalize, out=self.out, workspace=self.ws)
 
@@ -156,6 +180,8 @@ class SongMixer:
         for i, a in enumerate(tracks):
             pipe.upload(self.pcm[i], a)
         self.launch()
+        if self.kind == 'loudness':
+            return self.out.cpu().numpy(), self.gains.cpu().numpy()
         out = pipe.download(self.out)
         if self.kind == 'spectral':
             return out.reshape(-1), pipe.download(self.masked)
@@ -165,17 +191,20 @@ class SongMixer:
 _mixers = {}
 
 
-def _mixer(model, stems, loaded_tracks, chunk_length, sr, kind, normalize, out_dtype, hop_length=1024):
+def _mixer(model, stems, loaded_tracks, chunk_length, sr, kind, normalize, out_dtype, hop_length=1024, target_lufs=-20.0):
     first = np.asarray(loaded_tracks[stems[0]])
     if first.ndim != 2:
         raise ValueError('loaded_tracks[track] must be [channels, n] arrays')
     ch, n = first.shape
     dt = torch.float32 if first.dtype == np.float32 else torch.float64
-    key = (id(model), len(stems), ch, n, dt, chunk_length * sr, kind, bool(normalize), out_dtype, hop_length)
+    if normalize != 'loudness':
+        normalize, target_lufs = bool(normalize), None
+    key = (id(model), len(stems), ch, n, dt, chunk_length * sr, kind, normalize, out_dtype, hop_length, sr, target_lufs)
     m = _mixers.get(key)
     if m is None:
         _mixers.clear()                        # one geometry at a time: a song's buffers are hundreds of MB
-        m = SongMixer(model, len(stems), ch, n, dt, chunk_length * sr, kind, normalize, out_dtype, hop_length=hop_length)
+        m = SongMixer(model, len(stems), ch, n, dt, chunk_length * sr, kind, normalize, out_dtype, hop_length=hop_length, sr=sr,
+                      target_lufs=-20.0 if target_lufs is None else target_lufs)
         _mixers[key] = m
     np_dt = np.float32 if dt == torch.float32 else np.float64
     return m, [np.asarray(loaded_tracks[t], dtype=np_dt) for t in stems]
@@ -191,14 +220,29 @@ def mix_song_smooth(dataset, model, loaded_tracks: dict, chunk_length=1, sr=4410
     return {t: out[i] for i, t in enumerate(stems)}, raw_gains, smooth_gains
 
 
-def mix_song_to_master(dataset, model, loaded_tracks: dict, chunk_length=1, sr=44100, normalize=True, dtype=np.float64):
+def mix_song_loudness(dataset, model, loaded_tracks: dict, chunk_length=1, sr=44100):
+    """The loudness of what mix_song_smooth would return, without producing it: the BS.1770 integrated loudness of every
+    stem times its smoothed gain ramp (what evaluation.py:102-105 measures of the model's mix), the ramp applied inside
+    the meter.  Returns (lufs {track: float}, raw_gains, smooth_gains)."""
+    stems = [t for t in dataset.get_tracklist() if t != 'mix']
+    m, arrays = _mixer(model, stems, loaded_tracks, chunk_length, sr, 'loudness', False, torch.float64)
+    lufs, gains = m.run(arrays)
+    raw_gains = {t: [float(v) for v in gains[0, i]] for i, t in enumerate(stems)}
+    return ({t: float(lufs[i]) for i, t in enumerate(stems)}, raw_gains,
+            {t: list(gains[1, i]) for i, t in enumerate(stems)})
+
+
+def mix_song_to_master(dataset, model, loaded_tracks: dict, chunk_length=1, sr=44100, normalize=True, dtype=np.float64,
+                       target_lufs=-20.0):
     """mix_song_smooth followed by what every caller of the reference does next (inference.ipynb cells 9/11,
     evaluation.py:59-66): ``track_sum = np.sum(list(mixed_tracks.values()), axis=0)`` and, if ``normalize``,
     ``librosa.util.normalize(track_sum, axis=1)`` -- fused into one pass over the song on the GPU (the per-stem mixed
-    tracks are never materialised).  Returns (mix ndarray[channels, n], raw_gains, smooth_gains)."""
+    tracks are never materialised).  ``normalize='loudness'`` is evaluation.py:59-66 without the file write instead: the
+    sum is measured (BS.1770) and scaled to ``target_lufs``, in the same graph.
+    Returns (mix ndarray[channels, n], raw_gains, smooth_gains)."""
     stems = [t for t in dataset.get_tracklist() if t != 'mix']
     out_dt = torch.float32 if np.dtype(dtype) == np.float32 else torch.float64
-    m, arrays = _mixer(model, stems, loaded_tracks, chunk_length, sr, 'master', normalize, out_dt)
+    m, arrays = _mixer(model, stems, loaded_tracks, chunk_length, sr, 'master', normalize, out_dt, target_lufs=target_lufs)
     out, gains = m.run(arrays)
     raw_gains = {t: [float(v) for v in gains[0, i]] for i, t in enumerate(stems)}
     return out, raw_gains, {t: list(gains[1, i]) for i, t in enumerate(stems)}

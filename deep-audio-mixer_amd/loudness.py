@@ -10,6 +10,15 @@ mean_loudness_model.py:17), with the same names, argument meaning and error beha
 The samples are filtered and block-averaged by ``dam_loudness_block_energy`` (HIP, float64; csrc/dam_loudness.hip); the
 gating over the few thousand block energies is the host logic below, a restatement of pyloudnorm 0.1.x ``meter.py``.
 There is no CPU path: without the HIP library this raises.
+
+Batched device form, for callers that measure many tracks (evaluation.py:77-116) or sit inside a captured pipeline:
+
+    lufs = meter.integrated_loudness_batch(pcm.transpose(1, 2))          # [N, samples, channels] -> CUDA float64 [N]
+    lufs = meter.integrated_loudness_batch(stems, gains=smooth)          # loudness of stems * gain ramp, nothing written
+    out = normalize_loudness_device(stems, lufs, -20.0)
+
+filter, block energies, gating (``dam_loudness_gate``) and the normalisation gain (``dam_loudness_target_gains``) all
+run on the device: no host synchronisation, hipGraph-capturable.
 """
 import ctypes
 import warnings
@@ -55,6 +64,7 @@ class Meter:
         _lib.check(_lib.lib().dam_loudness_kweight_coeffs(float(rate), coef), 'dam_loudness_kweight_coeffs')
         self._coef = coef
         self.coefficients = np.array(list(coef)).reshape(2, 6)          # [stage][b0 b1 b2 a0 a1 a2]
+        self._bounds = {}                                               # _block_bounds' cache
 
     # ---- device part: block mean squares z[channel][block]
     def block_energies(self, data):
@@ -86,6 +96,130 @@ class Meter:
     def integrated_loudness(self, data):
         z = self.block_energies(data)
         return gated_loudness(z)
+
+
+    # ---- batched device form: nothing below synchronises with the host
+    def _block_bounds(self, n, dev):
+        """Device block bounds of an n-sample track, cached per (device, n, rate, block size) so that a captured call
+        holds stable pointers."""
+        key = (dev, n, self.rate, self.block_size)
+        if key not in self._bounds:
+            T_g, step = self.block_size, 0.25
+            num_blocks = int(np.round(((n / self.rate - T_g) / (T_g * step))) + 1)
+            j = np.arange(0, num_blocks)
+            lo = (T_g * (j * step) * self.rate).astype(np.int64)              # the same truncations as block_energies
+            hi = (T_g * (j * step + 1) * self.rate).astype(np.int64)
+            self._bounds[key] = (torch.from_numpy(lo).to(dev), torch.from_numpy(hi).to(dev))
+        return self._bounds[key]
+
+    def block_energies_batch(self, data, gains=None, out=None):
+        """data: CUDA float32/float64 [N, samples, channels] with any strides (planar [N, channels, n] storage is passed
+        as ``pcm.transpose(1, 2)``, no copy).  gains: optional CUDA float64 [N, n_gains] (or [N]): every track is
+        measured as ``data[t] * interpolate_mask(gains[t])`` -- the float64 product ops.gain_ramp_apply would store --
+        without that product being written.  Returns z [N, channels, blocks] float64 on the device."""
+        if not torch.is_tensor(data):
+            raise ValueError('Data must be of type torch.Tensor.')
+        _lib.require_cuda(data, gains, out)
+        if data.dtype not in (torch.float32, torch.float64):
+            raise ValueError('Data must be floating point.')
+        if data.dim() != 3:
+            raise ValueError('Audio must be [tracks, samples, channels].')
+        N, n, ch = data.shape
+        if ch > 5:
+            raise ValueError('Audio must have five channels or less.')
+        if n < self.block_size * self.rate:
+            raise ValueError('Audio must have length greater than the block size.')
+        dev = data.device
+        n_gains = 0
+        if gains is not None:
+            if gains.dtype != torch.float64:
+                raise TypeError('gains must be float64')
+            gains = gains.reshape(N, -1).contiguous()
+            n_gains = gains.shape[1]
+            if not 1 <= n_gains <= n:
+                raise ValueError('between one gain and one gain per sample expected')
+        lo_d, hi_d = self._block_bounds(n, dev)
+        num_blocks = lo_d.numel()
+        if out is None:
+            out = torch.empty((N, ch, num_blocks), dtype=torch.float64, device=dev)
+        elif tuple(out.shape) != (N, ch, num_blocks) or out.dtype != torch.float64 or not out.is_contiguous():
+            raise ValueError('bad out tensor')
+        L = _lib.lib()
+        ws = torch.empty(L.dam_loudness_batch_workspace_bytes(N, n, ch, num_blocks) // 8 + 1, dtype=torch.float64, device=dev)
+        with torch.cuda.device(dev):
+            _lib.check(L.dam_loudness_block_energy_batch(
+                _lib.ptr(data), 1 if data.dtype == torch.float64 else 0, N, n, ch, data.stride(0), data.stride(1),
+                data.stride(2), _lib.ptr(gains), n_gains, self._coef, _lib.ptr(lo_d), _lib.ptr(hi_d), num_blocks,
+                float(self.block_size * self.rate), _lib.ptr(out), _lib.ptr(ws), _lib.stream()),
+                'dam_loudness_block_energy_batch')
+        return out
+
+    def integrated_loudness_batch(self, data, gains=None, out=None):
+        """Integrated loudness of every track of ``data`` (see block_energies_batch) -> CUDA float64 [N]; a track the gates
+        empty reads -inf.  No host synchronisation."""
+        return gate_loudness_device(self.block_energies_batch(data, gains), out=out)
+
+
+def gate_loudness_device(z, out=None):
+    """gated_loudness on the device: z CUDA float64 [N, channels, blocks] -> LUFS [N] (dam_loudness_gate)."""
+    _lib.require_cuda(z, out)
+    if z.dtype != torch.float64 or z.dim() != 3:
+        raise ValueError('z must be float64 [tracks, channels, blocks]')
+    z = z.contiguous()
+    N, ch, nb = z.shape
+    if ch > 5:
+        raise ValueError('Audio must have five channels or less.')
+    if out is None:
+        out = torch.empty(N, dtype=torch.float64, device=z.device)
+    elif tuple(out.shape) != (N,) or out.dtype != torch.float64 or not out.is_contiguous():
+        raise ValueError('bad out tensor')
+    with torch.cuda.device(z.device):
+        _lib.check(_lib.lib().dam_loudness_gate(_lib.ptr(z), N, ch, nb, _lib.ptr(out), _lib.stream()), 'dam_loudness_gate')
+    return out
+
+
+def target_gains_device(lufs_dev, target, out=None):
+    """10 ** ((target - lufs) / 20) per track on the device (dam_loudness_target_gains).  lufs_dev: CUDA float64 [N];
+    target: a float, a sequence of N floats or a CUDA float64 [N] tensor (pass a tensor inside a graph capture: a host
+    value is uploaded).  A silent track (lufs -inf) gets the gain +inf, as ``np.power`` gives in normalize_loudness."""
+    _lib.require_cuda(lufs_dev, out)
+    if lufs_dev.dtype != torch.float64:
+        raise TypeError('lufs must be float64')
+    lufs_dev = lufs_dev.contiguous().view(-1)
+    N = lufs_dev.numel()
+    if torch.is_tensor(target):
+        _lib.require_cuda(target)
+        tgt = target.to(torch.float64).contiguous().view(-1)
+    else:
+        t = np.asarray(target, dtype=np.float64)
+        tgt = torch.from_numpy(np.ascontiguousarray(np.broadcast_to(t, (N,)) if t.ndim == 0 else t)).to(lufs_dev.device)
+    if tgt.numel() != N:
+        raise ValueError('one target per track expected')
+    if out is None:
+        out = torch.empty(N, dtype=torch.float64, device=lufs_dev.device)
+    elif out.numel() != N or out.dtype != torch.float64 or not out.is_contiguous():
+        raise ValueError('bad out tensor')
+    with torch.cuda.device(lufs_dev.device):
+        _lib.check(_lib.lib().dam_loudness_target_gains(_lib.ptr(lufs_dev), _lib.ptr(tgt), N, _lib.ptr(out), _lib.stream()),
+                   'dam_loudness_target_gains')
+    return out
+
+
+def normalize_loudness_device(data, lufs_dev, target, out_dtype=None):
+    """normalize_loudness for a batch that stays on the device: data CUDA [N, ...] (every track one leading index, any
+    layout behind it), lufs_dev CUDA float64 [N] (integrated_loudness_batch), target a float or per-track targets.
+    The gain comes from dam_loudness_target_gains, the product is ops.gain_ramp_apply with one gain per track; the result
+    is float64 unless out_dtype says otherwise (the float32-track * float64-gain product).  Unlike normalize_loudness
+    this issues NO 'Possible clipped samples' warning: looking at the peak would need a host synchronisation."""
+    from . import ops
+    _lib.require_cuda(data)
+    N = data.shape[0]
+    g = target_gains_device(lufs_dev, target)
+    # a dense tensor stored as [N, channels, n] and viewed as [N, n, channels] is scaled in place of its storage order
+    if data.dim() == 3 and not data.is_contiguous() and data.transpose(1, 2).is_contiguous():
+        return ops.gain_ramp_apply(data.transpose(1, 2), g.view(N, 1), out_dtype=out_dtype).transpose(1, 2)
+    flat = data.contiguous().view(N, 1, -1)
+    return ops.gain_ramp_apply(flat, g.view(N, 1), out_dtype=out_dtype).view(data.shape)
 
 
 def gated_loudness(z):

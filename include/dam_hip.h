@@ -55,7 +55,7 @@ struct dam_bn_bwd_sums; /* defined in the BatchNorm section */
 /* Library / build identification ("gfx950").  DAM_ABI_VERSION is bumped whenever a signature below changes; a binding
  * compares dam_abi_version() of the library it loaded with the version it was written against and refuses a stale one
  * (deep-audio-mixer_amd/_lib.py: EXPECTED_ABI). */
-#define DAM_ABI_VERSION 18
+#define DAM_ABI_VERSION 19
 const char* dam_arch(void);
 int dam_abi_version(void);
 
@@ -554,7 +554,30 @@ int dam_mixdown_peak_normalize(const void* audio, int audio_is_f64, const double
  *     bounds exactly as the reference's int() truncations produce them; blk_lo/blk_hi/z are device pointers).
  *     x: float32 or float64 (x_is_f64), sample n of channel ch at x[ch*channel_stride + n*sample_stride].
  *     workspace: dam_loudness_workspace_bytes(n_samples, channels) bytes.
- * The gating of the block energies (absolute -70 LUFS, relative -10 LU) is host logic (loudness.py).
+ * For these one-track calls the gating of the block energies (absolute -70 LUFS, relative -10 LU) is host logic
+ * (loudness.gated_loudness); the batched calls below have it on the device.
+ *
+ * Batched, sync-free form (evaluation.py:77-116 measures 4 stems for each of 9 variants of a song).  Every call below
+ * is stateless, does not allocate, does not synchronise with the host and is hipGraph-capturable.
+ *   dam_loudness_block_energy_batch: the block energies of n_tracks tracks of n_samples x channels in one set of
+ *     launches.  Sample n of channel ch of track t is x[t*track_stride + n*sample_stride + ch*channel_stride] (element
+ *     strides: [N][channels][n] planar storage and its transposes are read in place).  coef12_host, blk_lo, blk_hi
+ *     (device, each nondecreasing) and block_len as above, shared by all tracks.  gains (device, may be NULL):
+ *     [n_tracks][n_gains] float64; sample n of every channel of track t is filtered as
+ *       (double)x * gains[t][min(n / (n_samples / n_gains), n_gains-1)]
+ *     -- the index and the float64 product of dam_gain_ramp_apply with out_is_f64, so the scaled stems are never
+ *     written (n_gains = 1: a constant gain per track).  z [n_tracks][channels][n_blocks] float64.  y^2 is not stored per
+ *     sample: the second filter pass sums it between consecutive block bounds, a block is the fixed-order sum of its
+ *     pieces; no atomics, and a track's result does not depend on the other tracks of the call (bitwise).
+ *     workspace: dam_loudness_batch_workspace_bytes(n_tracks, n_samples, channels, n_blocks) bytes, 8-byte aligned.
+ *     n_tracks * channels <= 65535.
+ *   dam_loudness_gate: lufs[t] (device float64) from z [n_tracks][channels <= 5][n_blocks], exactly
+ *     loudness.gated_loudness: channel weights 1, 1, 1, 1.41, 1.41; stage 1 keeps l_j >= -70; stage 2 keeps
+ *     l_j > Gamma_r and l_j > -70 with Gamma_r = loudness of the stage-1 means - 10; an empty stage-2 set gives -inf.
+ *     Fixed-order float64 reductions, any n_blocks >= 1.
+ *   dam_loudness_target_gains: gains[i] = 10^((target[i] - lufs[i]) / 20) (pyloudnorm normalize.loudness), all device
+ *     float64.  A silent track (lufs = -inf) gets the IEEE result +inf, as np.power gives; it is not special-cased.
+ *     The scaled audio itself is dam_gain_ramp_apply with n_gains = 1.
  * --------------------------------------------------------------------------------- */
 int dam_loudness_kweight_coeffs(double rate, double* coef12);
 int64_t dam_loudness_workspace_bytes(int64_t n_samples, int channels);
@@ -562,6 +585,14 @@ int dam_loudness_block_energy(const void* x, int x_is_f64, int64_t n_samples, in
                               int64_t channel_stride, const double* coef12_host, const int64_t* blk_lo,
                               const int64_t* blk_hi, int n_blocks, double block_len, double* z, void* workspace,
                               void* stream);
+int64_t dam_loudness_batch_workspace_bytes(int n_tracks, int64_t n_samples, int channels, int n_blocks);
+int dam_loudness_block_energy_batch(const void* x, int x_is_f64, int n_tracks, int64_t n_samples, int channels,
+                                    int64_t track_stride, int64_t sample_stride, int64_t channel_stride,
+                                    const double* gains, int n_gains, const double* coef12_host, const int64_t* blk_lo,
+                                    const int64_t* blk_hi, int n_blocks, double block_len, double* z, void* workspace,
+                                    void* stream);
+int dam_loudness_gate(const double* z, int n_tracks, int channels, int n_blocks, double* lufs, void* stream);
+int dam_loudness_target_gains(const double* lufs, const double* target, int n, double* gains, void* stream);
 
 /* ---------------------------------------------------------------------------------
  * Stem input layout: x [B][C][HW] (C <= 16 planes, the reference's [B,S,F,T] feature stack) -> y [B][HW][16] with
