@@ -56,13 +56,23 @@ def _record(target, sig):
         fh.write(sig + '\n')
 
 
-def _compile(src, extra=(), suffix=''):
-    """-> (object path, signature of what it was compiled from)"""
-    obj = os.path.join(OBJ, os.path.basename(src)[:-4] + suffix + '.o')
+def _signature(src, extra=()):
+    """Signature of what an object of `src` is compiled from: the source, every header, the compiler and the flags."""
     headers = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith('.h'))
     headers.append(os.path.join(ROOT, 'include', 'dam_hip.h'))
     flags = [a for a in FLAGS if not os.path.isabs(a)] + list(extra)          # (include paths differ between boxes)
-    sig = _digest([src] + headers, [HIPCC] + flags)
+    return _digest([src] + headers, [HIPCC] + flags)
+
+
+def _lib_signature(sigs):
+    import hashlib
+    return hashlib.sha256(''.join(sigs).encode()).hexdigest()
+
+
+def _compile(src, extra=(), suffix=''):
+    """-> (object path, signature of what it was compiled from)"""
+    obj = os.path.join(OBJ, os.path.basename(src)[:-4] + suffix + '.o')
+    sig = _signature(src, extra)
     if not _current(obj, sig):
         cmd = [HIPCC] + FLAGS + list(extra) + ['-c', src, '-o', obj]
         r = subprocess.run(cmd, capture_output=True, text=True)
@@ -82,14 +92,20 @@ def build_lib(force=False, jobs=None):
             os.remove(os.path.join(OBJ, f))
     srcs = sources()
     diag_src = os.path.join(CSRC, DIAG_SOURCE)
+    if not force:
+        # both libraries already built from exactly these sources: nothing to compile, even where the objects did not
+        # travel with the tree (a snapshot that carries the libraries but no csrc/_build/)
+        sigs = [_signature(p) for p in srcs]
+        diag_sigs = [_signature(p, DIAG_FLAGS) if p == diag_src else sig for p, sig in zip(srcs, sigs)]
+        if _current(LIB, _lib_signature(sigs)) and _current(LIB_DIAG, _lib_signature(diag_sigs)):
+            return LIB
     with ThreadPoolExecutor(max_workers=jobs or min(8, len(srcs) + 1)) as ex:
         diag = ex.submit(_compile, diag_src, DIAG_FLAGS, '.diag')
         built = list(ex.map(_compile, srcs))
         diag_built = diag.result()
     diag_members = [diag_built if os.path.basename(o) == DIAG_SOURCE[:-4] + '.o' else (o, sig) for o, sig in built]
     for lib, members in ((LIB, built), (LIB_DIAG, diag_members)):
-        import hashlib
-        sig = hashlib.sha256(''.join(sig for _, sig in members).encode()).hexdigest()
+        sig = _lib_signature(sig for _, sig in members)
         if force or not _current(lib, sig):
             cmd = [HIPCC, '--offload-arch=gfx950', '-shared', '-fPIC', '-o', lib] + [o for o, _ in members]
             r = subprocess.run(cmd, capture_output=True, text=True)

@@ -133,10 +133,23 @@ def close_cached_files(force=False):
             _fd_of_path.clear()
 
 
-def wav_header(path):
-    """Parses the RIFF chunks of a WAV file once: {'tag' (1 integer PCM / 3 IEEE float), 'channels', 'rate', 'bits',
-    'frame_bytes', 'data_offset', 'frames'}.  WAVE_FORMAT_EXTENSIBLE files (what DAWs write for 24-bit / multichannel
-    audio; the stdlib ``wave`` module rejects them) are resolved through their sub-format."""
+def wav_header(path_or_sr, channels=None, subtype=None, n_frames=None):
+    """Two uses, told apart by the TYPE of the first argument: a path (str / bytes / os.PathLike) is parsed, a sample rate
+    (a number) starts the four arguments of a header to be built.
+
+    ``wav_header(path)`` parses the RIFF chunks of a WAV file once: {'tag' (1 integer PCM / 3 IEEE float), 'channels',
+    'rate', 'bits', 'frame_bytes', 'data_offset', 'frames'}.  WAVE_FORMAT_EXTENSIBLE files (what DAWs write for 24-bit /
+    multichannel audio; the stdlib ``wave`` module rejects them) are resolved through their sub-format.
+
+    ``wav_header(sr, channels, subtype, n_frames) -> bytes`` builds the header of a file to be written: everything up to
+    and including the `data` chunk's size field (see ``build_wav_header``)."""
+    if not isinstance(path_or_sr, (str, bytes, os.PathLike)):
+        if channels is None or subtype is None or n_frames is None:
+            raise TypeError('wav_header(sr, channels, subtype, n_frames): all four arguments are needed to build a header')
+        return build_wav_header(path_or_sr, channels, subtype, n_frames)
+    if channels is not None or subtype is not None or n_frames is not None:
+        raise TypeError('wav_header(path) takes no further arguments')
+    path = path_or_sr
     st = os.stat(path)
     key = (path, st.st_mtime_ns, st.st_size)
     if key in _headers:
@@ -321,3 +334,92 @@ def load_tracks_musdb18(base_dir, song_name, tracklist=('bass', 'drums', 'vocals
     """data/dataset_utils.py:71-83, MUSDB18-HQ layout: {song}/{bass,drums,vocals,other,mixture}.wav."""
     return {track: _load(os.path.join(base_dir, song_name, '{}.wav'.format('mixture' if track == 'mix' else track)), sr)
             for track in tracklist}
+
+
+# ---- WAV encoding (stands in for soundfile.write) -------------------------------------------------------------------
+WAV_SUBTYPES = {'PCM_16': (_WAVE_FORMAT_PCM, 16), 'PCM_24': (_WAVE_FORMAT_PCM, 24), 'PCM_32': (_WAVE_FORMAT_PCM, 32),
+                'FLOAT': (_WAVE_FORMAT_IEEE_FLOAT, 32)}          # soundfile's subtype names -> (format tag, bits)
+# KSDATAFORMAT_SUBTYPE_PCM / _IEEE_FLOAT without their first two bytes (the format tag)
+_KSDATAFORMAT_TAIL = bytes([0x00, 0x00, 0x00, 0x00, 0x10, 0x00, 0x80, 0x00, 0x00, 0xAA, 0x00, 0x38, 0x9B, 0x71])
+
+
+def build_wav_header(sr, channels, subtype, n_frames):
+    """RIFF/WAVE header for `n_frames` frames of `channels` interleaved samples, up to and including the `data` chunk's size:
+    the sample bytes follow, then one pad byte if their count is odd (``wav_pad``; the RIFF size counts it).  Format tag 1
+    for the integer subtypes with at most two channels, tag 3 plus a `fact` chunk for FLOAT, WAVE_FORMAT_EXTENSIBLE (with
+    the plain front/left-to-right speaker mask) for more than two channels."""
+    if subtype not in WAV_SUBTYPES:
+        raise ValueError('subtype must be one of %s, got %r' % (sorted(WAV_SUBTYPES), subtype))
+    sr, channels, n_frames = int(sr), int(channels), int(n_frames)
+    if sr < 1 or not 1 <= channels <= 65535 or n_frames < 0:
+        raise ValueError('bad WAV geometry: rate %d, %d channels, %d frames' % (sr, channels, n_frames))
+    tag, bits = WAV_SUBTYPES[subtype]
+    frame_bytes = channels * bits // 8
+    data_bytes = n_frames * frame_bytes
+    fmt = struct.pack('<HHIIHH', _WAVE_FORMAT_EXTENSIBLE if channels > 2 else tag, channels, sr, sr * frame_bytes, frame_bytes,
+                      bits)
+    if channels > 2:
+        mask = (1 << channels) - 1 if channels <= 18 else 0
+        fmt += struct.pack('<HHI', 22, bits, mask) + struct.pack('<H', tag) + _KSDATAFORMAT_TAIL
+    elif tag == _WAVE_FORMAT_IEEE_FLOAT:
+        fmt += struct.pack('<H', 0)                                 # cbSize: non-PCM formats carry the extended fmt chunk
+    chunks = b'fmt ' + struct.pack('<I', len(fmt)) + fmt
+    if tag == _WAVE_FORMAT_IEEE_FLOAT:
+        chunks += b'fact' + struct.pack('<II', 4, n_frames)
+    riff_size = 4 + len(chunks) + 8 + data_bytes + (data_bytes & 1)
+    if riff_size > 0xFFFFFFFF:
+        raise ValueError('%d frames do not fit a RIFF file (4 GiB)' % n_frames)
+    return b'RIFF' + struct.pack('<I', riff_size) + b'WAVE' + chunks + b'data' + struct.pack('<I', data_bytes)
+
+
+def wav_pad(sr, channels, subtype, n_frames):
+    """The RIFF pad byte that follows a `data` chunk of odd size (b'' otherwise)."""
+    return b'\0' if (int(n_frames) * int(channels) * WAV_SUBTYPES[subtype][1] // 8) & 1 else b''
+
+
+def write_wav(path, data, sr, subtype='PCM_16', dither_seed=None) -> int:
+    """``soundfile.write(path, data, sr, subtype)`` for .wav files, quantised on the GPU (ops.pcm_encode; there is no host
+    quantiser).  data: a host array [frames, channels] or [frames] (sf.write's orientation; uploaded), or a CUDA tensor
+    [channels, n] / [n] that is already resident.  The encoded bytes come back through the page-locked pipe and are written
+    behind the header.  Returns the number of samples that had to be clamped (NaN included), and warns when it is not zero."""
+    import torch
+    from .. import ops, staging
+    if subtype not in WAV_SUBTYPES:
+        raise ValueError('subtype must be one of %s, got %r' % (sorted(WAV_SUBTYPES), subtype))
+    if isinstance(data, torch.Tensor) and data.is_cuda:
+        x = data if data.dim() == 2 else data.reshape(1, -1)
+        if x.dtype not in (torch.float32, torch.float64):
+            raise TypeError('write_wav: float32 or float64 audio expected, got %s' % x.dtype)
+        x = x.contiguous()
+        pipe = staging.pipe_for(x.device)
+    else:
+        a = np.asarray(data.cpu() if isinstance(data, torch.Tensor) else data)
+        if a.ndim == 1:
+            a = a[:, None]
+        if a.ndim != 2:
+            raise ValueError('write_wav: [frames, channels] or [frames] expected, got shape %s' % (a.shape,))
+        if a.dtype not in (np.float32, np.float64):
+            raise TypeError('write_wav: float32 or float64 audio expected, got %s' % a.dtype)
+        planar = np.ascontiguousarray(a.T)
+        dev = torch.device('cuda', torch.cuda.current_device())
+        pipe = staging.pipe_for(dev)
+        x = pipe.upload(torch.empty(planar.shape, dtype=torch.from_numpy(planar).dtype, device=dev), planar)
+    ch, n = x.shape
+    clip = torch.empty(ch, dtype=torch.int64, device=x.device)
+    enc = ops.pcm_encode(x, subtype, dither_seed=dither_seed, clip_count=clip)
+    payload = pipe.download(enc)
+    clipped = int(clip.sum().item())
+    write_wav_bytes(path, payload, sr, ch, subtype, n, clipped)
+    return clipped
+
+
+def write_wav_bytes(path, payload, sr, channels, subtype, n_frames, clipped=0):
+    """Header + encoded sample bytes (a uint8 array as ops.pcm_encode yields them) + pad -> file; warns about `clipped`."""
+    if clipped:
+        import warnings
+        warnings.warn('%s: %d of %d samples were outside [-1, 1) and have been clipped' % (path, clipped, n_frames * channels),
+                      RuntimeWarning, stacklevel=3)
+    with open(path, 'wb') as fh:
+        fh.write(build_wav_header(sr, channels, subtype, n_frames))
+        fh.write(memoryview(np.ascontiguousarray(payload)).cast('B'))
+        fh.write(wav_pad(sr, channels, subtype, n_frames))

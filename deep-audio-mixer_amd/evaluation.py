@@ -7,8 +7,10 @@ argument meaning; the meter is the HIP one (loudness.Meter), stems stay on the d
 The whole-song path uploads a song's stems once and never writes a scaled copy of them: the loudnorm and random variants
 are constant gains, the model's mix is a gain ramp, and the batched meter applies either as it loads the samples
 (Meter.integrated_loudness_batch(gains=...)); the mix variant is the 'loudness' kind of inference_utils.SongMixer, one
-hipGraph from PCM to the four LUFS values.  The reference's spreadsheet / WAV export (openpyxl, soundfile) stays out:
-``process_songlist`` returns the rows and the means instead of writing ./stats.xlsx.
+hipGraph from PCM to the four LUFS values.  With ``write_wavs_to_disk`` every variant's stem sum is also rendered on the
+device from the same resident PCM -- mixdown with the variant's gains, batched meter, gain to -20 LUFS, PCM encoder with
+that gain -- and written as ``{song_name}_{identifier}.wav`` (evaluation.py:58-66).  The reference's spreadsheet
+(openpyxl) stays out: ``process_songlist`` returns the rows and the means instead of writing ./stats.xlsx.
 """
 import os
 from collections import OrderedDict
@@ -17,8 +19,8 @@ from statistics import mean
 import numpy as np
 import torch
 
-from . import inference_utils, staging
-from .loudness import Meter, normalize_loudness
+from . import inference_utils, ops, staging
+from .loudness import Meter, normalize_loudness, target_gains_device
 from .models.baselines.mean_loudness_model import MeanLoudnessModel
 from .models.baselines.random_model import RandomModel
 
@@ -94,20 +96,49 @@ class LoudnessEvaluator:
             pipe.upload(pcm[i], np.asarray(tracks[name], dtype=np_dt))
         return pcm
 
+    def write_sum_to_target(self, pcm, gains, path, target_lufs: float = -20.0, subtype='PCM_16'):
+        """evaluation.py:58-66 with its ``sf.write``, for stems resident on the device: pcm CUDA [stems, channels, n],
+        gains None, CUDA float64 [stems] (a constant per stem) or [stems, n_gains] (a gain ramp).  The float64 stem sum is
+        measured, the gain to ``target_lufs`` stays on the device and is applied inside the encoder; the host receives the
+        file's sample bytes.  Returns the clipped-sample count."""
+        from .data.dataset_utils import write_wav_bytes
+        n_stems, channels, n = pcm.shape
+        if gains is None:
+            gains = torch.ones((n_stems, 1), dtype=torch.float64, device=pcm.device)
+        mix = ops.mixdown_peak_normalize(pcm, gains.view(n_stems, -1), normalize=False, out_dtype=torch.float64)
+        lufs = self.meter.integrated_loudness_batch(mix.t().unsqueeze(0))
+        gain = target_gains_device(lufs, torch.full((1,), float(target_lufs), dtype=torch.float64, device=pcm.device))
+        clip = torch.empty(channels, dtype=torch.int64, device=pcm.device)
+        payload = staging.pipe_for(pcm.device).download(ops.pcm_encode(mix, subtype, scale=gain, clip_count=clip))
+        clipped = int(clip.sum().item())
+        write_wav_bytes(path, payload, self.sr, channels, subtype, n, clipped)
+        return clipped
+
     def process_song_tracks(self, loaded_tracks: dict, reference_tracks: dict, song_name: str, n_random_samples: int = 5,
-                            chunk_length: int = 2) -> dict:
+                            chunk_length: int = 2, write_wavs_to_disk=False, results_dir='./experiment') -> dict:
         """evaluation.py:77-116 on stems already in memory ({name: ndarray [channels, n]} each): the loudness profile of
         ``reference_tracks`` against the profiles of ``loaded_tracks`` summed as they are ('sum_error'), normalised to the
         training set's mean loudness ('loudnorm_error'), mixed by the model ('mix_error') and scaled by random gains
         ('random_error', the mean over n_random_samples draws, drawn in the reference's order).  Returns the reference's
-        stats dict plus 'smooth_gains' {name: list}, the gains the mix variant used."""
+        stats dict plus 'smooth_gains' {name: list}, the gains the mix variant used.  write_wavs_to_disk: every variant's
+        stem sum at -20 LUFS goes to ``results_dir/{song_name}_{identifier}.wav`` (reference, sum, loudnorm, mix,
+        random_0 ...; 16-bit); the stats and the order of the random draws do not depend on the switch."""
         if self.d is None or self.mix_model is None or self.mean_loudness_model is None:
             raise ValueError('process_song needs the dataset, d_mean_loudness and mix_model constructor arguments')
         stems = [t for t in self.d.get_tracklist() if t != 'mix']
         if tuple(stems) != self.keys or self.keys != self.random_model.tracklist:
             raise ValueError('the dataset tracklist and the evaluator keys must both be %s' % (self.random_model.tracklist,))
         stats = {'song_name': song_name}
-        reference = OrderedDict(zip(self.keys, self.evaluate_loudness_batch(self._upload(reference_tracks))))
+
+        def write(identifier, pcm, gains=None):
+            if write_wavs_to_disk:
+                os.makedirs(results_dir, exist_ok=True)
+                self.write_sum_to_target(pcm, gains, os.path.join(results_dir, '{}_{}.wav'.format(song_name, identifier)))
+
+        reference_pcm = self._upload(reference_tracks)
+        reference = OrderedDict(zip(self.keys, self.evaluate_loudness_batch(reference_pcm)))
+        write('reference', reference_pcm)
+        del reference_pcm
 
         def error(profile):
             return self._calculate_diff_between_loudness_dicts(OrderedDict(zip(self.keys, profile)), reference)
@@ -119,32 +150,41 @@ class LoudnessEvaluator:
         pcm = mixer.pcm
         lufs = self.meter.integrated_loudness_batch(pcm.transpose(1, 2))
         stats['sum_error'] = error(self._profile(lufs.cpu().tolist()))
+        write('sum', pcm)
         # each multitrack is normalized to the mean loudness of the corresponding track from train set
-        stats['loudnorm_error'] = error(self.evaluate_loudness_batch(pcm, self.mean_loudness_model.device_gains(pcm, lufs)))
+        loudnorm_gains = self.mean_loudness_model.device_gains(pcm, lufs)
+        stats['loudnorm_error'] = error(self.evaluate_loudness_batch(pcm, loudnorm_gains))
+        write('loudnorm', pcm, loudnorm_gains)
         stats['mix_error'] = error(self._profile([float(v) for v in mix_lufs]))
+        write('mix', pcm, mixer.gains[1])
         random_errors = []
         for exp_i in range(n_random_samples):
             drawn = self.random_model.draw()
             g = torch.tensor([drawn[name] for name in self.keys], dtype=torch.float64, device=pcm.device)
             random_errors.append(error(self.evaluate_loudness_batch(pcm, g)))
+            write('random_{}'.format(exp_i), pcm, g)
         stats['random_error'] = mean(random_errors)
         stats['smooth_gains'] = {name: list(gains[1, i]) for i, name in enumerate(self.keys)}
         return stats
 
-    def process_song(self, base_dir: str, song_name: str, n_random_samples: int = 5, chunk_length: int = 2) -> dict:
+    def process_song(self, base_dir: str, song_name: str, n_random_samples: int = 5, chunk_length: int = 2,
+                     write_wavs_to_disk=False, results_dir='./experiment') -> dict:
         """evaluation.py:77-116: the reference mix from ``base_dir/manual_gain_mixes``, the stems from ``base_dir/test``."""
         from .data.dataset_utils import load_tracks_musdb18
         reference_tracks = load_tracks_musdb18(os.path.join(base_dir, 'manual_gain_mixes'), song_name, tracklist=self.keys,
                                                sr=self.sr)
         loaded_tracks = load_tracks_musdb18(os.path.join(base_dir, 'test'), song_name, tracklist=self.keys, sr=self.sr)
-        return self.process_song_tracks(loaded_tracks, reference_tracks, song_name, n_random_samples, chunk_length)
+        return self.process_song_tracks(loaded_tracks, reference_tracks, song_name, n_random_samples, chunk_length,
+                                        write_wavs_to_disk, results_dir)
 
-    def process_songlist(self, base_dir, songlist, n_random_samples: int = 5, chunk_length: int = 2):
+    def process_songlist(self, base_dir, songlist, n_random_samples: int = 5, chunk_length: int = 2,
+                         write_wavs_to_disk=False, results_dir='./experiment'):
         """evaluation.py:118-144 without the spreadsheet: (rows, means) -- one stats dict per song and the mean of every
         error over the songs (the sheet's last row)."""
         keys = ['sum_error', 'random_error', 'loudnorm_error', 'mix_error']
         rows = []
         for i, song_name in enumerate(songlist):
             print('{}/{}: {}'.format(i + 1, len(songlist), song_name))
-            rows.append(self.process_song(base_dir, song_name, n_random_samples, chunk_length))
+            rows.append(self.process_song(base_dir, song_name, n_random_samples, chunk_length, write_wavs_to_disk,
+                                          results_dir))
         return rows, {key: mean(row[key] for row in rows) for key in keys}

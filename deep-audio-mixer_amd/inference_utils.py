@@ -10,7 +10,9 @@ hipGraph (``SongMixer``): strided STFT front-end over all chunks of all stems st
 (dam_stft_logmag_strided_f32) -> model forward of the whole chunk batch -> 10 ** (0.5 g) and the Savitzky-Golay
 smoothing (dam_gains_smooth) -> sample-rate gain ramp x audio (dam_gain_ramp_apply), or for ``mix_song_to_master`` the
 fused stem sum + peak normalisation (dam_mixdown_peak_normalize) or, with ``normalize='loudness'``, the stem sum brought to
-a target BS.1770 loudness; ``mix_song_loudness`` ends in the batched meter instead (the per-stem loudness of the mixed
+a target BS.1770 loudness -- and, for ``mix_song_to_wav``, the PCM encoder as the graph's last node (dam_pcm_encode: the
+loudness gain is applied inside it, the host receives the file's sample bytes instead of the float master);
+``mix_song_loudness`` ends in the batched meter instead (the per-stem loudness of the mixed
 stems, dam_loudness_block_energy_batch with the gain ramp applied at load: the mixed stems are never written).
 ``mix_song_spectral`` renders in the spectral domain
 instead (experiments.ipynb cells 44-53): the model's predicted dB spectrogram ``masked`` on the phases of the stems' sum
@@ -64,9 +66,15 @@ class SongMixer:
     chunk length, output kind).  ``run(tracks)`` uploads, replays, downloads."""
 
     def __init__(self, model, n_stems, channels, n_samples, dtype, chunk_samples, kind, normalize=True,
-                 out_dtype=torch.float64, use_graph=True, hop_length=1024, sr=44100, target_lufs=-20.0):
+                 out_dtype=torch.float64, use_graph=True, hop_length=1024, sr=44100, target_lufs=-20.0, encode=None,
+                 dither_seed=None):
+        """encode (kind 'master' only): None, or a WAV subtype ('PCM_16', 'PCM_24', 'PCM_32', 'FLOAT') -- the master is then
+        quantised by the last node of the same graph and ``run`` returns its sample bytes and the clipped-sample count."""
         if kind not in ('stems', 'master', 'spectral', 'loudness'):
             raise ValueError(kind)
+        if encode is not None and (kind != 'master' or encode not in ops.PCM_FORMATS):
+            raise ValueError("encode needs kind='master' and one of %s, got %r" % (sorted(ops.PCM_FORMATS), encode))
+        self.encode, self.dither_seed = encode, dither_seed
         if normalize not in (True, False, 'loudness'):
             raise ValueError("normalize must be True, False or 'loudness'")
         self.model, self.kind, self.normalize = model, kind, normalize
@@ -100,7 +108,11 @@ class SongMixer:
             self.out = torch.empty(n_stems, dtype=torch.float64, device=dev)                       # LUFS of every mixed stem
             self.ws = None
         else:
-            self.out = torch.empty((channels, n_samples), dtype=out_dtype, device=dev)
+            if encode is None or normalize != 'loudness':          # (the encoder reads the float64 sum and scales it itself)
+                self.out = torch.empty((channels, n_samples), dtype=out_dtype, device=dev)
+            if encode is not None:
+                self.enc = torch.empty(n_samples * channels * ops.PCM_FORMATS[encode][1], dtype=torch.uint8, device=dev)
+                self.clip = torch.empty(channels, dtype=torch.int64, device=dev)
             if normalize == 'loudness':
                 # evaluation.py:59-66: the float64 stem sum is measured and scaled; only the result takes out_dtype
                 self.meter = loudness.Meter(sr)
@@ -142,9 +154,15 @@ class SongMixer:
             ops.mixdown_peak_normalize(self.pcm, smooth, normalize=False, out=self.mix, workspace=self.ws)
             self.meter.integrated_loudness_batch(self.mix.t().unsqueeze(0), out=self.lufs)
             loudness.target_gains_device(self.lufs, self.target, out=self.master_gain)
-            ops.gain_ramp_apply(self.mix, self.master_gain, out=self.out)
+            if self.encode is None:
+                ops.gain_ramp_apply(self.mix, self.master_gain, out=self.out)
+            else:                                  # mix * gain is rounded once to float64 either way: the same samples
+                ops.pcm_encode(self.mix, self.encode, scale=self.master_gain, dither_seed=self.dither_seed, out=self.enc,
+                               clip_count=self.clip)
         else:
             ops.mixdown_peak_normalize(self.pcm, smooth, normalize=self.normalize, out=self.out, workspace=self.ws)
+            if self.encode is not None:
+                ops.pcm_encode(self.out, self.encode, dither_seed=self.dither_seed, out=self.enc, clip_count=self.clip)
 
     def _model_key(self):
         # the captured forward holds the FOLDED conv + BatchNorm images (layers.FoldedConvBn), computed when it was captured:
@@ -175,13 +193,16 @@ class SongMixer:
         self.graph.replay()
 
     def run(self, tracks):
-        """tracks: list of n_stems host arrays [channels, n_samples].  Returns (out ndarray, gains ndarray [2, S, n_proc])."""
+        """tracks: list of n_stems host arrays [channels, n_samples].  Returns (out ndarray, gains ndarray [2, S, n_proc]);
+        with ``encode``, out is (sample bytes uint8 ndarray, clipped-sample count)."""
         pipe = staging.pipe_for(self.dev)
         for i, a in enumerate(tracks):
             pipe.upload(self.pcm[i], a)
         self.launch()
         if self.kind == 'loudness':
             return self.out.cpu().numpy(), self.gains.cpu().numpy()
+        if self.encode is not None:
+            return (pipe.download(self.enc), int(self.clip.sum().item())), self.gains.cpu().numpy()
         out = pipe.download(self.out)
         if self.kind == 'spectral':
             return out.reshape(-1), pipe.download(self.masked)
@@ -191,7 +212,8 @@ class SongMixer:
 _mixers = {}
 
 
-def _mixer(model, stems, loaded_tracks, chunk_length, sr, kind, normalize, out_dtype, hop_length=1024, target_lufs=-20.0):
+def _mixer(model, stems, loaded_tracks, chunk_length, sr, kind, normalize, out_dtype, hop_length=1024, target_lufs=-20.0,
+           encode=None, dither_seed=None):
     first = np.asarray(loaded_tracks[stems[0]])
     if first.ndim != 2:
         raise ValueError('loaded_tracks[track] must be [channels, n] arrays')
@@ -199,12 +221,13 @@ def _mixer(model, stems, loaded_tracks, chunk_length, sr, kind, normalize, out_d
     dt = torch.float32 if first.dtype == np.float32 else torch.float64
     if normalize != 'loudness':
         normalize, target_lufs = bool(normalize), None
-    key = (id(model), len(stems), ch, n, dt, chunk_length * sr, kind, normalize, out_dtype, hop_length, sr, target_lufs)
+    key = (id(model), len(stems), ch, n, dt, chunk_length * sr, kind, normalize, out_dtype, hop_length, sr, target_lufs,
+           encode, dither_seed if encode is not None else None)
     m = _mixers.get(key)
     if m is None:
         _mixers.clear()                        # one geometry at a time: a song's buffers are hundreds of MB
         m = SongMixer(model, len(stems), ch, n, dt, chunk_length * sr, kind, normalize, out_dtype, hop_length=hop_length, sr=sr,
-                      target_lufs=-20.0 if target_lufs is None else target_lufs)
+                      target_lufs=-20.0 if target_lufs is None else target_lufs, encode=encode, dither_seed=dither_seed)
         _mixers[key] = m
     np_dt = np.float32 if dt == torch.float32 else np.float64
     return m, [np.asarray(loaded_tracks[t], dtype=np_dt) for t in stems]
@@ -246,6 +269,24 @@ def mix_song_to_master(dataset, model, loaded_tracks: dict, chunk_length=1, sr=4
     out, gains = m.run(arrays)
     raw_gains = {t: [float(v) for v in gains[0, i]] for i, t in enumerate(stems)}
     return out, raw_gains, {t: list(gains[1, i]) for i, t in enumerate(stems)}
+
+
+def mix_song_to_wav(dataset, model, loaded_tracks: dict, path, chunk_length=1, sr=44100, normalize=True, subtype='PCM_16',
+                    target_lufs=-20.0, dither_seed=None):
+    """mix_song_to_master followed by the callers' ``sf.write(path, master.T, sr)`` (inference.ipynb cells 9/11;
+    evaluation.py:59-66 with ``normalize='loudness'``): the float64 master is quantised to ``subtype`` by the last node of
+    the song's graph (ops.pcm_encode, TPDF dither if ``dither_seed`` is given), so the host receives the file's sample
+    bytes -- a quarter of the float64 master for 'PCM_16' -- and writes them behind a WAV header.  The samples are those
+    tests/_pcm_ref.py's quantiser makes of mix_song_to_master(..., dtype=float64).
+    Returns (clipped sample count, raw_gains, smooth_gains); warns (RuntimeWarning) when samples had to be clipped."""
+    from .data.dataset_utils import write_wav_bytes
+    stems = [t for t in dataset.get_tracklist() if t != 'mix']
+    m, arrays = _mixer(model, stems, loaded_tracks, chunk_length, sr, 'master', normalize, torch.float64, target_lufs=target_lufs,
+                       encode=subtype, dither_seed=dither_seed)
+    (payload, clipped), gains = m.run(arrays)
+    write_wav_bytes(path, payload, sr, m.channels, subtype, m.n, clipped)
+    raw_gains = {t: [float(v) for v in gains[0, i]] for i, t in enumerate(stems)}
+    return clipped, raw_gains, {t: list(gains[1, i]) for i, t in enumerate(stems)}
 
 
 def mix_song_spectral(dataset, model, loaded_tracks: dict, chunk_length=1, sr=44100, hop_length=1024, dtype=np.float32):

@@ -756,6 +756,54 @@ def mixdown_peak_normalize(audio, gains, normalize=True, out=None, out_dtype=Non
     return out
 
 
+# ----------------------------------------------------------------------------- PCM encoder (WAV payload)
+PCM_FORMATS = {'PCM_16': (0, 2), 'PCM_24': (1, 3), 'PCM_32': (2, 4), 'FLOAT': (3, 4)}    # soundfile's subtype names -> (DAM_WAV_*, bytes)
+PCM_MAX_CHANNELS = 8                   # DAM_PCM_MAX_CHANNELS
+
+
+def pcm_grid_frames(dtype):
+    """Frames one pass of the encoder's capped grid covers for float32 / float64 input, asked of the library
+    (dam_pcm_tile_frames x dam_pcm_max_blocks): longer buffers are walked tile by tile."""
+    L = _lib.lib()
+    return L.dam_pcm_tile_frames(1 if dtype in (torch.float64, 'float64') else 0) * L.dam_pcm_max_blocks()
+
+
+def pcm_encode(x, subtype, scale=None, dither_seed=None, out=None, clip_count=None):
+    """x: CUDA float32 / float64 planar [channels, n] (or [n]) -> the interleaved little-endian sample bytes of a WAV `data`
+    chunk, uint8 [n * channels * bytes_per_sample] (include/dam_hip.h: dam_pcm_encode).  scale: CUDA float64 of 1 or
+    `channels` elements, multiplied in float64 before quantisation.  dither_seed: None = no dither, else the seed of the
+    +-1 LSB TPDF dither.  clip_count: CUDA int64 [channels], overwritten with the clamped-sample counts."""
+    _lib.require_cuda(x, scale, out, clip_count)
+    if subtype not in PCM_FORMATS:
+        raise ValueError('pcm_encode: subtype must be one of %s, got %r' % (sorted(PCM_FORMATS), subtype))
+    fmt, width = PCM_FORMATS[subtype]
+    xk = _audio_kind(x, 'x')
+    if x.dim() == 1:
+        x = x.unsqueeze(0)
+    if x.dim() != 2 or not x.is_contiguous():
+        raise ValueError('pcm_encode: a contiguous [channels, n] tensor expected (got shape %s, contiguous=%s)'
+                         % (tuple(x.shape), x.is_contiguous()))
+    ch, n = x.shape
+    if not 1 <= ch <= PCM_MAX_CHANNELS or n < 1:
+        raise ValueError('pcm_encode: 1..%d channels and at least one frame expected, got [%d, %d]' % (PCM_MAX_CHANNELS, ch, n))
+    n_scale = 0
+    if scale is not None:
+        if scale.dtype != torch.float64 or not scale.is_contiguous() or scale.numel() not in (1, ch):
+            raise ValueError('pcm_encode: scale must be a contiguous float64 tensor of 1 or %d elements' % ch)
+        n_scale = scale.numel()
+    if out is None:
+        out = torch.empty(n * ch * width, dtype=torch.uint8, device=x.device)
+    elif out.dtype != torch.uint8 or out.numel() != n * ch * width or not out.is_contiguous():
+        raise ValueError('pcm_encode: out must be a contiguous uint8 tensor of %d elements' % (n * ch * width))
+    if clip_count is not None and (clip_count.dtype != torch.int64 or clip_count.numel() != ch or not clip_count.is_contiguous()):
+        raise ValueError('pcm_encode: clip_count must be a contiguous int64 tensor of %d elements' % ch)
+    seed = 0 if dither_seed is None else int(dither_seed) & 0xFFFFFFFFFFFFFFFF
+    _lib.check(_lib.lib().dam_pcm_encode(_lib.ptr(x), xk, ch, n, _lib.ptr(scale), n_scale, fmt,
+                                         0 if dither_seed is None else 1, seed, _lib.ptr(out), _lib.ptr(clip_count),
+                                         _lib.stream()), 'dam_pcm_encode')
+    return out
+
+
 # ----------------------------------------------------------------------------- dropout
 _dropout_counters = {}
 

@@ -55,7 +55,7 @@ struct dam_bn_bwd_sums; /* defined in the BatchNorm section */
 /* Library / build identification ("gfx950").  DAM_ABI_VERSION is bumped whenever a signature below changes; a binding
  * compares dam_abi_version() of the library it loaded with the version it was written against and refuses a stale one
  * (deep-audio-mixer_amd/_lib.py: EXPECTED_ABI). */
-#define DAM_ABI_VERSION 19
+#define DAM_ABI_VERSION 20
 const char* dam_arch(void);
 int dam_abi_version(void);
 
@@ -593,6 +593,31 @@ int dam_loudness_block_energy_batch(const void* x, int x_is_f64, int n_tracks, i
                                     void* stream);
 int dam_loudness_gate(const double* z, int n_tracks, int channels, int n_blocks, double* lufs, void* stream);
 int dam_loudness_target_gains(const double* lufs, const double* target, int n, double* gains, void* stream);
+
+/* ---------------------------------------------------------------------------------
+ * PCM encoder: the payload of the WAV file every caller of the reference ends with (inference.ipynb `sf.write`,
+ * evaluation.py:58-66, data/listening_test_data_preparation.py), quantised on the device.
+ *   x: planar [channels][n_samples] float32 or float64 (x_is_f64), contiguous -- the layout of the master and of each
+ *      mixed stem; channels 1 .. DAM_PCM_MAX_CHANNELS.
+ *   scale (device float64, n_scale = 0: none, 1, or channels): v = (double)x * scale[..], one float64 rounding.
+ *   out: interleaved [n_samples][channels], little endian, DAM_WAV_S24 = 3 packed bytes; 4-byte aligned.
+ *   Integer formats, B = 16 / 24 / 32: a NaN v is written as 0 and counted; w = v * 2^(B-1) (exact); with `dither`
+ *   w = w + d, d = u1 - u2 with u1, u2 the high and low 32 bits of r over 2^32, r = the 64-bit splitmix64 finaliser of
+ *   seed * 0xD1342543DE82EF95 + (n * channels + c) (TPDF, +-1 LSB, a pure function of seed and element); q = rint(w)
+ *   (ties to even) clamped to [-2^(B-1), 2^(B-1) - 1].  DAM_WAV_F32 writes (float)v: no dither, nothing counted.
+ *   clip_count (device int64 [channels], may be NULL): OVERWRITTEN with the number of clamped (or NaN) elements per channel.
+ * The launch is capped at DAM_PCM_MAX_BLOCKS workgroups of 256 lanes x 16 input bytes per channel row; larger buffers are
+ * walked tile by tile.  Parity with libsndfile's converters is not claimed.
+ * --------------------------------------------------------------------------------- */
+typedef enum dam_wav_format { DAM_WAV_S16 = 0, DAM_WAV_S24 = 1, DAM_WAV_S32 = 2, DAM_WAV_F32 = 3 } dam_wav_format;
+#define DAM_PCM_MAX_CHANNELS 8
+#define DAM_PCM_MAX_BLOCKS 2048
+/* The launch geometry, for callers and tests that need the grid-stride boundary: frames of one tile (256 lanes x 16 input
+ * bytes per channel row) and the workgroup cap; one pass of the full grid covers their product. */
+int64_t dam_pcm_tile_frames(int x_is_f64);
+int dam_pcm_max_blocks(void);
+int dam_pcm_encode(const void* x, int x_is_f64, int channels, int64_t n_samples, const double* scale, int n_scale,
+                   int format, int dither, uint64_t seed, void* out, int64_t* clip_count, void* stream);
 
 /* ---------------------------------------------------------------------------------
  * Stem input layout: x [B][C][HW] (C <= 16 planes, the reference's [B,S,F,T] feature stack) -> y [B][HW][16] with
