@@ -96,6 +96,16 @@ struct PerDevice {
     T v[MAX_DEVICES] = {};
     T& operator()() { return v[device_slot()]; }
 };
+// Raises Kernel's dynamic-LDS limit to `bytes`, the first time it is asked on each device (every instantiation has its own
+// flags); false where the runtime refuses.
+template <auto Kernel>
+static inline bool raise_lds_limit(int bytes) {
+    static PerDevice<bool> raised_pd;
+    bool& raised = raised_pd();
+    if (!raised)
+        raised = hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, bytes) == hipSuccess;
+    return raised;
+}
 static inline int device_cus() {
     static PerDevice<int> cus;
     int& n = cus();

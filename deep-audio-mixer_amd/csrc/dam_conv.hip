@@ -268,15 +268,7 @@ template <int MB, int NB>
 int launch_conv_pack(const ConvGeoPack& pk, size_t lds, const float* X, const float* Wp, const float* bias, const float* sc,
                      const float* sh, float* Y, const float* res, const float* res_mask, float* splitk_ws, hipStream_t st) {
     constexpr int TM = 64 * MB;
-    if (lds > 64 * 1024) {
-        static PerDevice<bool> raised_pd; bool& raised = raised_pd();
-        if (!raised) {
-            if (hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_igemm_kernel<MB, NB>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
-                return DAM_ERR_LAUNCH;
-            raised = true;
-        }
-    }
+    if (lds > 64 * 1024 && !raise_lds_limit<&conv_igemm_kernel<MB, NB>>(160 * 1024)) return DAM_ERR_LAUNCH;
     int64_t gx = 0, gy = 0;
     for (int i = 0; i < pk.n; ++i) {
         const ConvGeo& g = pk.g[i];

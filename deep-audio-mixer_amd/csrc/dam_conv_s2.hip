@@ -292,14 +292,8 @@ int launch_conv_s2_pair(const float* x, const float* wp, const float* wp2, int B
     int64_t wgs = (int64_t)cus * per_cu;
     if (wgs > cdiv(units, WAVES)) wgs = cdiv(units, WAVES);
     if (parts_host) *parts_host = stats ? (int)wgs : 0;
-    static PerDevice<bool> raised_pd[2];
-    bool& raised = raised_pd[stats ? 1 : 0]();
-    if (lds > 64 * 1024 && !raised) {
-        const void* fn = stats ? reinterpret_cast<const void*>(&conv_s2_pair_kernel<NB, NCH, true, WAVES>)
-                               : reinterpret_cast<const void*>(&conv_s2_pair_kernel<NB, NCH, false, WAVES>);
-        if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) return DAM_ERR_LAUNCH;
-        raised = true;
-    }
+    if (lds > 64 * 1024 && !(stats ? raise_lds_limit<&conv_s2_pair_kernel<NB, NCH, true, WAVES>>(160 * 1024)
+                                   : raise_lds_limit<&conv_s2_pair_kernel<NB, NCH, false, WAVES>>(160 * 1024))) return DAM_ERR_LAUNCH;
     if (stats)
         hipLaunchKernelGGL((conv_s2_pair_kernel<NB, NCH, true, WAVES>), dim3((unsigned)wgs), dim3(64 * WAVES), lds, st, x, (unsigned)xb,
                            reinterpret_cast<const float4*>(wp), reinterpret_cast<const float4*>(wp2), Hd, Wd, H, W, y, ys, p1, p2, (int)px,

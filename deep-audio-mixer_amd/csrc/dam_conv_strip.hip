@@ -1146,15 +1146,7 @@ template <int MB, int NB, int NCH, bool T33, bool LW = false, int EPI = 0, int S
 static int launch_strip(ConvGeo& g, StripGeo& sg, size_t lds, const float* X, const float* Wp, const float* bias, float* Y,
                         const float* res, const float* res_mask, float* stats, const float* in_scale, const float* in_shift,
                         const BnBwdEpi& bwd, hipStream_t st) {
-    if (lds > 64 * 1024) {
-        static PerDevice<bool> raised_pd; bool& raised = raised_pd();
-        if (!raised) {
-            if (hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_strip_kernel<MB, NB, NCH, T33, LW, EPI, SO>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
-                return DAM_ERR_LAUNCH;
-            raised = true;
-        }
-    }
+    if (lds > 64 * 1024 && !raise_lds_limit<&conv_strip_kernel<MB, NB, NCH, T33, LW, EPI, SO>>(160 * 1024)) return DAM_ERR_LAUNCH;
     dim3 grid((unsigned)sg.strips, (unsigned)cdiv(g.N / 16, NB), (unsigned)g.B);
     hipLaunchKernelGGL((conv_strip_kernel<MB, NB, NCH, T33, LW, EPI, SO>), grid, dim3(SO ? 512 : STRIP_THREADS), lds, st, g, sg, X, reinterpret_cast<const float4*>(Wp), bias,
                        Y, res, res_mask, stats, in_scale, in_shift, bwd);

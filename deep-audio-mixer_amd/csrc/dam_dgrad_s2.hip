@@ -299,12 +299,7 @@ int launch_dgrad_s2(const float* dc, const float* wpt, const float* ds, const fl
     if (sums.u && wgs > BN_BWD_RECORDS_MAX) return DAM_ERR_UNSUPPORTED;
 #define DAM_S2_GO(PAIR_, SUMS_)                                                                                                   \
     do {                                                                                                                          \
-        static PerDevice<bool> raised_pd; bool& raised = raised_pd();\
-        if (!raised && lds > 64 * 1024) {                                                                                         \
-            if (hipFuncSetAttribute(reinterpret_cast<const void*>(&dgrad_s2_kernel<NB, NCH, MB, PAIR_, WAVES, SUMS_>),              \
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) return DAM_ERR_LAUNCH;     \
-            raised = true;                                                                                                        \
-        }                                                                                                                         \
+        if (lds > 64 * 1024 && !raise_lds_limit<&dgrad_s2_kernel<NB, NCH, MB, PAIR_, WAVES, SUMS_>>(160 * 1024)) return DAM_ERR_LAUNCH; \
         hipLaunchKernelGGL((dgrad_s2_kernel<NB, NCH, MB, PAIR_, WAVES, SUMS_>), dim3((unsigned)wgs), dim3(64 * WAVES), lds, st, dc, \
                            reinterpret_cast<const float4*>(wpt), ds, reinterpret_cast<const float4*>(wpt2), B, Hd, Wd, dx, H, W,      \
                            (int)px, (int)units, sums);                                                                            \

@@ -118,16 +118,8 @@ extern "C" int dam_istft_f32(const float* spec, const float* mag_db, int64_t n_t
     if (!spec || !window || !twiddles || !out) return DAM_ERR_BAD_ARG;
     (void)workspace;
     const size_t lds = (size_t)n_fft * sizeof(float2);                // two buffers of n_fft/2 complex points
-    if (lds > 48 * 1024) {                                            // 8192 / 16384-point windows: raise the kernel's LDS limit once
-        static PerDevice<bool> raised_pd;
-        bool& raised = raised_pd();
-        if (!raised) {
-            if (hipFuncSetAttribute(reinterpret_cast<const void*>(&istft_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    132 * 1024) != hipSuccess)
-                return DAM_ERR_LAUNCH;
-            raised = true;
-        }
-    }
+    // 8192 / 16384-point windows: beyond the default dynamic-LDS limit
+    if (lds > 48 * 1024 && !raise_lds_limit<&istft_kernel>(132 * 1024)) return DAM_ERR_LAUNCH;
     const dim3 grid((unsigned)cdiv(length, ISTFT_SEG), (unsigned)n_tracks);
     hipLaunchKernelGGL(istft_kernel, grid, dim3(FFT_THREADS), lds, (hipStream_t)stream, reinterpret_cast<const float2*>(spec),
                        mag_db, window, reinterpret_cast<const float2*>(twiddles), n_fft, hop, (int)n_frames, length, out);

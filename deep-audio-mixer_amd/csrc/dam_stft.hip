@@ -48,29 +48,7 @@ __device__ __forceinline__ void fft16(float2 (&v)[16]) {
 }
 __device__ __forceinline__ constexpr int fft16_pos(int k) { return 4 * (k & 3) + (k >> 2); }
 
-// Channel layouts: interleaved (PLANAR = false: sample p of channel c at trk[CH*p + c], what soundfile / a WAV decoder
-// hands over) and planar (PLANAR = true: trk[c*cs + p], the [channels, n] arrays inference_utils.py works on).
-// Integer PCM (DAM_PCM_S16 / DAM_PCM_S32: the samples as the WAV file holds them, data/dataset.py:192-196 reads them through
-// soundfile, which divides by 2^(bits-1)): every sample is converted to float exactly as that division rounds it, the
-// power-of-two scale 2^-(bits-1) rides on the window * gain product (exact), so the result is bit for bit what the float32
-// kernel computes from host-converted samples -- without the host conversion and with half the bytes over PCIe for 16 bit.
-template <typename PCM> struct pcm_traits { static constexpr bool integer = false; static constexpr float scale = 1.0f; };
-template <> struct pcm_traits<int16_t> { static constexpr bool integer = true; static constexpr float scale = 1.0f / 32768.0f; };
-template <> struct pcm_traits<int32_t> { static constexpr bool integer = true; static constexpr float scale = 1.0f / 2147483648.0f; };
-
-template <typename PCM>
-__device__ __forceinline__ float mean2(PCM a, PCM b) {
-    if constexpr (pcm_traits<PCM>::integer) return ((float)a + (float)b) * 0.5f;
-    else return (float)((a + b) * (PCM)0.5);
-}
-
-template <typename PCM, int CH, bool PLANAR>
-__device__ __forceinline__ float mono_at(const PCM* __restrict__ trk, int64_t cs, int64_t p) {
-    if (CH == 1) return (float)trk[p];
-    if (PLANAR) return mean2<PCM>(trk[p], trk[cs + p]);
-    return mean2<PCM>(trk[2 * p], trk[2 * p + 1]);
-}
-
+// (channel layouts, integer PCM, pcm_traits / mean2 / mono_at / reflect: dam_fft_lds.h)
 typedef float f32x2_u __attribute__((ext_vector_type(2), aligned(4)));
 typedef int i32x4 __attribute__((ext_vector_type(4)));
 typedef int i32x2 __attribute__((ext_vector_type(2)));
@@ -91,10 +69,6 @@ __device__ __forceinline__ float2 load_pair_interior(const PCM* __restrict__ trk
     } else {
         return make_float2(mono_at<PCM, CH, PLANAR>(trk, cs, p), mono_at<PCM, CH, PLANAR>(trk, cs, p + 1));
     }
-}
-__device__ __forceinline__ int64_t reflect(int64_t p, int64_t n) {
-    p = p < 0 ? -p : p;
-    return p >= n ? 2 * (n - 1) - p : p;
 }
 
 // 20*log10(max(m, amin)); the floor is passed in (computed in double on the host) so that
@@ -393,53 +367,30 @@ __global__ __launch_bounds__(TF2* WAVE, 4) void stft2048_kernel(
 // Any power-of-two window (data/dataset.py:132-133 exposes window_size / hop_length as parameters; every caller in the
 // reference leaves them at 2048 / 1024, which is what the kernel above is built for).  One workgroup = one frame:
 // M = n_fft/2 complex points z[n] = w[2n] x[2n] + i w[2n+1] x[2n+1] in LDS, log2(M) autosort (Stockham) radix-2 passes,
-// the same real-FFT split and dB epilogue, bins written straight out.  Not tuned: correctness path.
+// the real-FFT split (the pieces of dam_fft_lds.h) and the dB epilogue, bins written straight out.  Not tuned: correctness path.
 template <typename PCM, int CH, bool PLANAR>
-__global__ __launch_bounds__(256) void stft_generic_kernel(
+__global__ __launch_bounds__(FFT_THREADS) void stft_generic_kernel(
     const PCM* __restrict__ pcm, int64_t n_samples, int64_t outer_stride, int n_inner, int64_t inner_stride, int64_t cs,
     const float* __restrict__ window, const float2* __restrict__ tw /* W_nfft^k */, const float* __restrict__ gain, int n_fft,
     int hop, int n_frames, float amin, float floor_db, int normalize, float* __restrict__ out, float* __restrict__ out_tail,
     int n_tail, int indirect) {
     pcm = resolve_pcm(pcm, indirect);
     extern __shared__ __attribute__((aligned(16))) float2 buf[];      // [2][M]
-    __shared__ float red[256];
+    __shared__ float red[FFT_THREADS];
     const int tid = threadIdx.x;
     const int M = n_fft >> 1, nbins = M + 1;
     const int64_t track = blockIdx.y;
     const int t = blockIdx.x;
     const PCM* trk = pcm + (track / n_inner) * outer_stride + (track % n_inner) * inner_stride;
     const float g = (gain ? gain[track] : 1.0f) * pcm_traits<PCM>::scale;
-    const int64_t p0 = (int64_t)t * hop - M;
-    for (int n = tid; n < M; n += 256) {
-        const int64_t a = reflect(p0 + 2 * n, n_samples), b = reflect(p0 + 2 * n + 1, n_samples);
-        buf[n] = make_float2(mono_at<PCM, CH, PLANAR>(trk, cs, a) * (window[2 * n] * g),
-                             mono_at<PCM, CH, PLANAR>(trk, cs, b) * (window[2 * n + 1] * g));
-    }
+    lds_load_frame<PCM, CH, PLANAR>(buf, M, trk, 1, 0, cs, n_samples, (int64_t)t * hop - M, window, g, tid);
     __syncthreads();
-    float2* x = buf;
-    float2* y = buf + M;
-    int sshift = 0;                                   // s = 1 << sshift
-    for (int n = M; n > 1; n >>= 1, ++sshift) {
-        const int m = n >> 1, s = 1 << sshift;
-        for (int e = tid; e < (M >> 1); e += 256) {
-            const int p = e >> sshift, q = e & (s - 1);
-            const float2 a = x[q + s * p], b = x[q + s * (p + m)];
-            const float2 w = tw[(2 * p * s) & (n_fft - 1)];                 // W_n^p = W_nfft^(2 p s)
-            y[q + s * (2 * p)] = cadd(a, b);
-            y[q + s * (2 * p + 1)] = cmul(csub(a, b), w);
-        }
-        __syncthreads();
-        float2* tmp = x; x = y; y = tmp;
-    }
-    // real-FFT split + dB; the result of bin f goes to y[] as a float (reusing the other buffer)
-    float* db = reinterpret_cast<float*>(y);
+    const float2* x = lds_fft_radix2<false>(buf, buf + M, M, n_fft, tw, tid);
+    // real-FFT split + dB; the result of bin f goes to the other buffer as a float
+    float* db = reinterpret_cast<float*>(x == buf ? buf + M : buf);
     float mx = 0.f;
-    for (int k = tid; k <= M; k += 256) {
-        const float2 zk = x[k & (M - 1)], zn = x[(M - k) & (M - 1)];
-        const float2 e = make_float2(0.5f * (zk.x + zn.x), 0.5f * (zk.y - zn.y));
-        const float2 o = make_float2(0.5f * (zk.y + zn.y), -0.5f * (zk.x - zn.x));
-        const float2 wk = k < n_fft ? tw[k & (n_fft - 1)] : make_float2(1.f, 0.f);
-        const float2 xa = cadd(e, cmul(wk, o));
+    for (int k = tid; k <= M; k += FFT_THREADS) {
+        const float2 xa = real_fft_bin(x, k, M, tw);
         const float v = to_db(sqrtf(xa.x * xa.x + xa.y * xa.y), amin, floor_db);
         db[k] = v;
         mx = fmaxf(mx, fabsf(v));
@@ -448,7 +399,7 @@ __global__ __launch_bounds__(256) void stft_generic_kernel(
     if (normalize) {
         red[tid] = mx;
         __syncthreads();
-        for (int st = 128; st >= 1; st >>= 1) {
+        for (int st = FFT_THREADS / 2; st >= 1; st >>= 1) {
             if (tid < st) red[tid] = fmaxf(red[tid], red[tid + st]);
             __syncthreads();
         }
@@ -458,7 +409,7 @@ __global__ __launch_bounds__(256) void stft_generic_kernel(
     const int ig = (int)(track % n_inner), n_main = n_inner - n_tail;
     float* o = (ig < n_main ? out + ((og * n_main + ig) * (int64_t)nbins) * n_frames
                             : out_tail + ((og * n_tail + (ig - n_main)) * (int64_t)nbins) * n_frames) + t;
-    for (int k = tid; k <= M; k += 256) {
+    for (int k = tid; k <= M; k += FFT_THREADS) {
         float v = db[k];
         if (normalize && scale >= 1.17549435e-38f) v = v / scale;
         o[(int64_t)k * n_frames] = v;
@@ -470,7 +421,7 @@ __global__ __launch_bounds__(256) void stft_generic_kernel(
 // The reference needs them for the PHASES of a mix (experiments.ipynb cells 44 and 50: librosa.stft of the stems' sum, kept to
 // re-synthesise the predicted magnitudes in cell 53).  n_sum tracks, sum_stride apart, are added at load the way the channel
 // mean is formed at load, so "the STFT of the stems' sum" is one launch over the planar song.  One workgroup = one frame, any
-// power-of-two window, the scheme of stft_generic_kernel (not tuned: a listening path, not a training path).
+// power-of-two window, stft_generic_kernel with another epilogue (not tuned: a listening path, not a training path).
 template <typename PCM, int CH, bool PLANAR>
 __global__ __launch_bounds__(FFT_THREADS) void stft_complex_kernel(
     const PCM* __restrict__ pcm, int64_t n_samples, int64_t outer_stride, int n_inner, int64_t inner_stride, int n_sum,
@@ -483,26 +434,68 @@ __global__ __launch_bounds__(FFT_THREADS) void stft_complex_kernel(
     const int t = blockIdx.x;
     const PCM* trk = pcm + (track / n_inner) * outer_stride + (track % n_inner) * inner_stride;
     const float g = (gain ? gain[track] : 1.0f) * pcm_traits<PCM>::scale;
-    const int64_t p0 = (int64_t)t * hop - M;
-    for (int n = tid; n < M; n += FFT_THREADS) {
-        const int64_t a = reflect(p0 + 2 * n, n_samples), b = reflect(p0 + 2 * n + 1, n_samples);
-        float xa = 0.f, xb = 0.f;
-        for (int s = 0; s < n_sum; ++s) {
-            xa += mono_at<PCM, CH, PLANAR>(trk + s * sum_stride, cs, a);
-            xb += mono_at<PCM, CH, PLANAR>(trk + s * sum_stride, cs, b);
-        }
-        buf[n] = make_float2(xa * (window[2 * n] * g), xb * (window[2 * n + 1] * g));
-    }
+    lds_load_frame<PCM, CH, PLANAR>(buf, M, trk, n_sum, sum_stride, cs, n_samples, (int64_t)t * hop - M, window, g, tid);
     __syncthreads();
     const float2* x = lds_fft_radix2<false>(buf, buf + M, M, n_fft, tw, tid);
     float2* o = out + (track * (int64_t)(M + 1)) * n_frames + t;
     for (int k = tid; k <= M; k += FFT_THREADS) {
-        const float2 zk = x[k & (M - 1)], zn = x[(M - k) & (M - 1)];
-        const float2 e = make_float2(0.5f * (zk.x + zn.x), 0.5f * (zk.y - zn.y));
-        const float2 od = make_float2(0.5f * (zk.y + zn.y), -0.5f * (zk.x - zn.x));
-        float2 xk = cadd(e, cmul(tw[k & (n_fft - 1)], od));
+        float2 xk = real_fft_bin(x, k, M, tw);
         if (k == 0 || k == M) xk.y = 0.f;             // DC and Nyquist of a real signal
         o[(int64_t)k * n_frames] = xk;
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Launch side.  What every front-end checks about its PCM batch, in one place and one order; sets `planar`.  pcm_dtype comes
+// without the DAM_PCM_INDIRECT / DAM_PCM_ROTATE flags.
+int check_pcm_batch(int pcm_dtype, int64_t n_outer, int64_t n_inner, int64_t n_samples, int channels, int64_t sample_stride,
+                    int64_t channel_stride, int n_fft, bool* planar) {
+    if (n_samples <= n_fft / 2) return DAM_ERR_BAD_ARG;   // reflect padding needs N > n_fft/2 (torch.stft raises too)
+    if (channels != 1 && channels != 2) return DAM_ERR_UNSUPPORTED;
+    // any power of two 64 .. 16384 (the one-frame kernels hold two LDS buffers of n_fft/2 points: 128 KB at 16384)
+    if (n_fft < 64 || n_fft > 16384 || (n_fft & (n_fft - 1))) return DAM_ERR_UNSUPPORTED;
+    if (pcm_dtype != DAM_PCM_F32 && pcm_dtype != DAM_PCM_F64 && pcm_dtype != DAM_PCM_S16 && pcm_dtype != DAM_PCM_S32)
+        return DAM_ERR_UNSUPPORTED;
+    if (n_outer * n_inner > 65535 || n_inner > 0x7fffffff) return DAM_ERR_UNSUPPORTED;
+    if (channels == 1) {
+        if (sample_stride != 1) return DAM_ERR_UNSUPPORTED;
+        *planar = false;
+    } else if (sample_stride == channels && channel_stride == 1) {
+        *planar = false;
+    } else if (sample_stride == 1 && channel_stride >= n_samples) {
+        *planar = true;
+    } else {
+        return DAM_ERR_UNSUPPORTED;
+    }
+    const bool integer = pcm_dtype == DAM_PCM_S16 || pcm_dtype == DAM_PCM_S32;
+    if (integer && *planar) return DAM_ERR_UNSUPPORTED;    // integer PCM is what a WAV decoder hands over: interleaved
+    return DAM_OK;
+}
+
+template <typename PCM, int CH, bool PLANAR>
+struct pcm_tag {
+    using pcm = PCM;
+    static constexpr int ch = CH;
+    static constexpr bool planar = PLANAR;
+};
+
+// Calls f(pcm_tag<PCM, CH, PLANAR>) for a batch that passed check_pcm_batch: the ten instantiations of a front-end kernel
+// (float32 / float64: mono, interleaved, planar; int16 / int32: mono, interleaved).
+template <class F>
+int dispatch_pcm(int pcm_dtype, int channels, bool planar, F&& f) {
+    auto layouts = [&](auto sample) {
+        using T = decltype(sample);
+        if (channels == 1) return f(pcm_tag<T, 1, false>{});
+        if constexpr (!pcm_traits<T>::integer) {
+            if (planar) return f(pcm_tag<T, 2, true>{});
+        }
+        return f(pcm_tag<T, 2, false>{});
+    };
+    switch (pcm_dtype) {
+        case DAM_PCM_F32: return layouts(float{});
+        case DAM_PCM_S16: return layouts(int16_t{});
+        case DAM_PCM_S32: return layouts(int32_t{});
+        default: return layouts(double{});
     }
 }
 
@@ -529,106 +522,53 @@ extern "C" int dam_stft_logmag_strided_f32(const void* pcm, int pcm_dtype, int64
     using namespace dam;
     if (!pcm || !window || !twiddles || !out || n_outer <= 0 || n_inner <= 0 || hop <= 0) return DAM_ERR_BAD_ARG;
     if (n_tail < 0 || n_tail >= n_inner || (n_tail > 0 && !out_tail)) return DAM_ERR_BAD_ARG;
-    if (n_samples <= n_fft / 2) return DAM_ERR_BAD_ARG;   // reflect padding needs N > n_fft/2 (torch.stft raises too)
-    if (channels != 1 && channels != 2) return DAM_ERR_UNSUPPORTED;
-    bool fast = n_fft == NFFT && !(hop & 1);               // the tuned 2048-point kernel; else any power of two 64..4096
-    // 16-bit mono tracks at an odd sample stride start on odd 2-byte boundaries: the tuned kernel's 4-byte point loads would
-    // be misaligned, the generic kernel reads sample by sample
-    if ((pcm_dtype & ~(DAM_PCM_INDIRECT | DAM_PCM_ROTATE)) == DAM_PCM_S16 && channels == 1 && ((outer_stride | inner_stride) & 1)) fast = false;
-    if (!fast && (n_fft < 64 || n_fft > 16384 || (n_fft & (n_fft - 1)))) return DAM_ERR_UNSUPPORTED;    // (two LDS buffers of n_fft/2 points: 128 KB at 16384)
     if ((pcm_dtype & DAM_PCM_INDIRECT) && (pcm_dtype & DAM_PCM_ROTATE)) return DAM_ERR_BAD_ARG;
     const int indirect = (pcm_dtype & DAM_PCM_ROTATE) ? 2 : (pcm_dtype & DAM_PCM_INDIRECT) ? 1 : 0;
     pcm_dtype &= ~(DAM_PCM_INDIRECT | DAM_PCM_ROTATE);
-    if (pcm_dtype != DAM_PCM_F32 && pcm_dtype != DAM_PCM_F64 && pcm_dtype != DAM_PCM_S16 && pcm_dtype != DAM_PCM_S32)
-        return DAM_ERR_UNSUPPORTED;
-    const int64_t n_tracks = n_outer * n_inner;
-    if (n_tracks > 65535 || n_inner > 0x7fffffff) return DAM_ERR_UNSUPPORTED;
     bool planar;
-    if (channels == 1) {
-        if (sample_stride != 1) return DAM_ERR_UNSUPPORTED;
-        planar = false;
-    } else if (sample_stride == channels && channel_stride == 1) {
-        planar = false;
-    } else if (sample_stride == 1 && channel_stride >= n_samples) {
-        planar = true;
-    } else {
-        return DAM_ERR_UNSUPPORTED;
-    }
-    const bool integer = pcm_dtype == DAM_PCM_S16 || pcm_dtype == DAM_PCM_S32;
-    if (integer && planar) return DAM_ERR_UNSUPPORTED;     // integer PCM is what a WAV decoder hands over: interleaved
+    const int rc = check_pcm_batch(pcm_dtype, n_outer, n_inner, n_samples, channels, sample_stride, channel_stride, n_fft, &planar);
+    if (rc != DAM_OK) return rc;
+    bool fast = n_fft == NFFT && !(hop & 1);               // the tuned 2048-point kernel; else the generic one
+    // 16-bit mono tracks at an odd sample stride start on odd 2-byte boundaries: the tuned kernel's 4-byte point loads would
+    // be misaligned, the generic kernel reads sample by sample
+    if (pcm_dtype == DAM_PCM_S16 && channels == 1 && ((outer_stride | inner_stride) & 1)) fast = false;
     // the 2-byte kernels fetch a complex point (two frames) with one aligned 4- / 8-byte load
     if (pcm_dtype == DAM_PCM_S16 && !indirect && ((uintptr_t)pcm & 3)) return DAM_ERR_BAD_ARG;
+    const int64_t n_tracks = n_outer * n_inner;
     const int n_frames = (int)(1 + n_samples / hop);
-    dim3 grid, block;
     hipStream_t s = (hipStream_t)stream;
     const float2* tw = reinterpret_cast<const float2*>(twiddles);
     const float floor_db = (float)(20.0 * log10((double)amin));
     if (!fast) {
         if (n_frames > 0x7fffffff / 2) return DAM_ERR_UNSUPPORTED;
-        const dim3 ggrid((unsigned)n_frames, (unsigned)n_tracks);
+        const dim3 grid((unsigned)n_frames, (unsigned)n_tracks);
         const size_t lds = (size_t)n_fft * sizeof(float2);        // two buffers of n_fft/2 complex points
-#define DAM_STFT_GENERIC(T, C, P)                                                                                     \
-    do {                                                                                                              \
-        if (lds > 48 * 1024) {                                     /* 8192 / 16384-point windows: raise the kernel's LDS limit once */ \
-            static PerDevice<bool> raised_pd; bool& raised = raised_pd();\
-            if (!raised) {                                                                                            \
-                if (hipFuncSetAttribute(reinterpret_cast<const void*>(&stft_generic_kernel<T, C, P>),                 \
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, 132 * 1024) != hipSuccess)        \
-                    return DAM_ERR_LAUNCH;                                                                            \
-                raised = true;                                                                                        \
-            }                                                                                                         \
-        }                                                                                                             \
-        hipLaunchKernelGGL((stft_generic_kernel<T, C, P>), ggrid, dim3(256), lds, s, (const T*)pcm, n_samples, outer_stride, \
-                           (int)n_inner, inner_stride, channel_stride, window, tw, gain, n_fft, hop, n_frames, amin, floor_db, \
-                           normalize, out, out_tail, n_tail, indirect);                                               \
-    } while (0)
-        if (pcm_dtype == DAM_PCM_F32) {
-            if (channels == 1) DAM_STFT_GENERIC(float, 1, false);
-            else if (planar) DAM_STFT_GENERIC(float, 2, true);
-            else DAM_STFT_GENERIC(float, 2, false);
-        } else if (pcm_dtype == DAM_PCM_S16) {
-            if (channels == 1) DAM_STFT_GENERIC(int16_t, 1, false);
-            else DAM_STFT_GENERIC(int16_t, 2, false);
-        } else if (pcm_dtype == DAM_PCM_S32) {
-            if (channels == 1) DAM_STFT_GENERIC(int32_t, 1, false);
-            else DAM_STFT_GENERIC(int32_t, 2, false);
-        } else {
-            if (channels == 1) DAM_STFT_GENERIC(double, 1, false);
-            else if (planar) DAM_STFT_GENERIC(double, 2, true);
-            else DAM_STFT_GENERIC(double, 2, false);
-        }
-#undef DAM_STFT_GENERIC
-        DAM_CHECK_LAUNCH();
-        return DAM_OK;
+        return dispatch_pcm(pcm_dtype, channels, planar, [&](auto tag) -> int {
+            using T = typename decltype(tag)::pcm;
+            constexpr int C = decltype(tag)::ch;
+            constexpr bool P = decltype(tag)::planar;
+            // 8192 / 16384-point windows: beyond the default dynamic-LDS limit
+            if (lds > 48 * 1024 && !raise_lds_limit<&stft_generic_kernel<T, C, P>>(132 * 1024)) return DAM_ERR_LAUNCH;
+            hipLaunchKernelGGL((stft_generic_kernel<T, C, P>), grid, dim3(FFT_THREADS), lds, s, (const T*)pcm, n_samples,
+                               outer_stride, (int)n_inner, inner_stride, channel_stride, window, tw, gain, n_fft, hop, n_frames, amin,
+                               floor_db, normalize, out, out_tail, n_tail, indirect);
+            DAM_CHECK_LAUNCH();
+            return DAM_OK;
+        });
     }
     const int tiles_per_track = (int)cdiv(n_frames, TF2);
     const int64_t n_tiles64 = (int64_t)tiles_per_track * n_tracks;
     if (n_tiles64 > 0x7fffffff) return DAM_ERR_UNSUPPORTED;
     const int n_tiles = (int)n_tiles64;
-    grid = dim3((unsigned)(n_tiles < 512 ? n_tiles : 512));           // persistent: two workgroups per CU
-    block = dim3(TF2 * WAVE);
-#define DAM_STFT_LAUNCH(T, C, P)                                                                              \
-    hipLaunchKernelGGL((stft2048_kernel<T, C, P>), grid, block, 0, s, (const T*)pcm, n_samples, outer_stride, \
-                       (int)n_inner, inner_stride, channel_stride, window, tw, gain, hop, n_frames, tiles_per_track, \
-                       n_tiles, amin, floor_db, normalize, out, out_tail, n_tail, indirect)
-    if (pcm_dtype == DAM_PCM_F32) {
-        if (channels == 1) DAM_STFT_LAUNCH(float, 1, false);
-        else if (planar) DAM_STFT_LAUNCH(float, 2, true);
-        else DAM_STFT_LAUNCH(float, 2, false);
-    } else if (pcm_dtype == DAM_PCM_S16) {
-        if (channels == 1) DAM_STFT_LAUNCH(int16_t, 1, false);
-        else DAM_STFT_LAUNCH(int16_t, 2, false);
-    } else if (pcm_dtype == DAM_PCM_S32) {
-        if (channels == 1) DAM_STFT_LAUNCH(int32_t, 1, false);
-        else DAM_STFT_LAUNCH(int32_t, 2, false);
-    } else {
-        if (channels == 1) DAM_STFT_LAUNCH(double, 1, false);
-        else if (planar) DAM_STFT_LAUNCH(double, 2, true);
-        else DAM_STFT_LAUNCH(double, 2, false);
-    }
-#undef DAM_STFT_LAUNCH
-    DAM_CHECK_LAUNCH();
-    return DAM_OK;
+    const dim3 grid((unsigned)(n_tiles < 512 ? n_tiles : 512));      // persistent: two workgroups per CU
+    return dispatch_pcm(pcm_dtype, channels, planar, [&](auto tag) -> int {
+        using T = typename decltype(tag)::pcm;
+        hipLaunchKernelGGL((stft2048_kernel<T, decltype(tag)::ch, decltype(tag)::planar>), grid, dim3(TF2 * WAVE), 0, s,
+                           (const T*)pcm, n_samples, outer_stride, (int)n_inner, inner_stride, channel_stride, window, tw, gain, hop,
+                           n_frames, tiles_per_track, n_tiles, amin, floor_db, normalize, out, out_tail, n_tail, indirect);
+        DAM_CHECK_LAUNCH();
+        return DAM_OK;
+    });
 }
 
 extern "C" int dam_stft_logmag_f32(const void* pcm, int pcm_dtype, int64_t n_tracks, int64_t n_samples, int channels,
@@ -646,64 +586,28 @@ extern "C" int dam_stft_complex_strided_f32(const void* pcm, int pcm_dtype, int6
                                             float* out, void* stream) {
     using namespace dam;
     if (n_outer <= 0 || n_inner <= 0 || n_sum <= 0 || n_samples <= 0 || n_fft <= 0 || hop <= 0) return DAM_ERR_BAD_ARG;
-    if (n_fft < 64 || n_fft > 16384 || (n_fft & (n_fft - 1))) return DAM_ERR_UNSUPPORTED;
-    if (n_samples <= n_fft / 2) return DAM_ERR_BAD_ARG;   // reflect padding needs N > n_fft/2 (torch.stft raises too)
-    if (channels != 1 && channels != 2) return DAM_ERR_UNSUPPORTED;
-    if (pcm_dtype != DAM_PCM_F32 && pcm_dtype != DAM_PCM_F64 && pcm_dtype != DAM_PCM_S16 && pcm_dtype != DAM_PCM_S32)
-        return DAM_ERR_UNSUPPORTED;
+    bool planar;
+    const int rc = check_pcm_batch(pcm_dtype, n_outer, n_inner, n_samples, channels, sample_stride, channel_stride, n_fft, &planar);
+    if (rc != DAM_OK) return rc;
     const int64_t n_tracks = n_outer * n_inner;
     const int64_t n_frames = 1 + n_samples / hop;
-    if (n_tracks > 65535 || n_inner > 0x7fffffff || n_sum > 0x7fffffff || n_frames > 0x7fffffff / 2) return DAM_ERR_UNSUPPORTED;
-    bool planar;
-    if (channels == 1) {
-        if (sample_stride != 1) return DAM_ERR_UNSUPPORTED;
-        planar = false;
-    } else if (sample_stride == channels && channel_stride == 1) {
-        planar = false;
-    } else if (sample_stride == 1 && channel_stride >= n_samples) {
-        planar = true;
-    } else {
-        return DAM_ERR_UNSUPPORTED;
-    }
-    const bool integer = pcm_dtype == DAM_PCM_S16 || pcm_dtype == DAM_PCM_S32;
-    if (integer && planar) return DAM_ERR_UNSUPPORTED;     // integer PCM is what a WAV decoder hands over: interleaved
+    if (n_sum > 0x7fffffff || n_frames > 0x7fffffff / 2) return DAM_ERR_UNSUPPORTED;
     if (!pcm || !window || !twiddles || !out) return DAM_ERR_BAD_ARG;
     const dim3 grid((unsigned)n_frames, (unsigned)n_tracks);
     const size_t lds = (size_t)n_fft * sizeof(float2);        // two buffers of n_fft/2 complex points
-#define DAM_STFT_COMPLEX(T, C, P)                                                                                     \
-    do {                                                                                                              \
-        if (lds > 48 * 1024) {                                     /* 8192 / 16384-point windows: raise the kernel's LDS limit once */ \
-            static PerDevice<bool> raised_pd; bool& raised = raised_pd();\
-            if (!raised) {                                                                                            \
-                if (hipFuncSetAttribute(reinterpret_cast<const void*>(&stft_complex_kernel<T, C, P>),                 \
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, 132 * 1024) != hipSuccess)        \
-                    return DAM_ERR_LAUNCH;                                                                            \
-                raised = true;                                                                                        \
-            }                                                                                                         \
-        }                                                                                                             \
-        hipLaunchKernelGGL((stft_complex_kernel<T, C, P>), grid, dim3(FFT_THREADS), lds, (hipStream_t)stream, (const T*)pcm, \
-                           n_samples, outer_stride, (int)n_inner, inner_stride, (int)n_sum, sum_stride, channel_stride, window, \
-                           reinterpret_cast<const float2*>(twiddles), gain, n_fft, hop, (int)n_frames,                \
-                           reinterpret_cast<float2*>(out));                                                           \
-    } while (0)
-    if (pcm_dtype == DAM_PCM_F32) {
-        if (channels == 1) DAM_STFT_COMPLEX(float, 1, false);
-        else if (planar) DAM_STFT_COMPLEX(float, 2, true);
-        else DAM_STFT_COMPLEX(float, 2, false);
-    } else if (pcm_dtype == DAM_PCM_S16) {
-        if (channels == 1) DAM_STFT_COMPLEX(int16_t, 1, false);
-        else DAM_STFT_COMPLEX(int16_t, 2, false);
-    } else if (pcm_dtype == DAM_PCM_S32) {
-        if (channels == 1) DAM_STFT_COMPLEX(int32_t, 1, false);
-        else DAM_STFT_COMPLEX(int32_t, 2, false);
-    } else {
-        if (channels == 1) DAM_STFT_COMPLEX(double, 1, false);
-        else if (planar) DAM_STFT_COMPLEX(double, 2, true);
-        else DAM_STFT_COMPLEX(double, 2, false);
-    }
-#undef DAM_STFT_COMPLEX
-    DAM_CHECK_LAUNCH();
-    return DAM_OK;
+    return dispatch_pcm(pcm_dtype, channels, planar, [&](auto tag) -> int {
+        using T = typename decltype(tag)::pcm;
+        constexpr int C = decltype(tag)::ch;
+        constexpr bool P = decltype(tag)::planar;
+        // 8192 / 16384-point windows: beyond the default dynamic-LDS limit
+        if (lds > 48 * 1024 && !raise_lds_limit<&stft_complex_kernel<T, C, P>>(132 * 1024)) return DAM_ERR_LAUNCH;
+        hipLaunchKernelGGL((stft_complex_kernel<T, C, P>), grid, dim3(FFT_THREADS), lds, (hipStream_t)stream, (const T*)pcm,
+                           n_samples, outer_stride, (int)n_inner, inner_stride, (int)n_sum, sum_stride, channel_stride, window,
+                           reinterpret_cast<const float2*>(twiddles), gain, n_fft, hop, (int)n_frames,
+                           reinterpret_cast<float2*>(out));
+        DAM_CHECK_LAUNCH();
+        return DAM_OK;
+    });
 }
 
 extern "C" int dam_stft_complex_f32(const void* pcm, int pcm_dtype, int64_t n_tracks, int64_t n_samples, int channels,

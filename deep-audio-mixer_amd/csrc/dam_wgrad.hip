@@ -755,13 +755,7 @@ int launch_wgrad_rows(int B, int H, int W, int C, const float* X, const float* d
     }
     const int nsplit = B * g.spi;
     if ((int64_t)nsplit * nx * NBLK * 256 > ws_floats) return DAM_ERR_WORKSPACE;
-    static PerDevice<bool> raised_pd; bool& raised = raised_pd();
-    if (!raised) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_rows_kernel<TNB, TKB, STEPS, KP, GPP, HV, NL>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
-            return DAM_ERR_LAUNCH;
-        raised = true;
-    }
+    if (!raise_lds_limit<&wgrad_rows_kernel<TNB, TKB, STEPS, KP, GPP, HV, NL>>(160 * 1024)) return DAM_ERR_LAUNCH;
     hipLaunchKernelGGL((wgrad_rows_kernel<TNB, TKB, STEPS, KP, GPP, HV, NL>), dim3(nx, nsplit), dim3((256 + 64 * NL)), lds, st, g, X, dY, in_scale,
                        in_shift, relu_in, partial);
     DAM_CHECK_LAUNCH();
@@ -1056,13 +1050,7 @@ int launch_wgrad_rows_s2(int B, int H, int W, int C, int Ho, int Wo, int N, cons
     }
     const int nsplit = B * g.spi;
     if ((int64_t)nsplit * nx * NBLK * 256 > ws_floats) return DAM_ERR_WORKSPACE;
-    static PerDevice<bool> raised_pd; bool& raised = raised_pd();
-    if (!raised) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_rows_s2_kernel<TNB, STEPS, KP, GPPX, GPPD, HV>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
-            return DAM_ERR_LAUNCH;
-        raised = true;
-    }
+    if (!raise_lds_limit<&wgrad_rows_s2_kernel<TNB, STEPS, KP, GPPX, GPPD, HV>>(160 * 1024)) return DAM_ERR_LAUNCH;
     hipLaunchKernelGGL((wgrad_rows_s2_kernel<TNB, STEPS, KP, GPPX, GPPD, HV>), dim3(nx, nsplit), dim3(RW_THREADS), lds, st, g, X, dY,
                        partial);
     DAM_CHECK_LAUNCH();
@@ -1285,16 +1273,7 @@ int launch_wgrad_jobs(WgradGeo g, const WgradJobs& jobs, int njobs, int64_t ws_f
     if ((int64_t)nsplit * nx * NBLK * 256 > ws_floats) return DAM_ERR_WORKSPACE;
     g.nsplit = nsplit;
     if (lds > 160 * 1024) return DAM_ERR_UNSUPPORTED;
-    if (lds > 64 * 1024) {
-        static PerDevice<bool> raised_pd;
-        bool& raised = raised_pd();
-        if (!raised) {
-            if (hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_kernel<TNB, TKB, TA, TB>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    160 * 1024) != hipSuccess)
-                return DAM_ERR_LAUNCH;
-            raised = true;
-        }
-    }
+    if (lds > 64 * 1024 && !raise_lds_limit<&wgrad_kernel<TNB, TKB, TA, TB>>(160 * 1024)) return DAM_ERR_LAUNCH;
     hipLaunchKernelGGL((wgrad_kernel<TNB, TKB, TA, TB>), dim3(nx, nsplit, njobs), dim3(256), lds, st, g, jobs);
     DAM_CHECK_LAUNCH();
     for (int i = 0; i < njobs; ++i) {

@@ -136,6 +136,23 @@ def test_round_trip(features, n, n_fft, hop, kind):
     check_wave(got[0].cpu().numpy(), x.astype(np.float64), 'round trip %s n=%d n_fft=%d hop=%d' % (kind, n, n_fft, hop))
 
 
+@pytest.mark.parametrize('n,n_fft,hop', [(20013, 8192, 2048), (20013, 16384, 4096)])
+def test_large_windows_raise_the_lds_limit(features, n, n_fft, hop):
+    """8192- and 16384-point windows hold 64 / 128 KB of LDS, above a kernel's default limit: the complex front-end and the
+    inverse transform raise theirs on the first call and find it raised on the second."""
+    x = make_audio('noise', n, seed=n + hop).astype(np.float32)
+    want = stft64(x, n_fft, hop)
+    dev = torch.from_numpy(x[None]).cuda()
+    for call in ('first', 'second'):
+        spec = features.stft(dev, n_fft, hop)
+        assert tuple(spec.shape) == (1, n_fft // 2 + 1, 1 + n // hop)
+        err = forward_error(spec[0].cpu().numpy(), want)
+        print('forward n=%d n_fft=%d hop=%d, %s call: %.3e' % (n, n_fft, hop, call, err))
+        assert err <= BOUND
+        check_wave(features.istft(spec, hop, n)[0].cpu().numpy(), x.astype(np.float64),
+                   'round trip n=%d n_fft=%d hop=%d, %s call' % (n, n_fft, hop, call))
+
+
 def _compose64(spec32, db32):
     """10^(0.05 db) * X/|X| in float64, (1, 0) where X == 0."""
     x = spec32.to(torch.complex128)
