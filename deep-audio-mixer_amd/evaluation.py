@@ -9,7 +9,9 @@ are constant gains, the model's mix is a gain ramp, and the batched meter applie
 (Meter.integrated_loudness_batch(gains=...)); the mix variant is the 'loudness' kind of inference_utils.SongMixer, one
 hipGraph from PCM to the four LUFS values.  With ``write_wavs_to_disk`` every variant's stem sum is also rendered on the
 device from the same resident PCM -- mixdown with the variant's gains, batched meter, gain to -20 LUFS, PCM encoder with
-that gain -- and written as ``{song_name}_{identifier}.wav`` (evaluation.py:58-66).  The reference's spreadsheet
+that gain -- and written as ``{song_name}_{identifier}.wav`` (evaluation.py:58-66); with ``ceiling_dbtp`` that gain is first
+clamped so that the file's true peak stays under the ceiling (dam_true_peak_batch of the resident sum) instead of being
+hard-clipped by the encoder.  The reference's spreadsheet
 (openpyxl) stays out: ``process_songlist`` returns the rows and the means instead of writing ./stats.xlsx.
 """
 import os
@@ -20,7 +22,7 @@ import numpy as np
 import torch
 
 from . import inference_utils, ops, staging
-from .loudness import Meter, normalize_loudness, target_gains_device
+from .loudness import Meter, limit_gains_device, normalize_loudness, target_gains_device, true_peak_batch
 from .models.baselines.mean_loudness_model import MeanLoudnessModel
 from .models.baselines.random_model import RandomModel
 
@@ -96,11 +98,13 @@ class LoudnessEvaluator:
             pipe.upload(pcm[i], np.asarray(tracks[name], dtype=np_dt))
         return pcm
 
-    def write_sum_to_target(self, pcm, gains, path, target_lufs: float = -20.0, subtype='PCM_16'):
+    def write_sum_to_target(self, pcm, gains, path, target_lufs: float = -20.0, subtype='PCM_16', ceiling_dbtp=None):
         """evaluation.py:58-66 with its ``sf.write``, for stems resident on the device: pcm CUDA [stems, channels, n],
         gains None, CUDA float64 [stems] (a constant per stem) or [stems, n_gains] (a gain ramp).  The float64 stem sum is
         measured, the gain to ``target_lufs`` stays on the device and is applied inside the encoder; the host receives the
-        file's sample bytes.  Returns the clipped-sample count."""
+        file's sample bytes.  ceiling_dbtp: the gain is clamped on the device to ``ceiling / true peak of the sum`` first, so
+        a sum whose -20 LUFS rendering would exceed the ceiling is written quieter instead of clipped.  Returns the
+        clipped-sample count."""
         from .data.dataset_utils import write_wav_bytes
         n_stems, channels, n = pcm.shape
         if gains is None:
@@ -108,6 +112,8 @@ class LoudnessEvaluator:
         mix = ops.mixdown_peak_normalize(pcm, gains.view(n_stems, -1), normalize=False, out_dtype=torch.float64)
         lufs = self.meter.integrated_loudness_batch(mix.t().unsqueeze(0))
         gain = target_gains_device(lufs, torch.full((1,), float(target_lufs), dtype=torch.float64, device=pcm.device))
+        if ceiling_dbtp is not None:
+            limit_gains_device(gain, true_peak_batch(mix.t().unsqueeze(0)), ceiling_dbtp)
         clip = torch.empty(channels, dtype=torch.int64, device=pcm.device)
         payload = staging.pipe_for(pcm.device).download(ops.pcm_encode(mix, subtype, scale=gain, clip_count=clip))
         clipped = int(clip.sum().item())
@@ -115,14 +121,16 @@ class LoudnessEvaluator:
         return clipped
 
     def process_song_tracks(self, loaded_tracks: dict, reference_tracks: dict, song_name: str, n_random_samples: int = 5,
-                            chunk_length: int = 2, write_wavs_to_disk=False, results_dir='./experiment') -> dict:
+                            chunk_length: int = 2, write_wavs_to_disk=False, results_dir='./experiment',
+                            ceiling_dbtp=None) -> dict:
         """evaluation.py:77-116 on stems already in memory ({name: ndarray [channels, n]} each): the loudness profile of
         ``reference_tracks`` against the profiles of ``loaded_tracks`` summed as they are ('sum_error'), normalised to the
         training set's mean loudness ('loudnorm_error'), mixed by the model ('mix_error') and scaled by random gains
         ('random_error', the mean over n_random_samples draws, drawn in the reference's order).  Returns the reference's
         stats dict plus 'smooth_gains' {name: list}, the gains the mix variant used.  write_wavs_to_disk: every variant's
         stem sum at -20 LUFS goes to ``results_dir/{song_name}_{identifier}.wav`` (reference, sum, loudnorm, mix,
-        random_0 ...; 16-bit); the stats and the order of the random draws do not depend on the switch."""
+        random_0 ...; 16-bit), each held under ``ceiling_dbtp`` dBTP if that is given; the stats and the order of the
+        random draws depend on neither."""
         if self.d is None or self.mix_model is None or self.mean_loudness_model is None:
             raise ValueError('process_song needs the dataset, d_mean_loudness and mix_model constructor arguments')
         stems = [t for t in self.d.get_tracklist() if t != 'mix']
@@ -133,7 +141,8 @@ class LoudnessEvaluator:
         def write(identifier, pcm, gains=None):
             if write_wavs_to_disk:
                 os.makedirs(results_dir, exist_ok=True)
-                self.write_sum_to_target(pcm, gains, os.path.join(results_dir, '{}_{}.wav'.format(song_name, identifier)))
+                self.write_sum_to_target(pcm, gains, os.path.join(results_dir, '{}_{}.wav'.format(song_name, identifier)),
+                                         ceiling_dbtp=ceiling_dbtp)
 
         reference_pcm = self._upload(reference_tracks)
         reference = OrderedDict(zip(self.keys, self.evaluate_loudness_batch(reference_pcm)))
@@ -168,17 +177,17 @@ class LoudnessEvaluator:
         return stats
 
     def process_song(self, base_dir: str, song_name: str, n_random_samples: int = 5, chunk_length: int = 2,
-                     write_wavs_to_disk=False, results_dir='./experiment') -> dict:
+                     write_wavs_to_disk=False, results_dir='./experiment', ceiling_dbtp=None) -> dict:
         """evaluation.py:77-116: the reference mix from ``base_dir/manual_gain_mixes``, the stems from ``base_dir/test``."""
         from .data.dataset_utils import load_tracks_musdb18
         reference_tracks = load_tracks_musdb18(os.path.join(base_dir, 'manual_gain_mixes'), song_name, tracklist=self.keys,
                                                sr=self.sr)
         loaded_tracks = load_tracks_musdb18(os.path.join(base_dir, 'test'), song_name, tracklist=self.keys, sr=self.sr)
         return self.process_song_tracks(loaded_tracks, reference_tracks, song_name, n_random_samples, chunk_length,
-                                        write_wavs_to_disk, results_dir)
+                                        write_wavs_to_disk, results_dir, ceiling_dbtp)
 
     def process_songlist(self, base_dir, songlist, n_random_samples: int = 5, chunk_length: int = 2,
-                         write_wavs_to_disk=False, results_dir='./experiment'):
+                         write_wavs_to_disk=False, results_dir='./experiment', ceiling_dbtp=None):
         """evaluation.py:118-144 without the spreadsheet: (rows, means) -- one stats dict per song and the mean of every
         error over the songs (the sheet's last row)."""
         keys = ['sum_error', 'random_error', 'loudnorm_error', 'mix_error']
@@ -186,5 +195,5 @@ class LoudnessEvaluator:
         for i, song_name in enumerate(songlist):
             print('{}/{}: {}'.format(i + 1, len(songlist), song_name))
             rows.append(self.process_song(base_dir, song_name, n_random_samples, chunk_length, write_wavs_to_disk,
-                                          results_dir))
+                                          results_dir, ceiling_dbtp))
         return rows, {key: mean(row[key] for row in rows) for key in keys}

@@ -10,7 +10,9 @@ hipGraph (``SongMixer``): strided STFT front-end over all chunks of all stems st
 (dam_stft_logmag_strided_f32) -> model forward of the whole chunk batch -> 10 ** (0.5 g) and the Savitzky-Golay
 smoothing (dam_gains_smooth) -> sample-rate gain ramp x audio (dam_gain_ramp_apply), or for ``mix_song_to_master`` the
 fused stem sum + peak normalisation (dam_mixdown_peak_normalize) or, with ``normalize='loudness'``, the stem sum brought to
-a target BS.1770 loudness -- and, for ``mix_song_to_wav``, the PCM encoder as the graph's last node (dam_pcm_encode: the
+a target BS.1770 loudness (optionally held under a true-peak ceiling, ``ceiling_dbtp``: dam_true_peak_batch of the float64
+sum, dam_peak_limit_gains on the loudness gain; ``normalize='true_peak'`` puts the true peak AT the ceiling instead) -- and,
+for ``mix_song_to_wav``, the PCM encoder as the graph's last node (dam_pcm_encode: the
 loudness gain is applied inside it, the host receives the file's sample bytes instead of the float master);
 ``mix_song_loudness`` ends in the batched meter instead (the per-stem loudness of the mixed
 stems, dam_loudness_block_energy_batch with the gain ramp applied at load: the mixed stems are never written).
@@ -67,16 +69,25 @@ class SongMixer:
 
     def __init__(self, model, n_stems, channels, n_samples, dtype, chunk_samples, kind, normalize=True,
                  out_dtype=torch.float64, use_graph=True, hop_length=1024, sr=44100, target_lufs=-20.0, encode=None,
-                 dither_seed=None):
+                 dither_seed=None, ceiling_dbtp=None):
         """encode (kind 'master' only): None, or a WAV subtype ('PCM_16', 'PCM_24', 'PCM_32', 'FLOAT') -- the master is then
-        quantised by the last node of the same graph and ``run`` returns its sample bytes and the clipped-sample count."""
+        quantised by the last node of the same graph and ``run`` returns its sample bytes and the clipped-sample count.
+        ceiling_dbtp (kind 'master' with normalize 'loudness' or 'true_peak'): the true peak (dBTP) the master must not
+        exceed.  With 'loudness' the gain to ``target_lufs`` is clamped to ``ceiling / true peak of the sum`` (one static
+        gain for all channels, no limiter); with 'true_peak' (default ceiling -1.0) that quotient IS the gain.  ``peaks()``
+        reports the measurement of the last run."""
         if kind not in ('stems', 'master', 'spectral', 'loudness'):
             raise ValueError(kind)
         if encode is not None and (kind != 'master' or encode not in ops.PCM_FORMATS):
             raise ValueError("encode needs kind='master' and one of %s, got %r" % (sorted(ops.PCM_FORMATS), encode))
         self.encode, self.dither_seed = encode, dither_seed
-        if normalize not in (True, False, 'loudness'):
-            raise ValueError("normalize must be True, False or 'loudness'")
+        if normalize not in (True, False, 'loudness', 'true_peak'):
+            raise ValueError("normalize must be True, False, 'loudness' or 'true_peak'")
+        if normalize == 'true_peak' and ceiling_dbtp is None:
+            ceiling_dbtp = -1.0
+        if ceiling_dbtp is not None and (kind != 'master' or normalize not in ('loudness', 'true_peak')):
+            raise ValueError("ceiling_dbtp needs kind='master' and normalize 'loudness' or 'true_peak'")
+        self.ceiling = None if ceiling_dbtp is None else float(ceiling_dbtp)
         self.model, self.kind, self.normalize = model, kind, normalize
         self.dev = next(model.parameters()).device
         self.n_stems, self.channels, self.n, self.chunk = n_stems, channels, n_samples, chunk_samples
@@ -108,7 +119,7 @@ class SongMixer:
             self.out = torch.empty(n_stems, dtype=torch.float64, device=dev)                       # LUFS of every mixed stem
             self.ws = None
         else:
-            if encode is None or normalize != 'loudness':          # (the encoder reads the float64 sum and scales it itself)
+            if encode is None or normalize not in ('loudness', 'true_peak'):      # (the encoder reads the float64 sum and scales it itself)
                 self.out = torch.empty((channels, n_samples), dtype=out_dtype, device=dev)
             if encode is not None:
                 self.enc = torch.empty(n_samples * channels * ops.PCM_FORMATS[encode][1], dtype=torch.uint8, device=dev)
@@ -120,7 +131,15 @@ class SongMixer:
                 self.target = torch.full((1,), float(target_lufs), dtype=torch.float64, device=dev)
                 self.lufs = torch.empty(1, dtype=torch.float64, device=dev)
                 self.master_gain = torch.empty(1, dtype=torch.float64, device=dev)
-            mix_dtype = torch.float64 if normalize == 'loudness' else out_dtype
+            if normalize == 'true_peak':
+                self.mix = torch.empty((channels, n_samples), dtype=torch.float64, device=dev)
+                self.master_gain = torch.empty(1, dtype=torch.float64, device=dev)
+            if self.ceiling is not None:
+                # the gain before the clamp ('true_peak': none asked for, +inf), the true and sample peaks of the sum
+                self.free_gain = torch.full((1,), float('inf'), dtype=torch.float64, device=dev)
+                self.tp = torch.empty((1, channels), dtype=torch.float64, device=dev)
+                self.sp = torch.empty((1, channels), dtype=torch.float64, device=dev)
+            mix_dtype = torch.float64 if normalize in ('loudness', 'true_peak') else out_dtype
             self.ws = torch.empty(ops._lib.lib().dam_mixdown_workspace_elems(channels), dtype=mix_dtype, device=dev)
         self.gains = torch.empty((2, n_stems, self.n_proc), dtype=torch.float64, device=dev)     # [raw amplitude, smoothed]
         self.graph = None
@@ -150,6 +169,19 @@ class SongMixer:
             ops.gain_ramp_apply(self.pcm, smooth, out=self.out)
         elif self.kind == 'loudness':
             self.meter.integrated_loudness_batch(self.pcm.transpose(1, 2), gains=smooth, out=self.out)
+        elif self.ceiling is not None:
+            ops.mixdown_peak_normalize(self.pcm, smooth, normalize=False, out=self.mix, workspace=self.ws)
+            if self.normalize == 'loudness':
+                self.meter.integrated_loudness_batch(self.mix.t().unsqueeze(0), out=self.lufs)
+                loudness.target_gains_device(self.lufs, self.target, out=self.free_gain)
+            self.master_gain.copy_(self.free_gain)
+            ops.true_peak_batch(self.mix.t().unsqueeze(0), out=self.tp, sample_peak_out=self.sp)
+            ops.peak_limit_gains(self.master_gain, self.tp, self.ceiling)          # the maximum over the channels
+            if self.encode is None:
+                ops.gain_ramp_apply(self.mix, self.master_gain, out=self.out)
+            else:
+                ops.pcm_encode(self.mix, self.encode, scale=self.master_gain, dither_seed=self.dither_seed, out=self.enc,
+                               clip_count=self.clip)
         elif self.normalize == 'loudness':
             ops.mixdown_peak_normalize(self.pcm, smooth, normalize=False, out=self.mix, workspace=self.ws)
             self.meter.integrated_loudness_batch(self.mix.t().unsqueeze(0), out=self.lufs)
@@ -209,25 +241,45 @@ class SongMixer:
         return out, self.gains.cpu().numpy()
 
 
+    def peaks(self):
+        """The peak measurement of the last run of a mixer with a ceiling, from the device tensors the graph wrote:
+        {'true_peak_db': [per channel], 'sample_peak_db': [per channel]} of the master as rendered (the measured sum times
+        the gain that was applied, before any quantisation), 'limited': whether the ceiling, not the loudness target, set
+        that gain (always so for normalize='true_peak' unless the sum is silent), and 'gain', the gain itself."""
+        if self.ceiling is None:
+            raise ValueError('this mixer was built without ceiling_dbtp')
+        tp, sp = self.tp.cpu().numpy()[0], self.sp.cpu().numpy()[0]
+        gain, free = float(self.master_gain.cpu()[0]), float(self.free_gain.cpu()[0])
+        with np.errstate(divide='ignore', invalid='ignore'):
+            return {'true_peak_db': [float(v) for v in 20.0 * np.log10(tp * gain)],
+                    'sample_peak_db': [float(v) for v in 20.0 * np.log10(sp * gain)],
+                    'limited': bool(gain < free), 'gain': gain}
+
+
 _mixers = {}
 
 
 def _mixer(model, stems, loaded_tracks, chunk_length, sr, kind, normalize, out_dtype, hop_length=1024, target_lufs=-20.0,
-           encode=None, dither_seed=None):
+           encode=None, dither_seed=None, ceiling_dbtp=None):
     first = np.asarray(loaded_tracks[stems[0]])
     if first.ndim != 2:
         raise ValueError('loaded_tracks[track] must be [channels, n] arrays')
     ch, n = first.shape
     dt = torch.float32 if first.dtype == np.float32 else torch.float64
-    if normalize != 'loudness':
+    if isinstance(normalize, str) and normalize == 'true_peak':
+        target_lufs = None
+        ceiling_dbtp = -1.0 if ceiling_dbtp is None else ceiling_dbtp
+    elif not (isinstance(normalize, str) and normalize == 'loudness'):
         normalize, target_lufs = bool(normalize), None
+    ceiling_dbtp = None if ceiling_dbtp is None else float(ceiling_dbtp)
     key = (id(model), len(stems), ch, n, dt, chunk_length * sr, kind, normalize, out_dtype, hop_length, sr, target_lufs,
-           encode, dither_seed if encode is not None else None)
+           encode, dither_seed if encode is not None else None, ceiling_dbtp)
     m = _mixers.get(key)
     if m is None:
         _mixers.clear()                        # one geometry at a time: a song's buffers are hundreds of MB
         m = SongMixer(model, len(stems), ch, n, dt, chunk_length * sr, kind, normalize, out_dtype, hop_length=hop_length, sr=sr,
-                      target_lufs=-20.0 if target_lufs is None else target_lufs, encode=encode, dither_seed=dither_seed)
+                      target_lufs=-20.0 if target_lufs is None else target_lufs, encode=encode, dither_seed=dither_seed,
+                      ceiling_dbtp=ceiling_dbtp)
         _mixers[key] = m
     np_dt = np.float32 if dt == torch.float32 else np.float64
     return m, [np.asarray(loaded_tracks[t], dtype=np_dt) for t in stems]
@@ -256,33 +308,38 @@ def mix_song_loudness(dataset, model, loaded_tracks: dict, chunk_length=1, sr=44
 
 
 def mix_song_to_master(dataset, model, loaded_tracks: dict, chunk_length=1, sr=44100, normalize=True, dtype=np.float64,
-                       target_lufs=-20.0):
+                       target_lufs=-20.0, ceiling_dbtp=None):
     """mix_song_smooth followed by what every caller of the reference does next (inference.ipynb cells 9/11,
     evaluation.py:59-66): ``track_sum = np.sum(list(mixed_tracks.values()), axis=0)`` and, if ``normalize``,
     ``librosa.util.normalize(track_sum, axis=1)`` -- fused into one pass over the song on the GPU (the per-stem mixed
     tracks are never materialised).  ``normalize='loudness'`` is evaluation.py:59-66 without the file write instead: the
-    sum is measured (BS.1770) and scaled to ``target_lufs``, in the same graph.
+    sum is measured (BS.1770) and scaled to ``target_lufs``, in the same graph.  ``ceiling_dbtp`` (with 'loudness'): the
+    master's true peak is held at or under that many dBTP -- at ``target_lufs`` if its peaks allow, quieter if not (one
+    static gain; SongMixer.peaks() of the cached mixer tells which).  ``normalize='true_peak'``: the plain sum scaled so
+    that its true peak sits at ``ceiling_dbtp`` (default -1.0), one gain for all channels.
     Returns (mix ndarray[channels, n], raw_gains, smooth_gains)."""
     stems = [t for t in dataset.get_tracklist() if t != 'mix']
     out_dt = torch.float32 if np.dtype(dtype) == np.float32 else torch.float64
-    m, arrays = _mixer(model, stems, loaded_tracks, chunk_length, sr, 'master', normalize, out_dt, target_lufs=target_lufs)
+    m, arrays = _mixer(model, stems, loaded_tracks, chunk_length, sr, 'master', normalize, out_dt, target_lufs=target_lufs,
+                       ceiling_dbtp=ceiling_dbtp)
     out, gains = m.run(arrays)
     raw_gains = {t: [float(v) for v in gains[0, i]] for i, t in enumerate(stems)}
     return out, raw_gains, {t: list(gains[1, i]) for i, t in enumerate(stems)}
 
 
 def mix_song_to_wav(dataset, model, loaded_tracks: dict, path, chunk_length=1, sr=44100, normalize=True, subtype='PCM_16',
-                    target_lufs=-20.0, dither_seed=None):
+                    target_lufs=-20.0, dither_seed=None, ceiling_dbtp=None):
     """mix_song_to_master followed by the callers' ``sf.write(path, master.T, sr)`` (inference.ipynb cells 9/11;
     evaluation.py:59-66 with ``normalize='loudness'``): the float64 master is quantised to ``subtype`` by the last node of
     the song's graph (ops.pcm_encode, TPDF dither if ``dither_seed`` is given), so the host receives the file's sample
     bytes -- a quarter of the float64 master for 'PCM_16' -- and writes them behind a WAV header.  The samples are those
-    tests/_pcm_ref.py's quantiser makes of mix_song_to_master(..., dtype=float64).
+    tests/_pcm_ref.py's quantiser makes of mix_song_to_master(..., dtype=float64).  ``ceiling_dbtp`` / ``normalize='true_peak'``
+    as there: with a ceiling below 0 dBTP the encoder has nothing to clip.
     Returns (clipped sample count, raw_gains, smooth_gains); warns (RuntimeWarning) when samples had to be clipped."""
     from .data.dataset_utils import write_wav_bytes
     stems = [t for t in dataset.get_tracklist() if t != 'mix']
     m, arrays = _mixer(model, stems, loaded_tracks, chunk_length, sr, 'master', normalize, torch.float64, target_lufs=target_lufs,
-                       encode=subtype, dither_seed=dither_seed)
+                       encode=subtype, dither_seed=dither_seed, ceiling_dbtp=ceiling_dbtp)
     (payload, clipped), gains = m.run(arrays)
     write_wav_bytes(path, payload, sr, m.channels, subtype, m.n, clipped)
     raw_gains = {t: [float(v) for v in gains[0, i]] for i, t in enumerate(stems)}

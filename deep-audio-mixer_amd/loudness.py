@@ -19,6 +19,16 @@ Batched device form, for callers that measure many tracks (evaluation.py:77-116)
 
 filter, block energies, gating (``dam_loudness_gate``) and the normalisation gain (``dam_loudness_target_gains``) all
 run on the device: no host synchronisation, hipGraph-capturable.
+
+Peaks -- ``pyln.normalize.peak`` and the true peak (BS.1770 Annex 2 / EBU R128: the 4x oversampled signal) it lacks:
+
+    out = normalize_peak(data, -1.0)                     # pyloudnorm: the SAMPLE peak at -1 dBFS
+    out = normalize_peak(data, -1.0, true_peak=True)     # the reconstructed waveform's peak at -1 dBTP
+    dbtp = true_peak(data)                               # per channel, numpy
+    tp = true_peak_batch(pcm.transpose(1, 2))            # [N, channels] linear, CUDA float64, no synchronisation
+    limit_gains_device(gain, tp, -1.0)                   # gain = min(gain, ceiling / max over channels), on the device
+
+The interpolator is this package's own 49-tap windowed sinc (include/dam_hip.h); parity with libebur128 is not claimed.
 """
 import ctypes
 import warnings
@@ -220,6 +230,54 @@ def normalize_loudness_device(data, lufs_dev, target, out_dtype=None):
         return ops.gain_ramp_apply(data.transpose(1, 2), g.view(N, 1), out_dtype=out_dtype).transpose(1, 2)
     flat = data.contiguous().view(N, 1, -1)
     return ops.gain_ramp_apply(flat, g.view(N, 1), out_dtype=out_dtype).view(data.shape)
+
+
+def true_peak_batch(data, gains=None, out=None):
+    """Linear true peak of every track and channel: data CUDA float32/float64 [N, samples, channels] with any strides, as
+    integrated_loudness_batch takes it; gains as there.  Returns CUDA float64 [N, channels] (dam_true_peak_batch); a
+    silent row reads exactly 0.0.  No host synchronisation."""
+    from . import ops
+    if not torch.is_tensor(data):
+        raise ValueError('Data must be of type torch.Tensor.')
+    _lib.require_cuda(data, gains, out)
+    if data.dtype not in (torch.float32, torch.float64):
+        raise ValueError('Data must be floating point.')
+    if data.dim() != 3:
+        raise ValueError('Audio must be [tracks, samples, channels].')
+    return ops.true_peak_batch(data, gains=gains, out=out)
+
+
+def true_peak(data):
+    """dBTP per channel of one [samples] or [samples, channels] array (numpy or torch) -> numpy float64 [channels];
+    silence reads -inf."""
+    x = _as_device_2d(data)
+    tp = true_peak_batch(x.unsqueeze(0))[0].cpu().numpy()
+    with np.errstate(divide='ignore'):
+        return 20.0 * np.log10(tp)
+
+
+def normalize_peak(data, target_db, true_peak=False):
+    """``pyloudnorm.normalize.peak``: constant gain so that the largest |sample| over all channels sits at ``target_db``
+    dBFS.  true_peak=True takes the same gain from the true peak instead (dBTP): the reconstructed waveform, not just
+    its samples, then stays at or under the target."""
+    if true_peak:
+        current_peak = float(true_peak_batch(_as_device_2d(data).unsqueeze(0)).max().item())
+    else:
+        current_peak = float(data.abs().max()) if torch.is_tensor(data) else float(np.max(np.abs(data)))
+    gain = np.power(10.0, target_db / 20.0) / current_peak
+    output = gain * data
+    peak = float(output.abs().max()) if torch.is_tensor(output) else float(np.max(np.abs(output)))
+    if peak >= 1.0:
+        warnings.warn('Possible clipped samples in output.')
+    return output
+
+
+def limit_gains_device(gains, peaks, ceiling_db):
+    """Clamps device gains (CUDA float64 [G], in place) so that ``gain * max(peaks[g])`` stays at or under ``ceiling_db``:
+    peaks CUDA float64 [G, k] linear (true_peak_batch of what the gain will scale: the maximum is taken over the k
+    channels).  A zero peak leaves the gain alone.  Returns gains; no host synchronisation (dam_peak_limit_gains)."""
+    from . import ops
+    return ops.peak_limit_gains(gains, peaks, ceiling_db)
 
 
 def gated_loudness(z):

@@ -804,6 +804,69 @@ def pcm_encode(x, subtype, scale=None, dither_seed=None, out=None, clip_count=No
     return out
 
 
+# ----------------------------------------------------------------------------- true peak and the gain ceiling
+def true_peak_geometry():
+    """(samples of one workgroup tile, workgroup cap of a launch) of dam_true_peak_batch, asked of the library: a row gets
+    max(1, cap // rows) workgroups which stride over its tiles."""
+    L = _lib.lib()
+    return L.dam_true_peak_tile_samples(), L.dam_true_peak_max_blocks()
+
+
+def true_peak_batch(data, gains=None, out=None, sample_peak_out=None):
+    """data: CUDA float32 / float64 [N, samples, channels] with any strides (planar [N, channels, n] storage is passed as
+    ``pcm.transpose(1, 2)``, no copy) -> the linear true peak of every (track, channel) row, float64 [N, channels]
+    (include/dam_hip.h: dam_true_peak_batch; 4x oversampled, >= the sample peak).  gains: optional CUDA float64
+    [N, n_gains] (or [N]), applied at load exactly as the batched loudness meter applies them.  sample_peak_out: optional
+    float64 [N, channels] that receives max |x| of every row.  No host synchronisation, hipGraph-capturable."""
+    _lib.require_cuda(data, gains, out, sample_peak_out)
+    xk = _audio_kind(data, 'data')
+    if data.dim() != 3:
+        raise ValueError('true_peak_batch: [tracks, samples, channels] expected, got shape %s' % (tuple(data.shape),))
+    N, n, ch = data.shape
+    if N < 1 or n < 1 or ch < 1 or N * ch > 65535:
+        raise ValueError('true_peak_batch: at least one track, sample and channel and at most 65535 rows expected, got %s'
+                         % (tuple(data.shape),))
+    n_gains = 0
+    if gains is not None:
+        if gains.dtype != torch.float64:
+            raise TypeError('gains must be float64')
+        gains = gains.reshape(N, -1).contiguous()
+        n_gains = gains.shape[1]
+        if not 1 <= n_gains <= n:
+            raise ValueError('between one gain and one gain per sample expected')
+    dev = data.device
+    if out is None:
+        out = torch.empty((N, ch), dtype=torch.float64, device=dev)
+    for o in (out, sample_peak_out):
+        if o is not None and (tuple(o.shape) != (N, ch) or o.dtype != torch.float64 or not o.is_contiguous()):
+            raise ValueError('true_peak_batch: outputs must be contiguous float64 [%d, %d] tensors' % (N, ch))
+    L = _lib.lib()
+    ws = torch.empty(L.dam_true_peak_workspace_bytes(N, n, ch) // 8, dtype=torch.float64, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(L.dam_true_peak_batch(_lib.ptr(data), xk, N, n, ch, data.stride(0), data.stride(1), data.stride(2),
+                                         _lib.ptr(gains), n_gains, _lib.ptr(sample_peak_out), _lib.ptr(out), _lib.ptr(ws),
+                                         _lib.stream()), 'dam_true_peak_batch')
+    return out
+
+
+def peak_limit_gains(gains, peaks, ceiling_db):
+    """gains: CUDA float64 [G], clamped IN PLACE to ``10 ** (ceiling_db / 20) / max(peaks[g])``; peaks: CUDA float64
+    [G, peaks_per_gain] (or [G]) linear peaks, e.g. the channels' true peaks of what the gain will scale.  A zero peak
+    leaves its gain unchanged.  Returns gains (include/dam_hip.h: dam_peak_limit_gains)."""
+    _lib.require_cuda(gains, peaks)
+    if gains.dtype != torch.float64 or peaks.dtype != torch.float64 or not gains.is_contiguous():
+        raise TypeError('peak_limit_gains: a contiguous float64 gains tensor and float64 peaks expected')
+    G = gains.numel()
+    if G < 1 or peaks.numel() < G or peaks.numel() % G:
+        raise ValueError('peak_limit_gains: %d peaks do not divide among %d gains' % (peaks.numel(), G))
+    peaks = peaks.contiguous()
+    with torch.cuda.device(gains.device):
+        _lib.check(_lib.lib().dam_peak_limit_gains(_lib.ptr(gains), _lib.ptr(peaks), G, peaks.numel() // G,
+                                                   float(10.0 ** (float(ceiling_db) / 20.0)), _lib.stream()),
+                   'dam_peak_limit_gains')
+    return gains
+
+
 # ----------------------------------------------------------------------------- dropout
 _dropout_counters = {}
 

@@ -55,7 +55,7 @@ struct dam_bn_bwd_sums; /* defined in the BatchNorm section */
 /* Library / build identification ("gfx950").  DAM_ABI_VERSION is bumped whenever a signature below changes; a binding
  * compares dam_abi_version() of the library it loaded with the version it was written against and refuses a stale one
  * (deep-audio-mixer_amd/_lib.py: EXPECTED_ABI). */
-#define DAM_ABI_VERSION 20
+#define DAM_ABI_VERSION 21
 const char* dam_arch(void);
 int dam_abi_version(void);
 
@@ -618,6 +618,44 @@ int64_t dam_pcm_tile_frames(int x_is_f64);
 int dam_pcm_max_blocks(void);
 int dam_pcm_encode(const void* x, int x_is_f64, int channels, int64_t n_samples, const double* scale, int n_scale,
                    int format, int dither, uint64_t seed, void* out, int64_t* clip_count, void* stream);
+
+/* ---------------------------------------------------------------------------------
+ * True peak (ITU-R BS.1770 Annex 2 / EBU R128: the peak of the 4x oversampled signal) and the gain ceiling built on it --
+ * what keeps a master "at -20 LUFS" from being clipped by dam_pcm_encode, which can only count.  Also the missing piece of
+ * the pyloudnorm surface (`pyln.normalize.peak`), measured on the reconstructed waveform instead of the samples.
+ *   Interpolator (dam_true_peak_taps_host, host float64, closed form): 49-tap Hann-windowed sinc
+ *     h[k] = sinc((k - 24) / 4) * 0.5 * (1 - cos(2 pi k / 48)), k = 0..48; h[24] = 1, h[24 +- 4m] = 0 exactly, symmetric.
+ *   For a row x[0..n) (x = 0 outside), p = 1, 2, 3 and i in [0, n):
+ *     y_p[i] = sum_{j=-6..5} x[i - j] * h[24 + p + 4 j]          (x[i-5 .. i+6]: the value between x[i] and x[i+1])
+ *     TP = max(max_i |x[i]|, max_{p,i} |y_p[i]|), linear; >= the sample peak by construction.
+ *   tests/_truepeak_ref.py restates this in numpy.  Parity with libebur128 or the ITU conformance table is not claimed.
+ *   dam_true_peak_batch: every (track, channel) row of the batch in one set of launches; addressing (element strides) and
+ *     `gains` exactly as dam_loudness_block_energy_batch: sample n of channel ch of track t is
+ *     x[t*track_stride + n*sample_stride + ch*channel_stride], measured as (double)x * gains[t][min(n / (n_samples /
+ *     n_gains), n_gains-1)] when gains (device [n_tracks][n_gains] float64) is not NULL.  sample_peak (may be NULL) and
+ *     true_peak: device float64 [n_tracks][channels].  workspace: dam_true_peak_workspace_bytes(...) bytes, 8-byte
+ *     aligned.  n_tracks * channels <= 65535.  Stateless, allocates nothing, does not synchronise, no atomics,
+ *     hipGraph-capturable; each y_p is 12 products summed in the fixed order j = -6 .. 5 and the result is a maximum, so
+ *     a row's two outputs do not depend on the other rows of the call or on the launch geometry (bitwise).  Argument
+ *     errors (NULL x / true_peak / workspace; a non-positive count; gains with n_gains < 1 or > n_samples; too many rows,
+ *     in this order) return DAM_ERR_BAD_ARG.  Non-finite samples are outside the contract: a NaN sample and the
+ *     interpolated values it reaches are skipped by the maximum, an infinite sample gives an infinite peak.
+ *   dam_true_peak_tile_samples / dam_true_peak_max_blocks: the launch geometry -- samples of one workgroup tile and the
+ *     workgroup cap of a launch (a row gets max(1, cap / rows) workgroups, each striding over the row's tiles) -- for
+ *     tests that place tile boundaries and the grid-stride wrap.
+ *   dam_peak_limit_gains: gains[i] = min(gains[i], ceiling_lin / max_{q < peaks_per_gain} peaks[i*peaks_per_gain + q]),
+ *     all device float64, ceiling_lin > 0 linear (10^(dBTP/20)).  A zero peak leaves the gain as it is (ceiling / 0 =
+ *     +inf); one static gain, no look-ahead limiter.
+ * --------------------------------------------------------------------------------- */
+int dam_true_peak_taps_host(double* h49);
+int64_t dam_true_peak_tile_samples(void);
+int dam_true_peak_max_blocks(void);
+int64_t dam_true_peak_workspace_bytes(int n_tracks, int64_t n_samples, int channels);
+int dam_true_peak_batch(const void* x, int x_is_f64, int n_tracks, int64_t n_samples, int channels, int64_t track_stride,
+                        int64_t sample_stride, int64_t channel_stride, const double* gains, int n_gains,
+                        double* sample_peak, double* true_peak, void* workspace, void* stream);
+int dam_peak_limit_gains(double* gains, const double* peaks, int n_gains, int peaks_per_gain, double ceiling_lin,
+                         void* stream);
 
 /* ---------------------------------------------------------------------------------
  * Stem input layout: x [B][C][HW] (C <= 16 planes, the reference's [B,S,F,T] feature stack) -> y [B][HW][16] with
