@@ -13,6 +13,11 @@ that gain -- and written as ``{song_name}_{identifier}.wav`` (evaluation.py:58-6
 clamped so that the file's true peak stays under the ceiling (dam_true_peak_batch of the resident sum) instead of being
 hard-clipped by the encoder.  The reference's spreadsheet
 (openpyxl) stays out: ``process_songlist`` returns the rows and the means instead of writing ./stats.xlsx.
+
+``dynamics=True`` adds the time axis a mixer of time-varying gains is judged on: the same comparison per 3 s short-term
+window (one every 100 ms; loudness.profile_error_device) -- '*_st_error' beside every '*_error' -- and the loudness range
+(EBU Tech 3342) of the reference stems.  Two mixes of equal integrated loudness per stem, one of which is 3 dB hot in the
+verses and 3 dB shy in the choruses, read the same '*_error'; their '*_st_error' differ.
 """
 import os
 from collections import OrderedDict
@@ -22,7 +27,8 @@ import numpy as np
 import torch
 
 from . import inference_utils, ops, staging
-from .loudness import Meter, limit_gains_device, normalize_loudness, target_gains_device, true_peak_batch
+from .loudness import (Meter, curve_stats_device, limit_gains_device, normalize_loudness, profile_error_device,
+                       target_gains_device, true_peak_batch, window_loudness_device)
 from .models.baselines.mean_loudness_model import MeanLoudnessModel
 from .models.baselines.random_model import RandomModel
 
@@ -83,6 +89,13 @@ class LoudnessEvaluator:
         lufs = self.meter.integrated_loudness_batch(pcm.transpose(1, 2), gains=gains)
         return self._profile(lufs.cpu().tolist())
 
+    def evaluate_short_term_batch(self, stems, gains=None):
+        """Short-term loudness curve (3 s window, one value per 100 ms) of every stem, measured as ``stem * gain ramp`` where
+        gains are given; stems and gains as evaluate_loudness_batch takes them -> CUDA float64 [stems, windows].  Nothing
+        comes to the host."""
+        pcm = stems if torch.is_tensor(stems) else torch.stack([stems[name] for name in self.keys])
+        return self.meter.short_term_loudness_batch(pcm.transpose(1, 2), gains=gains)
+
     @staticmethod
     def _profile(per_track_loudness):
         avg_loudness = mean(per_track_loudness)
@@ -122,7 +135,7 @@ class LoudnessEvaluator:
 
     def process_song_tracks(self, loaded_tracks: dict, reference_tracks: dict, song_name: str, n_random_samples: int = 5,
                             chunk_length: int = 2, write_wavs_to_disk=False, results_dir='./experiment',
-                            ceiling_dbtp=None) -> dict:
+                            ceiling_dbtp=None, dynamics=False) -> dict:
         """evaluation.py:77-116 on stems already in memory ({name: ndarray [channels, n]} each): the loudness profile of
         ``reference_tracks`` against the profiles of ``loaded_tracks`` summed as they are ('sum_error'), normalised to the
         training set's mean loudness ('loudnorm_error'), mixed by the model ('mix_error') and scaled by random gains
@@ -130,12 +143,18 @@ class LoudnessEvaluator:
         stats dict plus 'smooth_gains' {name: list}, the gains the mix variant used.  write_wavs_to_disk: every variant's
         stem sum at -20 LUFS goes to ``results_dir/{song_name}_{identifier}.wav`` (reference, sum, loudnorm, mix,
         random_0 ...; 16-bit), each held under ``ceiling_dbtp`` dBTP if that is given; the stats and the order of the
-        random draws depend on neither."""
+        random draws depend on neither.  dynamics: the stats gain 'sum_st_error', 'loudnorm_st_error', 'mix_st_error' and
+        'random_st_error' -- every variant's error taken per short-term window instead of per song, from the gains the
+        variant already passes to the meter -- and 'lra' {name: LU}, the loudness range of each reference stem; the other
+        keys, their values and the order of the random draws do not depend on it.  The reference mix and the stems must
+        then be of one length."""
         if self.d is None or self.mix_model is None or self.mean_loudness_model is None:
             raise ValueError('process_song needs the dataset, d_mean_loudness and mix_model constructor arguments')
         stems = [t for t in self.d.get_tracklist() if t != 'mix']
         if tuple(stems) != self.keys or self.keys != self.random_model.tracklist:
             raise ValueError('the dataset tracklist and the evaluator keys must both be %s' % (self.random_model.tracklist,))
+        if dynamics and np.asarray(reference_tracks[self.keys[0]]).shape[-1] != np.asarray(loaded_tracks[self.keys[0]]).shape[-1]:
+            raise ValueError('dynamics=True compares window by window: the reference mix and the stems differ in length')
         stats = {'song_name': song_name}
 
         def write(identifier, pcm, gains=None):
@@ -147,6 +166,11 @@ class LoudnessEvaluator:
         reference_pcm = self._upload(reference_tracks)
         reference = OrderedDict(zip(self.keys, self.evaluate_loudness_batch(reference_pcm)))
         write('reference', reference_pcm)
+        if dynamics:
+            reference_power, reference_st = window_loudness_device(
+                self.meter._curves(reference_pcm.transpose(1, 2), None, 30, 'short-term'), 30)
+            reference_lra = curve_stats_device(reference_power)[:, 0]
+            candidates_st = []                              # sum, loudnorm, mix, random_0 ...: [stems, windows] each
         del reference_pcm
 
         def error(profile):
@@ -160,40 +184,55 @@ class LoudnessEvaluator:
         lufs = self.meter.integrated_loudness_batch(pcm.transpose(1, 2))
         stats['sum_error'] = error(self._profile(lufs.cpu().tolist()))
         write('sum', pcm)
+        if dynamics:
+            candidates_st.append(self.evaluate_short_term_batch(pcm))
         # each multitrack is normalized to the mean loudness of the corresponding track from train set
         loudnorm_gains = self.mean_loudness_model.device_gains(pcm, lufs)
         stats['loudnorm_error'] = error(self.evaluate_loudness_batch(pcm, loudnorm_gains))
         write('loudnorm', pcm, loudnorm_gains)
+        if dynamics:
+            candidates_st.append(self.evaluate_short_term_batch(pcm, loudnorm_gains))
         stats['mix_error'] = error(self._profile([float(v) for v in mix_lufs]))
         write('mix', pcm, mixer.gains[1])
+        if dynamics:
+            candidates_st.append(self.evaluate_short_term_batch(pcm, mixer.gains[1]))
         random_errors = []
         for exp_i in range(n_random_samples):
             drawn = self.random_model.draw()
             g = torch.tensor([drawn[name] for name in self.keys], dtype=torch.float64, device=pcm.device)
             random_errors.append(error(self.evaluate_loudness_batch(pcm, g)))
             write('random_{}'.format(exp_i), pcm, g)
+            if dynamics:
+                candidates_st.append(self.evaluate_short_term_batch(pcm, g))
         stats['random_error'] = mean(random_errors)
         stats['smooth_gains'] = {name: list(gains[1, i]) for i, name in enumerate(self.keys)}
+        if dynamics:                                        # one launch for every variant, one copy to the host
+            st_errors = profile_error_device(reference_st, torch.stack(candidates_st))[0].cpu().tolist()
+            stats['sum_st_error'], stats['loudnorm_st_error'], stats['mix_st_error'] = st_errors[:3]
+            stats['random_st_error'] = mean(st_errors[3:])
+            stats['lra'] = dict(zip(self.keys, reference_lra.cpu().tolist()))
         return stats
 
     def process_song(self, base_dir: str, song_name: str, n_random_samples: int = 5, chunk_length: int = 2,
-                     write_wavs_to_disk=False, results_dir='./experiment', ceiling_dbtp=None) -> dict:
+                     write_wavs_to_disk=False, results_dir='./experiment', ceiling_dbtp=None, dynamics=False) -> dict:
         """evaluation.py:77-116: the reference mix from ``base_dir/manual_gain_mixes``, the stems from ``base_dir/test``."""
         from .data.dataset_utils import load_tracks_musdb18
         reference_tracks = load_tracks_musdb18(os.path.join(base_dir, 'manual_gain_mixes'), song_name, tracklist=self.keys,
                                                sr=self.sr)
         loaded_tracks = load_tracks_musdb18(os.path.join(base_dir, 'test'), song_name, tracklist=self.keys, sr=self.sr)
         return self.process_song_tracks(loaded_tracks, reference_tracks, song_name, n_random_samples, chunk_length,
-                                        write_wavs_to_disk, results_dir, ceiling_dbtp)
+                                        write_wavs_to_disk, results_dir, ceiling_dbtp, dynamics)
 
     def process_songlist(self, base_dir, songlist, n_random_samples: int = 5, chunk_length: int = 2,
-                         write_wavs_to_disk=False, results_dir='./experiment', ceiling_dbtp=None):
+                         write_wavs_to_disk=False, results_dir='./experiment', ceiling_dbtp=None, dynamics=False):
         """evaluation.py:118-144 without the spreadsheet: (rows, means) -- one stats dict per song and the mean of every
-        error over the songs (the sheet's last row)."""
+        error over the songs (the sheet's last row); with ``dynamics`` the four '*_st_error' keys too."""
         keys = ['sum_error', 'random_error', 'loudnorm_error', 'mix_error']
+        if dynamics:
+            keys += ['sum_st_error', 'random_st_error', 'loudnorm_st_error', 'mix_st_error']
         rows = []
         for i, song_name in enumerate(songlist):
             print('{}/{}: {}'.format(i + 1, len(songlist), song_name))
             rows.append(self.process_song(base_dir, song_name, n_random_samples, chunk_length, write_wavs_to_disk,
-                                          results_dir, ceiling_dbtp))
+                                          results_dir, ceiling_dbtp, dynamics))
         return rows, {key: mean(row[key] for row in rows) for key in keys}

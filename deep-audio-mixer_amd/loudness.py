@@ -29,6 +29,16 @@ Peaks -- ``pyln.normalize.peak`` and the true peak (BS.1770 Annex 2 / EBU R128: 
     limit_gains_device(gain, tp, -1.0)                   # gain = min(gain, ceiling / max over channels), on the device
 
 The interpolator is this package's own 49-tap windowed sinc (include/dam_hip.h); parity with libebur128 is not claimed.
+
+Loudness over time -- the other three readings of an EBU R128 meter, which pyloudnorm lacks: one value per 100 ms hop of
+the 400 ms (momentary) and 3 s (short-term) windows, and the loudness range of EBU Tech 3342 over the short-term curve:
+
+    d = meter.loudness_dynamics_batch(pcm.transpose(1, 2), gains=smooth)     # curves, their maxima, LRA: one filter pass
+    lra = meter.loudness_range_batch(pcm.transpose(1, 2))                    # CUDA float64 [N] LU
+    lu = loudness_range(data, 44100)                                         # one array, a float
+
+all on the device without synchronisation (dam_loudness_window_power, dam_loudness_curve_stats); profile_error_device
+compares the short-term curves of two mixes window by window (evaluation.LoudnessEvaluator, ``dynamics=True``).
 """
 import ctypes
 import warnings
@@ -75,6 +85,7 @@ class Meter:
         self._coef = coef
         self.coefficients = np.array(list(coef)).reshape(2, 6)          # [stage][b0 b1 b2 a0 a1 a2]
         self._bounds = {}                                               # _block_bounds' cache
+        self._hops = {}                                                 # _hop_bounds' cache
 
     # ---- device part: block mean squares z[channel][block]
     def block_energies(self, data):
@@ -168,6 +179,156 @@ class Meter:
         """Integrated loudness of every track of ``data`` (see block_energies_batch) -> CUDA float64 [N]; a track the gates
         empty reads -inf.  No host synchronisation."""
         return gate_loudness_device(self.block_energies_batch(data, gains), out=out)
+
+    # ---- loudness over time (EBU R128 momentary / short-term, Tech 3342 loudness range); device only, no synchronisation
+    def _hop_bounds(self, n, dev):
+        """Device bounds of the 100 ms hops of an n-sample track, cached per (device, n, rate) like _block_bounds."""
+        key = (dev, n, self.rate)
+        if key not in self._hops:
+            h = int(round(0.1 * self.rate))
+            lo = np.arange(n // h, dtype=np.int64) * h
+            self._hops[key] = (torch.from_numpy(lo).to(dev), torch.from_numpy(lo + h).to(dev), h)
+        return self._hops[key]
+
+    def hop_energies_batch(self, data, gains=None):
+        """Mean square of the K-weighted signal over every 100 ms hop: data and gains as block_energies_batch takes them
+        -> CUDA float64 [N, channels, H], H = samples // round(0.1 * rate) (a shorter tail is dropped).  The same filter
+        passes as the integrated meter (dam_loudness_block_energy_batch) with hop bounds in place of gating blocks."""
+        if not torch.is_tensor(data):
+            raise ValueError('Data must be of type torch.Tensor.')
+        if not data.is_cuda or (gains is not None and not gains.is_cuda):
+            raise ValueError('Data and gains must be CUDA tensors: the meter runs on the GPU only, there is no CPU fallback.')
+        if data.dtype not in (torch.float32, torch.float64):
+            raise ValueError('Data must be floating point.')
+        if data.dim() != 3:
+            raise ValueError('Audio must be [tracks, samples, channels].')
+        N, n, ch = data.shape
+        if ch > 5:
+            raise ValueError('Audio must have five channels or less.')
+        dev = data.device
+        lo_d, hi_d, h = self._hop_bounds(n, dev)
+        H = lo_d.numel()
+        if H < 1:
+            raise ValueError('Audio must have length greater than one 100 ms hop.')
+        n_gains = 0
+        if gains is not None:
+            if gains.dtype != torch.float64:
+                raise TypeError('gains must be float64')
+            gains = gains.reshape(N, -1).contiguous()
+            n_gains = gains.shape[1]
+            if not 1 <= n_gains <= n:
+                raise ValueError('between one gain and one gain per sample expected')
+        out = torch.empty((N, ch, H), dtype=torch.float64, device=dev)
+        L = _lib.lib()
+        ws = torch.empty(L.dam_loudness_batch_workspace_bytes(N, n, ch, H) // 8 + 1, dtype=torch.float64, device=dev)
+        with torch.cuda.device(dev):
+            _lib.check(L.dam_loudness_block_energy_batch(
+                _lib.ptr(data), 1 if data.dtype == torch.float64 else 0, N, n, ch, data.stride(0), data.stride(1),
+                data.stride(2), _lib.ptr(gains), n_gains, self._coef, _lib.ptr(lo_d), _lib.ptr(hi_d), H, float(h),
+                _lib.ptr(out), _lib.ptr(ws), _lib.stream()), 'dam_loudness_block_energy_batch')
+        return out
+
+    def _curves(self, data, gains, hops, what):
+        e = self.hop_energies_batch(data, gains)
+        if e.shape[2] < hops:
+            raise ValueError('Audio must be at least %d hops of 100 ms long for %s loudness.' % (hops, what))
+        return e
+
+    def momentary_loudness_batch(self, data, gains=None):
+        """Momentary loudness (EBU R128: 400 ms window, one value per 100 ms hop) of every track -> CUDA float64
+        [N, H - 3] LUFS; silence reads -inf.  The window is R128's whatever ``block_size`` this Meter was built with."""
+        return window_loudness_device(self._curves(data, gains, 4, 'momentary'), 4)[1]
+
+    def short_term_loudness_batch(self, data, gains=None):
+        """Short-term loudness (EBU R128: 3 s window, one value per 100 ms hop) of every track -> CUDA float64
+        [N, H - 29] LUFS; silence reads -inf.  The window is R128's whatever ``block_size`` this Meter was built with."""
+        return window_loudness_device(self._curves(data, gains, 30, 'short-term'), 30)[1]
+
+    def loudness_range_batch(self, data, gains=None):
+        """Loudness range (EBU Tech 3342: the 10th to 95th percentile of the short-term loudness gated at -70 LUFS and at
+        -20 LU under the gated mean) of every track -> CUDA float64 [N] LU; a track the gates empty reads 0."""
+        power = window_loudness_device(self._curves(data, gains, 30, 'short-term'), 30, want_lufs=False)[0]
+        return curve_stats_device(power)[:, 0]
+
+    def loudness_dynamics_batch(self, data, gains=None):
+        """Every time-resolved reading from one pass of the filter: {'momentary' [N, H - 3], 'short_term' [N, H - 29]
+        (LUFS curves), 'momentary_max', 'short_term_max', 'lra', 'lra_low', 'lra_high' ([N]; LU and the two percentile
+        levels in LUFS)}, all CUDA float64.  The windows are R128's 0.4 s and 3 s, one value per 100 ms, whatever
+        ``block_size`` this Meter was built with (that argument shapes the integrated measurement only)."""
+        e = self._curves(data, gains, 30, 'short-term')
+        m_power, m_lufs = window_loudness_device(e, 4)
+        s_power, s_lufs = window_loudness_device(e, 30)
+        m_stats, s_stats = curve_stats_device(m_power), curve_stats_device(s_power)
+        return {'momentary': m_lufs, 'short_term': s_lufs, 'momentary_max': m_stats[:, 5], 'short_term_max': s_stats[:, 5],
+                'lra': s_stats[:, 0], 'lra_low': s_stats[:, 1], 'lra_high': s_stats[:, 2]}
+
+
+def window_loudness_device(e, w, want_lufs=True):
+    """Sliding-window loudness of hop energies e CUDA float64 [N, channels, H]: windows of w hops, one per hop ->
+    (power [N, H - w + 1], LUFS of the same shape or None) (dam_loudness_window_power)."""
+    _lib.require_cuda(e)
+    if e.dtype != torch.float64 or e.dim() != 3:
+        raise ValueError('e must be float64 [tracks, channels, hops]')
+    e = e.contiguous()
+    N, ch, H = e.shape
+    if ch > 5:
+        raise ValueError('Audio must have five channels or less.')
+    if not 1 <= w <= H:
+        raise ValueError('a window of 1 to %d hops expected' % H)
+    power = torch.empty((N, H - w + 1), dtype=torch.float64, device=e.device)
+    lufs = torch.empty_like(power) if want_lufs else None
+    with torch.cuda.device(e.device):
+        _lib.check(_lib.lib().dam_loudness_window_power(_lib.ptr(e), N, ch, H, w, _lib.ptr(power), _lib.ptr(lufs),
+                                                        _lib.stream()), 'dam_loudness_window_power')
+    return power, lufs
+
+
+def curve_stats_device(power):
+    """Gated statistics of power curves: power CUDA float64 [N, W] (window_loudness_device) -> [N, 6] =
+    (LRA, low percentile LUFS, high percentile LUFS, relative gate LUFS, values kept, maximum LUFS) as
+    include/dam_hip.h defines them for dam_loudness_curve_stats.  Exact order statistics at any W."""
+    _lib.require_cuda(power)
+    if power.dtype != torch.float64 or power.dim() != 2 or power.shape[1] < 1:
+        raise ValueError('power must be float64 [tracks, windows]')
+    power = power.contiguous()
+    N, W = power.shape
+    out = torch.empty((N, 6), dtype=torch.float64, device=power.device)
+    with torch.cuda.device(power.device):
+        _lib.check(_lib.lib().dam_loudness_curve_stats(_lib.ptr(power), N, W, _lib.ptr(out), _lib.stream()),
+                   'dam_loudness_curve_stats')
+    return out
+
+
+def profile_error_device(ref_lufs, cand_lufs):
+    """Time-resolved loudness error: ref_lufs CUDA float64 [S, W], cand_lufs [V, S, W] (or [S, W]: one variant), short-term
+    curves of the S stems of a reference mix and of V candidates -> (err [V], active [V]): over the windows in which every
+    stem of both is at or above -70 LUFS, the mean |(C - mean_s C) - (R - mean_s R)|, and how many such windows there
+    were; NaN where there were none (dam_loudness_profile_error)."""
+    _lib.require_cuda(ref_lufs, cand_lufs)
+    if cand_lufs.dim() == 2:
+        cand_lufs = cand_lufs.unsqueeze(0)
+    if ref_lufs.dtype != torch.float64 or cand_lufs.dtype != torch.float64 or ref_lufs.dim() != 2 or cand_lufs.dim() != 3:
+        raise ValueError('float64 [stems, windows] and [variants, stems, windows] expected')
+    if tuple(cand_lufs.shape[1:]) != tuple(ref_lufs.shape):
+        raise ValueError('reference and candidate curves differ in shape: %s and %s'
+                         % (tuple(ref_lufs.shape), tuple(cand_lufs.shape[1:])))
+    ref_lufs, cand_lufs = ref_lufs.contiguous(), cand_lufs.contiguous()
+    V, S, W = cand_lufs.shape
+    if V < 1 or S < 1 or W < 1:
+        raise ValueError('at least one variant, stem and window expected')
+    err = torch.empty(V, dtype=torch.float64, device=ref_lufs.device)
+    active = torch.empty_like(err)
+    with torch.cuda.device(ref_lufs.device):
+        _lib.check(_lib.lib().dam_loudness_profile_error(_lib.ptr(ref_lufs), _lib.ptr(cand_lufs), V, S, W, _lib.ptr(err),
+                                                         _lib.ptr(active), _lib.stream()), 'dam_loudness_profile_error')
+    return err, active
+
+
+def loudness_range(data, rate):
+    """Loudness range in LU (EBU Tech 3342) of one [samples] or [samples, channels] array (numpy or torch) at ``rate`` Hz
+    -> float; the host convenience beside Meter.loudness_range_batch, as true_peak is beside true_peak_batch."""
+    x = _as_device_2d(data)
+    return float(Meter(rate).loudness_range_batch(x.unsqueeze(0)).item())
 
 
 def gate_loudness_device(z, out=None):

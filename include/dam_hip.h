@@ -55,7 +55,7 @@ struct dam_bn_bwd_sums; /* defined in the BatchNorm section */
 /* Library / build identification ("gfx950").  DAM_ABI_VERSION is bumped whenever a signature below changes; a binding
  * compares dam_abi_version() of the library it loaded with the version it was written against and refuses a stale one
  * (deep-audio-mixer_amd/_lib.py: EXPECTED_ABI). */
-#define DAM_ABI_VERSION 21
+#define DAM_ABI_VERSION 22
 const char* dam_arch(void);
 int dam_abi_version(void);
 
@@ -656,6 +656,46 @@ int dam_true_peak_batch(const void* x, int x_is_f64, int n_tracks, int64_t n_sam
                         double* sample_peak, double* true_peak, void* workspace, void* stream);
 int dam_peak_limit_gains(double* gains, const double* peaks, int n_gains, int peaks_per_gain, double ceiling_lin,
                          void* stream);
+
+/* ---------------------------------------------------------------------------------
+ * Loudness over time: momentary (400 ms) and short-term (3 s) loudness as EBU R128 names them, the loudness range of
+ * EBU Tech 3342 and a per-window loudness-profile error.  All float64, all device pointers; every entry is stateless,
+ * allocates nothing, does not synchronise with the host, uses no atomics and is hipGraph-capturable.
+ *   Hop energies.  h = round(0.1 * rate) samples, H = n / h hops (a shorter tail is dropped),
+ *     e[c][j] = (sum of y^2 over [j h, (j+1) h)) / h with y the K-weighted row, gain ramp included: this is
+ *     dam_loudness_block_energy_batch with blk_lo[j] = j h, blk_hi[j] = (j+1) h, block_len = h.  No other filter exists.
+ *   dam_loudness_window_power: e [n_tracks][channels <= 5][H], window of w hops (4: momentary, 30: short-term), one value
+ *     per hop, W = H - w + 1 >= 1:
+ *       s_c = sum_{k=0..w-1} e[c][i+k] (k ascending);  p_i = (sum_c G_c s_c, c ascending) / w, G = 1, 1, 1, 1.41, 1.41;
+ *       l_i = -0.691 + 10 log10(p_i)   (silence: p = 0, l = -inf).
+ *     Every value is its own fixed-order sum (no running sum, no prefix difference), so it depends on neither its
+ *     neighbours nor the rest of the batch.  power [n_tracks][W]; lufs [n_tracks][W] or NULL.  n_tracks <= 65535.
+ *   dam_loudness_curve_stats: the gated statistics of each track's power curve p[0..W), one workgroup per track.  Gates act
+ *     on powers, so no decision hangs on a log10 rounding:
+ *       absolute gate  keep p_i >= DAM_LOUDNESS_ABS_GATE_POWER (-70 LUFS);
+ *       relative gate  m = mean of the absolutely gated p_i (thread t sums t, t + 256, ..., then a tree over the 256
+ *                      partials, as dam_loudness_gate does); keep p_i >= 0.01 m as well (-20 LU, Tech 3342);
+ *       percentiles    n values pass both gates, q[] is those in ascending order:
+ *                      lo = q[((n-1)*10 + 50) / 100], hi = q[((n-1)*95 + 50) / 100]  (Tech 3342's round((n-1) P / 100) in
+ *                      integers), selected among the exact input doubles by an MSB-first radix select over their
+ *                      order-preserving 64-bit keys, read from global memory: any W, no sort, no workspace.
+ *     out [n_tracks][6] = { LRA = l(hi) - l(lo), l(lo), l(hi), Gamma_r = -0.691 + 10 log10(m) - 20, n, max_i l_i over
+ *     all W values (ungated) } with l(p) = -0.691 + 10 log10(p).  n = 0: LRA 0.0, both percentiles NaN; Gamma_r is NaN
+ *     when the absolute gate is already empty; the maximum of an all-silent curve is -inf.  A track's six values do not
+ *     depend on the other tracks of the call (bitwise).  Non-finite or negative powers are outside the contract.
+ *   dam_loudness_profile_error: ref_lufs [S][W] (the reference mix's stems), cand_lufs [V][S][W] (V candidate mixes).
+ *     Window i of variant v is ACTIVE when every ref_lufs[s][i] >= -70 and every cand_lufs[v][s][i] >= -70;
+ *       err[v] = mean over active i and all s of |(C[s][i] - mean_s C[.][i]) - (R[s][i] - mean_s R[.][i])|
+ *     (sums over s ascending; thread t takes windows t, t + 256, ..., then the tree), NaN when no window is active;
+ *     active[v] = the number of active windows as a double.  One workgroup per variant.
+ * Parity with libebur128 is not claimed: its short-term hop for LRA and its percentile interpolation differ.
+ * --------------------------------------------------------------------------------- */
+#define DAM_LOUDNESS_ABS_GATE_POWER 0x1.f791ec6e1d5b7p-24 /* 10^((-70 + 0.691) / 10) */
+int dam_loudness_window_power(const double* e, int n_tracks, int channels, int n_hops, int w, double* power, double* lufs,
+                              void* stream);
+int dam_loudness_curve_stats(const double* power, int n_tracks, int n_windows, double* out, void* stream);
+int dam_loudness_profile_error(const double* ref_lufs, const double* cand_lufs, int n_variants, int n_stems,
+                               int n_windows, double* err, double* active, void* stream);
 
 /* ---------------------------------------------------------------------------------
  * Stem input layout: x [B][C][HW] (C <= 16 planes, the reference's [B,S,F,T] feature stack) -> y [B][HW][16] with
