@@ -8,11 +8,12 @@ The whole-song path uploads a song's stems once and never writes a scaled copy o
 are constant gains, the model's mix is a gain ramp, and the batched meter applies either as it loads the samples
 (Meter.integrated_loudness_batch(gains=...)); the mix variant is the 'loudness' kind of inference_utils.SongMixer, one
 hipGraph from PCM to the four LUFS values.  With ``write_wavs_to_disk`` every variant's stem sum is also rendered on the
-device from the same resident PCM -- mixdown with the variant's gains, batched meter, gain to -20 LUFS, PCM encoder with
-that gain -- and written as ``{song_name}_{identifier}.wav`` (evaluation.py:58-66); with ``ceiling_dbtp`` that gain is first
-clamped so that the file's true peak stays under the ceiling (dam_true_peak_batch of the resident sum) instead of being
-hard-clipped by the encoder.  The reference's spreadsheet
-(openpyxl) stays out: ``process_songlist`` returns the rows and the means instead of writing ./stats.xlsx.
+device from the same resident PCM by the mixer's own master tail (inference_utils.MasterChain) -- mixdown with the
+variant's gains, batched meter, gain to -20 LUFS, PCM encoder with that gain -- and written as
+``{song_name}_{identifier}.wav`` (evaluation.py:58-66); with ``ceiling_dbtp`` that gain is first clamped so that the file's
+true peak stays under the ceiling (dam_true_peak_batch of the resident sum) instead of being hard-clipped by the encoder.
+The reference's spreadsheet (openpyxl) stays out: ``process_songlist`` returns the rows and the means instead of writing
+./stats.xlsx.
 
 ``dynamics=True`` adds the time axis a mixer of time-varying gains is judged on: the same comparison per 3 s short-term
 window (one every 100 ms; loudness.profile_error_device) -- '*_st_error' beside every '*_error' -- and the loudness range
@@ -26,9 +27,8 @@ from statistics import mean
 import numpy as np
 import torch
 
-from . import inference_utils, ops, staging
-from .loudness import (Meter, curve_stats_device, limit_gains_device, normalize_loudness, profile_error_device,
-                       target_gains_device, true_peak_batch, window_loudness_device)
+from . import inference_utils, staging
+from .loudness import Meter, curve_stats_device, normalize_loudness, profile_error_device
 from .models.baselines.mean_loudness_model import MeanLoudnessModel
 from .models.baselines.random_model import RandomModel
 
@@ -122,14 +122,12 @@ class LoudnessEvaluator:
         n_stems, channels, n = pcm.shape
         if gains is None:
             gains = torch.ones((n_stems, 1), dtype=torch.float64, device=pcm.device)
-        mix = ops.mixdown_peak_normalize(pcm, gains.view(n_stems, -1), normalize=False, out_dtype=torch.float64)
-        lufs = self.meter.integrated_loudness_batch(mix.t().unsqueeze(0))
-        gain = target_gains_device(lufs, torch.full((1,), float(target_lufs), dtype=torch.float64, device=pcm.device))
-        if ceiling_dbtp is not None:
-            limit_gains_device(gain, true_peak_batch(mix.t().unsqueeze(0)), ceiling_dbtp)
-        clip = torch.empty(channels, dtype=torch.int64, device=pcm.device)
-        payload = staging.pipe_for(pcm.device).download(ops.pcm_encode(mix, subtype, scale=gain, clip_count=clip))
-        clipped = int(clip.sum().item())
+        # built per call, not cached: excerpt lengths vary
+        chain = inference_utils.MasterChain(channels, n, pcm.device, 'loudness', sr=self.sr, target_lufs=target_lufs,
+                                            ceiling_dbtp=ceiling_dbtp, encode=subtype)
+        chain.render(pcm, gains.view(n_stems, -1))
+        payload = staging.pipe_for(pcm.device).download(chain.enc)
+        clipped = int(chain.clip.sum().item())
         write_wav_bytes(path, payload, self.sr, channels, subtype, n, clipped)
         return clipped
 
@@ -167,8 +165,7 @@ class LoudnessEvaluator:
         reference = OrderedDict(zip(self.keys, self.evaluate_loudness_batch(reference_pcm)))
         write('reference', reference_pcm)
         if dynamics:
-            reference_power, reference_st = window_loudness_device(
-                self.meter._curves(reference_pcm.transpose(1, 2), None, 30, 'short-term'), 30)
+            reference_power, reference_st = self.meter.short_term_batch(reference_pcm.transpose(1, 2))
             reference_lra = curve_stats_device(reference_power)[:, 0]
             candidates_st = []                              # sum, loudnorm, mix, random_0 ...: [stems, windows] each
         del reference_pcm

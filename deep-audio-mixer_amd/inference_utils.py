@@ -8,12 +8,13 @@ multichannel audio.
 Everything between the PCM upload and the result download stays on the device and -- for a model in eval mode -- is ONE
 hipGraph (``SongMixer``): strided STFT front-end over all chunks of all stems straight out of the planar song
 (dam_stft_logmag_strided_f32) -> model forward of the whole chunk batch -> 10 ** (0.5 g) and the Savitzky-Golay
-smoothing (dam_gains_smooth) -> sample-rate gain ramp x audio (dam_gain_ramp_apply), or for ``mix_song_to_master`` the
-fused stem sum + peak normalisation (dam_mixdown_peak_normalize) or, with ``normalize='loudness'``, the stem sum brought to
-a target BS.1770 loudness (optionally held under a true-peak ceiling, ``ceiling_dbtp``: dam_true_peak_batch of the float64
-sum, dam_peak_limit_gains on the loudness gain; ``normalize='true_peak'`` puts the true peak AT the ceiling instead) -- and,
-for ``mix_song_to_wav``, the PCM encoder as the graph's last node (dam_pcm_encode: the
-loudness gain is applied inside it, the host receives the file's sample bytes instead of the float master);
+smoothing (dam_gains_smooth) -> sample-rate gain ramp x audio (dam_gain_ramp_apply), or for ``mix_song_to_master`` and
+``mix_song_to_wav`` the master tail, ``MasterChain``: the fused stem sum + peak normalisation (dam_mixdown_peak_normalize)
+or, with ``normalize='loudness'``, the stem sum brought to a target BS.1770 loudness (optionally held under a true-peak
+ceiling, ``ceiling_dbtp``: dam_true_peak_batch of the float64 sum, dam_peak_limit_gains on the loudness gain;
+``normalize='true_peak'`` puts the true peak AT the ceiling instead), then the PCM encoder as the graph's last node where a
+file is asked for (dam_pcm_encode: the loudness gain is applied inside it, the host receives the file's sample bytes instead
+of the float master).  MasterChain is the single place a new output stage goes: the evaluator's WAV export runs the same one.
 ``mix_song_loudness`` ends in the batched meter instead (the per-stem loudness of the mixed
 stems, dam_loudness_block_energy_batch with the gain ramp applied at load: the mixed stems are never written).
 ``mix_song_spectral`` renders in the spectral domain
@@ -63,6 +64,94 @@ def predict_chunk_gains(model, pcm, n_stems, n_chunks, chunk_samples, window_siz
     return model.predict_gains(feats)
 
 
+class MasterChain:
+    """The master tail, the ONE implementation of it (SongMixer kind 'master' captures it into the song's graph,
+    evaluation.LoudnessEvaluator.write_sum_to_target runs it eagerly; a new output stage goes here): stem sum -> BS.1770
+    measurement -> target gain -> true-peak clamp -> gain apply or PCM encode.  It owns every buffer those steps need,
+    allocated once and only where the configuration uses it, so a captured ``render`` holds stable pointers.
+
+    normalize: True / False -- the sum, peak-normalised per channel or not (the callers' librosa.util.normalize);
+    'loudness' -- the float64 sum brought to ``target_lufs`` (evaluation.py:59-66); 'true_peak' -- the sum scaled so that its
+    true peak (dBTP) sits at ``ceiling_dbtp`` (default -1.0).  ceiling_dbtp (with 'loudness'): the gain to the target is
+    clamped to ``ceiling / true peak of the sum``, one static gain for all channels, no limiter.  encode: None (``out``
+    holds the master as ``out_dtype``) or a WAV subtype of ops.PCM_FORMATS (``enc`` holds the file's sample bytes, ``clip``
+    the clamped-sample count per channel; TPDF dither if ``dither_seed`` is given)."""
+
+    @staticmethod
+    def rules(normalize, ceiling_dbtp, encode):
+        """What the three arguments may be -> (normalize, ceiling); ValueError otherwise."""
+        if encode is not None and encode not in ops.PCM_FORMATS:
+            raise ValueError('encode must be one of %s, got %r' % (sorted(ops.PCM_FORMATS), encode))
+        if normalize not in (True, False, 'loudness', 'true_peak'):
+            raise ValueError("normalize must be True, False, 'loudness' or 'true_peak'")
+        if normalize == 'true_peak' and ceiling_dbtp is None:
+            ceiling_dbtp = -1.0
+        if ceiling_dbtp is not None and normalize not in ('loudness', 'true_peak'):
+            raise ValueError("ceiling_dbtp needs normalize 'loudness' or 'true_peak'")
+        return normalize, None if ceiling_dbtp is None else float(ceiling_dbtp)
+
+    def __init__(self, channels, n_samples, device, normalize=True, out_dtype=torch.float64, sr=44100, target_lufs=-20.0,
+                 ceiling_dbtp=None, encode=None, dither_seed=None):
+        self.normalize, self.ceiling = self.rules(normalize, ceiling_dbtp, encode)
+        self.encode, self.dither_seed = encode, dither_seed
+        scaled = self.normalize in ('loudness', 'true_peak')             # the float64 sum times one measured gain
+        f64 = dict(dtype=torch.float64, device=device)
+        self.out = self.enc = self.clip = self.master_gain = None
+        if encode is None or not scaled:                       # (the encoder reads the float64 sum and scales it itself)
+            self.out = torch.empty((channels, n_samples), dtype=out_dtype, device=device)
+        if encode is not None:
+            self.enc = torch.empty(n_samples * channels * ops.PCM_FORMATS[encode][1], dtype=torch.uint8, device=device)
+            self.clip = torch.empty(channels, dtype=torch.int64, device=device)
+        if scaled:
+            # evaluation.py:59-66: the float64 stem sum is measured and scaled; only the result takes out_dtype
+            self.mix = torch.empty((channels, n_samples), **f64)
+            self.master_gain = torch.empty(1, **f64)
+        if self.normalize == 'loudness':
+            self.meter = loudness.Meter(sr)
+            self.target = torch.full((1,), float(target_lufs), **f64)
+            self.lufs = torch.empty(1, **f64)
+        if self.ceiling is not None:
+            # the gain before the clamp (written by every render; 'true_peak' asks for none: +inf), the true and sample
+            # peaks of the sum
+            self.free_gain = torch.empty(1, **f64) if self.normalize == 'loudness' else torch.full((1,), float('inf'), **f64)
+            self.tp = torch.empty((1, channels), **f64)
+            self.sp = torch.empty((1, channels), **f64)
+        self.sum = self.mix if scaled else self.out
+        self.ws = torch.empty(ops._lib.lib().dam_mixdown_workspace_elems(channels), dtype=self.sum.dtype, device=device)
+
+    def render(self, pcm, gains):
+        """pcm CUDA [stems, channels, n], gains CUDA float64 [stems, n_gains] -> ``out`` or ``enc`` / ``clip``.  No host
+        synchronisation and no branch on a tensor's value: capturable."""
+        scaled = self.master_gain is not None
+        ops.mixdown_peak_normalize(pcm, gains, normalize=not scaled and self.normalize, out=self.sum, workspace=self.ws)
+        if self.normalize == 'loudness':
+            self.meter.integrated_loudness_batch(self.mix.t().unsqueeze(0), out=self.lufs)
+            loudness.target_gains_device(self.lufs, self.target, out=self.master_gain if self.ceiling is None else self.free_gain)
+        if self.ceiling is not None:
+            self.master_gain.copy_(self.free_gain)
+            ops.true_peak_batch(self.mix.t().unsqueeze(0), out=self.tp, sample_peak_out=self.sp)
+            ops.peak_limit_gains(self.master_gain, self.tp, self.ceiling)          # the maximum over the channels
+        if self.encode is not None:                # mix * gain is rounded once to float64 either way: the same samples
+            ops.pcm_encode(self.sum, self.encode, scale=self.master_gain, dither_seed=self.dither_seed, out=self.enc,
+                           clip_count=self.clip)
+        elif scaled:
+            ops.gain_ramp_apply(self.mix, self.master_gain, out=self.out)
+
+    def peaks(self):
+        """The peak measurement of the last render of a chain with a ceiling, from the device tensors the graph wrote:
+        {'true_peak_db': [per channel], 'sample_peak_db': [per channel]} of the master as rendered (the measured sum times
+        the gain that was applied, before any quantisation), 'limited': whether the ceiling, not the loudness target, set
+        that gain (always so for normalize='true_peak' unless the sum is silent), and 'gain', the gain itself."""
+        if self.ceiling is None:
+            raise ValueError('this master chain was built without ceiling_dbtp')
+        tp, sp = self.tp.cpu().numpy()[0], self.sp.cpu().numpy()[0]
+        gain, free = float(self.master_gain.cpu()[0]), float(self.free_gain.cpu()[0])
+        with np.errstate(divide='ignore', invalid='ignore'):
+            return {'true_peak_db': [float(v) for v in 20.0 * np.log10(tp * gain)],
+                    'sample_peak_db': [float(v) for v in 20.0 * np.log10(sp * gain)],
+                    'limited': bool(gain < free), 'gain': gain}
+
+
 class SongMixer:
     """Static device buffers and the captured hipGraph of one song geometry: (model, stems, channels, samples, dtype,
     chunk length, output kind).  ``run(tracks)`` uploads, replays, downloads."""
@@ -70,25 +159,17 @@ class SongMixer:
     def __init__(self, model, n_stems, channels, n_samples, dtype, chunk_samples, kind, normalize=True,
                  out_dtype=torch.float64, use_graph=True, hop_length=1024, sr=44100, target_lufs=-20.0, encode=None,
                  dither_seed=None, ceiling_dbtp=None):
-        """encode (kind 'master' only): None, or a WAV subtype ('PCM_16', 'PCM_24', 'PCM_32', 'FLOAT') -- the master is then
-        quantised by the last node of the same graph and ``run`` returns its sample bytes and the clipped-sample count.
-        ceiling_dbtp (kind 'master' with normalize 'loudness' or 'true_peak'): the true peak (dBTP) the master must not
-        exceed.  With 'loudness' the gain to ``target_lufs`` is clamped to ``ceiling / true peak of the sum`` (one static
-        gain for all channels, no limiter); with 'true_peak' (default ceiling -1.0) that quotient IS the gain.  ``peaks()``
-        reports the measurement of the last run."""
+        """normalize, out_dtype, sr, target_lufs, encode, dither_seed, ceiling_dbtp: what MasterChain takes, for kind
+        'master' (the other kinds accept neither ``encode`` nor a ceiling).  With ``encode`` the master is quantised by the
+        last node of the same graph and ``run`` returns its sample bytes and the clipped-sample count; ``peaks()`` reports
+        the true-peak measurement of the last run."""
         if kind not in ('stems', 'master', 'spectral', 'loudness'):
             raise ValueError(kind)
-        if encode is not None and (kind != 'master' or encode not in ops.PCM_FORMATS):
-            raise ValueError("encode needs kind='master' and one of %s, got %r" % (sorted(ops.PCM_FORMATS), encode))
-        self.encode, self.dither_seed = encode, dither_seed
-        if normalize not in (True, False, 'loudness', 'true_peak'):
-            raise ValueError("normalize must be True, False, 'loudness' or 'true_peak'")
-        if normalize == 'true_peak' and ceiling_dbtp is None:
-            ceiling_dbtp = -1.0
-        if ceiling_dbtp is not None and (kind != 'master' or normalize not in ('loudness', 'true_peak')):
-            raise ValueError("ceiling_dbtp needs kind='master' and normalize 'loudness' or 'true_peak'")
-        self.ceiling = None if ceiling_dbtp is None else float(ceiling_dbtp)
-        self.model, self.kind, self.normalize = model, kind, normalize
+        self.normalize, self.ceiling = MasterChain.rules(normalize, ceiling_dbtp, encode)
+        if kind != 'master' and (encode is not None or self.ceiling is not None):
+            raise ValueError("encode and ceiling_dbtp need kind='master'")
+        self.encode = encode
+        self.model, self.kind = model, kind
         self.dev = next(model.parameters()).device
         self.n_stems, self.channels, self.n, self.chunk = n_stems, channels, n_samples, chunk_samples
         self.num_chunks = int(n_samples / chunk_samples)
@@ -110,37 +191,18 @@ class SongMixer:
             self.spec = torch.empty((self.n_proc, 1025, t), dtype=torch.complex64, device=dev)     # phase source
             self.masked = None                                                                       # set by every launch
             self.out = torch.empty((self.n_proc, chunk_samples), dtype=torch.float32, device=dev)
-            self.ws = None
         elif kind == 'stems':
             self.out = torch.empty((n_stems, channels, n_samples), dtype=out_dtype, device=dev)
-            self.ws = None
         elif kind == 'loudness':
             self.meter = loudness.Meter(sr)
             self.out = torch.empty(n_stems, dtype=torch.float64, device=dev)                       # LUFS of every mixed stem
-            self.ws = None
         else:
-            if encode is None or normalize not in ('loudness', 'true_peak'):      # (the encoder reads the float64 sum and scales it itself)
-                self.out = torch.empty((channels, n_samples), dtype=out_dtype, device=dev)
+            self.chain = MasterChain(channels, n_samples, dev, self.normalize, out_dtype, sr, target_lufs, self.ceiling, encode,
+                                     dither_seed)
             if encode is not None:
-                self.enc = torch.empty(n_samples * channels * ops.PCM_FORMATS[encode][1], dtype=torch.uint8, device=dev)
-                self.clip = torch.empty(channels, dtype=torch.int64, device=dev)
-            if normalize == 'loudness':
-                # evaluation.py:59-66: the float64 stem sum is measured and scaled; only the result takes out_dtype
-                self.meter = loudness.Meter(sr)
-                self.mix = torch.empty((channels, n_samples), dtype=torch.float64, device=dev)
-                self.target = torch.full((1,), float(target_lufs), dtype=torch.float64, device=dev)
-                self.lufs = torch.empty(1, dtype=torch.float64, device=dev)
-                self.master_gain = torch.empty(1, dtype=torch.float64, device=dev)
-            if normalize == 'true_peak':
-                self.mix = torch.empty((channels, n_samples), dtype=torch.float64, device=dev)
-                self.master_gain = torch.empty(1, dtype=torch.float64, device=dev)
-            if self.ceiling is not None:
-                # the gain before the clamp ('true_peak': none asked for, +inf), the true and sample peaks of the sum
-                self.free_gain = torch.full((1,), float('inf'), dtype=torch.float64, device=dev)
-                self.tp = torch.empty((1, channels), dtype=torch.float64, device=dev)
-                self.sp = torch.empty((1, channels), dtype=torch.float64, device=dev)
-            mix_dtype = torch.float64 if normalize in ('loudness', 'true_peak') else out_dtype
-            self.ws = torch.empty(ops._lib.lib().dam_mixdown_workspace_elems(channels), dtype=mix_dtype, device=dev)
+                self.enc, self.clip = self.chain.enc, self.chain.clip
+            if self.chain.out is not None:                     # (no float master is kept beside an encoded, gain-scaled one)
+                self.out = self.chain.out
         self.gains = torch.empty((2, n_stems, self.n_proc), dtype=torch.float64, device=dev)     # [raw amplitude, smoothed]
         self.graph = None
         self.use_graph = use_graph
@@ -169,32 +231,8 @@ class SongMixer:
             ops.gain_ramp_apply(self.pcm, smooth, out=self.out)
         elif self.kind == 'loudness':
             self.meter.integrated_loudness_batch(self.pcm.transpose(1, 2), gains=smooth, out=self.out)
-        elif self.ceiling is not None:
-            ops.mixdown_peak_normalize(self.pcm, smooth, normalize=False, out=self.mix, workspace=self.ws)
-            if self.normalize == 'loudness':
-                self.meter.integrated_loudness_batch(self.mix.t().unsqueeze(0), out=self.lufs)
-                loudness.target_gains_device(self.lufs, self.target, out=self.free_gain)
-            self.master_gain.copy_(self.free_gain)
-            ops.true_peak_batch(self.mix.t().unsqueeze(0), out=self.tp, sample_peak_out=self.sp)
-            ops.peak_limit_gains(self.master_gain, self.tp, self.ceiling)          # the maximum over the channels
-            if self.encode is None:
-                ops.gain_ramp_apply(self.mix, self.master_gain, out=self.out)
-            else:
-                ops.pcm_encode(self.mix, self.encode, scale=self.master_gain, dither_seed=self.dither_seed, out=self.enc,
-                               clip_count=self.clip)
-        elif self.normalize == 'loudness':
-            ops.mixdown_peak_normalize(self.pcm, smooth, normalize=False, out=self.mix, workspace=self.ws)
-            self.meter.integrated_loudness_batch(self.mix.t().unsqueeze(0), out=self.lufs)
-            loudness.target_gains_device(self.lufs, self.target, out=self.master_gain)
-            if self.encode is None:
-                ops.gain_ramp_apply(self.mix, self.master_gain, out=self.out)
-            else:                                  # mix * gain is rounded once to float64 either way: the same samples
-                ops.pcm_encode(self.mix, self.encode, scale=self.master_gain, dither_seed=self.dither_seed, out=self.enc,
-                               clip_count=self.clip)
         else:
-            ops.mixdown_peak_normalize(self.pcm, smooth, normalize=self.normalize, out=self.out, workspace=self.ws)
-            if self.encode is not None:
-                ops.pcm_encode(self.out, self.encode, dither_seed=self.dither_seed, out=self.enc, clip_count=self.clip)
+            self.chain.render(self.pcm, smooth)
 
     def _model_key(self):
         # the captured forward holds the FOLDED conv + BatchNorm images (layers.FoldedConvBn), computed when it was captured:
@@ -240,20 +278,11 @@ class SongMixer:
             return out.reshape(-1), pipe.download(self.masked)
         return out, self.gains.cpu().numpy()
 
-
     def peaks(self):
-        """The peak measurement of the last run of a mixer with a ceiling, from the device tensors the graph wrote:
-        {'true_peak_db': [per channel], 'sample_peak_db': [per channel]} of the master as rendered (the measured sum times
-        the gain that was applied, before any quantisation), 'limited': whether the ceiling, not the loudness target, set
-        that gain (always so for normalize='true_peak' unless the sum is silent), and 'gain', the gain itself."""
-        if self.ceiling is None:
+        """MasterChain.peaks() of the last run."""
+        if self.kind != 'master':
             raise ValueError('this mixer was built without ceiling_dbtp')
-        tp, sp = self.tp.cpu().numpy()[0], self.sp.cpu().numpy()[0]
-        gain, free = float(self.master_gain.cpu()[0]), float(self.free_gain.cpu()[0])
-        with np.errstate(divide='ignore', invalid='ignore'):
-            return {'true_peak_db': [float(v) for v in 20.0 * np.log10(tp * gain)],
-                    'sample_peak_db': [float(v) for v in 20.0 * np.log10(sp * gain)],
-                    'limited': bool(gain < free), 'gain': gain}
+        return self.chain.peaks()
 
 
 _mixers = {}
@@ -266,12 +295,11 @@ def _mixer(model, stems, loaded_tracks, chunk_length, sr, kind, normalize, out_d
         raise ValueError('loaded_tracks[track] must be [channels, n] arrays')
     ch, n = first.shape
     dt = torch.float32 if first.dtype == np.float32 else torch.float64
-    if isinstance(normalize, str) and normalize == 'true_peak':
-        target_lufs = None
-        ceiling_dbtp = -1.0 if ceiling_dbtp is None else ceiling_dbtp
-    elif not (isinstance(normalize, str) and normalize == 'loudness'):
-        normalize, target_lufs = bool(normalize), None
-    ceiling_dbtp = None if ceiling_dbtp is None else float(ceiling_dbtp)
+    if normalize not in ('loudness', 'true_peak'):
+        normalize = bool(normalize)            # the callers' ``if normalize:`` (inference.ipynb cells 9/11)
+    normalize, ceiling_dbtp = MasterChain.rules(normalize, ceiling_dbtp, encode)
+    if normalize != 'loudness':
+        target_lufs = None                     # (not part of such a mixer: one key whatever the caller passed)
     key = (id(model), len(stems), ch, n, dt, chunk_length * sr, kind, normalize, out_dtype, hop_length, sr, target_lufs,
            encode, dither_seed if encode is not None else None, ceiling_dbtp)
     m = _mixers.get(key)
@@ -285,13 +313,20 @@ def _mixer(model, stems, loaded_tracks, chunk_length, sr, kind, normalize, out_d
     return m, [np.asarray(loaded_tracks[t], dtype=np_dt) for t in stems]
 
 
-def mix_song_smooth(dataset, model, loaded_tracks: dict, chunk_length=1, sr=44100):
-    """Returns (mixed_tracks {track: ndarray[channels, n] float64}, raw_gains {track: [float]}, smooth_gains {track: list})."""
+def _mix_song(dataset, model, loaded_tracks, chunk_length, sr, kind, normalize, out_dtype, **kw):
+    """One song through the cached mixer of its geometry -> (mixer, stems, what ``run`` returned first,
+    raw_gains {track: [float]}, smooth_gains {track: list of numpy float64})."""
     stems = [t for t in dataset.get_tracklist() if t != 'mix']
-    m, arrays = _mixer(model, stems, loaded_tracks, chunk_length, sr, 'stems', False, torch.float64)
+    m, arrays = _mixer(model, stems, loaded_tracks, chunk_length, sr, kind, normalize, out_dtype, **kw)
     out, gains = m.run(arrays)
     raw_gains = {t: [float(v) for v in gains[0, i]] for i, t in enumerate(stems)}
-    smooth_gains = {t: list(gains[1, i]) for i, t in enumerate(stems)}
+    return m, stems, out, raw_gains, {t: list(gains[1, i]) for i, t in enumerate(stems)}
+
+
+def mix_song_smooth(dataset, model, loaded_tracks: dict, chunk_length=1, sr=44100):
+    """Returns (mixed_tracks {track: ndarray[channels, n] float64}, raw_gains {track: [float]}, smooth_gains {track: list})."""
+    _, stems, out, raw_gains, smooth_gains = _mix_song(dataset, model, loaded_tracks, chunk_length, sr, 'stems', False,
+                                                       torch.float64)
     return {t: out[i] for i, t in enumerate(stems)}, raw_gains, smooth_gains
 
 
@@ -299,12 +334,9 @@ def mix_song_loudness(dataset, model, loaded_tracks: dict, chunk_length=1, sr=44
     """The loudness of what mix_song_smooth would return, without producing it: the BS.1770 integrated loudness of every
     stem times its smoothed gain ramp (what evaluation.py:102-105 measures of the model's mix), the ramp applied inside
     the meter.  Returns (lufs {track: float}, raw_gains, smooth_gains)."""
-    stems = [t for t in dataset.get_tracklist() if t != 'mix']
-    m, arrays = _mixer(model, stems, loaded_tracks, chunk_length, sr, 'loudness', False, torch.float64)
-    lufs, gains = m.run(arrays)
-    raw_gains = {t: [float(v) for v in gains[0, i]] for i, t in enumerate(stems)}
-    return ({t: float(lufs[i]) for i, t in enumerate(stems)}, raw_gains,
-            {t: list(gains[1, i]) for i, t in enumerate(stems)})
+    _, stems, lufs, raw_gains, smooth_gains = _mix_song(dataset, model, loaded_tracks, chunk_length, sr, 'loudness', False,
+                                                        torch.float64)
+    return {t: float(lufs[i]) for i, t in enumerate(stems)}, raw_gains, smooth_gains
 
 
 def mix_song_to_master(dataset, model, loaded_tracks: dict, chunk_length=1, sr=44100, normalize=True, dtype=np.float64,
@@ -318,13 +350,10 @@ def mix_song_to_master(dataset, model, loaded_tracks: dict, chunk_length=1, sr=4
     static gain; SongMixer.peaks() of the cached mixer tells which).  ``normalize='true_peak'``: the plain sum scaled so
     that its true peak sits at ``ceiling_dbtp`` (default -1.0), one gain for all channels.
     Returns (mix ndarray[channels, n], raw_gains, smooth_gains)."""
-    stems = [t for t in dataset.get_tracklist() if t != 'mix']
     out_dt = torch.float32 if np.dtype(dtype) == np.float32 else torch.float64
-    m, arrays = _mixer(model, stems, loaded_tracks, chunk_length, sr, 'master', normalize, out_dt, target_lufs=target_lufs,
-                       ceiling_dbtp=ceiling_dbtp)
-    out, gains = m.run(arrays)
-    raw_gains = {t: [float(v) for v in gains[0, i]] for i, t in enumerate(stems)}
-    return out, raw_gains, {t: list(gains[1, i]) for i, t in enumerate(stems)}
+    _, _, out, raw_gains, smooth_gains = _mix_song(dataset, model, loaded_tracks, chunk_length, sr, 'master', normalize, out_dt,
+                                                   target_lufs=target_lufs, ceiling_dbtp=ceiling_dbtp)
+    return out, raw_gains, smooth_gains
 
 
 def mix_song_to_wav(dataset, model, loaded_tracks: dict, path, chunk_length=1, sr=44100, normalize=True, subtype='PCM_16',
@@ -337,13 +366,11 @@ def mix_song_to_wav(dataset, model, loaded_tracks: dict, path, chunk_length=1, s
     as there: with a ceiling below 0 dBTP the encoder has nothing to clip.
     Returns (clipped sample count, raw_gains, smooth_gains); warns (RuntimeWarning) when samples had to be clipped."""
     from .data.dataset_utils import write_wav_bytes
-    stems = [t for t in dataset.get_tracklist() if t != 'mix']
-    m, arrays = _mixer(model, stems, loaded_tracks, chunk_length, sr, 'master', normalize, torch.float64, target_lufs=target_lufs,
-                       encode=subtype, dither_seed=dither_seed, ceiling_dbtp=ceiling_dbtp)
-    (payload, clipped), gains = m.run(arrays)
+    m, _, (payload, clipped), raw_gains, smooth_gains = _mix_song(
+        dataset, model, loaded_tracks, chunk_length, sr, 'master', normalize, torch.float64, target_lufs=target_lufs,
+        encode=subtype, dither_seed=dither_seed, ceiling_dbtp=ceiling_dbtp)
     write_wav_bytes(path, payload, sr, m.channels, subtype, m.n, clipped)
-    raw_gains = {t: [float(v) for v in gains[0, i]] for i, t in enumerate(stems)}
-    return clipped, raw_gains, {t: list(gains[1, i]) for i, t in enumerate(stems)}
+    return clipped, raw_gains, smooth_gains
 
 
 def mix_song_spectral(dataset, model, loaded_tracks: dict, chunk_length=1, sr=44100, hop_length=1024, dtype=np.float32):

@@ -91,18 +91,12 @@ class Meter:
     def block_energies(self, data):
         x = _as_device_2d(data)
         n, ch = x.shape
-        T_g, step = self.block_size, 0.25                                # 75 % overlap
+        T_g = self.block_size
         if n < T_g * self.rate:
             raise ValueError('Audio must have length greater than the block size.')
-        T = n / self.rate
-        num_blocks = int(np.round(((T - T_g) / (T_g * step))) + 1)
-        j = np.arange(0, num_blocks)
-        # meter.py: l = int(T_g * (j * step) * rate), u = int(T_g * (j * step + 1) * rate) -- the same float64 operations
-        # in the same order, element-wise (int() and astype both truncate)
-        lo = (T_g * (j * step) * self.rate).astype(np.int64)
-        hi = (T_g * (j * step + 1) * self.rate).astype(np.int64)
         dev = x.device
-        lo_d, hi_d = torch.from_numpy(lo).to(dev), torch.from_numpy(hi).to(dev)
+        lo_d, hi_d = self._block_bounds(n, dev)
+        num_blocks = lo_d.numel()
         z = torch.empty((ch, num_blocks), dtype=torch.float64, device=dev)
         L = _lib.lib()
         ws = torch.empty(L.dam_loudness_workspace_bytes(n, ch), dtype=torch.uint8, device=dev)
@@ -125,13 +119,41 @@ class Meter:
         holds stable pointers."""
         key = (dev, n, self.rate, self.block_size)
         if key not in self._bounds:
-            T_g, step = self.block_size, 0.25
+            T_g, step = self.block_size, 0.25                                # 75 % overlap
             num_blocks = int(np.round(((n / self.rate - T_g) / (T_g * step))) + 1)
             j = np.arange(0, num_blocks)
-            lo = (T_g * (j * step) * self.rate).astype(np.int64)              # the same truncations as block_energies
+            # meter.py: l = int(T_g * (j * step) * rate), u = int(T_g * (j * step + 1) * rate) -- the same float64 operations
+            # in the same order, element-wise (int() and astype both truncate)
+            lo = (T_g * (j * step) * self.rate).astype(np.int64)
             hi = (T_g * (j * step + 1) * self.rate).astype(np.int64)
             self._bounds[key] = (torch.from_numpy(lo).to(dev), torch.from_numpy(hi).to(dev))
         return self._bounds[key]
+
+    def _energies_batch(self, data, gains, lo_d, hi_d, length, out=None):
+        """Sum of squares of the K-weighted ``data * gain ramp`` over the samples [lo_d[k], hi_d[k]) of every track and
+        channel, divided by ``length`` -> [N, channels, K] float64: the one call of dam_loudness_block_energy_batch.  data
+        is a CUDA [N, samples, channels] tensor here (the public methods have checked that much)."""
+        from . import ops
+        if data.dtype not in (torch.float32, torch.float64):
+            raise ValueError('Data must be floating point.')
+        N, n, ch = data.shape
+        if ch > 5:
+            raise ValueError('Audio must have five channels or less.')
+        dev = data.device
+        gains, n_gains = ops.gain_ramp_arg(gains, N, n)
+        K = lo_d.numel()
+        if out is None:
+            out = torch.empty((N, ch, K), dtype=torch.float64, device=dev)
+        elif tuple(out.shape) != (N, ch, K) or out.dtype != torch.float64 or not out.is_contiguous():
+            raise ValueError('bad out tensor')
+        L = _lib.lib()
+        ws = torch.empty(L.dam_loudness_batch_workspace_bytes(N, n, ch, K) // 8 + 1, dtype=torch.float64, device=dev)
+        with torch.cuda.device(dev):
+            _lib.check(L.dam_loudness_block_energy_batch(
+                _lib.ptr(data), 1 if data.dtype == torch.float64 else 0, N, n, ch, data.stride(0), data.stride(1),
+                data.stride(2), _lib.ptr(gains), n_gains, self._coef, _lib.ptr(lo_d), _lib.ptr(hi_d), K, float(length),
+                _lib.ptr(out), _lib.ptr(ws), _lib.stream()), 'dam_loudness_block_energy_batch')
+        return out
 
     def block_energies_batch(self, data, gains=None, out=None):
         """data: CUDA float32/float64 [N, samples, channels] with any strides (planar [N, channels, n] storage is passed
@@ -141,39 +163,12 @@ class Meter:
         if not torch.is_tensor(data):
             raise ValueError('Data must be of type torch.Tensor.')
         _lib.require_cuda(data, gains, out)
-        if data.dtype not in (torch.float32, torch.float64):
-            raise ValueError('Data must be floating point.')
         if data.dim() != 3:
             raise ValueError('Audio must be [tracks, samples, channels].')
-        N, n, ch = data.shape
-        if ch > 5:
-            raise ValueError('Audio must have five channels or less.')
-        if n < self.block_size * self.rate:
+        if data.shape[1] < self.block_size * self.rate:
             raise ValueError('Audio must have length greater than the block size.')
-        dev = data.device
-        n_gains = 0
-        if gains is not None:
-            if gains.dtype != torch.float64:
-                raise TypeError('gains must be float64')
-            gains = gains.reshape(N, -1).contiguous()
-            n_gains = gains.shape[1]
-            if not 1 <= n_gains <= n:
-                raise ValueError('between one gain and one gain per sample expected')
-        lo_d, hi_d = self._block_bounds(n, dev)
-        num_blocks = lo_d.numel()
-        if out is None:
-            out = torch.empty((N, ch, num_blocks), dtype=torch.float64, device=dev)
-        elif tuple(out.shape) != (N, ch, num_blocks) or out.dtype != torch.float64 or not out.is_contiguous():
-            raise ValueError('bad out tensor')
-        L = _lib.lib()
-        ws = torch.empty(L.dam_loudness_batch_workspace_bytes(N, n, ch, num_blocks) // 8 + 1, dtype=torch.float64, device=dev)
-        with torch.cuda.device(dev):
-            _lib.check(L.dam_loudness_block_energy_batch(
-                _lib.ptr(data), 1 if data.dtype == torch.float64 else 0, N, n, ch, data.stride(0), data.stride(1),
-                data.stride(2), _lib.ptr(gains), n_gains, self._coef, _lib.ptr(lo_d), _lib.ptr(hi_d), num_blocks,
-                float(self.block_size * self.rate), _lib.ptr(out), _lib.ptr(ws), _lib.stream()),
-                'dam_loudness_block_energy_batch')
-        return out
+        lo_d, hi_d = self._block_bounds(data.shape[1], data.device)
+        return self._energies_batch(data, gains, lo_d, hi_d, self.block_size * self.rate, out)
 
     def integrated_loudness_batch(self, data, gains=None, out=None):
         """Integrated loudness of every track of ``data`` (see block_energies_batch) -> CUDA float64 [N]; a track the gates
@@ -198,35 +193,12 @@ class Meter:
             raise ValueError('Data must be of type torch.Tensor.')
         if not data.is_cuda or (gains is not None and not gains.is_cuda):
             raise ValueError('Data and gains must be CUDA tensors: the meter runs on the GPU only, there is no CPU fallback.')
-        if data.dtype not in (torch.float32, torch.float64):
-            raise ValueError('Data must be floating point.')
         if data.dim() != 3:
             raise ValueError('Audio must be [tracks, samples, channels].')
-        N, n, ch = data.shape
-        if ch > 5:
-            raise ValueError('Audio must have five channels or less.')
-        dev = data.device
-        lo_d, hi_d, h = self._hop_bounds(n, dev)
-        H = lo_d.numel()
-        if H < 1:
+        lo_d, hi_d, h = self._hop_bounds(data.shape[1], data.device)
+        if lo_d.numel() < 1:
             raise ValueError('Audio must have length greater than one 100 ms hop.')
-        n_gains = 0
-        if gains is not None:
-            if gains.dtype != torch.float64:
-                raise TypeError('gains must be float64')
-            gains = gains.reshape(N, -1).contiguous()
-            n_gains = gains.shape[1]
-            if not 1 <= n_gains <= n:
-                raise ValueError('between one gain and one gain per sample expected')
-        out = torch.empty((N, ch, H), dtype=torch.float64, device=dev)
-        L = _lib.lib()
-        ws = torch.empty(L.dam_loudness_batch_workspace_bytes(N, n, ch, H) // 8 + 1, dtype=torch.float64, device=dev)
-        with torch.cuda.device(dev):
-            _lib.check(L.dam_loudness_block_energy_batch(
-                _lib.ptr(data), 1 if data.dtype == torch.float64 else 0, N, n, ch, data.stride(0), data.stride(1),
-                data.stride(2), _lib.ptr(gains), n_gains, self._coef, _lib.ptr(lo_d), _lib.ptr(hi_d), H, float(h),
-                _lib.ptr(out), _lib.ptr(ws), _lib.stream()), 'dam_loudness_block_energy_batch')
-        return out
+        return self._energies_batch(data, gains, lo_d, hi_d, h)
 
     def _curves(self, data, gains, hops, what):
         e = self.hop_energies_batch(data, gains)
@@ -239,16 +211,20 @@ class Meter:
         [N, H - 3] LUFS; silence reads -inf.  The window is R128's whatever ``block_size`` this Meter was built with."""
         return window_loudness_device(self._curves(data, gains, 4, 'momentary'), 4)[1]
 
+    def short_term_batch(self, data, gains=None, want_lufs=True):
+        """The short-term windows (EBU R128: 3 s, one per 100 ms hop) of every track -> (power, LUFS or None), CUDA
+        float64 [N, H - 29] each: what curve_stats_device and profile_error_device take."""
+        return window_loudness_device(self._curves(data, gains, 30, 'short-term'), 30, want_lufs)
+
     def short_term_loudness_batch(self, data, gains=None):
         """Short-term loudness (EBU R128: 3 s window, one value per 100 ms hop) of every track -> CUDA float64
         [N, H - 29] LUFS; silence reads -inf.  The window is R128's whatever ``block_size`` this Meter was built with."""
-        return window_loudness_device(self._curves(data, gains, 30, 'short-term'), 30)[1]
+        return self.short_term_batch(data, gains)[1]
 
     def loudness_range_batch(self, data, gains=None):
         """Loudness range (EBU Tech 3342: the 10th to 95th percentile of the short-term loudness gated at -70 LUFS and at
         -20 LU under the gated mean) of every track -> CUDA float64 [N] LU; a track the gates empty reads 0."""
-        power = window_loudness_device(self._curves(data, gains, 30, 'short-term'), 30, want_lufs=False)[0]
-        return curve_stats_device(power)[:, 0]
+        return curve_stats_device(self.short_term_batch(data, gains, want_lufs=False)[0])[:, 0]
 
     def loudness_dynamics_batch(self, data, gains=None):
         """Every time-resolved reading from one pass of the filter: {'momentary' [N, H - 3], 'short_term' [N, H - 29]

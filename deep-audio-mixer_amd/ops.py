@@ -689,6 +689,19 @@ def _audio_kind(t, what):
     return 1 if t.dtype == torch.float64 else 0
 
 
+def gain_ramp_arg(gains, N, n):
+    """The optional gain ramps of N tracks of n samples as the batched meters take them: None, or CUDA float64
+    [N, n_gains] (or [N]) -> (contiguous [N, n_gains] or None, n_gains or 0)."""
+    if gains is None:
+        return None, 0
+    if gains.dtype != torch.float64:
+        raise TypeError('gains must be float64')
+    gains = gains.reshape(N, -1).contiguous()
+    if not 1 <= gains.shape[1] <= n:
+        raise ValueError('between one gain and one gain per sample expected')
+    return gains, gains.shape[1]
+
+
 def gains_smooth(raw_db, window, polyorder=2, out=None, want_f32=False):
     """raw_db: CUDA float32 [n_chunks, S] (model outputs) -> out [2, S, n_chunks] float64 = (10 ** (0.5 * g),
     scipy.signal.savgol_filter(that, window, polyorder) in its default mode 'interp'), computed on the device.
@@ -826,14 +839,7 @@ def true_peak_batch(data, gains=None, out=None, sample_peak_out=None):
     if N < 1 or n < 1 or ch < 1 or N * ch > 65535:
         raise ValueError('true_peak_batch: at least one track, sample and channel and at most 65535 rows expected, got %s'
                          % (tuple(data.shape),))
-    n_gains = 0
-    if gains is not None:
-        if gains.dtype != torch.float64:
-            raise TypeError('gains must be float64')
-        gains = gains.reshape(N, -1).contiguous()
-        n_gains = gains.shape[1]
-        if not 1 <= n_gains <= n:
-            raise ValueError('between one gain and one gain per sample expected')
+    gains, n_gains = gain_ramp_arg(gains, N, n)
     dev = data.device
     if out is None:
         out = torch.empty((N, ch), dtype=torch.float64, device=dev)

@@ -6,7 +6,8 @@ model or song fixture, its make_audio supplies the impulse the click stems are b
 Bounds: "at the ceiling" is asserted with tests/_truepeak_ref.py on the returned float64 master to 1e-12 relative -- the
 device peak agrees with the definition to 1e-13 of max|x| (tests/test_truepeak_gpu.py), the gain is one division and the
 master one rounding per sample, each ~1e-16.  One gain for all channels: the ratio of two float64 values, 1e-15.
-Everything else here is bitwise.  Largest observed errors: NOT YET RECORDED -- no GPU could be obtained while this file was
+Everything else here is bitwise, the song's WAV against the evaluator's export of the same PCM and gains included (both run
+inference_utils.MasterChain).  Largest observed errors: NOT YET RECORDED -- no GPU could be obtained while this file was
 written; each test prints its figures before asserting."""
 import os
 import warnings
@@ -204,3 +205,53 @@ def test_evaluator_export_under_the_ceiling(env, tmp_path):
             # the sample peak is under the true peak: no code beyond the ceiling (+ half an LSB of rounding)
             assert max(largest.values()) <= int(np.ceil(10.0 ** (-1.0 / 20.0) * 32768.0))
     assert stats[None] == stats[-1.0]
+
+
+@pytest.mark.parametrize('ceiling', [None, -1.0])
+def test_song_wav_and_evaluator_export_are_one_chain(env, tmp_path, ceiling):
+    """mix_song_to_wav (the chain inside the song's graph) and LoudnessEvaluator.write_sum_to_target (the chain run
+    eagerly) on the same resident PCM and the same smoothed gains: the same deterministic launches, so the same file."""
+    from deep_audio_mixer_amd import inference_utils
+    from deep_audio_mixer_amd.evaluation import LoudnessEvaluator
+    model, d, click = env[0], env[1], env[4]
+    song, export = tmp_path / 'song.wav', tmp_path / 'export.wav'
+    with warnings.catch_warnings():
+        warnings.simplefilter('ignore', RuntimeWarning)                  # without the ceiling this song clips
+        clipped = inference_utils.mix_song_to_wav(d, model, click, str(song), chunk_length=CHUNK_LENGTH, sr=SR,
+                                                  normalize='loudness', subtype='PCM_16', ceiling_dbtp=ceiling)[0]
+        m = next(iter(inference_utils._mixers.values()))
+        exported = LoudnessEvaluator(SR, KEYS).write_sum_to_target(m.pcm, m.gains[1], str(export), target_lufs=-20.0,
+                                                                   subtype='PCM_16', ceiling_dbtp=ceiling)
+    a, b = song.read_bytes(), export.read_bytes()
+    print('ceiling %s: clipped %d (song) / %d (export); %d of %d file bytes differ'
+          % (ceiling, clipped, exported, sum(x != y for x, y in zip(a, b)) + abs(len(a) - len(b)), len(a)))
+    assert m.graph is not None and a == b and clipped == exported
+
+
+# What SongMixer(kind='master') did with (normalize, ceiling_dbtp) before MasterChain existed: the ceiling it ended up
+# with, or ValueError.  An encode outside ops.PCM_FORMATS ('PCM_8') raised whatever the other two were.
+MASTER_RULES = {(True, None): None, (True, -1.0): ValueError, (False, None): None, (False, -1.0): ValueError,
+                ('loudness', None): None, ('loudness', -1.0): -1.0, ('true_peak', None): -1.0, ('true_peak', -1.0): -1.0}
+
+
+@pytest.mark.parametrize('encode', [None, 'PCM_16', 'PCM_8'])
+@pytest.mark.parametrize('normalize,ceiling', sorted(MASTER_RULES, key=str))
+def test_master_rules_live_in_one_place(env, normalize, ceiling, encode):
+    from deep_audio_mixer_amd.inference_utils import MasterChain, SongMixer
+    model = env[0]
+    want = ValueError if encode == 'PCM_8' else MASTER_RULES[normalize, ceiling]
+
+    def chain():
+        return MasterChain(2, 64, torch.device('cuda'), normalize=normalize, out_dtype=torch.float64, sr=SR, target_lufs=-20.0,
+                           ceiling_dbtp=ceiling, encode=encode, dither_seed=None)
+
+    def mixer():
+        return SongMixer(model, 4, 2, N, torch.float32, CHUNK_LENGTH * SR, 'master', normalize, sr=SR, encode=encode,
+                         ceiling_dbtp=ceiling)
+
+    if want is ValueError:
+        for build in (chain, mixer):
+            with pytest.raises(ValueError):
+                build()
+    else:
+        assert chain().ceiling == want and mixer().ceiling == want
