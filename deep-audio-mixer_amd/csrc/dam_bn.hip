@@ -15,7 +15,7 @@
 //     both BasicBlock shortcuts (identity, or the shortcut conv's own BatchNorm folded in);
 //   * backward: one reduction pass (sum dz, sum dz*xhat; dz = dy * (y > 0)) and one apply pass
 //     dx = c1*dz + c2*x + c3 with per-channel constants.
-#include <cstdlib>
+#include <type_traits>
 #include "dam_common.h"
 
 namespace dam {
@@ -46,6 +46,59 @@ inline BnLaunch bn_plan(int64_t P, int C, int max_parts = BN_MAX_PARTS) {
     l.ppb = cdiv(P, parts);
     l.parts = (int)cdiv(P, l.ppb);
     return l;
+}
+
+// The tail of every record producer: thread (cq, pr) holds NV values for each of its 4 channels; they go to LDS [R][C][NV], a
+// tree merges the R pixel rows (all threads active; fixed order -> deterministic) and row 0 stores the workgroup's record
+// [C][NV] (store_sc1: dam_common.h).  Merge::step(a, b) folds record b into record a.
+struct RecAdd {
+    template <int NV>
+    static __device__ __forceinline__ void step(float* a, const float* b) {
+#pragma unroll
+        for (int k = 0; k < NV; ++k) a[k] += b[k];
+    }
+};
+struct RecChan {        // (n, mean, M2) records
+    template <int NV>
+    static __device__ __forceinline__ void step(float* a, const float* b) {
+        static_assert(NV == 3, "(n, mean, M2)");
+        const float na = a[0], nb = b[0];
+        if (nb != 0.f) {
+            const float nn = na + nb, d = b[1] - a[1];
+            a[1] += d * (nb / nn);
+            a[2] += b[2] + d * d * (na * nb / nn);
+            a[0] = nn;
+        }
+    }
+};
+template <int NV, typename Merge>
+__device__ __forceinline__ void record_tail(float* sm, const float (&v)[NV][4], int C, int cq, int pr, int R,
+                                            float* __restrict__ record /* this workgroup's [C][NV] */) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        float* o = sm + ((size_t)pr * C + cq * 4 + i) * NV;
+#pragma unroll
+        for (int k = 0; k < NV; ++k) o[k] = v[k][i];
+    }
+    __syncthreads();
+    int span = 1;
+    while (span < R) span <<= 1;
+    for (int stride = span >> 1; stride >= 1; stride >>= 1) {
+        if (pr < stride && pr + stride < R) {
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+                Merge::template step<NV>(sm + ((size_t)pr * C + cq * 4 + i) * NV, sm + ((size_t)(pr + stride) * C + cq * 4 + i) * NV);
+        }
+        __syncthreads();
+    }
+    if (pr == 0) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int c = cq * 4 + i;
+#pragma unroll
+            for (int k = 0; k < NV; ++k) store_sc1(record + (size_t)c * NV + k, sm[(size_t)c * NV + k]);
+        }
+    }
 }
 
 // gridDim.y == 2: a second tensor of the same shape (x2 -> partial2) in the same launch (dam_bn_stats_pair_f32).
@@ -81,44 +134,15 @@ __global__ void bn_stats_partial_kernel(const float* __restrict__ x, int64_t P, 
             }
         }
     }
+    float v[3][4];
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
-        float* o = sm + ((size_t)pr * C + cq * 4 + i) * 3;
         const float md = n ? s1[i] / n : 0.f;
-        o[0] = (float)n;
-        o[1] = k[i] + md;
-        o[2] = n ? fmaxf(s2[i] - s1[i] * md, 0.f) : 0.f;
+        v[0][i] = (float)n;
+        v[1][i] = k[i] + md;
+        v[2][i] = n ? fmaxf(s2[i] - s1[i] * md, 0.f) : 0.f;
     }
-    __syncthreads();
-    // tree merge over the R pixel rows (Chan), all threads active; fixed order -> deterministic
-    int span = 1;
-    while (span < R) span <<= 1;
-    for (int stride = span >> 1; stride >= 1; stride >>= 1) {
-        if (pr < stride && pr + stride < R) {
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                float* a = sm + ((size_t)pr * C + cq * 4 + i) * 3;
-                const float* b = sm + ((size_t)(pr + stride) * C + cq * 4 + i) * 3;
-                const float na = a[0], nb = b[0];
-                if (nb != 0.f) {
-                    const float nn = na + nb, d = b[1] - a[1];
-                    a[1] += d * (nb / nn);
-                    a[2] += b[2] + d * d * (na * nb / nn);
-                    a[0] = nn;
-                }
-            }
-        }
-        __syncthreads();
-    }
-    if (pr == 0) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int c = cq * 4 + i;
-            const float* a = sm + (size_t)c * 3;
-            float* out = partial + ((size_t)blockIdx.x * C + c) * 3;
-            store_sc1(out, a[0]); store_sc1(out + 1, a[1]); store_sc1(out + 2, a[2]);
-        }
-    }
+    record_tail<3, RecChan>(sm, v, C, cq, pr, R, partial + (size_t)blockIdx.x * C * 3);
 }
 
 // One wave per channel: lanes merge a strided subset of the partials (Chan), then a shuffle tree merges the lanes.
@@ -227,85 +251,124 @@ __global__ void bn_apply_kernel(const float* __restrict__ x, int64_t nquads, int
     }
 }
 
-// partial[blk][c] = (sum dz, sum dz*xhat)
 __device__ __forceinline__ float4 sign_quad(unsigned b) {       // sign byte -> (1 or 0) x 4
     return make_float4((float)(b & 1u), (float)((b >> 1) & 1u), (float)((b >> 2) & 1u), (float)((b >> 3) & 1u));
 }
 
+// ---- backward.  One family for NB = 1 BatchNorm, or NB = 2 that share dy and the ReLU mask (a residual block's bn2 and its
+// shortcut BatchNorm, both fed by the block's output gradient): dy and the mask are read once per pass instead of twice, two
+// launches instead of four.  Same sums in the same order for either NB: the pair is bitwise two single calls.
+struct BnBwdSide {            // one BatchNorm of a backward launch (device pointers)
+    const float* x;
+    const float* gamma;
+    const float* mean;
+    const float* invstd;
+    float* dx;
+    float* dgamma;
+    float* dbeta;
+};
+template <int NB>
+struct BnBwdSides { BnBwdSide s[NB]; };
+
+// partial[blk][c] = (sum dz, sum dz*xhat of every side)
 // MASK: 3 = from the sign bytes written by bn_apply (one byte per channel quad: y_mask then points at bytes);
 // MASK: 0 none, 1 from y_mask (saved output), 2 recomputed as fma(x, mscale, mshift) > 0 -- the forward's own expression, so
-// the bits agree and the saved activation is not read at all
-template <int MASK>
-__global__ void bn_bwd_partial_kernel(const float* __restrict__ dy, const float* __restrict__ y_mask,
-                                      const float* __restrict__ x, int64_t P, int C, int Q, int R, int64_t ppb,
-                                      const float* __restrict__ mean, const float* __restrict__ invstd,
-                                      const float* __restrict__ mscale, const float* __restrict__ mshift,
-                                      float* __restrict__ partial /* [parts][C][2] */) {
-    extern __shared__ __attribute__((aligned(16))) float sm[];    // [R][C][2]
+// the bits agree and the saved activation is not read at all (NB = 1 only: the pair's mask is the block output's, 1 or 3)
+template <int MASK, int NB>
+__global__ void bn_bwd_partial_kernel(const float* __restrict__ dy, const float* __restrict__ y_mask, const BnBwdSides<NB> sd,
+                                      int64_t P, int C, int Q, int R, int64_t ppb, const float* __restrict__ mscale,
+                                      const float* __restrict__ mshift, float* __restrict__ partial /* [parts][C][1 + NB] */) {
+    extern __shared__ __attribute__((aligned(16))) float sm[];    // [R][C][1 + NB]
     const int cq = threadIdx.x % Q, pr = threadIdx.x / Q;
     const int64_t lo = blockIdx.x * ppb, hi = (lo + ppb < P) ? lo + ppb : P;
-    const float4 mu = reinterpret_cast<const float4*>(mean)[cq], is = reinterpret_cast<const float4*>(invstd)[cq];
+    float4 mu[NB], is[NB];
+#pragma unroll
+    for (int s = 0; s < NB; ++s) {
+        mu[s] = reinterpret_cast<const float4*>(sd.s[s].mean)[cq];
+        is[s] = reinterpret_cast<const float4*>(sd.s[s].invstd)[cq];
+    }
     float4 msc = make_float4(0.f, 0.f, 0.f, 0.f), msh = msc;
     if (MASK == 2) { msc = reinterpret_cast<const float4*>(mscale)[cq]; msh = reinterpret_cast<const float4*>(mshift)[cq]; }
-    float a[4] = {0, 0, 0, 0}, b[4] = {0, 0, 0, 0};
-    constexpr int U = 4;      // 3 streams x 4 loads in flight per thread
+    float acc[1 + NB][4] = {};      // [0]: sum dz, [1 + s]: sum dz * xhat of side s
+    // 12 loads in flight per thread: 3 streams x 4 pieces for one BatchNorm, 4 x 3 for a pair.  With 4 x 4 the pair needs more than
+    // the 128 registers a kernel without launch bounds gets, and every form of it spilled addresses inside this loop (a reload
+    // waits for all the loads requested before it): 17 - 18 us per launch of the C3 step against 14.4 us for this one
+    // (profiles/r06_bn_pair_kernel_variants.txt).  A thread adds its pixels in the same order for any U.
+    constexpr int U = NB == 1 ? 4 : 3;
     for (int64_t p = lo + pr; p < hi; p += (int64_t)R * U) {
-        float4 gv[U], mv[U], xv[U];
+        float4 gv[U], mv[U], xv[NB][U];
 #pragma unroll
         for (int u = 0; u < U; ++u) {
             const int64_t q = p + (int64_t)u * R;
             const bool ok = q < hi;
             const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
-            gv[u] = ok ? *reinterpret_cast<const float4*>(dy + q * C + cq * 4) : z;
-            xv[u] = ok ? *reinterpret_cast<const float4*>(x + q * C + cq * 4) : z;
-            mv[u] = (ok && MASK == 1) ? *reinterpret_cast<const float4*>(y_mask + q * C + cq * 4) : make_float4(1.f, 1.f, 1.f, 1.f);
+            // `if (ok)` around the loads, not `ok ? *p : z` per stream: the compiler turns that form into a select between p
+            // and a copy of z in scratch (32 bytes per lane for one BatchNorm, 80 - 96 for two, and 87 registers without a mask:
+            // five waves per SIMD where this form has six; profiles/r06_dam_bn_resource_usage_*.txt)
+            gv[u] = z; mv[u] = make_float4(1.f, 1.f, 1.f, 1.f);
+#pragma unroll
+            for (int s = 0; s < NB; ++s) xv[s][u] = z;
+            if (ok) {
+                gv[u] = *reinterpret_cast<const float4*>(dy + q * C + cq * 4);
+#pragma unroll
+                for (int s = 0; s < NB; ++s) xv[s][u] = *reinterpret_cast<const float4*>(sd.s[s].x + q * C + cq * 4);
+                if (MASK == 1) mv[u] = *reinterpret_cast<const float4*>(y_mask + q * C + cq * 4);
+            }
             if (MASK == 3) mv[u] = sign_quad(ok ? reinterpret_cast<const unsigned char*>(y_mask)[q * Q + cq] : 0);
         }
 #pragma unroll
         for (int u = 0; u < U; ++u) {
             float4 g = gv[u];
-            const float4 v = xv[u];
             float4 m = mv[u];
-            if (MASK == 2) m = make_float4(fmaf(v.x, msc.x, msh.x), fmaf(v.y, msc.y, msh.y), fmaf(v.z, msc.z, msh.z), fmaf(v.w, msc.w, msh.w));
+            if (MASK == 2) {
+                const float4 v = xv[0][u];
+                m = make_float4(fmaf(v.x, msc.x, msh.x), fmaf(v.y, msc.y, msh.y), fmaf(v.z, msc.z, msh.z), fmaf(v.w, msc.w, msh.w));
+            }
             g.x = m.x > 0.f ? g.x : 0.f; g.y = m.y > 0.f ? g.y : 0.f; g.z = m.z > 0.f ? g.z : 0.f; g.w = m.w > 0.f ? g.w : 0.f;
-            a[0] += g.x; a[1] += g.y; a[2] += g.z; a[3] += g.w;
-            b[0] = fmaf(g.x, (v.x - mu.x) * is.x, b[0]); b[1] = fmaf(g.y, (v.y - mu.y) * is.y, b[1]);
-            b[2] = fmaf(g.z, (v.z - mu.z) * is.z, b[2]); b[3] = fmaf(g.w, (v.w - mu.w) * is.w, b[3]);
-        }
-    }
+            acc[0][0] += g.x; acc[0][1] += g.y; acc[0][2] += g.z; acc[0][3] += g.w;
 #pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        float* o = sm + ((size_t)pr * C + cq * 4 + i) * 2;
-        o[0] = a[i]; o[1] = b[i];
-    }
-    __syncthreads();
-    int span = 1;
-    while (span < R) span <<= 1;
-    for (int stride = span >> 1; stride >= 1; stride >>= 1) {
-        if (pr < stride && pr + stride < R) {
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                float* a2 = sm + ((size_t)pr * C + cq * 4 + i) * 2;
-                const float* b2 = sm + ((size_t)(pr + stride) * C + cq * 4 + i) * 2;
-                a2[0] += b2[0]; a2[1] += b2[1];
+            for (int s = 0; s < NB; ++s) {
+                const float4 v = xv[s][u];
+                float* b = acc[1 + s];
+                b[0] = fmaf(g.x, (v.x - mu[s].x) * is[s].x, b[0]); b[1] = fmaf(g.y, (v.y - mu[s].y) * is[s].y, b[1]);
+                b[2] = fmaf(g.z, (v.z - mu[s].z) * is[s].z, b[2]); b[3] = fmaf(g.w, (v.w - mu[s].w) * is[s].w, b[3]);
             }
         }
-        __syncthreads();
     }
-    if (pr == 0) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int c = cq * 4 + i;
-            store_sc1(partial + ((size_t)blockIdx.x * C + c) * 2, sm[(size_t)c * 2]);
-            store_sc1(partial + ((size_t)blockIdx.x * C + c) * 2 + 1, sm[(size_t)c * 2 + 1]);
-        }
-    }
+    record_tail<1 + NB, RecAdd>(sm, acc, C, cq, pr, R, partial + (size_t)blockIdx.x * C * (1 + NB));
 }
 
 __device__ __forceinline__ double wave_sum64_f64(double v) {
 #pragma unroll
     for (int off = 32; off >= 1; off >>= 1) v += __shfl_down(v, off);
     return v;
+}
+
+// One wave per channel sums NV record columns [parts][C][NV] in double: lane 0 ends up with the totals in s[].  Every lane
+// requests ALL its records (<= 16: parts <= 1024) before the first add (see bn_stats_finalize_kernel).
+template <int NV>
+__device__ __forceinline__ void wave_record_sums(const float* __restrict__ partial, int parts, int C, int c, double (&s)[NV]) {
+    const int lane = threadIdx.x;
+    constexpr int U = 16;
+    float r[U][NV];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+        const int p = lane + 64 * u;
+        const float* o = partial + ((size_t)(p < parts ? p : 0) * C + c) * NV;
+#pragma unroll
+        for (int k = 0; k < NV; ++k) r[u][k] = p < parts ? o[k] : 0.f;
+    }
+#pragma unroll
+    for (int k = 0; k < NV; ++k) s[k] = 0;
+#pragma unroll
+    for (int u = 0; u < U; ++u)
+#pragma unroll
+        for (int k = 0; k < NV; ++k) s[k] += (double)r[u][k];
+    for (int p = lane + 64 * U; p < parts; p += 64)        // more than 1024 records: not produced by this library
+#pragma unroll
+        for (int k = 0; k < NV; ++k) s[k] += partial[((size_t)p * C + c) * NV + k];
+#pragma unroll
+    for (int k = 0; k < NV; ++k) s[k] = wave_sum64_f64(s[k]);
 }
 
 // One wave per channel.
@@ -315,23 +378,10 @@ __global__ __launch_bounds__(64) void bn_bwd_finalize_kernel(const float* __rest
                                        float* __restrict__ dbeta, float* __restrict__ coef /* [3][C] */) {
     const int c = blockIdx.x, lane = threadIdx.x;
     const float gam_c = gamma[c], inv_c = invstd[c], mean_c = mean[c];      // (requested with the records, see bn_stats_finalize_kernel)
-    double s1 = 0, s2 = 0;
-    {   // all loads of the lane in flight before the first add (see bn_stats_finalize_kernel)
-        constexpr int U = 16;
-        float ra[U], rb[U];
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const int p = lane + 64 * u;
-            const float* o = partial + ((size_t)(p < parts ? p : 0) * C + c) * 2;
-            ra[u] = p < parts ? o[0] : 0.f; rb[u] = p < parts ? o[1] : 0.f;
-        }
-#pragma unroll
-        for (int u = 0; u < U; ++u) { s1 += (double)ra[u]; s2 += (double)rb[u]; }
-        for (int p = lane + 64 * U; p < parts; p += 64) { s1 += partial[((size_t)p * C + c) * 2]; s2 += partial[((size_t)p * C + c) * 2 + 1]; }
-    }
-    s1 = wave_sum64_f64(s1);
-    s2 = wave_sum64_f64(s2);
+    double s[2];
+    wave_record_sums<2>(partial, parts, C, c, s);
     if (lane != 0) return;
+    const double s1 = s[0], s2 = s[1];
     dbeta[c] = (float)s1;
     dgamma[c] = (float)s2;
     const double g = (double)gam_c * inv_c;
@@ -373,151 +423,13 @@ __global__ void bn_bwd_apply_kernel(const float* __restrict__ dy, const float* _
     }
 }
 
-// ---- two BatchNorms that share dy and the ReLU mask (a residual block's bn2 and its shortcut BatchNorm, both fed by the
-// block's output gradient): one partial / finalize / apply launch for both -- dy and the mask are read once per pass
-// instead of twice, three launches instead of six.  Same sums in the same order as the single form: bitwise the same result.
-template <bool BITS>        // y_mask points at the sign bytes of bn_apply instead of the float output
-__global__ void bn_bwd_partial_pair_kernel(const float* __restrict__ dy, const float* __restrict__ y_mask,
-                                           const float* __restrict__ xa, const float* __restrict__ xb, int64_t P, int C, int Q,
-                                           int R, int64_t ppb, const float* __restrict__ mean_a, const float* __restrict__ invstd_a,
-                                           const float* __restrict__ mean_b, const float* __restrict__ invstd_b,
-                                           float* __restrict__ partial /* [parts][C][3]: sum dz, sum dz*xhat_a, sum dz*xhat_b */) {
-    extern __shared__ __attribute__((aligned(16))) float sm[];    // [R][C][3]
-    const int cq = threadIdx.x % Q, pr = threadIdx.x / Q;
-    const int64_t lo = blockIdx.x * ppb, hi = (lo + ppb < P) ? lo + ppb : P;
-    const float4 mua = reinterpret_cast<const float4*>(mean_a)[cq], isa = reinterpret_cast<const float4*>(invstd_a)[cq];
-    const float4 mub = reinterpret_cast<const float4*>(mean_b)[cq], isb = reinterpret_cast<const float4*>(invstd_b)[cq];
-    float a[4] = {0, 0, 0, 0}, ba[4] = {0, 0, 0, 0}, bb[4] = {0, 0, 0, 0};
-    constexpr int U = 4;
-    for (int64_t p = lo + pr; p < hi; p += (int64_t)R * U) {
-        float4 gv[U], mv[U], va[U], vb[U];
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const int64_t q = p + (int64_t)u * R;
-            const bool ok = q < hi;
-            const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
-            gv[u] = ok ? *reinterpret_cast<const float4*>(dy + q * C + cq * 4) : z;
-            va[u] = ok ? *reinterpret_cast<const float4*>(xa + q * C + cq * 4) : z;
-            vb[u] = ok ? *reinterpret_cast<const float4*>(xb + q * C + cq * 4) : z;
-            if (BITS) mv[u] = sign_quad(ok ? reinterpret_cast<const unsigned char*>(y_mask)[q * Q + cq] : 0);
-            else mv[u] = ok ? *reinterpret_cast<const float4*>(y_mask + q * C + cq * 4) : z;
-        }
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            float4 g = gv[u];
-            const float4 m = mv[u], v = va[u], w = vb[u];
-            g.x = m.x > 0.f ? g.x : 0.f; g.y = m.y > 0.f ? g.y : 0.f; g.z = m.z > 0.f ? g.z : 0.f; g.w = m.w > 0.f ? g.w : 0.f;
-            a[0] += g.x; a[1] += g.y; a[2] += g.z; a[3] += g.w;
-            ba[0] = fmaf(g.x, (v.x - mua.x) * isa.x, ba[0]); ba[1] = fmaf(g.y, (v.y - mua.y) * isa.y, ba[1]);
-            ba[2] = fmaf(g.z, (v.z - mua.z) * isa.z, ba[2]); ba[3] = fmaf(g.w, (v.w - mua.w) * isa.w, ba[3]);
-            bb[0] = fmaf(g.x, (w.x - mub.x) * isb.x, bb[0]); bb[1] = fmaf(g.y, (w.y - mub.y) * isb.y, bb[1]);
-            bb[2] = fmaf(g.z, (w.z - mub.z) * isb.z, bb[2]); bb[3] = fmaf(g.w, (w.w - mub.w) * isb.w, bb[3]);
-        }
-    }
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        float* o = sm + ((size_t)pr * C + cq * 4 + i) * 3;
-        o[0] = a[i]; o[1] = ba[i]; o[2] = bb[i];
-    }
-    __syncthreads();
-    int span = 1;
-    while (span < R) span <<= 1;
-    for (int stride = span >> 1; stride >= 1; stride >>= 1) {
-        if (pr < stride && pr + stride < R) {
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                float* a2 = sm + ((size_t)pr * C + cq * 4 + i) * 3;
-                const float* b2 = sm + ((size_t)(pr + stride) * C + cq * 4 + i) * 3;
-                a2[0] += b2[0]; a2[1] += b2[1]; a2[2] += b2[2];
-            }
-        }
-        __syncthreads();
-    }
-    if (pr == 0) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int c = cq * 4 + i;
-            float* o = partial + ((size_t)blockIdx.x * C + c) * 3;
-            o[0] = sm[(size_t)c * 3]; o[1] = sm[(size_t)c * 3 + 1]; o[2] = sm[(size_t)c * 3 + 2];
-        }
-    }
-}
-
-// One wave per channel; coef [2][3][C].
-__global__ __launch_bounds__(64) void bn_bwd_finalize_pair_kernel(const float* __restrict__ partial, int parts, int C, double count,
-                                                                  const float* __restrict__ gamma_a, const float* __restrict__ mean_a,
-                                                                  const float* __restrict__ invstd_a, const float* __restrict__ gamma_b,
-                                                                  const float* __restrict__ mean_b, const float* __restrict__ invstd_b,
-                                                                  int training, float* __restrict__ dgamma_a, float* __restrict__ dbeta_a,
-                                                                  float* __restrict__ dgamma_b, float* __restrict__ dbeta_b,
-                                                                  float* __restrict__ coef) {
-    const int c = blockIdx.x, lane = threadIdx.x;
-    const float gam_a = gamma_a[c], inv_a = invstd_a[c], mu_a = mean_a[c];   // (requested with the records)
-    const float gam_b = gamma_b[c], inv_b = invstd_b[c], mu_b = mean_b[c];
-    double s1 = 0, s2 = 0, s3 = 0;
-    {   // all loads of the lane in flight before the first add (see bn_stats_finalize_kernel)
-        constexpr int U = 16;
-        float ra[U], rb[U], rc[U];
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const int p = lane + 64 * u;
-            const float* o = partial + ((size_t)(p < parts ? p : 0) * C + c) * 3;
-            ra[u] = p < parts ? o[0] : 0.f; rb[u] = p < parts ? o[1] : 0.f; rc[u] = p < parts ? o[2] : 0.f;
-        }
-#pragma unroll
-        for (int u = 0; u < U; ++u) { s1 += (double)ra[u]; s2 += (double)rb[u]; s3 += (double)rc[u]; }
-        for (int p = lane + 64 * U; p < parts; p += 64) {
-            const float* o = partial + ((size_t)p * C + c) * 3;
-            s1 += o[0]; s2 += o[1]; s3 += o[2];
-        }
-    }
-    s1 = wave_sum64_f64(s1);
-    s2 = wave_sum64_f64(s2);
-    s3 = wave_sum64_f64(s3);
-    if (lane != 0) return;
-    dbeta_a[c] = (float)s1; dbeta_b[c] = (float)s1;
-    dgamma_a[c] = (float)s2; dgamma_b[c] = (float)s3;
-    const double ga = (double)gam_a * inv_a, gb = (double)gam_b * inv_b;
-    double a2 = 0, a3 = 0, b2 = 0, b3 = 0;
-    if (training) {
-        a2 = -ga * inv_a * s2 / count; a3 = -ga * s1 / count - a2 * mu_a;
-        b2 = -gb * inv_b * s3 / count; b3 = -gb * s1 / count - b2 * mu_b;
-    }
-    coef[c] = (float)ga; coef[C + c] = (float)a2; coef[2 * C + c] = (float)a3;
-    coef[3 * C + c] = (float)gb; coef[4 * C + c] = (float)b2; coef[5 * C + c] = (float)b3;
-}
-
-template <bool BITS>
-__global__ void bn_bwd_apply_pair_kernel(const float* __restrict__ dy, const float* __restrict__ y_mask,
-                                         const float* __restrict__ xa, const float* __restrict__ xb, int64_t nquads, int Q, int C,
-                                         const float* __restrict__ coef, float* __restrict__ dxa, float* __restrict__ dxb) {
-    for (int64_t e = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; e < nquads; e += (int64_t)gridDim.x * blockDim.x) {
-        const int cq = (int)(e % Q);
-        float4 g = reinterpret_cast<const float4*>(dy)[e];
-        const float4 m = BITS ? sign_quad(reinterpret_cast<const unsigned char*>(y_mask)[e]) : reinterpret_cast<const float4*>(y_mask)[e];
-        const float4 v = reinterpret_cast<const float4*>(xa)[e], w = reinterpret_cast<const float4*>(xb)[e];
-        g.x = m.x > 0.f ? g.x : 0.f; g.y = m.y > 0.f ? g.y : 0.f; g.z = m.z > 0.f ? g.z : 0.f; g.w = m.w > 0.f ? g.w : 0.f;
-        const float4 a1 = reinterpret_cast<const float4*>(coef)[cq], a2 = reinterpret_cast<const float4*>(coef + C)[cq],
-                     a3 = reinterpret_cast<const float4*>(coef + 2 * C)[cq];
-        const float4 b1 = reinterpret_cast<const float4*>(coef + 3 * C)[cq], b2 = reinterpret_cast<const float4*>(coef + 4 * C)[cq],
-                     b3 = reinterpret_cast<const float4*>(coef + 5 * C)[cq];
-        float4 o, r;
-        o.x = fmaf(a1.x, g.x, fmaf(a2.x, v.x, a3.x)); o.y = fmaf(a1.y, g.y, fmaf(a2.y, v.y, a3.y));
-        o.z = fmaf(a1.z, g.z, fmaf(a2.z, v.z, a3.z)); o.w = fmaf(a1.w, g.w, fmaf(a2.w, v.w, a3.w));
-        r.x = fmaf(b1.x, g.x, fmaf(b2.x, w.x, b3.x)); r.y = fmaf(b1.y, g.y, fmaf(b2.y, w.y, b3.y));
-        r.z = fmaf(b1.z, g.z, fmaf(b2.z, w.z, b3.z)); r.w = fmaf(b1.w, g.w, fmaf(b2.w, w.w, b3.w));
-        reinterpret_cast<float4*>(dxa)[e] = o;
-        reinterpret_cast<float4*>(dxb)[e] = r;
-    }
-}
-
 // out[c] = sum over pixels of x[p][c] (conv bias gradient); reuses the bwd partial layout with one column.
 __global__ void channel_sum_partial_kernel(const float* __restrict__ x, int64_t P, int C, int Q, int R, int64_t ppb,
                                            float* __restrict__ partial) {
     extern __shared__ float sm[];
     const int cq = threadIdx.x % Q, pr = threadIdx.x / Q;
     const int64_t lo = blockIdx.x * ppb, hi = (lo + ppb < P) ? lo + ppb : P;
-    float a[4] = {0, 0, 0, 0};
+    float a[1][4] = {};
     constexpr int U = 8;
     for (int64_t p = lo + pr; p < hi; p += (int64_t)R * U) {
         float4 v[U];
@@ -527,32 +439,15 @@ __global__ void channel_sum_partial_kernel(const float* __restrict__ x, int64_t 
             v[u] = q < hi ? *reinterpret_cast<const float4*>(x + q * C + cq * 4) : make_float4(0.f, 0.f, 0.f, 0.f);
         }
 #pragma unroll
-        for (int u = 0; u < U; ++u) { a[0] += v[u].x; a[1] += v[u].y; a[2] += v[u].z; a[3] += v[u].w; }
+        for (int u = 0; u < U; ++u) { a[0][0] += v[u].x; a[0][1] += v[u].y; a[0][2] += v[u].z; a[0][3] += v[u].w; }
     }
-#pragma unroll
-    for (int i = 0; i < 4; ++i) sm[(size_t)pr * C + cq * 4 + i] = a[i];
-    __syncthreads();
-    int span = 1;
-    while (span < R) span <<= 1;
-    for (int stride = span >> 1; stride >= 1; stride >>= 1) {
-        if (pr < stride && pr + stride < R) {
-#pragma unroll
-            for (int i = 0; i < 4; ++i) sm[(size_t)pr * C + cq * 4 + i] += sm[(size_t)(pr + stride) * C + cq * 4 + i];
-        }
-        __syncthreads();
-    }
-    if (pr == 0) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) partial[(size_t)blockIdx.x * C + cq * 4 + i] = sm[cq * 4 + i];
-    }
+    record_tail<1, RecAdd>(sm, a, C, cq, pr, R, partial + (size_t)blockIdx.x * C);
 }
 __global__ __launch_bounds__(64) void channel_sum_finalize_kernel(const float* __restrict__ partial, int parts, int C, int n_real,
                                             float* __restrict__ out) {
-    const int c = blockIdx.x, lane = threadIdx.x;
-    double s = 0;
-    for (int p = lane; p < parts; p += 64) s += partial[(size_t)p * C + c];
-    s = wave_sum64_f64(s);
-    if (lane == 0) out[c] = (float)s;
+    double s[1];
+    wave_record_sums<1>(partial, parts, C, blockIdx.x, s);
+    if (threadIdx.x == 0) out[blockIdx.x] = (float)s[0];
 }
 
 // ================================================================================================================================
@@ -569,7 +464,7 @@ __global__ __launch_bounds__(64) void channel_sum_finalize_kernel(const float* _
 //     dgamma / dbeta in the backward form).
 // The records' producers ran in earlier launches (the kernel boundary is the synchronisation), so plain loads are fine.
 // ================================================================================================================================
-#define DAM_Z4 make_float4(0.f, 0.f, 0.f, 0.f)
+__device__ __forceinline__ float4 zero4() { return make_float4(0.f, 0.f, 0.f, 0.f); }
 constexpr int FA_THREADS = 256;
 constexpr int FA_U = 4;                 // pixel pieces per thread, stream and register set (two sets: the next batch's loads are
                                         // requested before the current batch is computed and stored)
@@ -646,18 +541,23 @@ __device__ __forceinline__ void fa_slice_sums(const float* __restrict__ partial,
             for (int k = 0; k < NV; ++k) acc[k] += red[(tid + i * CS) * NV + k];
 }
 
-// Two register sets alternate: LOAD(set, p0) requests a batch, EMIT(set, p0) computes and stores it.
-#define DAM_FA_STREAM(LOAD_, EMIT_, STEP_)                                                                                     \
-    for (int64_t p0 = lo + tp;;) {                                                                                            \
-        if (p0 + (STEP_) < hi) { LOAD_(1, p0 + (STEP_)); }                                                                    \
-        EMIT_(0, p0);                                                                                                         \
-        p0 += (STEP_);                                                                                                        \
-        if (p0 >= hi) break;                                                                                                  \
-        if (p0 + (STEP_) < hi) { LOAD_(0, p0 + (STEP_)); }                                                                    \
-        EMIT_(1, p0);                                                                                                         \
-        p0 += (STEP_);                                                                                                        \
-        if (p0 >= hi) break;                                                                                                  \
+// The fused kernels' stream over a workgroup's pixel range.  Two register sets alternate: load(set, p0) requests a batch,
+// emit(set, p0) computes and stores it.  The set is a type (FaSet<0> / FaSet<1>), so that it indexes the callers' register
+// arrays as a compile-time constant and both sets stay in registers.  The caller has already requested set 0 at p0.
+template <int S> using FaSet = std::integral_constant<int, S>;
+template <typename Load, typename Emit>
+__device__ __forceinline__ void fa_stream(int64_t p0, int64_t hi, int64_t step, Load load, Emit emit) {
+    for (;;) {
+        if (p0 + step < hi) load(FaSet<1>{}, p0 + step);
+        emit(FaSet<0>{}, p0);
+        p0 += step;
+        if (p0 >= hi) break;
+        if (p0 + step < hi) load(FaSet<0>{}, p0 + step);
+        emit(FaSet<1>{}, p0);
+        p0 += step;
+        if (p0 >= hi) break;
     }
+}
 
 __global__ __launch_bounds__(FA_THREADS) void bn_fin_apply_kernel(const float* __restrict__ partial, int parts, int C, int CS,
                                                                    const BnFinArgs fin, const float* __restrict__ x, int64_t P,
@@ -671,15 +571,18 @@ __global__ __launch_bounds__(FA_THREADS) void bn_fin_apply_kernel(const float* _
     const int64_t lo = blockIdx.x * ppr, hi = (lo + ppr < P) ? lo + ppr : P;
     const int64_t step = (int64_t)ppi * FA_U;
     float4 xv[2][FA_U], rv[2][FA_U];
-#define DAM_FA_LOAD(S_, P0_)                                                                                                  \
-    _Pragma("unroll") for (int u = 0; u < FA_U; ++u) {                                                                        \
-        const int64_t p = (P0_) + (int64_t)u * ppi;                                                                           \
-        xv[S_][u] = p < hi ? reinterpret_cast<const float4*>(x)[p * Q + cq] : DAM_Z4;                                         \
-        if (res) rv[S_][u] = p < hi ? reinterpret_cast<const float4*>(res)[p * Q + cq] : DAM_Z4;                              \
-    }
+    auto load = [&](auto set, int64_t p0) {
+        constexpr int S = decltype(set)::value;
+#pragma unroll
+        for (int u = 0; u < FA_U; ++u) {
+            const int64_t p = p0 + (int64_t)u * ppi;
+            xv[S][u] = p < hi ? reinterpret_cast<const float4*>(x)[p * Q + cq] : zero4();
+            if (res) rv[S][u] = p < hi ? reinterpret_cast<const float4*>(res)[p * Q + cq] : zero4();
+        }
+    };
     // the first pieces are requested before the records: the table's round trip hides behind them
-    DAM_FA_LOAD(0, lo + tp)
-    float4 ra = make_float4(1.f, 1.f, 1.f, 1.f), rb = DAM_Z4;
+    load(FaSet<0>{}, lo + tp);
+    float4 ra = make_float4(1.f, 1.f, 1.f, 1.f), rb = zero4();
     if (rscale) { ra = reinterpret_cast<const float4*>(rscale)[cq]; rb = reinterpret_cast<const float4*>(rshift)[cq]; }
     {
         const int cl = tid % CS, ch = slice * CS + cl;
@@ -712,180 +615,120 @@ __global__ __launch_bounds__(FA_THREADS) void bn_fin_apply_kernel(const float* _
         __syncthreads();
     }
     const float4 sc = *reinterpret_cast<const float4*>(tab + tq * 4), sh = *reinterpret_cast<const float4*>(tab + CS + tq * 4);
-#define DAM_FA_EMIT(S_, P0_)                                                                                                  \
-    _Pragma("unroll") for (int u = 0; u < FA_U; ++u) {                                                                        \
-        const int64_t p = (P0_) + (int64_t)u * ppi;                                                                           \
-        if (p < hi) {                                                                                                         \
-            const float4 v = xv[S_][u];                                                                                       \
-            float4 o = make_float4(fmaf(v.x, sc.x, sh.x), fmaf(v.y, sc.y, sh.y), fmaf(v.z, sc.z, sh.z), fmaf(v.w, sc.w, sh.w)); \
-            if (res) {                                                                                                        \
-                float4 r = rv[S_][u];                                                                                         \
-                if (rscale) r = make_float4(fmaf(r.x, ra.x, rb.x), fmaf(r.y, ra.y, rb.y), fmaf(r.z, ra.z, rb.z), fmaf(r.w, ra.w, rb.w)); \
-                o.x += r.x; o.y += r.y; o.z += r.z; o.w += r.w;                                                               \
-            }                                                                                                                 \
-            if (relu) { o.x = fmaxf(o.x, 0.f); o.y = fmaxf(o.y, 0.f); o.z = fmaxf(o.z, 0.f); o.w = fmaxf(o.w, 0.f); }         \
-            reinterpret_cast<float4*>(y)[p * Q + cq] = o;                                                                     \
-            if (sign_bits)                                                                                                    \
-                sign_bits[p * Q + cq] = (unsigned char)((o.x > 0.f) | ((o.y > 0.f) << 1) | ((o.z > 0.f) << 2) | ((o.w > 0.f) << 3)); \
-        }                                                                                                                     \
-    }
-    DAM_FA_STREAM(DAM_FA_LOAD, DAM_FA_EMIT, step)
-#undef DAM_FA_LOAD
-#undef DAM_FA_EMIT
+    fa_stream(lo + tp, hi, step, load, [&](auto set, int64_t p0) {
+        constexpr int S = decltype(set)::value;
+#pragma unroll
+        for (int u = 0; u < FA_U; ++u) {
+            const int64_t p = p0 + (int64_t)u * ppi;
+            if (p < hi) {
+                const float4 v = xv[S][u];
+                float4 o = make_float4(fmaf(v.x, sc.x, sh.x), fmaf(v.y, sc.y, sh.y), fmaf(v.z, sc.z, sh.z), fmaf(v.w, sc.w, sh.w));
+                if (res) {
+                    float4 r = rv[S][u];
+                    if (rscale) r = make_float4(fmaf(r.x, ra.x, rb.x), fmaf(r.y, ra.y, rb.y), fmaf(r.z, ra.z, rb.z), fmaf(r.w, ra.w, rb.w));
+                    o.x += r.x; o.y += r.y; o.z += r.z; o.w += r.w;
+                }
+                if (relu) { o.x = fmaxf(o.x, 0.f); o.y = fmaxf(o.y, 0.f); o.z = fmaxf(o.z, 0.f); o.w = fmaxf(o.w, 0.f); }
+                reinterpret_cast<float4*>(y)[p * Q + cq] = o;
+                if (sign_bits)
+                    sign_bits[p * Q + cq] = (unsigned char)((o.x > 0.f) | ((o.y > 0.f) << 1) | ((o.z > 0.f) << 2) | ((o.w > 0.f) << 3));
+            }
+        }
+    });
 }
 
-// Backward: records [parts][C][2] = (sum dz, sum dz * xhat) -> dgamma / dbeta (range 0 writes them) and dx = c1 dz + c2 x + c3.
-template <int MASK>
+// Backward: records [parts][C][1 + NB] = (sum dz, sum dz * xhat of every side) -> dgamma / dbeta (range 0 writes them) and
+// dx = c1 dz + c2 x + c3 per side.
+template <int MASK, int NB>
 __global__ __launch_bounds__(FA_THREADS) void bn_bwd_fin_apply_kernel(const float* __restrict__ partial, int parts, int C, int CS,
-                                                                       double count, const float* __restrict__ gamma,
-                                                                       const float* __restrict__ mean, const float* __restrict__ invstd,
-                                                                       int training, float* __restrict__ dgamma, float* __restrict__ dbeta,
+                                                                       double count, int training, const BnBwdSides<NB> sd,
                                                                        const float* __restrict__ dy, const float* __restrict__ y_mask,
-                                                                       const float* __restrict__ x, int64_t P, int64_t ppr,
-                                                                       const float* __restrict__ mscale, const float* __restrict__ mshift,
-                                                                       float* __restrict__ dx) {
-    __shared__ double red[FA_THREADS * 2];
-    __shared__ __attribute__((aligned(16))) float tab[3 * 32];
+                                                                       int64_t P, int64_t ppr, const float* __restrict__ mscale,
+                                                                       const float* __restrict__ mshift) {
+    constexpr int NR = 1 + NB;
+    __shared__ double red[FA_THREADS * NR];
+    __shared__ __attribute__((aligned(16))) float tab[3 * NB * 32];       // [NB][3][CS]: c1, c2, c3 of every side
     const int tid = threadIdx.x, slice = blockIdx.y, q = CS / 4, tq = tid % q, tp = tid / q, ppi = FA_THREADS / q;
     const int Q = C / 4, cq = slice * q + tq;
     const int64_t lo = blockIdx.x * ppr, hi = (lo + ppr < P) ? lo + ppr : P;
-    constexpr int UB = 3;               // three streams: three pieces each per register set
+    constexpr int UB = NB == 1 ? 3 : 2;         // 2 + NB streams: three (one BatchNorm) or two (a pair) pieces each per register set
     const int64_t step = (int64_t)ppi * UB;
-    float4 gv[2][UB], xv[2][UB], mv[2][UB];
-#define DAM_FA_LOAD(S_, P0_)                                                                                                  \
-    _Pragma("unroll") for (int u = 0; u < UB; ++u) {                                                                          \
-        const int64_t p = (P0_) + (int64_t)u * ppi;                                                                           \
-        const bool ok = p < hi;                                                                                               \
-        gv[S_][u] = ok ? reinterpret_cast<const float4*>(dy)[p * Q + cq] : DAM_Z4;                                            \
-        xv[S_][u] = ok ? reinterpret_cast<const float4*>(x)[p * Q + cq] : DAM_Z4;                                             \
-        if (MASK == 1) mv[S_][u] = ok ? reinterpret_cast<const float4*>(y_mask)[p * Q + cq] : DAM_Z4;                         \
-        if (MASK == 3) mv[S_][u] = sign_quad(ok ? reinterpret_cast<const unsigned char*>(y_mask)[p * Q + cq] : 0);            \
-    }
-    DAM_FA_LOAD(0, lo + tp)
-    float4 msc = DAM_Z4, msh = DAM_Z4;
+    float4 gv[2][UB], xv[NB][2][UB], mv[2][UB];
+    auto load = [&](auto set, int64_t p0) {
+        constexpr int S = decltype(set)::value;
+#pragma unroll
+        for (int u = 0; u < UB; ++u) {
+            const int64_t p = p0 + (int64_t)u * ppi;
+            const bool ok = p < hi;
+            gv[S][u] = ok ? reinterpret_cast<const float4*>(dy)[p * Q + cq] : zero4();
+#pragma unroll
+            for (int s = 0; s < NB; ++s) xv[s][S][u] = ok ? reinterpret_cast<const float4*>(sd.s[s].x)[p * Q + cq] : zero4();
+            if (MASK == 1) mv[S][u] = ok ? reinterpret_cast<const float4*>(y_mask)[p * Q + cq] : zero4();
+            if (MASK == 3) mv[S][u] = sign_quad(ok ? reinterpret_cast<const unsigned char*>(y_mask)[p * Q + cq] : 0);
+        }
+    };
+    load(FaSet<0>{}, lo + tp);
+    float4 msc = zero4(), msh = zero4();
     if (MASK == 2) { msc = reinterpret_cast<const float4*>(mscale)[cq]; msh = reinterpret_cast<const float4*>(mshift)[cq]; }
     {
         const int cl = tid % CS, ch = slice * CS + cl;
-        const float gam = gamma[ch], inv = invstd[ch], mu = mean[ch];
-        double acc[2];
-        fa_slice_sums<2, 2>(partial, parts, C, ch, CS, red, acc, [](const float (&r)[2], double (&v)[2]) { v[0] = (double)r[0]; v[1] = (double)r[1]; });
+        float gam[NB], inv[NB], mu[NB];
+#pragma unroll
+        for (int s = 0; s < NB; ++s) { gam[s] = sd.s[s].gamma[ch]; inv[s] = sd.s[s].invstd[ch]; mu[s] = sd.s[s].mean[ch]; }
+        double acc[NR];
+        fa_slice_sums<NR, NR>(partial, parts, C, ch, CS, red, acc, [](const float (&r)[NR], double (&v)[NR]) {
+#pragma unroll
+            for (int k = 0; k < NR; ++k) v[k] = (double)r[k];
+        });
         if (tid < CS) {
-            const double s1 = acc[0], s2 = acc[1];
-            const double g = (double)gam * inv;
-            double c2 = 0, c3 = 0;
-            if (training) { c2 = -g * inv * s2 / count; c3 = -g * s1 / count - c2 * mu; }
-            tab[cl] = (float)g; tab[CS + cl] = (float)c2; tab[2 * CS + cl] = (float)c3;
-            if (blockIdx.x == 0) { dbeta[ch] = (float)s1; dgamma[ch] = (float)s2; }
+#pragma unroll
+            for (int s = 0; s < NB; ++s) {
+                const double s1 = acc[0], s2 = acc[1 + s];
+                const double g = (double)gam[s] * inv[s];
+                double c2 = 0, c3 = 0;
+                if (training) { c2 = -g * inv[s] * s2 / count; c3 = -g * s1 / count - c2 * mu[s]; }
+                float* t = tab + 3 * s * CS;
+                t[cl] = (float)g; t[CS + cl] = (float)c2; t[2 * CS + cl] = (float)c3;
+                if (blockIdx.x == 0) { sd.s[s].dbeta[ch] = (float)s1; sd.s[s].dgamma[ch] = (float)s2; }
+            }
         }
         __syncthreads();
     }
-    const float4 c1 = *reinterpret_cast<const float4*>(tab + tq * 4), c2 = *reinterpret_cast<const float4*>(tab + CS + tq * 4),
-                 c3 = *reinterpret_cast<const float4*>(tab + 2 * CS + tq * 4);
-#define DAM_FA_EMIT(S_, P0_)                                                                                                  \
-    _Pragma("unroll") for (int u = 0; u < UB; ++u) {                                                                          \
-        const int64_t p = (P0_) + (int64_t)u * ppi;                                                                           \
-        if (p < hi) {                                                                                                         \
-            float4 g = gv[S_][u];                                                                                             \
-            const float4 v = xv[S_][u];                                                                                       \
-            if (MASK != 0) {                                                                                                  \
-                float4 m = mv[S_][u];                                                                                         \
-                if (MASK == 2) m = make_float4(fmaf(v.x, msc.x, msh.x), fmaf(v.y, msc.y, msh.y), fmaf(v.z, msc.z, msh.z), fmaf(v.w, msc.w, msh.w)); \
-                g.x = m.x > 0.f ? g.x : 0.f; g.y = m.y > 0.f ? g.y : 0.f; g.z = m.z > 0.f ? g.z : 0.f; g.w = m.w > 0.f ? g.w : 0.f; \
-            }                                                                                                                 \
-            float4 o;                                                                                                         \
-            o.x = fmaf(c1.x, g.x, fmaf(c2.x, v.x, c3.x)); o.y = fmaf(c1.y, g.y, fmaf(c2.y, v.y, c3.y));                       \
-            o.z = fmaf(c1.z, g.z, fmaf(c2.z, v.z, c3.z)); o.w = fmaf(c1.w, g.w, fmaf(c2.w, v.w, c3.w));                       \
-            reinterpret_cast<float4*>(dx)[p * Q + cq] = o;                                                                    \
-        }                                                                                                                     \
-    }
-    DAM_FA_STREAM(DAM_FA_LOAD, DAM_FA_EMIT, step)
-#undef DAM_FA_LOAD
-#undef DAM_FA_EMIT
+    float4 k[NB][3];
+#pragma unroll
+    for (int i = 0; i < 3 * NB; ++i) k[i / 3][i % 3] = *reinterpret_cast<const float4*>(tab + i * CS + tq * 4);
+    fa_stream(lo + tp, hi, step, load, [&](auto set, int64_t p0) {
+        constexpr int S = decltype(set)::value;
+#pragma unroll
+        for (int u = 0; u < UB; ++u) {
+            const int64_t p = p0 + (int64_t)u * ppi;
+            if (p < hi) {
+                float4 g = gv[S][u];
+                if (MASK != 0) {
+                    float4 m = mv[S][u];
+                    if (MASK == 2) {
+                        const float4 v = xv[0][S][u];
+                        m = make_float4(fmaf(v.x, msc.x, msh.x), fmaf(v.y, msc.y, msh.y), fmaf(v.z, msc.z, msh.z), fmaf(v.w, msc.w, msh.w));
+                    }
+                    g.x = m.x > 0.f ? g.x : 0.f; g.y = m.y > 0.f ? g.y : 0.f; g.z = m.z > 0.f ? g.z : 0.f; g.w = m.w > 0.f ? g.w : 0.f;
+                }
+                float4 o[NB];
+#pragma unroll
+                for (int s = 0; s < NB; ++s) {
+                    const float4 v = xv[s][S][u], c1 = k[s][0], c2 = k[s][1], c3 = k[s][2];
+                    o[s].x = fmaf(c1.x, g.x, fmaf(c2.x, v.x, c3.x)); o[s].y = fmaf(c1.y, g.y, fmaf(c2.y, v.y, c3.y));
+                    o[s].z = fmaf(c1.z, g.z, fmaf(c2.z, v.z, c3.z)); o[s].w = fmaf(c1.w, g.w, fmaf(c2.w, v.w, c3.w));
+                }
+#pragma unroll
+                for (int s = 0; s < NB; ++s) reinterpret_cast<float4*>(sd.s[s].dx)[p * Q + cq] = o[s];
+            }
+        }
+    });
 }
 
-// The pair form (a residual block's bn2 and its shortcut BatchNorm): records [parts][C][3] = (sum dz, sum dz xhat_a, sum dz xhat_b).
-template <bool BITS>
-__global__ __launch_bounds__(FA_THREADS) void bn_bwd_fin_apply_pair_kernel(const float* __restrict__ partial, int parts, int C, int CS,
-        double count, const float* __restrict__ gamma_a, const float* __restrict__ mean_a, const float* __restrict__ invstd_a,
-        const float* __restrict__ gamma_b, const float* __restrict__ mean_b, const float* __restrict__ invstd_b, int training,
-        float* __restrict__ dgamma_a, float* __restrict__ dbeta_a, float* __restrict__ dgamma_b, float* __restrict__ dbeta_b,
-        const float* __restrict__ dy, const float* __restrict__ y_mask, const float* __restrict__ xa, const float* __restrict__ xb,
-        int64_t P, int64_t ppr, float* __restrict__ dxa, float* __restrict__ dxb) {
-    __shared__ double red[FA_THREADS * 3];
-    __shared__ __attribute__((aligned(16))) float tab[6 * 32];
-    const int tid = threadIdx.x, slice = blockIdx.y, q = CS / 4, tq = tid % q, tp = tid / q, ppi = FA_THREADS / q;
-    const int Q = C / 4, cq = slice * q + tq;
-    const int64_t lo = blockIdx.x * ppr, hi = (lo + ppr < P) ? lo + ppr : P;
-    constexpr int UP = 2;               // four streams: two pieces each per register set
-    const int64_t step = (int64_t)ppi * UP;
-    float4 gv[2][UP], va[2][UP], vb[2][UP], mv[2][UP];
-#define DAM_FA_LOAD(S_, P0_)                                                                                                  \
-    _Pragma("unroll") for (int u = 0; u < UP; ++u) {                                                                          \
-        const int64_t p = (P0_) + (int64_t)u * ppi;                                                                           \
-        const bool ok = p < hi;                                                                                               \
-        gv[S_][u] = ok ? reinterpret_cast<const float4*>(dy)[p * Q + cq] : DAM_Z4;                                            \
-        va[S_][u] = ok ? reinterpret_cast<const float4*>(xa)[p * Q + cq] : DAM_Z4;                                            \
-        vb[S_][u] = ok ? reinterpret_cast<const float4*>(xb)[p * Q + cq] : DAM_Z4;                                            \
-        if (BITS) mv[S_][u] = sign_quad(ok ? reinterpret_cast<const unsigned char*>(y_mask)[p * Q + cq] : 0);                 \
-        else mv[S_][u] = ok ? reinterpret_cast<const float4*>(y_mask)[p * Q + cq] : DAM_Z4;                                   \
-    }
-    DAM_FA_LOAD(0, lo + tp)
-    {
-        const int cl = tid % CS, ch = slice * CS + cl;
-        const float ga_ = gamma_a[ch], ia = invstd_a[ch], ma = mean_a[ch], gb_ = gamma_b[ch], ib = invstd_b[ch], mb = mean_b[ch];
-        double acc[3];
-        fa_slice_sums<3, 3>(partial, parts, C, ch, CS, red, acc,
-                            [](const float (&r)[3], double (&v)[3]) { v[0] = (double)r[0]; v[1] = (double)r[1]; v[2] = (double)r[2]; });
-        if (tid < CS) {
-            const double s1 = acc[0], s2 = acc[1], s3 = acc[2];
-            const double ga = (double)ga_ * ia, gb = (double)gb_ * ib;
-            double a2 = 0, a3 = 0, b2 = 0, b3 = 0;
-            if (training) {
-                a2 = -ga * ia * s2 / count; a3 = -ga * s1 / count - a2 * ma;
-                b2 = -gb * ib * s3 / count; b3 = -gb * s1 / count - b2 * mb;
-            }
-            tab[cl] = (float)ga; tab[CS + cl] = (float)a2; tab[2 * CS + cl] = (float)a3;
-            tab[3 * CS + cl] = (float)gb; tab[4 * CS + cl] = (float)b2; tab[5 * CS + cl] = (float)b3;
-            if (blockIdx.x == 0) {
-                dbeta_a[ch] = (float)s1; dbeta_b[ch] = (float)s1; dgamma_a[ch] = (float)s2; dgamma_b[ch] = (float)s3;
-            }
-        }
-        __syncthreads();
-    }
-    float4 k[6];
-#pragma unroll
-    for (int i = 0; i < 6; ++i) k[i] = *reinterpret_cast<const float4*>(tab + i * CS + tq * 4);
-#define DAM_FA_EMIT(S_, P0_)                                                                                                  \
-    _Pragma("unroll") for (int u = 0; u < UP; ++u) {                                                                          \
-        const int64_t p = (P0_) + (int64_t)u * ppi;                                                                           \
-        if (p < hi) {                                                                                                         \
-            float4 g = gv[S_][u];                                                                                             \
-            const float4 m = mv[S_][u], v = va[S_][u], w = vb[S_][u];                                                         \
-            g.x = m.x > 0.f ? g.x : 0.f; g.y = m.y > 0.f ? g.y : 0.f; g.z = m.z > 0.f ? g.z : 0.f; g.w = m.w > 0.f ? g.w : 0.f; \
-            float4 o, r;                                                                                                      \
-            o.x = fmaf(k[0].x, g.x, fmaf(k[1].x, v.x, k[2].x)); o.y = fmaf(k[0].y, g.y, fmaf(k[1].y, v.y, k[2].y));           \
-            o.z = fmaf(k[0].z, g.z, fmaf(k[1].z, v.z, k[2].z)); o.w = fmaf(k[0].w, g.w, fmaf(k[1].w, v.w, k[2].w));           \
-            r.x = fmaf(k[3].x, g.x, fmaf(k[4].x, w.x, k[5].x)); r.y = fmaf(k[3].y, g.y, fmaf(k[4].y, w.y, k[5].y));           \
-            r.z = fmaf(k[3].z, g.z, fmaf(k[4].z, w.z, k[5].z)); r.w = fmaf(k[3].w, g.w, fmaf(k[4].w, w.w, k[5].w));           \
-            reinterpret_cast<float4*>(dxa)[p * Q + cq] = o;                                                                   \
-            reinterpret_cast<float4*>(dxb)[p * Q + cq] = r;                                                                   \
-        }                                                                                                                     \
-    }
-    DAM_FA_STREAM(DAM_FA_LOAD, DAM_FA_EMIT, step)
-#undef DAM_FA_LOAD
-#undef DAM_FA_EMIT
-}
-#undef DAM_FA_STREAM
-#undef DAM_Z4
 inline int elt_blocks(int64_t n) {
     int64_t b = cdiv(n, 256);
     return (int)(b < 4096 ? (b < 1 ? 1 : b) : 4096);
-}
-
-// DAM_BN_FUSED_FIN=0 keeps the separate finalize launches (A/B switch, read once)
-inline bool fa_enabled() {
-    static const bool on = [] { const char* e = getenv("DAM_BN_FUSED_FIN"); return !(e && e[0] == '0'); }();
-    return on;
 }
 
 // records a partial pass may leave for a fused consumer: a workgroup's slice table stays <= FA_PARTS_KB KB
@@ -894,6 +737,50 @@ inline int fa_max_parts(int C, int rec_floats) {
     int m = FA_PARTS_KB * 1024 / (fa_cs(C) * rec_floats * 4);
     if (m > BN_MAX_PARTS) m = BN_MAX_PARTS;
     return m < 64 ? 64 : m;
+}
+
+// dam_bn_fin (include/dam_hip.h) -> the kernels' BnFinArgs; false where the struct or one of its required pointers is missing
+inline bool fin_args(const dam_bn_fin* f, BnFinArgs* a) {
+    if (!f || !f->gamma || !f->beta || !f->save_mean || !f->save_invstd || !f->scale || !f->shift) return false;
+    *a = BnFinArgs{f->gamma, f->beta, f->running_mean, f->running_var, (long long*)f->num_batches_tracked, f->momentum,
+                   f->eps, f->save_mean, f->save_invstd, f->scale, f->shift};
+    return true;
+}
+
+// The run-time mask mode as a template argument: calls f(std::integral_constant<int, M>) for the M of MASKS... that equals mask;
+// false (and no call) where none does.
+template <int... MASKS, typename F>
+inline bool with_mask(int mask, F f) {
+    return ((mask == MASKS ? (f(std::integral_constant<int, MASKS>{}), true) : false) || ...);
+}
+
+// The backward launches of NB BatchNorms in the mask modes MASKS...: the partial pass (unless the records are given) and, where
+// `fused`, the finalize inside the apply launch.  Given records that are not fused launch nothing here: the caller
+// (dam_bn_backward_f32) then runs the finalize and apply launches of its own.
+template <int NB, int... MASKS>
+inline int bn_bwd_launch(const BnLaunch& l, bool given, bool fused, int mask, const BnBwdSides<NB>& sd, const float* dy,
+                         const float* y_mask, int64_t P, int C, int training, const float* mask_scale, const float* mask_shift,
+                         float* workspace, hipStream_t st) {
+    if (!given) {
+        const bool known = with_mask<MASKS...>(mask, [&](auto m) {
+            hipLaunchKernelGGL((bn_bwd_partial_kernel<decltype(m)::value, NB>), dim3(l.parts), dim3(l.threads),
+                               (size_t)l.r * C * (1 + NB) * sizeof(float), st, dy, y_mask, sd, P, C, l.q, l.r, l.ppb, mask_scale,
+                               mask_shift, workspace);
+        });
+        if (!known) return DAM_ERR_BAD_ARG;
+        DAM_CHECK_LAUNCH();
+    }
+    if (fused) {
+        const FaPlan f = fa_plan(P, C);
+        const bool known = with_mask<MASKS...>(mask, [&](auto m) {
+            hipLaunchKernelGGL((bn_bwd_fin_apply_kernel<decltype(m)::value, NB>), dim3(f.nranges, f.nslices), dim3(FA_THREADS), 0, st,
+                               (const float*)workspace, l.parts, C, f.cs, (double)P, training, sd, dy, y_mask, P, f.ppr, mask_scale,
+                               mask_shift);
+        });
+        if (!known) return DAM_ERR_BAD_ARG;
+        DAM_CHECK_LAUNCH();
+    }
+    return DAM_OK;
 }
 
 }  // namespace
@@ -922,12 +809,12 @@ extern "C" int dam_bn_stats_partial_f32(const float* x, int64_t n_pixels, int C,
 extern "C" int dam_bn_finalize_apply_f32(const float* partial, int parts, int C, const dam_bn_fin* fin, const float* x,
                                          int64_t n_pixels, const float* res, const float* res_scale, const float* res_shift,
                                          int relu, float* y, uint8_t* sign_bits, void* stream) {
-    if (!partial || parts <= 0 || !fin || !x || !y || n_pixels <= 0) return DAM_ERR_BAD_ARG;
-    if (!fin->gamma || !fin->beta || !fin->save_mean || !fin->save_invstd || !fin->scale || !fin->shift) return DAM_ERR_BAD_ARG;
+    BnFinArgs a;
+    if (!partial || parts <= 0 || !fin_args(fin, &a) || !x || !y || n_pixels <= 0) return DAM_ERR_BAD_ARG;
     if (res_scale && (!res || !res_shift)) return DAM_ERR_BAD_ARG;
     if (C % 16 || C > 1024) return DAM_ERR_UNSUPPORTED;
     hipStream_t st = (hipStream_t)stream;
-    if (!fa_enabled() || !fa_fwd_table_ok(C, parts)) {
+    if (!fa_fwd_table_ok(C, parts)) {
         int rc = dam_bn_finalize_f32(partial, parts, C, fin->gamma, fin->beta, fin->running_mean, fin->running_var,
                                      fin->num_batches_tracked, fin->momentum, fin->eps, fin->save_mean, fin->save_invstd, fin->scale,
                                      fin->shift, stream);
@@ -935,8 +822,6 @@ extern "C" int dam_bn_finalize_apply_f32(const float* partial, int parts, int C,
         return dam_bn_apply_f32(x, n_pixels, C, fin->scale, fin->shift, res, res_scale, res_shift, relu, y, sign_bits, stream);
     }
     const FaPlan f = fa_plan(n_pixels, C);
-    const BnFinArgs a{fin->gamma, fin->beta, fin->running_mean, fin->running_var, (long long*)fin->num_batches_tracked, fin->momentum,
-                      fin->eps, fin->save_mean, fin->save_invstd, fin->scale, fin->shift};
     hipLaunchKernelGGL(bn_fin_apply_kernel, dim3(f.nranges, f.nslices), dim3(FA_THREADS), 0, st, partial, parts, C, f.cs, a, x,
                        n_pixels, f.ppr, res, res_scale, res_shift, relu, y, sign_bits);
     DAM_CHECK_LAUNCH();
@@ -966,10 +851,8 @@ extern "C" int dam_bn_stats_f32(const float* x, int64_t n_pixels, int C, const f
 // independent BatchNorms that become ready together) in one partial + one finalize launch.
 extern "C" int dam_bn_stats_pair_f32(const float* x_a, const float* x_b, int64_t n_pixels, int C, const dam_bn_fin* a,
                                      const dam_bn_fin* b, float* workspace, void* stream) {
-    if (!x_a || !x_b || !a || !b || !workspace || n_pixels <= 0) return DAM_ERR_BAD_ARG;
-    if (!a->gamma || !a->beta || !a->save_mean || !a->save_invstd || !a->scale || !a->shift || !b->gamma || !b->beta ||
-        !b->save_mean || !b->save_invstd || !b->scale || !b->shift)
-        return DAM_ERR_BAD_ARG;
+    BnFinArgs fa, fb;
+    if (!x_a || !x_b || !fin_args(a, &fa) || !fin_args(b, &fb) || !workspace || n_pixels <= 0) return DAM_ERR_BAD_ARG;
     if (C % 16 || C > 1024) return DAM_ERR_UNSUPPORTED;
     const BnLaunch l = bn_plan(n_pixels, C);
     hipStream_t st = (hipStream_t)stream;
@@ -977,11 +860,9 @@ extern "C" int dam_bn_stats_pair_f32(const float* x_a, const float* x_b, int64_t
     hipLaunchKernelGGL(bn_stats_partial_kernel, dim3(l.parts, 2), dim3(l.threads), (size_t)l.r * C * 3 * sizeof(float), st, x_a,
                        n_pixels, C, l.q, l.r, l.ppb, workspace, x_b, ws_b);
     DAM_CHECK_LAUNCH();
-    const BnFinArgs fb{b->gamma, b->beta, b->running_mean, b->running_var, (long long*)b->num_batches_tracked, b->momentum,
-                       b->eps, b->save_mean, b->save_invstd, b->scale, b->shift};
-    hipLaunchKernelGGL(bn_stats_finalize_kernel, dim3(C, 2), dim3(64), 0, st, workspace, l.parts, C, a->gamma, a->beta,
-                       a->running_mean, a->running_var, (long long*)a->num_batches_tracked, a->momentum, a->eps, a->save_mean,
-                       a->save_invstd, a->scale, a->shift, fb, (const float*)ws_b);
+    hipLaunchKernelGGL(bn_stats_finalize_kernel, dim3(C, 2), dim3(64), 0, st, workspace, l.parts, C, fa.gamma, fa.beta,
+                       fa.running_mean, fa.running_var, fa.num_batches, fa.momentum, fa.eps, fa.save_mean, fa.save_invstd, fa.scale,
+                       fa.shift, fb, (const float*)ws_b);
     DAM_CHECK_LAUNCH();
     return DAM_OK;
 }
@@ -1001,15 +882,11 @@ extern "C" int dam_bn_finalize_f32(const float* partial, int parts, int C, const
 
 extern "C" int dam_bn_finalize_pair_f32(const float* partial_a, const float* partial_b, int parts, int C, const dam_bn_fin* a,
                                         const dam_bn_fin* b, void* stream) {
-    if (!partial_a || !partial_b || parts <= 0 || C <= 0 || !a || !b) return DAM_ERR_BAD_ARG;
-    if (!a->gamma || !a->beta || !a->save_mean || !a->save_invstd || !a->scale || !a->shift || !b->gamma || !b->beta ||
-        !b->save_mean || !b->save_invstd || !b->scale || !b->shift)
-        return DAM_ERR_BAD_ARG;
-    const BnFinArgs fb{b->gamma, b->beta, b->running_mean, b->running_var, (long long*)b->num_batches_tracked, b->momentum,
-                       b->eps, b->save_mean, b->save_invstd, b->scale, b->shift};
-    hipLaunchKernelGGL(bn_stats_finalize_kernel, dim3(C, 2), dim3(64), 0, (hipStream_t)stream, partial_a, parts, C, a->gamma, a->beta,
-                       a->running_mean, a->running_var, (long long*)a->num_batches_tracked, a->momentum, a->eps, a->save_mean,
-                       a->save_invstd, a->scale, a->shift, fb, partial_b);
+    BnFinArgs fa, fb;
+    if (!partial_a || !partial_b || parts <= 0 || C <= 0 || !fin_args(a, &fa) || !fin_args(b, &fb)) return DAM_ERR_BAD_ARG;
+    hipLaunchKernelGGL(bn_stats_finalize_kernel, dim3(C, 2), dim3(64), 0, (hipStream_t)stream, partial_a, parts, C, fa.gamma, fa.beta,
+                       fa.running_mean, fa.running_var, fa.num_batches, fa.momentum, fa.eps, fa.save_mean, fa.save_invstd, fa.scale,
+                       fa.shift, fb, partial_b);
     DAM_CHECK_LAUNCH();
     return DAM_OK;
 }
@@ -1048,41 +925,27 @@ extern "C" int dam_bn_backward_f32(const float* dy, const float* y_mask, const f
         return DAM_ERR_BAD_ARG;
     if (mask_bits) y_mask = reinterpret_cast<const float*>(mask_bits);       // MASK == 3 reads it as bytes
     if (C % 16 || C > 1024) return DAM_ERR_UNSUPPORTED;
-    const bool fused = fa_enabled();
-    BnLaunch l = bn_plan(n_pixels, C, fused ? fa_max_parts(C, 2) : BN_MAX_PARTS);
+    BnLaunch l = bn_plan(n_pixels, C, fa_max_parts(C, 2));
     if (partials_given < 0 || partials_given > BN_MAX_PARTS) return DAM_ERR_BAD_ARG;
     if (partials_given) l.parts = partials_given;       // records from a data-gradient epilogue
-    const bool fuse_now = fused && fa_table_ok(C, l.parts, 2);
+    // ... which may be more than a fused consumer's table takes: then the finalize and the apply launch of their own
+    const bool fused = fa_table_ok(C, l.parts, 2);
     hipStream_t st = (hipStream_t)stream;
-    float* coef = workspace + (size_t)BN_MAX_PARTS * C * 2;    // workspace holds [parts][C][2] then [3][C]
     const int mask = mask_bits ? 3 : (y_mask ? 1 : (mask_scale ? 2 : 0));
-#define DAM_BN_PARTIAL(M_)                                                                                                   \
-    hipLaunchKernelGGL(bn_bwd_partial_kernel<M_>, dim3(l.parts), dim3(l.threads), (size_t)l.r * C * 2 * sizeof(float), st, dy, \
-                       y_mask, x, n_pixels, C, l.q, l.r, l.ppb, save_mean, save_invstd, mask_scale, mask_shift, workspace)
-    if (partials_given) { }
-    else if (mask == 1) DAM_BN_PARTIAL(1); else if (mask == 2) DAM_BN_PARTIAL(2); else if (mask == 3) DAM_BN_PARTIAL(3); else DAM_BN_PARTIAL(0);
-#undef DAM_BN_PARTIAL
-    DAM_CHECK_LAUNCH();
-    if (fuse_now) {     // finalize inside the apply launch (bn_bwd_fin_apply_kernel)
-        const FaPlan f = fa_plan(n_pixels, C);
-#define DAM_BN_FA(M_)                                                                                                        \
-    hipLaunchKernelGGL(bn_bwd_fin_apply_kernel<M_>, dim3(f.nranges, f.nslices), dim3(FA_THREADS), 0, st, workspace, l.parts, C, \
-                       f.cs, (double)n_pixels, gamma, save_mean, save_invstd, training, dgamma, dbeta, dy, y_mask, x, n_pixels, \
-                       f.ppr, mask_scale, mask_shift, dx)
-        if (mask == 1) DAM_BN_FA(1); else if (mask == 2) DAM_BN_FA(2); else if (mask == 3) DAM_BN_FA(3); else DAM_BN_FA(0);
-#undef DAM_BN_FA
-        DAM_CHECK_LAUNCH();
-        return DAM_OK;
-    }
+    const BnBwdSides<1> sd{{{x, gamma, save_mean, save_invstd, dx, dgamma, dbeta}}};
+    const int rc = bn_bwd_launch<1, 0, 1, 2, 3>(l, partials_given != 0, fused, mask, sd, dy, y_mask, n_pixels, C, training,
+                                                mask_scale, mask_shift, workspace, st);
+    if (rc != DAM_OK || fused) return rc;
+    float* coef = workspace + (size_t)BN_MAX_PARTS * C * 2;    // workspace holds [parts][C][2] then [3][C]
     hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3(C), dim3(64), 0, st, workspace, l.parts, C,
                        (double)n_pixels, gamma, save_mean, save_invstd, training, dgamma, dbeta, coef);
     DAM_CHECK_LAUNCH();
     const int64_t nq = n_pixels * (C / 4);
-#define DAM_BN_APPLY(M_)                                                                                                     \
-    hipLaunchKernelGGL(bn_bwd_apply_kernel<M_>, dim3(elt_blocks(nq)), dim3(256), 0, st, dy, y_mask, x, nq, C / 4, C, coef,   \
-                       mask_scale, mask_shift, dx)
-    if (mask == 1) DAM_BN_APPLY(1); else if (mask == 2) DAM_BN_APPLY(2); else if (mask == 3) DAM_BN_APPLY(3); else DAM_BN_APPLY(0);
-#undef DAM_BN_APPLY
+    const bool known = with_mask<0, 1, 2, 3>(mask, [&](auto m) {
+        hipLaunchKernelGGL(bn_bwd_apply_kernel<decltype(m)::value>, dim3(elt_blocks(nq)), dim3(256), 0, st, dy, y_mask, x, nq, C / 4,
+                           C, (const float*)coef, mask_scale, mask_shift, dx);
+    });
+    if (!known) return DAM_ERR_BAD_ARG;
     DAM_CHECK_LAUNCH();
     return DAM_OK;
 }
@@ -1102,43 +965,13 @@ extern "C" int dam_bn_backward_pair_f32(const float* dy, const float* y_mask, co
         !mean_b || !invstd_b || !dx_b || !dgamma_b || !dbeta_b || !workspace || n_pixels <= 0)
         return DAM_ERR_BAD_ARG;
     if (C % 16 || C > 1024) return DAM_ERR_UNSUPPORTED;
-    const bool fused = fa_enabled();
-    const BnLaunch l = bn_plan(n_pixels, C, fused ? fa_max_parts(C, 3) : BN_MAX_PARTS);
+    // at most fa_max_parts records, so the fused consumer's table (<= FA_PARTS_KB) is always within FA_TABLE_BYTES_MAX
+    const BnLaunch l = bn_plan(n_pixels, C, fa_max_parts(C, 3));
     if ((size_t)l.r * C * 3 * sizeof(float) > 64 * 1024) return DAM_ERR_UNSUPPORTED;
-    hipStream_t st = (hipStream_t)stream;
-    float* coef = workspace + (size_t)BN_MAX_PARTS * C * 3;
-    if (bits)
-        hipLaunchKernelGGL(bn_bwd_partial_pair_kernel<true>, dim3(l.parts), dim3(l.threads), (size_t)l.r * C * 3 * sizeof(float), st,
-                           dy, y_mask, x_a, x_b, n_pixels, C, l.q, l.r, l.ppb, mean_a, invstd_a, mean_b, invstd_b, workspace);
-    else
-        hipLaunchKernelGGL(bn_bwd_partial_pair_kernel<false>, dim3(l.parts), dim3(l.threads), (size_t)l.r * C * 3 * sizeof(float), st,
-                           dy, y_mask, x_a, x_b, n_pixels, C, l.q, l.r, l.ppb, mean_a, invstd_a, mean_b, invstd_b, workspace);
-    DAM_CHECK_LAUNCH();
-    if (fused) {
-        const FaPlan f = fa_plan(n_pixels, C);
-        if (bits)
-            hipLaunchKernelGGL(bn_bwd_fin_apply_pair_kernel<true>, dim3(f.nranges, f.nslices), dim3(FA_THREADS), 0, st, workspace, l.parts,
-                               C, f.cs, (double)n_pixels, gamma_a, mean_a, invstd_a, gamma_b, mean_b, invstd_b, training, dgamma_a,
-                               dbeta_a, dgamma_b, dbeta_b, dy, y_mask, x_a, x_b, n_pixels, f.ppr, dx_a, dx_b);
-        else
-            hipLaunchKernelGGL(bn_bwd_fin_apply_pair_kernel<false>, dim3(f.nranges, f.nslices), dim3(FA_THREADS), 0, st, workspace, l.parts,
-                               C, f.cs, (double)n_pixels, gamma_a, mean_a, invstd_a, gamma_b, mean_b, invstd_b, training, dgamma_a,
-                               dbeta_a, dgamma_b, dbeta_b, dy, y_mask, x_a, x_b, n_pixels, f.ppr, dx_a, dx_b);
-        DAM_CHECK_LAUNCH();
-        return DAM_OK;
-    }
-    hipLaunchKernelGGL(bn_bwd_finalize_pair_kernel, dim3(C), dim3(64), 0, st, workspace, l.parts, C, (double)n_pixels, gamma_a,
-                       mean_a, invstd_a, gamma_b, mean_b, invstd_b, training, dgamma_a, dbeta_a, dgamma_b, dbeta_b, coef);
-    DAM_CHECK_LAUNCH();
-    const int64_t nq = n_pixels * (C / 4);
-    if (bits)
-        hipLaunchKernelGGL(bn_bwd_apply_pair_kernel<true>, dim3(elt_blocks(nq)), dim3(256), 0, st, dy, y_mask, x_a, x_b, nq, C / 4, C,
-                           coef, dx_a, dx_b);
-    else
-        hipLaunchKernelGGL(bn_bwd_apply_pair_kernel<false>, dim3(elt_blocks(nq)), dim3(256), 0, st, dy, y_mask, x_a, x_b, nq, C / 4, C,
-                           coef, dx_a, dx_b);
-    DAM_CHECK_LAUNCH();
-    return DAM_OK;
+    const BnBwdSides<2> sd{{{x_a, gamma_a, mean_a, invstd_a, dx_a, dgamma_a, dbeta_a},
+                            {x_b, gamma_b, mean_b, invstd_b, dx_b, dgamma_b, dbeta_b}}};
+    return bn_bwd_launch<2, 1, 3>(l, false, true, bits ? 3 : 1, sd, dy, y_mask, n_pixels, C, training, nullptr, nullptr, workspace,
+                                  (hipStream_t)stream);
 }
 
 extern "C" int dam_channel_sum_f32(const float* x, int64_t n_pixels, int C, int n_real, float* out, float* workspace,

@@ -73,7 +73,7 @@ class ConvSpec:
         convolution epilogue's, or a partial pass over c) are merged INSIDE the apply launch (ops.bn_finalize_apply): no
         finalize launch between the two."""
         rs, rh = res_affine if res_affine is not None else (None, None)
-        if training and ops.FUSED_FINALIZE:
+        if training:
             c, rec = self.fwd_conv(x, w, bn, training, bias=bias, in_affine=in_affine, finalize=False)
             rec = rec if rec is not None else ops.bn_stats_partial(c)
             (m, i, sc, sh), out = ops.bn_finalize_apply(rec[0], rec[1], _bn_args(bn, training), c, relu=True, res=res,

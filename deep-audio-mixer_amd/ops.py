@@ -42,11 +42,6 @@ def pack_weights_multi(desc, n_tensors, max_total):
                'dam_conv_pack_weights_multi_f32')
 
 
-# Finalize inside the elementwise consumer (dam_bn_finalize_apply_f32; the backward entry points do the same internally):
-# DAM_BN_FUSED_FIN=0 keeps the separate finalize launches (A/B switch; the library reads the same variable)
-FUSED_FINALIZE = os.environ.get('DAM_BN_FUSED_FIN', '1') != '0'
-
-
 # strided 3x3 data gradients of the thin stages as one launch (dam_dgrad_s2_3x3_f32); DAM_NO_DGRAD_S2=1: the parity-class launches (A/B)
 DGRAD_S2 = not os.environ.get('DAM_NO_DGRAD_S2')
 dgrad_s2_launches = 0        # launches dam_dgrad_s2_3x3_f32 accepted (tests check that a shape took the one-launch form)

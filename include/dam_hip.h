@@ -411,8 +411,8 @@ int dam_bn_stats_partial_f32(const float* x, int64_t n_pixels, int C, float* wor
  * and ConvBlock2d's relu(bn(conv(x))), models/model_resnet.py:97, models/model_scalar_1s.py:184-186): every workgroup merges the
  * records of the 16 or 32 channels it applies in its prologue -- no finalize launch (4.6-5 us each, whatever it does).
  * fin: the BatchNorm's parameters and outputs as dam_bn_finalize_f32 takes them (all four outputs and the running statistics
- * are written); the remaining arguments as dam_bn_apply_f32.  DAM_BN_FUSED_FIN=0 in the environment
- * makes this (and the backward entry points below) run the separate launches instead (A/B switch). */
+ * are written); the remaining arguments as dam_bn_apply_f32.  Tables beyond 24 KB per workgroup take the separate finalize and
+ * apply launches instead. */
 int dam_bn_finalize_apply_f32(const float* partial, int parts, int C, const struct dam_bn_fin* fin, const float* x,
                               int64_t n_pixels, const float* res, const float* res_scale, const float* res_shift, int relu,
                               float* y, uint8_t* sign_bits, void* stream);

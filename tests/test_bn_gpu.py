@@ -166,9 +166,9 @@ def test_finalize_inside_the_apply_launch(ops, B, H, W, C, form):
 
 
 def test_fused_backward_equals_separate_launches(ops, monkeypatch):
-    """dam_bn_backward_f32 / _pair_f32 merge their records inside the apply launch; DAM_BN_FUSED_FIN=0 (read once per process:
-    checked through a child process) keeps the three-launch form.  Here: every mask mode on shapes that exercise one and many
-    slices, ragged ranges and the record cap, against float64."""
+    """dam_bn_backward_f32 / _pair_f32 merge their records inside the apply launch (the single form keeps the three-launch
+    form for given records beyond the table bound: the next test).  Here: every mask mode on shapes that exercise one and
+    many slices, ragged ranges and the record cap, against float64."""
     g = torch.Generator().manual_seed(12)
     for shape in [(8, 257, 33, 64), (8, 513, 65, 32), (4, 129, 17, 96), (8, 33, 5, 256), (1, 5, 3, 16)]:
         C = shape[-1]
@@ -190,3 +190,42 @@ def test_fused_backward_equals_separate_launches(ops, monkeypatch):
             dx, dgm, dbt = ops.bn_backward(dy.cuda(), y_mask, x.cuda(), gamma.cuda(), mean.detach().float().cuda(),
                                            invstd.detach().float().cuda(), True, **kw)
             close(dx, xr.grad, 1e-4); close(dgm, gr.grad, 1e-4); close(dbt, br.grad, 1e-4)
+
+
+@pytest.mark.parametrize('C,parts', [(16, 600), (16, 700), (64, 600), (64, 700), (32, 300), (32, 340)])
+@pytest.mark.parametrize('mask', ['affine', 'bits'])
+def test_backward_with_given_records_both_sides_of_the_table_bound(ops, C, parts, mask):
+    """dam_bn_backward_f32 with partials_given: records (sum dz, sum dz * xhat) that someone else left (a data-gradient
+    epilogue; here torch, over ragged chunks of the pixel axis).  The entry point merges them inside the apply launch while a
+    workgroup's table stays within parts * slice channels * 8 <= 81920 bytes (640 records at C 16 and 64, 320 at C 32) and
+    in a finalize launch of their own beyond it: both sides, both mask forms such a caller has, against float64 autograd and
+    against the entry point's own reduction pass."""
+    from deep_audio_mixer_amd import _lib
+    g = torch.Generator().manual_seed(1000 * C + parts)
+    shape = (2, 41, 33, C)
+    x, dy = torch.randn(shape, generator=g) * 2 + 1, torch.randn(shape, generator=g)
+    gamma = torch.rand(C, generator=g) + 0.5
+    xr = x.double().requires_grad_(True)
+    gr = gamma.double().requires_grad_(True)
+    br = torch.zeros(C, dtype=torch.float64, requires_grad=True)
+    mean, var = xr.mean(dim=(0, 1, 2)), xr.var(dim=(0, 1, 2), unbiased=False)
+    invstd = 1.0 / torch.sqrt(var + 1e-5)
+    torch.relu((xr - mean) * invstd * gr + br).backward(dy.double())
+    sc = (gamma.double() * invstd.detach()).float().cuda()
+    sh = (-mean.detach() * gamma.double() * invstd.detach()).float().cuda()
+    xd, dyd, gd = x.cuda(), dy.cuda(), gamma.cuda()
+    mu, iv = mean.detach().float().cuda(), invstd.detach().float().cuda()
+    y, bits = ops.bn_apply(xd, sc, sh, relu=True, sign_bits=True)
+    dz = (dyd * (y > 0)).view(-1, C).double()
+    dzx = dz * ((xd - mu) * iv).view(-1, C).double()
+    rec = torch.stack([torch.stack((a.sum(0), b.sum(0)), dim=-1)
+                       for a, b in zip(torch.tensor_split(dz, parts), torch.tensor_split(dzx, parts))]).float()
+    assert rec.shape == (parts, C, 2)
+    kw = dict(mask_affine=(sc, sh)) if mask == 'affine' else dict(mask_bits=bits)
+    buf = torch.empty(_lib.lib().dam_bn_workspace_floats(C), dtype=torch.float32, device=xd.device)
+    buf[:rec.numel()] = rec.flatten()
+    got = ops.bn_backward(dyd, None, xd, gd, mu, iv, True, partials=(buf, parts), **kw)
+    own = ops.bn_backward(dyd, None, xd, gd, mu, iv, True, **kw)
+    for a, b, want in zip(got, own, (xr.grad, gr.grad, br.grad)):
+        close(a, want, 1e-4)
+        close(a, b.cpu(), 1e-4)
