@@ -12,7 +12,7 @@ LIB_PATH = os.environ.get('DAM_LIB_PATH') or os.path.join(_HERE, 'libdam_hip.so'
 # include/dam_hip.h: bumped whenever a C signature changes (together with dam_abi_version() in csrc/dam_api.hip and
 # DAM_ABI_VERSION in the header).  libdam_hip.so is git-ignored and travels prebuilt: a stale one would read device pointers
 # as streams, so lib() refuses it instead of launching.
-EXPECTED_ABI = 22
+EXPECTED_ABI = 23
 
 _STATUS = {0: 'DAM_OK', -1: 'DAM_ERR_BAD_ARG', -2: 'DAM_ERR_UNSUPPORTED', -3: 'DAM_ERR_LAUNCH',
            -4: 'DAM_ERR_WORKSPACE'}
@@ -107,6 +107,11 @@ SIGNATURES = {
     'dam_true_peak_workspace_bytes': (c_i64, [c_i, c_i64, c_i]),
     'dam_true_peak_batch': (c_i, [c_p, c_i, c_i, c_i64, c_i, c_i64, c_i64, c_i64, c_p, c_i, c_p, c_p, c_p, c_p]),
     'dam_peak_limit_gains': (c_i, [c_p, c_p, c_i, c_i, c_d, c_p]),
+    'dam_limiter_tile_samples': (c_i64, []),
+    'dam_limiter_max_lookahead': (c_i, []),
+    'dam_limiter_max_hold': (c_i, []),
+    'dam_limiter_workspace_bytes': (c_i64, [c_i, c_i64]),
+    'dam_limiter_apply': (c_i, [c_p, c_i, c_i, c_i64, c_i, c_i64, c_i64, c_i64, c_p, c_d, c_i, c_i, c_p, c_i, c_p, c_p, c_p, c_p]),
     'dam_loudness_window_power': (c_i, [c_p, c_i, c_i, c_i, c_i, c_p, c_p, c_p]),
     'dam_loudness_curve_stats': (c_i, [c_p, c_i, c_i, c_p, c_p]),
     'dam_loudness_profile_error': (c_i, [c_p, c_p, c_i, c_i, c_i, c_p, c_p, c_p]),

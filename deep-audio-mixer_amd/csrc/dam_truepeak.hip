@@ -23,27 +23,14 @@
 // No atomics.  fmax() drops a NaN operand, so a NaN sample (and the interpolated values it poisons) is skipped; an
 // infinite sample gives an infinite peak.  Non-finite input is outside the contract.
 #include "dam_common.h"
+#include "dam_truepeak_fir.h"
 
 #include <math.h>
 
 namespace dam {
 namespace {
 
-constexpr int TP_THREADS = 256;
-constexpr int TP_RUN = 8;                              // consecutive samples per lane
-constexpr int TP_TILE = TP_THREADS * TP_RUN;           // samples per tile
-constexpr int TP_BEFORE = 5, TP_AFTER = 6;             // halo: y_p[i] reads x[i-5 .. i+6]
-constexpr int TP_SPAN = TP_TILE + TP_BEFORE + TP_AFTER;
-constexpr int TP_LOADS = (TP_SPAN + TP_THREADS - 1) / TP_THREADS;
-constexpr int TP_LDS = TP_SPAN + (TP_SPAN >> 3) + 1;   // image element e lives at e + e / 8
 constexpr int TP_MAX_BLOCKS = 2048;                    // workgroups of one launch (256 CUs x 8)
-
-// The taps are symmetric (h49[k] == h49[48 - k], by construction in dam_true_peak_taps_host), so phase 3 is phase 1
-// reversed and phase 2 is its own mirror: 18 distinct values, which stay in scalar registers.
-struct TpTaps {
-    double a[12];                                      // a[j+6] = h49[24 + 1 + 4 j]; h49[24 + 3 + 4 j] = a[5 - j]
-    double b[6];                                       // b[j+6] = h49[24 + 2 + 4 j] for j < 0; = b[5 - j] for j >= 0
-};
 
 struct TpGeo {
     int64_t n_samples;
@@ -114,22 +101,13 @@ __global__ __launch_bounds__(TP_THREADS) void true_peak_tile_kernel(const T* __r
         __syncthreads();
         if (tile + gridDim.x < tiles) fetch(tile + gridDim.x);
 
-        // w[k] = x[i0 - 5 + k], i0 = the lane's first sample; element t * 8 + k sits at t * 9 + k + k / 8
         double w[TP_RUN + TP_BEFORE + TP_AFTER];
-        const double* base = img + t * (TP_RUN + 1);
-#pragma unroll
-        for (int k = 0; k < TP_RUN + TP_BEFORE + TP_AFTER; ++k) w[k] = base[k + (k >> 3)];
+        tp_window(img, t, w);
         const int64_t left = g.n_samples - (tile * TP_TILE + (int64_t)t * TP_RUN);      // samples of the row from i0 on
 #pragma unroll
         for (int r = 0; r < TP_RUN; ++r) {
-            // x[i - j] = w[r + 5 - j]: j = -6 reads w[r + 11], j = 5 reads w[r]
-            double y0 = w[r + 11] * taps.a[0], y1 = w[r + 11] * taps.b[0], y2 = w[r + 11] * taps.a[11];
-#pragma unroll
-            for (int q = 1; q < 12; ++q) {
-                y0 = fma(w[r + 11 - q], taps.a[q], y0);
-                y1 = fma(w[r + 11 - q], taps.b[q < 6 ? q : 11 - q], y1);
-                y2 = fma(w[r + 11 - q], taps.a[11 - q], y2);
-            }
+            double y0, y1, y2;
+            tp_phases(w, r, taps, y0, y1, y2);
             if (r < left) {                            // (a sample past the row's end is zero, but its y_p is not)
                 m_sample = fmax(m_sample, fabs(w[r + TP_BEFORE]));
                 m_inter = fmax(m_inter, fmax(fabs(y0), fmax(fabs(y1), fabs(y2))));
@@ -219,11 +197,7 @@ extern "C" int dam_true_peak_batch(const void* x, int x_is_f64, int n_tracks, in
     if (gains && (n_gains <= 0 || n_gains > n_samples)) return DAM_ERR_BAD_ARG;
     const int64_t rows = (int64_t)n_tracks * channels;
     if (rows > 65535) return DAM_ERR_BAD_ARG;
-    double h[49];
-    dam_true_peak_taps_host(h);
-    TpTaps taps;
-    for (int j = -6; j <= 5; ++j) taps.a[j + 6] = h[24 + 1 + 4 * j];
-    for (int j = -6; j < 0; ++j) taps.b[j + 6] = h[24 + 2 + 4 * j];
+    const TpTaps taps = tp_taps_host();
     TpGeo g;
     g.n_samples = n_samples;
     g.track_stride = track_stride; g.sample_stride = sample_stride; g.channel_stride = channel_stride;

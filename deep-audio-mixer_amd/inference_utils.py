@@ -12,7 +12,8 @@ smoothing (dam_gains_smooth) -> sample-rate gain ramp x audio (dam_gain_ramp_app
 ``mix_song_to_wav`` the master tail, ``MasterChain``: the fused stem sum + peak normalisation (dam_mixdown_peak_normalize)
 or, with ``normalize='loudness'``, the stem sum brought to a target BS.1770 loudness (optionally held under a true-peak
 ceiling, ``ceiling_dbtp``: dam_true_peak_batch of the float64 sum, dam_peak_limit_gains on the loudness gain;
-``normalize='true_peak'`` puts the true peak AT the ceiling instead), then the PCM encoder as the graph's last node where a
+``normalize='true_peak'`` puts the true peak AT the ceiling instead; ``limiter=`` turns down only the peaks over the ceiling,
+dam_limiter_apply, so the song keeps its loudness), then the PCM encoder as the graph's last node where a
 file is asked for (dam_pcm_encode: the loudness gain is applied inside it, the host receives the file's sample bytes instead
 of the float master).  MasterChain is the single place a new output stage goes: the evaluator's WAV export runs the same one.
 ``mix_song_loudness`` ends in the batched meter instead (the per-stem loudness of the mixed
@@ -67,15 +68,21 @@ def predict_chunk_gains(model, pcm, n_stems, n_chunks, chunk_samples, window_siz
 class MasterChain:
     """The master tail, the ONE implementation of it (SongMixer kind 'master' captures it into the song's graph,
     evaluation.LoudnessEvaluator.write_sum_to_target runs it eagerly; a new output stage goes here): stem sum -> BS.1770
-    measurement -> target gain -> true-peak clamp -> gain apply or PCM encode.  It owns every buffer those steps need,
-    allocated once and only where the configuration uses it, so a captured ``render`` holds stable pointers.
+    measurement -> target gain -> look-ahead limiter -> true-peak clamp -> gain apply or PCM encode.  It owns every buffer
+    those steps need, allocated once and only where the configuration uses it, so a captured ``render`` holds stable pointers.
 
     normalize: True / False -- the sum, peak-normalised per channel or not (the callers' librosa.util.normalize);
     'loudness' -- the float64 sum brought to ``target_lufs`` (evaluation.py:59-66); 'true_peak' -- the sum scaled so that its
     true peak (dBTP) sits at ``ceiling_dbtp`` (default -1.0).  ceiling_dbtp (with 'loudness'): the gain to the target is
-    clamped to ``ceiling / true peak of the sum``, one static gain for all channels, no limiter.  encode: None (``out``
+    clamped to ``ceiling / true peak of the sum``, one static gain for all channels.  encode: None (``out``
     holds the master as ``out_dtype``) or a WAV subtype of ops.PCM_FORMATS (``enc`` holds the file's sample bytes, ``clip``
-    the clamped-sample count per channel; TPDF dither if ``dither_seed`` is given)."""
+    the clamped-sample count per channel; TPDF dither if ``dither_seed`` is given).  limiter (with 'loudness'; None / False:
+    none, True: the defaults, or {'lookahead_ms': 5.0, 'hold_ms': 20.0}): the sum at the target gain goes through the
+    look-ahead true-peak limiter (dam_limiter_apply, ceiling -1.0 dBTP unless ``ceiling_dbtp`` says otherwise) into a float64
+    limited master; the true-peak clamp then measures THAT and is the residual trim, a few 1e-5 dB, that makes the ceiling
+    exact."""
+
+    LIMITER_DEFAULTS = {'lookahead_ms': 5.0, 'hold_ms': 20.0}
 
     @staticmethod
     def rules(normalize, ceiling_dbtp, encode):
@@ -90,9 +97,28 @@ class MasterChain:
             raise ValueError("ceiling_dbtp needs normalize 'loudness' or 'true_peak'")
         return normalize, None if ceiling_dbtp is None else float(ceiling_dbtp)
 
+    @staticmethod
+    def limiter_rules(limiter, normalize, ceiling):
+        """What ``limiter`` may be, given what ``rules`` returned -> (None or (lookahead_ms, hold_ms), ceiling); ValueError
+        otherwise.  A limiter without a ceiling takes -1.0 dBTP."""
+        if limiter is None or limiter is False:
+            return None, ceiling
+        if limiter is True:
+            limiter = {}
+        if not isinstance(limiter, dict) or set(limiter) - set(MasterChain.LIMITER_DEFAULTS):
+            raise ValueError('limiter must be None, a bool or a dict with keys of %s, got %r'
+                             % (sorted(MasterChain.LIMITER_DEFAULTS), limiter))
+        if normalize != 'loudness':
+            raise ValueError("limiter needs normalize 'loudness'")
+        times = tuple(float(limiter.get(k, v)) for k, v in MasterChain.LIMITER_DEFAULTS.items())
+        if not all(t > 0.0 for t in times):
+            raise ValueError('limiter times must be positive, got %r' % (limiter,))
+        return times, -1.0 if ceiling is None else ceiling
+
     def __init__(self, channels, n_samples, device, normalize=True, out_dtype=torch.float64, sr=44100, target_lufs=-20.0,
-                 ceiling_dbtp=None, encode=None, dither_seed=None):
+                 ceiling_dbtp=None, encode=None, dither_seed=None, limiter=None):
         self.normalize, self.ceiling = self.rules(normalize, ceiling_dbtp, encode)
+        self.limiter, self.ceiling = self.limiter_rules(limiter, self.normalize, self.ceiling)
         self.encode, self.dither_seed = encode, dither_seed
         scaled = self.normalize in ('loudness', 'true_peak')             # the float64 sum times one measured gain
         f64 = dict(dtype=torch.float64, device=device)
@@ -116,6 +142,19 @@ class MasterChain:
             self.free_gain = torch.empty(1, **f64) if self.normalize == 'loudness' else torch.full((1,), float('inf'), **f64)
             self.tp = torch.empty((1, channels), **f64)
             self.sp = torch.empty((1, channels), **f64)
+        if self.limiter is not None:
+            # look-ahead and hold in samples (ValueError beyond the kernel's caps), the limited master, its statistics, its
+            # loudness and the kernel's workspace
+            self.lookahead, self.hold = (ops.limiter_samples(ms, sr) for ms in self.limiter)
+            _, max_lookahead, max_hold = ops.limiter_geometry()
+            if self.lookahead > max_lookahead or self.hold > max_hold:
+                raise ValueError('limiter: %d / %d samples of look-ahead / hold at %d Hz exceed the caps %d / %d'
+                                 % (self.lookahead, self.hold, sr, max_lookahead, max_hold))
+            self.limited = torch.empty((channels, n_samples), **f64)
+            self.min_gain = torch.empty(1, **f64)
+            self.n_limited = torch.empty(1, dtype=torch.int64, device=device)
+            self.limited_lufs = torch.empty(1, **f64)
+            self.limiter_ws = torch.empty(ops._lib.lib().dam_limiter_workspace_bytes(1, n_samples) // 8, **f64)
         self.sum = self.mix if scaled else self.out
         self.ws = torch.empty(ops._lib.lib().dam_mixdown_workspace_elems(channels), dtype=self.sum.dtype, device=device)
 
@@ -127,29 +166,51 @@ class MasterChain:
         if self.normalize == 'loudness':
             self.meter.integrated_loudness_batch(self.mix.t().unsqueeze(0), out=self.lufs)
             loudness.target_gains_device(self.lufs, self.target, out=self.master_gain if self.ceiling is None else self.free_gain)
-        if self.ceiling is not None:
+        source = self.sum                          # what master_gain scales
+        if self.limiter is not None:
+            # the sum at the target gain, its peaks turned down; the clamp below measures the result: master_gain is the trim
+            ops.limiter_apply(self.mix.t().unsqueeze(0), self.ceiling, self.lookahead, self.hold, pre_gain=self.free_gain,
+                              out=self.limited, min_gain_out=self.min_gain, n_limited_out=self.n_limited,
+                              workspace=self.limiter_ws)
+            source = self.limited
+            self.master_gain.fill_(1.0)
+        elif self.ceiling is not None:
             self.master_gain.copy_(self.free_gain)
-            ops.true_peak_batch(self.mix.t().unsqueeze(0), out=self.tp, sample_peak_out=self.sp)
+        if self.ceiling is not None:
+            ops.true_peak_batch(source.t().unsqueeze(0), out=self.tp, sample_peak_out=self.sp)
             ops.peak_limit_gains(self.master_gain, self.tp, self.ceiling)          # the maximum over the channels
         if self.encode is not None:                # mix * gain is rounded once to float64 either way: the same samples
-            ops.pcm_encode(self.sum, self.encode, scale=self.master_gain, dither_seed=self.dither_seed, out=self.enc,
+            ops.pcm_encode(source, self.encode, scale=self.master_gain, dither_seed=self.dither_seed, out=self.enc,
                            clip_count=self.clip)
         elif scaled:
-            ops.gain_ramp_apply(self.mix, self.master_gain, out=self.out)
+            ops.gain_ramp_apply(source, self.master_gain, out=self.out)
+        if self.limiter is not None:               # the loudness of the limited master; peaks() adds the trim
+            self.meter.integrated_loudness_batch(self.limited.t().unsqueeze(0), out=self.limited_lufs)
 
     def peaks(self):
         """The peak measurement of the last render of a chain with a ceiling, from the device tensors the graph wrote:
         {'true_peak_db': [per channel], 'sample_peak_db': [per channel]} of the master as rendered (the measured sum times
         the gain that was applied, before any quantisation), 'limited': whether the ceiling, not the loudness target, set
-        that gain (always so for normalize='true_peak' unless the sum is silent), and 'gain', the gain itself."""
+        that gain (always so for normalize='true_peak' unless the sum is silent), and 'gain', the gain itself.  With a
+        limiter the same keys describe the limited master ('gain': the target gain times the trim; 'limited': the limiter
+        reduced a sample or the trim is below 1) and four more say what the limiter did: 'max_reduction_db' (20 log10 of its
+        smallest gain, 0.0: untouched), 'limited_share' (the share of samples with a gain below 1), 'trim_db' (the residual
+        static gain that makes the ceiling exact) and 'loudness_lufs' (BS.1770, of the master as rendered)."""
         if self.ceiling is None:
             raise ValueError('this master chain was built without ceiling_dbtp')
         tp, sp = self.tp.cpu().numpy()[0], self.sp.cpu().numpy()[0]
         gain, free = float(self.master_gain.cpu()[0]), float(self.free_gain.cpu()[0])
         with np.errstate(divide='ignore', invalid='ignore'):
-            return {'true_peak_db': [float(v) for v in 20.0 * np.log10(tp * gain)],
-                    'sample_peak_db': [float(v) for v in 20.0 * np.log10(sp * gain)],
-                    'limited': bool(gain < free), 'gain': gain}
+            out = {'true_peak_db': [float(v) for v in 20.0 * np.log10(tp * gain)],
+                   'sample_peak_db': [float(v) for v in 20.0 * np.log10(sp * gain)],
+                   'limited': bool(gain < free), 'gain': gain}
+            if self.limiter is not None:
+                min_gain, trim_db = float(self.min_gain.cpu()[0]), float(20.0 * np.log10(gain))
+                out.update({'limited': bool(min_gain < 1.0 or gain < 1.0), 'gain': free * gain,
+                            'max_reduction_db': float(20.0 * np.log10(min_gain)),
+                            'limited_share': int(self.n_limited.cpu()[0]) / self.limited.shape[1], 'trim_db': trim_db,
+                            'loudness_lufs': float(self.limited_lufs.cpu()[0]) + trim_db})
+        return out
 
 
 class SongMixer:
@@ -158,16 +219,17 @@ class SongMixer:
 
     def __init__(self, model, n_stems, channels, n_samples, dtype, chunk_samples, kind, normalize=True,
                  out_dtype=torch.float64, use_graph=True, hop_length=1024, sr=44100, target_lufs=-20.0, encode=None,
-                 dither_seed=None, ceiling_dbtp=None):
-        """normalize, out_dtype, sr, target_lufs, encode, dither_seed, ceiling_dbtp: what MasterChain takes, for kind
-        'master' (the other kinds accept neither ``encode`` nor a ceiling).  With ``encode`` the master is quantised by the
-        last node of the same graph and ``run`` returns its sample bytes and the clipped-sample count; ``peaks()`` reports
-        the true-peak measurement of the last run."""
+                 dither_seed=None, ceiling_dbtp=None, limiter=None):
+        """normalize, out_dtype, sr, target_lufs, encode, dither_seed, ceiling_dbtp, limiter: what MasterChain takes, for kind
+        'master' (the other kinds accept neither ``encode`` nor a ceiling nor a limiter).  With ``encode`` the master is
+        quantised by the last node of the same graph and ``run`` returns its sample bytes and the clipped-sample count;
+        ``peaks()`` reports the true-peak measurement of the last run."""
         if kind not in ('stems', 'master', 'spectral', 'loudness'):
             raise ValueError(kind)
         self.normalize, self.ceiling = MasterChain.rules(normalize, ceiling_dbtp, encode)
-        if kind != 'master' and (encode is not None or self.ceiling is not None):
-            raise ValueError("encode and ceiling_dbtp need kind='master'")
+        self.limiter, self.ceiling = MasterChain.limiter_rules(limiter, self.normalize, self.ceiling)
+        if kind != 'master' and (encode is not None or self.ceiling is not None or self.limiter is not None):
+            raise ValueError("encode, ceiling_dbtp and limiter need kind='master'")
         self.encode = encode
         self.model, self.kind = model, kind
         self.dev = next(model.parameters()).device
@@ -198,7 +260,7 @@ class SongMixer:
             self.out = torch.empty(n_stems, dtype=torch.float64, device=dev)                       # LUFS of every mixed stem
         else:
             self.chain = MasterChain(channels, n_samples, dev, self.normalize, out_dtype, sr, target_lufs, self.ceiling, encode,
-                                     dither_seed)
+                                     dither_seed, limiter)
             if encode is not None:
                 self.enc, self.clip = self.chain.enc, self.chain.clip
             if self.chain.out is not None:                     # (no float master is kept beside an encoded, gain-scaled one)
@@ -289,7 +351,7 @@ _mixers = {}
 
 
 def _mixer(model, stems, loaded_tracks, chunk_length, sr, kind, normalize, out_dtype, hop_length=1024, target_lufs=-20.0,
-           encode=None, dither_seed=None, ceiling_dbtp=None):
+           encode=None, dither_seed=None, ceiling_dbtp=None, limiter=None):
     first = np.asarray(loaded_tracks[stems[0]])
     if first.ndim != 2:
         raise ValueError('loaded_tracks[track] must be [channels, n] arrays')
@@ -298,16 +360,17 @@ def _mixer(model, stems, loaded_tracks, chunk_length, sr, kind, normalize, out_d
     if normalize not in ('loudness', 'true_peak'):
         normalize = bool(normalize)            # the callers' ``if normalize:`` (inference.ipynb cells 9/11)
     normalize, ceiling_dbtp = MasterChain.rules(normalize, ceiling_dbtp, encode)
+    times, ceiling_dbtp = MasterChain.limiter_rules(limiter, normalize, ceiling_dbtp)
     if normalize != 'loudness':
         target_lufs = None                     # (not part of such a mixer: one key whatever the caller passed)
     key = (id(model), len(stems), ch, n, dt, chunk_length * sr, kind, normalize, out_dtype, hop_length, sr, target_lufs,
-           encode, dither_seed if encode is not None else None, ceiling_dbtp)
+           encode, dither_seed if encode is not None else None, ceiling_dbtp, times)
     m = _mixers.get(key)
     if m is None:
         _mixers.clear()                        # one geometry at a time: a song's buffers are hundreds of MB
         m = SongMixer(model, len(stems), ch, n, dt, chunk_length * sr, kind, normalize, out_dtype, hop_length=hop_length, sr=sr,
                       target_lufs=-20.0 if target_lufs is None else target_lufs, encode=encode, dither_seed=dither_seed,
-                      ceiling_dbtp=ceiling_dbtp)
+                      ceiling_dbtp=ceiling_dbtp, limiter=limiter)
         _mixers[key] = m
     np_dt = np.float32 if dt == torch.float32 else np.float64
     return m, [np.asarray(loaded_tracks[t], dtype=np_dt) for t in stems]
@@ -340,7 +403,7 @@ def mix_song_loudness(dataset, model, loaded_tracks: dict, chunk_length=1, sr=44
 
 
 def mix_song_to_master(dataset, model, loaded_tracks: dict, chunk_length=1, sr=44100, normalize=True, dtype=np.float64,
-                       target_lufs=-20.0, ceiling_dbtp=None):
+                       target_lufs=-20.0, ceiling_dbtp=None, limiter=None):
     """mix_song_smooth followed by what every caller of the reference does next (inference.ipynb cells 9/11,
     evaluation.py:59-66): ``track_sum = np.sum(list(mixed_tracks.values()), axis=0)`` and, if ``normalize``,
     ``librosa.util.normalize(track_sum, axis=1)`` -- fused into one pass over the song on the GPU (the per-stem mixed
@@ -348,27 +411,30 @@ def mix_song_to_master(dataset, model, loaded_tracks: dict, chunk_length=1, sr=4
     sum is measured (BS.1770) and scaled to ``target_lufs``, in the same graph.  ``ceiling_dbtp`` (with 'loudness'): the
     master's true peak is held at or under that many dBTP -- at ``target_lufs`` if its peaks allow, quieter if not (one
     static gain; SongMixer.peaks() of the cached mixer tells which).  ``normalize='true_peak'``: the plain sum scaled so
-    that its true peak sits at ``ceiling_dbtp`` (default -1.0), one gain for all channels.
+    that its true peak sits at ``ceiling_dbtp`` (default -1.0), one gain for all channels.  ``limiter`` (with 'loudness';
+    True or {'lookahead_ms', 'hold_ms'}): only the peaks over the ceiling (-1.0 dBTP unless given) are turned down, by a gain
+    that dips ahead of each and ramps back after it, so the master stays near ``target_lufs``; SongMixer.peaks() reports the
+    largest reduction, the share of samples touched and the loudness reached.
     Returns (mix ndarray[channels, n], raw_gains, smooth_gains)."""
     out_dt = torch.float32 if np.dtype(dtype) == np.float32 else torch.float64
     _, _, out, raw_gains, smooth_gains = _mix_song(dataset, model, loaded_tracks, chunk_length, sr, 'master', normalize, out_dt,
-                                                   target_lufs=target_lufs, ceiling_dbtp=ceiling_dbtp)
+                                                   target_lufs=target_lufs, ceiling_dbtp=ceiling_dbtp, limiter=limiter)
     return out, raw_gains, smooth_gains
 
 
 def mix_song_to_wav(dataset, model, loaded_tracks: dict, path, chunk_length=1, sr=44100, normalize=True, subtype='PCM_16',
-                    target_lufs=-20.0, dither_seed=None, ceiling_dbtp=None):
+                    target_lufs=-20.0, dither_seed=None, ceiling_dbtp=None, limiter=None):
     """mix_song_to_master followed by the callers' ``sf.write(path, master.T, sr)`` (inference.ipynb cells 9/11;
     evaluation.py:59-66 with ``normalize='loudness'``): the float64 master is quantised to ``subtype`` by the last node of
     the song's graph (ops.pcm_encode, TPDF dither if ``dither_seed`` is given), so the host receives the file's sample
     bytes -- a quarter of the float64 master for 'PCM_16' -- and writes them behind a WAV header.  The samples are those
     tests/_pcm_ref.py's quantiser makes of mix_song_to_master(..., dtype=float64).  ``ceiling_dbtp`` / ``normalize='true_peak'``
-    as there: with a ceiling below 0 dBTP the encoder has nothing to clip.
+    and ``limiter`` as there: with a ceiling below 0 dBTP the encoder has nothing to clip.
     Returns (clipped sample count, raw_gains, smooth_gains); warns (RuntimeWarning) when samples had to be clipped."""
     from .data.dataset_utils import write_wav_bytes
     m, _, (payload, clipped), raw_gains, smooth_gains = _mix_song(
         dataset, model, loaded_tracks, chunk_length, sr, 'master', normalize, torch.float64, target_lufs=target_lufs,
-        encode=subtype, dither_seed=dither_seed, ceiling_dbtp=ceiling_dbtp)
+        encode=subtype, dither_seed=dither_seed, ceiling_dbtp=ceiling_dbtp, limiter=limiter)
     write_wav_bytes(path, payload, sr, m.channels, subtype, m.n, clipped)
     return clipped, raw_gains, smooth_gains
 

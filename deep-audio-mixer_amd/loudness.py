@@ -27,6 +27,7 @@ Peaks -- ``pyln.normalize.peak`` and the true peak (BS.1770 Annex 2 / EBU R128: 
     dbtp = true_peak(data)                               # per channel, numpy
     tp = true_peak_batch(pcm.transpose(1, 2))            # [N, channels] linear, CUDA float64, no synchronisation
     limit_gains_device(gain, tp, -1.0)                   # gain = min(gain, ceiling / max over channels), on the device
+    out, info = limit_true_peak(data, 44100, -1.0)       # look-ahead limiter: only the peaks are turned down
 
 The interpolator is this package's own 49-tap windowed sinc (include/dam_hip.h); parity with libebur128 is not claimed.
 
@@ -415,6 +416,39 @@ def limit_gains_device(gains, peaks, ceiling_db):
     channels).  A zero peak leaves the gain alone.  Returns gains; no host synchronisation (dam_peak_limit_gains)."""
     from . import ops
     return ops.peak_limit_gains(gains, peaks, ceiling_db)
+
+
+def limit_true_peak_device(data, rate, ceiling_dbtp=-1.0, lookahead_ms=5.0, hold_ms=20.0, pre_gain=None, out_dtype=None):
+    """Look-ahead true-peak limiter on the device: data CUDA float32/float64 [N, samples, channels] with any strides (N
+    masters, the channels of each limited together), pre_gain an optional CUDA float64 [N] applied first.  Returns
+    (limited planar [N, channels, samples], float64 unless out_dtype is given; min_gain CUDA float64 [N]; n_limited CUDA
+    int64 [N]).  The gain dips ``lookahead_ms`` before a peak that would pass ``ceiling_dbtp``, holds ``hold_ms`` behind it
+    and ramps back linearly (dam_limiter_apply); where nothing comes near the ceiling the samples pass bit for bit.  The true
+    peak of the result can exceed the ceiling by a few 1e-5 dB.  No host synchronisation."""
+    from . import ops
+    if not torch.is_tensor(data):
+        raise ValueError('Data must be of type torch.Tensor.')
+    _lib.require_cuda(data, pre_gain)
+    if data.dtype not in (torch.float32, torch.float64):
+        raise ValueError('Data must be floating point.')
+    if data.dim() != 3:
+        raise ValueError('Audio must be [tracks, samples, channels].')
+    return ops.limiter_apply(data, ceiling_dbtp, ops.limiter_samples(lookahead_ms, rate), ops.limiter_samples(hold_ms, rate),
+                             pre_gain=pre_gain, out_dtype=out_dtype)
+
+
+def limit_true_peak(data, rate, ceiling_dbtp=-1.0, lookahead_ms=5.0, hold_ms=20.0):
+    """One [samples] or [samples, channels] array (numpy or torch) through the look-ahead true-peak limiter, in the style of
+    normalize_peak: returns (limited, info) with ``limited`` a numpy array of data's shape and dtype and info =
+    {'max_reduction_db': 20 log10 of the smallest gain (0.0: untouched), 'limited_share': the share of samples whose gain is
+    below 1, 'lookahead_samples', 'hold_samples'}."""
+    from . import ops
+    x = _as_device_2d(data)
+    L, H = ops.limiter_samples(lookahead_ms, rate), ops.limiter_samples(hold_ms, rate)
+    out, min_gain, n_limited = ops.limiter_apply(x.unsqueeze(0), ceiling_dbtp, L, H, out_dtype=x.dtype)
+    limited = out[0].t().cpu().numpy().reshape(tuple(data.shape))
+    return limited, {'max_reduction_db': float(20.0 * np.log10(min_gain.item())),
+                     'limited_share': n_limited.item() / x.shape[0], 'lookahead_samples': L, 'hold_samples': H}
 
 
 def gated_loudness(z):

@@ -868,6 +868,68 @@ def peak_limit_gains(gains, peaks, ceiling_db):
     return gains
 
 
+# ----------------------------------------------------------------------------- look-ahead true-peak limiter
+def limiter_geometry():
+    """(samples one workgroup owns, largest look-ahead, largest hold) of dam_limiter_apply, asked of the library."""
+    L = _lib.lib()
+    return L.dam_limiter_tile_samples(), L.dam_limiter_max_lookahead(), L.dam_limiter_max_hold()
+
+
+def limiter_samples(ms, sr):
+    """A look-ahead or hold time in milliseconds as samples: max(1, int(ms * sr / 1000 + 0.5))."""
+    return max(1, int(float(ms) * sr / 1000.0 + 0.5))
+
+
+def limiter_apply(data, ceiling_db, lookahead, hold, pre_gain=None, out=None, out_dtype=None, min_gain_out=None,
+                  n_limited_out=None, workspace=None):
+    """data: CUDA float32 / float64 [N, samples, channels] with any strides (planar [N, channels, n] storage is passed as
+    ``pcm.transpose(1, 2)``, no copy): N row sets, the channels of each limited together so that the true peak of
+    ``data * pre_gain`` stays at ``ceiling_db`` dBTP (include/dam_hip.h: dam_limiter_apply states the definition).
+    lookahead, hold: samples, 1 .. the caps of limiter_geometry() (ValueError beyond them).  pre_gain: optional CUDA float64
+    [N], multiplied in before limiting.  Returns (out planar [N, channels, samples] of ``out_dtype`` (float64 unless given),
+    min_gain float64 [N], n_limited int64 [N]).  workspace: optional float64 tensor of dam_limiter_workspace_bytes / 8
+    elements.  No host synchronisation, hipGraph-capturable."""
+    _lib.require_cuda(data, pre_gain, out, min_gain_out, n_limited_out, workspace)
+    xk = _audio_kind(data, 'data')
+    if data.dim() != 3:
+        raise ValueError('limiter_apply: [row sets, samples, channels] expected, got shape %s' % (tuple(data.shape),))
+    N, n, ch = data.shape
+    if N < 1 or n < 1 or ch < 1 or N > 65535:
+        raise ValueError('limiter_apply: 1..65535 row sets and at least one sample and channel expected, got %s'
+                         % (tuple(data.shape),))
+    L = _lib.lib()
+    lookahead, hold = int(lookahead), int(hold)
+    if not 1 <= lookahead <= L.dam_limiter_max_lookahead() or not 1 <= hold <= L.dam_limiter_max_hold():
+        raise ValueError('limiter_apply: lookahead must be 1..%d samples and hold 1..%d, got %d and %d'
+                         % (L.dam_limiter_max_lookahead(), L.dam_limiter_max_hold(), lookahead, hold))
+    if pre_gain is not None and (pre_gain.dtype != torch.float64 or pre_gain.numel() != N or not pre_gain.is_contiguous()):
+        raise ValueError('limiter_apply: pre_gain must be a contiguous float64 tensor of %d elements' % N)
+    dev = data.device
+    if out is None:
+        out = torch.empty((N, ch, n), dtype=out_dtype or torch.float64, device=dev)
+    elif out.numel() != N * ch * n or not out.is_contiguous():
+        raise ValueError('limiter_apply: out must be a contiguous tensor of %d x %d x %d elements' % (N, ch, n))
+    ok = _audio_kind(out, 'out')
+    if min_gain_out is None:
+        min_gain_out = torch.empty(N, dtype=torch.float64, device=dev)
+    if n_limited_out is None:
+        n_limited_out = torch.empty(N, dtype=torch.int64, device=dev)
+    for o, dt in ((min_gain_out, torch.float64), (n_limited_out, torch.int64)):
+        if o.dtype != dt or o.numel() != N or not o.is_contiguous():
+            raise ValueError('limiter_apply: min_gain_out / n_limited_out must be contiguous float64 / int64 tensors of %d' % N)
+    need = L.dam_limiter_workspace_bytes(N, n) // 8
+    if workspace is None:
+        workspace = torch.empty(need, dtype=torch.float64, device=dev)
+    elif workspace.dtype != torch.float64 or workspace.numel() < need or not workspace.is_contiguous():
+        raise ValueError('limiter_apply: workspace must be a contiguous float64 tensor of at least %d elements' % need)
+    with torch.cuda.device(dev):
+        _lib.check(L.dam_limiter_apply(_lib.ptr(data), xk, N, n, ch, data.stride(0), data.stride(1), data.stride(2),
+                                       _lib.ptr(pre_gain), float(10.0 ** (float(ceiling_db) / 20.0)), lookahead, hold,
+                                       _lib.ptr(out), ok, _lib.ptr(min_gain_out), _lib.ptr(n_limited_out), _lib.ptr(workspace),
+                                       _lib.stream()), 'dam_limiter_apply')
+    return out, min_gain_out, n_limited_out
+
+
 # ----------------------------------------------------------------------------- dropout
 _dropout_counters = {}
 

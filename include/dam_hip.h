@@ -55,7 +55,7 @@ struct dam_bn_bwd_sums; /* defined in the BatchNorm section */
 /* Library / build identification ("gfx950").  DAM_ABI_VERSION is bumped whenever a signature below changes; a binding
  * compares dam_abi_version() of the library it loaded with the version it was written against and refuses a stale one
  * (deep-audio-mixer_amd/_lib.py: EXPECTED_ABI). */
-#define DAM_ABI_VERSION 22
+#define DAM_ABI_VERSION 23
 const char* dam_arch(void);
 int dam_abi_version(void);
 
@@ -656,6 +656,50 @@ int dam_true_peak_batch(const void* x, int x_is_f64, int n_tracks, int64_t n_sam
                         double* sample_peak, double* true_peak, void* workspace, void* stream);
 int dam_peak_limit_gains(double* gains, const double* peaks, int n_gains, int peaks_per_gain, double ceiling_lin,
                          void* stream);
+
+/* ---------------------------------------------------------------------------------
+ * Look-ahead true-peak limiter: a time-varying gain that holds the reconstructed waveform of a row set (the channels of one
+ * master, limited together) under a ceiling, where dam_peak_limit_gains can only turn the whole signal down.  Everything is
+ * float64 and closed form: no recurrence, no state, every output sample a function of a bounded input window.
+ *   Per row set: rows x[c][i] (c < channels, i in [0, n)), the scalar s = pre_gain[set] (1 if pre_gain is NULL), the linear
+ *   ceiling `ceil` = 10^(dBTP/20) > 0, the look-ahead L >= 1 and the hold H >= 1 in samples.
+ *     1. xs[c][i] = (double)x[c][i] * s                                              (one rounding)
+ *     2. demand   d[i] = max_c max(|xs[c][i]|, |y_1[c][i]|, |y_2[c][i]|, |y_3[c][i]|), y_p exactly the interpolated phase of
+ *        dam_true_peak_batch: the same 49 taps, xs = 0 outside the row, 12 products added in the order j = -6 .. 5.
+ *     3. required gain  r[i] = min(1, ceil / d[i]); r[i] = 1 where d[i] = 0 and for i outside [0, n).
+ *     4. hold and look-ahead  m[j] = min_{k in [j-H, j+L]} r[k]                      (a minimum: exact and order-free)
+ *     5. attack / release ramp  g[i] = (sum_{j=i-L..i} m[j]) / (double)(L+1), each g[i] its own sum of L+1 terms added in
+ *        the order j = i-L .. i -- never a running sum or a prefix difference (as dam_loudness_window_power).  Every
+ *        window [j-H, j+L] with j in [i-L, i] contains [i-H, i], so g[i] <= r[k] for k in [i-H, i]: the samples on both
+ *        sides of every inter-sample value carry a gain no larger than that value asks for (hence H >= 1).
+ *     6. out[c][i] = xs[c][i] * g[i], converted to the output type.
+ *     7. min_gain = min_i g[i];  n_limited = #{i : g[i] < 1}.
+ *   Latency is zero in file time (the look-ahead reads samples that are already resident).  Where d <= ceil over
+ *   [i-H-L, i+2L], g[i] = (L+1) * 1.0 / (L+1) = 1.0 exactly and out == xs bit for bit.  The true peak of `out` can exceed the
+ *   ceiling by a few 1e-5 dB (interpolating a product is not the product of the interpolations): callers that need the
+ *   ceiling exactly measure `out` and trim (inference_utils.MasterChain).  tests/_limiter_ref.py restates this in numpy.
+ *   dam_limiter_apply: n_sets row sets in one set of launches.  Sample i of channel c of set b is
+ *     x[b*set_stride + i*sample_stride + c*channel_stride] (element strides, float32 or float64 by x_is_f64), as
+ *     dam_true_peak_batch addresses a track.  pre_gain: device float64 [n_sets] or NULL.  out: planar, contiguous
+ *     [n_sets][channels][n_samples], float32 or float64 (out_is_f64); it must not overlap x.  min_gain (device float64
+ *     [n_sets]) and n_limited (device int64 [n_sets]) may each be NULL.  workspace: dam_limiter_workspace_bytes(n_sets,
+ *     n_samples) bytes, 8-byte aligned (r per sample and two partials per tile).  Stateless, allocates nothing, does not
+ *     synchronise, no atomics, hipGraph-capturable; out, min_gain and n_limited of a row set depend on neither the launch
+ *     geometry nor the other row sets (bitwise).  Argument errors (NULL x / out / workspace; a non-positive count; more than
+ *     65535 row sets; a ceiling that is not > 0; lookahead outside 1 .. dam_limiter_max_lookahead(); hold outside
+ *     1 .. dam_limiter_max_hold(), in this order) return DAM_ERR_BAD_ARG.  Non-finite samples or gains are outside the
+ *     contract.
+ *   dam_limiter_tile_samples: the samples one workgroup owns, for tests that place tile boundaries.
+ *   dam_limiter_max_lookahead / dam_limiter_max_hold: the caps (512 / 4096 samples: 10 ms / 85 ms at 48 kHz), set by the
+ *     LDS image of a tile and its halo.
+ * --------------------------------------------------------------------------------- */
+int64_t dam_limiter_tile_samples(void);
+int dam_limiter_max_lookahead(void);
+int dam_limiter_max_hold(void);
+int64_t dam_limiter_workspace_bytes(int n_sets, int64_t n_samples);
+int dam_limiter_apply(const void* x, int x_is_f64, int n_sets, int64_t n_samples, int channels, int64_t set_stride,
+                      int64_t sample_stride, int64_t channel_stride, const double* pre_gain, double ceiling_lin, int lookahead,
+                      int hold, void* out, int out_is_f64, double* min_gain, int64_t* n_limited, void* workspace, void* stream);
 
 /* ---------------------------------------------------------------------------------
  * Loudness over time: momentary (400 ms) and short-term (3 s) loudness as EBU R128 names them, the loudness range of
