@@ -20,6 +20,12 @@ The reference's spreadsheet (openpyxl) stays out: ``process_songlist`` returns t
 window (one every 100 ms; loudness.profile_error_device) -- '*_st_error' beside every '*_error' -- and the loudness range
 (EBU Tech 3342) of the reference stems.  Two mixes of equal integrated loudness per stem, one of which is 3 dB hot in the
 verses and 3 dB shy in the choruses, read the same '*_error'; their '*_st_error' differ.
+
+``spectral=True`` adds the tonal axis the model is trained on (model_trainer.py:34-35 minimises a spectrogram distance,
+the loudness errors only see level): every variant's long-term average spectrum in third-octave bands against the
+reference mix's, each relative to its own total (spectrum.band_power_mix / balance_error_device) -- '*_spec_error' beside
+every '*_error', in dB -- and 'ltas', the two spectra themselves.  Two mixes of equal loudness error, one of them
+bass-heavy, differ here; scaling every stem by a common gain changes neither figure.
 """
 import os
 from collections import OrderedDict
@@ -28,7 +34,7 @@ from statistics import mean
 import numpy as np
 import torch
 
-from . import inference_utils, staging
+from . import inference_utils, spectrum, staging
 from .loudness import Meter, curve_stats_device, normalize_loudness, profile_error_device
 from .models.baselines.mean_loudness_model import MeanLoudnessModel
 from .models.baselines.random_model import RandomModel
@@ -97,6 +103,31 @@ class LoudnessEvaluator:
         pcm = stems if torch.is_tensor(stems) else torch.stack([stems[name] for name in self.keys])
         return self.meter.short_term_loudness_batch(pcm.transpose(1, 2), gains=gains)
 
+    SPECTRAL_DEFAULTS = {'n_fft': 8192, 'hop': None, 'fraction': 3, 'f_lo': 25.0, 'f_hi': 20000.0}     # hop None: n_fft / 2
+
+    def _spectral_args(self, spectral):
+        """``spectral`` as the whole-song methods take it (True, or a dict with any of n_fft, hop, fraction, f_lo, f_hi)
+        -> (n_fft, hop, edges, centres)."""
+        given = {} if spectral is True else dict(spectral)
+        unknown = set(given) - set(self.SPECTRAL_DEFAULTS)
+        if unknown:
+            raise ValueError('spectral: unknown keys %s (expected any of %s)' % (sorted(unknown), sorted(self.SPECTRAL_DEFAULTS)))
+        o = dict(self.SPECTRAL_DEFAULTS, **given)
+        hop = o['n_fft'] // 2 if o['hop'] is None else o['hop']
+        edges, centres = spectrum.band_edges(self.sr, o['n_fft'], o['fraction'], o['f_lo'], o['f_hi'])
+        return o['n_fft'], hop, edges, centres
+
+    def evaluate_spectrum_batch(self, stems, gains=None, **spectral):
+        """Band powers of the stem sum (long-term average spectrum in fractional-octave bands at the evaluator's rate),
+        measured as ``sum of stem * gain ramp`` where gains are given, without that sum being written.  stems as
+        evaluate_loudness_batch takes them; gains: None, CUDA float64 [stems] or [stems, n_gains] (one mix), or
+        [R, stems, n_gains] (R mixes in one call); keywords n_fft, hop, fraction, f_lo, f_hi (8192, n_fft / 2, 3, 25, 20000)
+        -> CUDA float64 [R, bands]; spectrum.relative_levels_db turns a row into dB re its total.  Nothing comes to the
+        host."""
+        n_fft, hop, edges, _ = self._spectral_args(spectral)
+        pcm = stems if torch.is_tensor(stems) else torch.stack([stems[name] for name in self.keys])
+        return spectrum.band_power_mix(pcm.transpose(1, 2), gains, n_fft=n_fft, hop=hop, edges=edges)
+
     @staticmethod
     def _profile(per_track_loudness):
         avg_loudness = mean(per_track_loudness)
@@ -136,7 +167,7 @@ class LoudnessEvaluator:
 
     def process_song_tracks(self, loaded_tracks: dict, reference_tracks: dict, song_name: str, n_random_samples: int = 5,
                             chunk_length: int = 2, write_wavs_to_disk=False, results_dir='./experiment',
-                            ceiling_dbtp=None, dynamics=False, limiter=None) -> dict:
+                            ceiling_dbtp=None, dynamics=False, limiter=None, spectral=False) -> dict:
         """evaluation.py:77-116 on stems already in memory ({name: ndarray [channels, n]} each): the loudness profile of
         ``reference_tracks`` against the profiles of ``loaded_tracks`` summed as they are ('sum_error'), normalised to the
         training set's mean loudness ('loudnorm_error'), mixed by the model ('mix_error') and scaled by random gains
@@ -149,7 +180,13 @@ class LoudnessEvaluator:
         'random_st_error' -- every variant's error taken per short-term window instead of per song, from the gains the
         variant already passes to the meter -- and 'lra' {name: LU}, the loudness range of each reference stem; the other
         keys, their values and the order of the random draws do not depend on it.  The reference mix and the stems must
-        then be of one length."""
+        then be of one length.
+        spectral (True, or a dict with any of n_fft, hop, fraction, f_lo, f_hi; defaults 8192, n_fft / 2, 3, 25, 20000): the
+        stats gain, after any dynamics keys, 'sum_spec_error', 'loudnorm_spec_error', 'mix_spec_error', 'random_spec_error'
+        (the mean over the draws) -- the spectral-balance error in dB of every variant's stem sum against the reference
+        stems' sum, measured from the gains the variant already passes to the meter (the draws in one call) -- and 'ltas'
+        {'centres': [Hz], 'reference': [dB re total], 'mix': [...]}.  Nothing else depends on it; the lengths may differ
+        (a long-term AVERAGE spectrum)."""
         if self.d is None or self.mix_model is None or self.mean_loudness_model is None:
             raise ValueError('process_song needs the dataset, d_mean_loudness and mix_model constructor arguments')
         stems = [t for t in self.d.get_tracklist() if t != 'mix']
@@ -172,6 +209,13 @@ class LoudnessEvaluator:
             reference_power, reference_st = self.meter.short_term_batch(reference_pcm.transpose(1, 2))
             reference_lra = curve_stats_device(reference_power)[:, 0]
             candidates_st = []                              # sum, loudnorm, mix, random_0 ...: [stems, windows] each
+        if spectral:
+            n_fft, hop, edges, centres = self._spectral_args(spectral)
+
+            def band_power(stem_pcm, g=None):               # -> [mixes, bands]; g: None, [stems], [stems, n] or [R, stems, 1]
+                return spectrum.band_power_mix(stem_pcm.transpose(1, 2), g, n_fft=n_fft, hop=hop, edges=edges)
+            reference_spec = band_power(reference_pcm)
+            drawn_gains = []
         del reference_pcm
 
         def error(profile):
@@ -187,16 +231,22 @@ class LoudnessEvaluator:
         write('sum', pcm)
         if dynamics:
             candidates_st.append(self.evaluate_short_term_batch(pcm))
+        if spectral:
+            candidates_spec = [band_power(pcm)]             # sum, loudnorm, mix, then the draws: [1 or draws, bands] each
         # each multitrack is normalized to the mean loudness of the corresponding track from train set
         loudnorm_gains = self.mean_loudness_model.device_gains(pcm, lufs)
         stats['loudnorm_error'] = error(self.evaluate_loudness_batch(pcm, loudnorm_gains))
         write('loudnorm', pcm, loudnorm_gains)
         if dynamics:
             candidates_st.append(self.evaluate_short_term_batch(pcm, loudnorm_gains))
+        if spectral:
+            candidates_spec.append(band_power(pcm, loudnorm_gains))
         stats['mix_error'] = error(self._profile([float(v) for v in mix_lufs]))
         write('mix', pcm, mixer.gains[1])
         if dynamics:
             candidates_st.append(self.evaluate_short_term_batch(pcm, mixer.gains[1]))
+        if spectral:
+            candidates_spec.append(band_power(pcm, mixer.gains[1]))
         random_errors = []
         for exp_i in range(n_random_samples):
             drawn = self.random_model.draw()
@@ -205,6 +255,8 @@ class LoudnessEvaluator:
             write('random_{}'.format(exp_i), pcm, g)
             if dynamics:
                 candidates_st.append(self.evaluate_short_term_batch(pcm, g))
+            if spectral:
+                drawn_gains.append(g)
         stats['random_error'] = mean(random_errors)
         stats['smooth_gains'] = {name: list(gains[1, i]) for i, name in enumerate(self.keys)}
         if dynamics:                                        # one launch for every variant, one copy to the host
@@ -212,30 +264,50 @@ class LoudnessEvaluator:
             stats['sum_st_error'], stats['loudnorm_st_error'], stats['mix_st_error'] = st_errors[:3]
             stats['random_st_error'] = mean(st_errors[3:])
             stats['lra'] = dict(zip(self.keys, reference_lra.cpu().tolist()))
+        if spectral:                                        # the draws in one call, one launch for every variant, one copy
+            if drawn_gains:
+                candidates_spec.append(band_power(pcm, torch.stack(drawn_gains).unsqueeze(-1)))
+            cand = torch.cat(candidates_spec)
+            spec_errors = spectrum.balance_error_device(reference_spec[0], cand)[0]
+            # (a [1, bands] row each, as evaluate_spectrum_batch returns one: the same reduction, the same bits)
+            levels = [spectrum.relative_levels_db(reference_spec), spectrum.relative_levels_db(cand[2:3])]
+            host = torch.cat([spec_errors, levels[0][0], levels[1][0]]).cpu().tolist()
+            n_var, n_bands = cand.shape[0], len(centres)
+            stats['sum_spec_error'], stats['loudnorm_spec_error'], stats['mix_spec_error'] = host[:3]
+            stats['random_spec_error'] = mean(host[3:n_var])
+            stats['ltas'] = {'centres': centres.tolist(), 'reference': host[n_var:n_var + n_bands],
+                             'mix': host[n_var + n_bands:]}
         return stats
 
     def process_song(self, base_dir: str, song_name: str, n_random_samples: int = 5, chunk_length: int = 2,
-                     write_wavs_to_disk=False, results_dir='./experiment', ceiling_dbtp=None, dynamics=False, limiter=None) -> dict:
+                     write_wavs_to_disk=False, results_dir='./experiment', ceiling_dbtp=None, dynamics=False, limiter=None,
+                     spectral=False) -> dict:
         """evaluation.py:77-116: the reference mix from ``base_dir/manual_gain_mixes``, the stems from ``base_dir/test``."""
         from .data.dataset_utils import load_tracks_musdb18
         reference_tracks = load_tracks_musdb18(os.path.join(base_dir, 'manual_gain_mixes'), song_name, tracklist=self.keys,
                                                sr=self.sr)
         loaded_tracks = load_tracks_musdb18(os.path.join(base_dir, 'test'), song_name, tracklist=self.keys, sr=self.sr)
         return self.process_song_tracks(loaded_tracks, reference_tracks, song_name, n_random_samples, chunk_length,
-                                        write_wavs_to_disk, results_dir, ceiling_dbtp, dynamics, limiter)
+                                        write_wavs_to_disk, results_dir, ceiling_dbtp, dynamics, limiter, spectral)
 
     def process_songlist(self, base_dir, songlist, n_random_samples: int = 5, chunk_length: int = 2,
-                         write_wavs_to_disk=False, results_dir='./experiment', ceiling_dbtp=None, dynamics=False, limiter=None):
+                         write_wavs_to_disk=False, results_dir='./experiment', ceiling_dbtp=None, dynamics=False, limiter=None,
+                         spectral=False):
         """evaluation.py:118-144 without the spreadsheet: (rows, means) -- one stats dict per song and the mean of every
-        error over the songs (the sheet's last row); with ``dynamics`` the four '*_st_error' keys too."""
+        error over the songs (the sheet's last row); with ``dynamics`` the four '*_st_error' keys too, with ``spectral``
+        the four '*_spec_error' keys."""
         keys = ['sum_error', 'random_error', 'loudnorm_error', 'mix_error']
         if dynamics:
             keys += ['sum_st_error', 'random_st_error', 'loudnorm_st_error', 'mix_st_error']
+        if spectral:
+            keys += ['sum_spec_error', 'random_spec_error', 'loudnorm_spec_error', 'mix_spec_error']
         rows = []
         for i, song_name in enumerate(songlist):
             print('{}/{}: {}'.format(i + 1, len(songlist), song_name))
-            # (the keyword only where a limiter is asked for: the call without one is the call of before, argument for argument)
+            # (either keyword only where it is asked for: the call without them is the call of before, argument for argument)
             extra = {} if limiter is None or limiter is False else {'limiter': limiter}
+            if spectral:
+                extra['spectral'] = spectral
             rows.append(self.process_song(base_dir, song_name, n_random_samples, chunk_length, write_wavs_to_disk,
                                           results_dir, ceiling_dbtp, dynamics, **extra))
         return rows, {key: mean(row[key] for row in rows) for key in keys}

@@ -2,6 +2,7 @@
 torch's caching allocator, launch on the current torch stream.  No arithmetic happens here and
 there is no CPU fallback."""
 import ctypes
+import numbers
 import os
 
 import torch
@@ -928,6 +929,99 @@ def limiter_apply(data, ceiling_db, lookahead, hold, pre_gain=None, out=None, ou
                                        _lib.ptr(out), ok, _lib.ptr(min_gain_out), _lib.ptr(n_limited_out), _lib.ptr(workspace),
                                        _lib.stream()), 'dam_limiter_apply')
     return out, min_gain_out, n_limited_out
+
+
+# ----------------------------------------------------------------------------- band spectrum and spectral balance
+def spectrum_geometry():
+    """(frames one workgroup owns, largest number of bands) of dam_spectrum_band_power, asked of the library."""
+    L = _lib.lib()
+    return L.dam_spectrum_frames_per_block(), L.dam_spectrum_max_bands()
+
+
+def spectrum_band_power(data, gains, window, twiddles, n_fft, hop, edges, out=None, workspace=None):
+    """data: CUDA float32 / float64 [R, S, samples, channels] with any strides (an expanded leading axis, stride 0, makes
+    every mix read the same stems; no copy is made) -> the time-averaged band powers of the R mixes ``sum_s stem_s *
+    gains[r, s]``, float64 [R, B] (include/dam_hip.h: dam_spectrum_band_power states the definition).  gains: None (every
+    gain exactly 1) or CUDA float64 [R, S, n_gains], applied at load exactly as the batched loudness meter applies them.
+    window, twiddles: the float32 tables of features._get_tables for ``n_fft``.  edges: CUDA int32 [B + 1], strictly
+    ascending bin edges within 0 .. n_fft/2 + 1 -- their CONTENT cannot be checked here without a copy to the host
+    (spectrum.band_power_mix checks the host table it uploads).  workspace: optional float64 tensor of
+    dam_spectrum_workspace_bytes / 8 elements.  No host synchronisation, hipGraph-capturable."""
+    _lib.require_cuda(data, gains, window, twiddles, edges, out, workspace)
+    xk = _audio_kind(data, 'data')
+    if data.dim() != 4:
+        raise ValueError('spectrum_band_power: [mixes, stems, samples, channels] expected, got shape %s' % (tuple(data.shape),))
+    R, S, n, ch = data.shape
+    if R < 1 or S < 1 or R > 65535:
+        raise ValueError('spectrum_band_power: 1..65535 mixes of at least one stem expected, got %s' % (tuple(data.shape),))
+    if ch not in (1, 2):
+        raise ValueError('spectrum_band_power: 1 or 2 channels expected, got %d' % ch)
+    if not isinstance(n_fft, numbers.Integral) or not isinstance(hop, numbers.Integral):
+        raise TypeError('spectrum_band_power: n_fft and hop must be integers')
+    n_fft, hop = int(n_fft), int(hop)
+    if n_fft < 64 or n_fft > 16384 or n_fft & (n_fft - 1):
+        raise ValueError('spectrum_band_power: n_fft must be a power of two from 64 to 16384')
+    if hop < 1:
+        raise ValueError('spectrum_band_power: hop must be positive')
+    if n <= n_fft // 2:
+        raise ValueError('spectrum_band_power: reflect padding needs more than n_fft / 2 samples (got %d)' % n)
+    gains, n_gains = gain_ramp_arg(gains, R * S, n)
+    L = _lib.lib()
+    if edges.dtype != torch.int32 or edges.dim() != 1 or not edges.is_contiguous():
+        raise TypeError('spectrum_band_power: edges must be a contiguous int32 [bands + 1] tensor')
+    B = edges.numel() - 1
+    if not 1 <= B <= L.dam_spectrum_max_bands():
+        raise ValueError('spectrum_band_power: 1..%d bands expected, got %d' % (L.dam_spectrum_max_bands(), B))
+    for t, what, count in ((window, 'window', n_fft), (twiddles, 'twiddles', 2 * n_fft)):
+        if t.dtype != torch.float32 or t.numel() != count or not t.is_contiguous():
+            raise ValueError('spectrum_band_power: %s must be a contiguous float32 tensor of %d elements' % (what, count))
+    dev = data.device
+    if out is None:
+        out = torch.empty((R, B), dtype=torch.float64, device=dev)
+    elif tuple(out.shape) != (R, B) or out.dtype != torch.float64 or not out.is_contiguous():
+        raise ValueError('spectrum_band_power: out must be a contiguous float64 [%d, %d] tensor' % (R, B))
+    need = L.dam_spectrum_workspace_bytes(R, n, hop, B) // 8
+    if workspace is None:
+        workspace = torch.empty(need, dtype=torch.float64, device=dev)
+    elif workspace.dtype != torch.float64 or workspace.numel() < need or not workspace.is_contiguous():
+        raise ValueError('spectrum_band_power: workspace must be a contiguous float64 tensor of at least %d elements' % need)
+    with torch.cuda.device(dev):
+        _lib.check(L.dam_spectrum_band_power(_lib.ptr(data), xk, R, S, ch, n, data.stride(0), data.stride(1), data.stride(2),
+                                             data.stride(3), _lib.ptr(gains), n_gains, _lib.ptr(window), _lib.ptr(twiddles),
+                                             n_fft, hop, _lib.ptr(edges), B, _lib.ptr(out), _lib.ptr(workspace),
+                                             _lib.stream()), 'dam_spectrum_band_power')
+    return out
+
+
+def spectrum_balance_error(ref_power, cand_power, err_out=None, n_kept_out=None):
+    """ref_power CUDA float64 [B], cand_power [V, B] (or [B]: one candidate) -> (err float64 [V], n_kept int32 [V]): the mean
+    absolute difference in dB of the band levels relative to each spectrum's total, over the bands both hold at or above
+    -70 dB of their total; NaN where there is none (include/dam_hip.h: dam_spectrum_balance_error)."""
+    _lib.require_cuda(ref_power, cand_power, err_out, n_kept_out)
+    if cand_power.dim() == 1:
+        cand_power = cand_power.unsqueeze(0)
+    if ref_power.dtype != torch.float64 or cand_power.dtype != torch.float64:
+        raise TypeError('spectrum_balance_error: float64 band powers expected')
+    if ref_power.dim() != 1 or cand_power.dim() != 2 or cand_power.shape[1] != ref_power.shape[0]:
+        raise ValueError('spectrum_balance_error: [bands] and [variants, bands] expected, got %s and %s'
+                         % (tuple(ref_power.shape), tuple(cand_power.shape)))
+    ref_power, cand_power = ref_power.contiguous(), cand_power.contiguous()
+    V, B = cand_power.shape
+    L = _lib.lib()
+    if V < 1 or not 1 <= B <= L.dam_spectrum_max_bands():
+        raise ValueError('spectrum_balance_error: at least one variant and 1..%d bands expected' % L.dam_spectrum_max_bands())
+    dev = ref_power.device
+    if err_out is None:
+        err_out = torch.empty(V, dtype=torch.float64, device=dev)
+    if n_kept_out is None:
+        n_kept_out = torch.empty(V, dtype=torch.int32, device=dev)
+    for o, dt in ((err_out, torch.float64), (n_kept_out, torch.int32)):
+        if o.dtype != dt or o.numel() != V or not o.is_contiguous():
+            raise ValueError('spectrum_balance_error: err_out / n_kept_out must be contiguous float64 / int32 tensors of %d' % V)
+    with torch.cuda.device(dev):
+        _lib.check(L.dam_spectrum_balance_error(_lib.ptr(ref_power), _lib.ptr(cand_power), V, B, _lib.ptr(err_out),
+                                                _lib.ptr(n_kept_out), _lib.stream()), 'dam_spectrum_balance_error')
+    return err_out, n_kept_out
 
 
 # ----------------------------------------------------------------------------- dropout

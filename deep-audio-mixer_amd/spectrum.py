@@ -1,0 +1,168 @@
+"""Band spectrum of a mix and the spectral-balance error between two mixes -- the tonal counterpart of the loudness
+profile evaluation.py compares (include/dam_hip.h: dam_spectrum_band_power / dam_spectrum_balance_error state the
+definitions; csrc/dam_spectrum.hip holds the kernels).
+
+The long-term average spectrum (LTAS) of ``sum_s stem_s * gain ramp_s`` is measured in fractional-octave bands straight
+from the resident stems: the stems are summed with their gains as a frame is loaded, the frame goes through the front-end's
+FFT in LDS and only float64 band powers leave the kernel -- no mix and no spectrogram is written.  Two spectra are compared
+by their band levels RELATIVE TO THEIR TOTAL, so the figure does not move when every stem is scaled by a common gain, as
+the loudness error does not (evaluation.py:39-53: loudness relative to the stems' mean).
+
+Importable without a GPU (``band_edges`` and ``relative_levels_db`` are host arithmetic); the measuring functions need
+CUDA tensors and raise otherwise -- there is no CPU fallback.
+"""
+import math
+import numbers
+
+import numpy as np
+import torch
+
+from . import features, ops
+
+_edge_tables = {}
+
+
+def band_edges(sr, n_fft, fraction=3, f_lo=25.0, f_hi=20000.0):
+    """Fractional-octave bands (``fraction`` per octave, base 2, centred on 1 kHz) as runs of FFT bins -> (edges int32
+    [B + 1], centres float64 [B] in Hz): band b is the bins edges[b] .. edges[b+1]-1 of an ``n_fft``-point transform at
+    ``sr`` Hz.  Band indices i run from ceil(fraction log2(f_lo / 1000)) to floor(fraction log2(min(f_hi, sr/2) / 1000)),
+    each formed with a slack of 1e-9 so that an exact centre is not lost to rounding; centres 1000 * 2^(i / fraction); the
+    edge frequencies f_j = 1000 * 2^((2j - 1) / (2 fraction)), j = i_lo .. i_hi + 1, are computed once, so neighbouring
+    bands share an edge exactly; edge bins e_j = min(n_fft/2 + 1, ceil(f_j n_fft / sr)).  A band without a bin of its own
+    (e_{j+1} == e_j: below the transform's resolution, or above sr/2) is dropped together with its centre."""
+    if not isinstance(n_fft, numbers.Integral) or not isinstance(fraction, numbers.Integral):
+        raise TypeError('band_edges: n_fft and fraction must be integers')
+    n_fft, fraction, sr, f_lo, f_hi = int(n_fft), int(fraction), float(sr), float(f_lo), float(f_hi)
+    if n_fft < 2 or fraction < 1 or not sr > 0.0 or not f_lo > 0.0 or not f_hi >= f_lo:
+        raise ValueError('band_edges: n_fft >= 2, fraction >= 1, sr > 0 and 0 < f_lo <= f_hi expected')
+    i_lo = math.ceil(fraction * math.log2(f_lo / 1000.0) - 1e-9)
+    i_hi = math.floor(fraction * math.log2(min(f_hi, sr / 2.0) / 1000.0) + 1e-9)
+    top = n_fft // 2 + 1
+    e = [min(top, math.ceil(1000.0 * 2.0 ** ((2 * j - 1) / (2.0 * fraction)) * n_fft / sr)) for j in range(i_lo, i_hi + 2)]
+    edges, centres = [], []
+    for q, i in enumerate(range(i_lo, i_hi + 1)):
+        if e[q + 1] > e[q]:
+            if not edges:
+                edges.append(e[q])
+            edges.append(e[q + 1])
+            centres.append(1000.0 * 2.0 ** (i / float(fraction)))
+    if not centres:
+        raise ValueError('band_edges: no band between %g and %g Hz holds a bin at sr = %g, n_fft = %d' % (f_lo, f_hi, sr, n_fft))
+    return np.asarray(edges, dtype=np.int32), np.asarray(centres, dtype=np.float64)
+
+
+def check_edges(edges, n_fft):
+    """The host copy of an edge table as the kernel needs it -> contiguous int32 [B + 1]; ValueError / TypeError for
+    what dam_spectrum_band_power cannot take (the C entry only sees a device pointer: the content is checked here)."""
+    if torch.is_tensor(edges):
+        if edges.is_cuda:
+            raise TypeError('edges must be a host table (numpy, list or CPU tensor): its content is checked before the upload')
+        edges = edges.numpy()
+    e = np.asarray(edges)
+    if e.ndim != 1 or not np.issubdtype(e.dtype, np.integer):
+        raise TypeError('edges must be a one-dimensional integer table')
+    e = np.ascontiguousarray(e, dtype=np.int64)
+    if e.size < 2:
+        raise ValueError('edges: at least one band (two edges) expected')
+    if e[0] < 0 or e[-1] > n_fft // 2 + 1 or np.any(np.diff(e) <= 0):
+        raise ValueError('edges must ascend strictly within 0 .. n_fft/2 + 1 = %d, got %s' % (n_fft // 2 + 1, e.tolist()))
+    return e.astype(np.int32)
+
+
+def _device_edges(edges, n_fft, device):
+    e = check_edges(edges, n_fft)
+    _, max_bands = ops.spectrum_geometry()
+    if e.size - 1 > max_bands:
+        raise ValueError('at most %d bands, got %d' % (max_bands, e.size - 1))
+    key = (device.type, device.index, e.tobytes())
+    if key not in _edge_tables:                     # uploaded once per table and device: a captured call finds it resident
+        _edge_tables[key] = torch.from_numpy(e).to(device)
+    return _edge_tables[key]
+
+
+def _frame_args(n_fft, hop, n, channels):
+    if not isinstance(n_fft, numbers.Integral) or (hop is not None and not isinstance(hop, numbers.Integral)):
+        raise TypeError('n_fft and hop must be integers')
+    n_fft = int(n_fft)
+    hop = n_fft // 2 if hop is None else int(hop)
+    features._check_n_fft(n_fft, hop, n)
+    if channels not in (1, 2):
+        raise ValueError('1 or 2 channels expected, got %d' % channels)
+    return n_fft, hop
+
+
+def _measure(data, gains, n_fft, hop, edges):
+    if not data.is_cuda:
+        raise RuntimeError('deep_audio_mixer_amd kernels run on the GPU only (got a %s tensor); there is no CPU fallback'
+                           % data.device)
+    if data.dtype not in (torch.float32, torch.float64):
+        raise TypeError('float32 or float64 samples expected')
+    n_fft, hop = _frame_args(n_fft, hop, data.shape[2], data.shape[3])
+    if data.shape[0] < 1 or data.shape[1] < 1 or data.shape[0] > 65535:
+        raise ValueError('1..65535 mixes of at least one stem expected')
+    if gains is not None:
+        if not gains.is_cuda:
+            raise RuntimeError('gains must be a CUDA tensor')
+        if gains.dtype != torch.float64:
+            raise TypeError('gains must be float64')
+        if not 1 <= gains.shape[-1] <= data.shape[2]:
+            raise ValueError('between one gain and one gain per sample expected')
+    dev_edges = _device_edges(edges, n_fft, data.device)      # (checked before anything is launched)
+    win, tw = features._get_tables(data.device, n_fft)
+    return ops.spectrum_band_power(data, gains, win, tw, n_fft, hop, dev_edges)
+
+
+def band_power_mix(stems, gains=None, *, n_fft=8192, hop=None, edges):
+    """stems: CUDA float32 / float64 [S, samples, channels] with any strides (planar [S, channels, n] storage is passed
+    as ``pcm.transpose(1, 2)``, no copy).  gains: None (the plain sum), CUDA float64 [S] or [S, n_gains] (one mix) or
+    [R, S, n_gains] (R mixes of the same stems in one call).  edges: a host table of bin edges, ``band_edges(...)[0]``
+    (strictly ascending within 0 .. n_fft/2 + 1, at most ops.spectrum_geometry()[1] bands).  hop defaults to n_fft / 2.
+    -> CUDA float64 [R, B]: the time-averaged power of ``sum_s channel_mean(stem_s) * gain ramp`` in every band
+    (frames and window exactly those of features.stft).  A row does not depend on the other rows (bitwise).  No host
+    synchronisation once the tables are resident; hipGraph-capturable then."""
+    if stems.dim() != 3:
+        raise ValueError('stems must be [stems, samples, channels], got shape %s' % (tuple(stems.shape),))
+    S = stems.shape[0]
+    R = 1
+    if gains is not None:
+        if gains.dim() == 1:
+            gains = gains.view(1, -1, 1)
+        elif gains.dim() == 2:
+            gains = gains.unsqueeze(0)
+        if gains.dim() != 3 or gains.shape[1] != S:
+            raise ValueError('gains must be [S], [S, n_gains] or [R, S, n_gains] with S = %d, got shape %s'
+                             % (S, tuple(gains.shape)))
+        R = gains.shape[0]
+    return _measure(stems.unsqueeze(0).expand(R, -1, -1, -1), gains, n_fft, hop, edges)
+
+
+def band_power_tracks(data, gains=None, *, n_fft=8192, hop=None, edges):
+    """data: CUDA float32 / float64 [N, samples, channels] with any strides: N independent tracks.  gains: None or CUDA
+    float64 [N] / [N, n_gains].  Otherwise as band_power_mix -> CUDA float64 [N, B]."""
+    if data.dim() != 3:
+        raise ValueError('data must be [tracks, samples, channels], got shape %s' % (tuple(data.shape),))
+    N = data.shape[0]
+    if gains is not None:
+        if gains.dim() == 1:
+            gains = gains.view(-1, 1)
+        if gains.dim() != 2 or gains.shape[0] != N:
+            raise ValueError('gains must be [N] or [N, n_gains] with N = %d, got shape %s' % (N, tuple(gains.shape)))
+        gains = gains.unsqueeze(1)
+    return _measure(data.unsqueeze(1), gains, n_fft, hop, edges)
+
+
+def balance_error_device(ref_power, cand_power):
+    """ref_power CUDA float64 [B], cand_power [V, B] (or [B]) -> (err float64 [V] in dB, n_kept int32 [V]): with
+    L[b] = 10 log10(P[b] / sum P), the mean of |L_cand[b] - L_ref[b]| over the bands that hold at least -70 dB of the total
+    in both spectra; NaN where no band does.  One launch for all candidates, nothing comes to the host."""
+    return ops.spectrum_balance_error(ref_power, cand_power)
+
+
+def relative_levels_db(power):
+    """Band powers [..., B] (torch tensor or numpy array, float64) -> 10 log10(P / sum_b P), the band levels in dB relative
+    to the spectrum's total; the same kind of array comes back."""
+    if torch.is_tensor(power):
+        return 10.0 * torch.log10(power / power.sum(dim=-1, keepdim=True))
+    power = np.asarray(power, dtype=np.float64)
+    with np.errstate(divide='ignore', invalid='ignore'):
+        return 10.0 * np.log10(power / power.sum(axis=-1, keepdims=True))

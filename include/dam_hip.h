@@ -55,7 +55,7 @@ struct dam_bn_bwd_sums; /* defined in the BatchNorm section */
 /* Library / build identification ("gfx950").  DAM_ABI_VERSION is bumped whenever a signature below changes; a binding
  * compares dam_abi_version() of the library it loaded with the version it was written against and refuses a stale one
  * (deep-audio-mixer_amd/_lib.py: EXPECTED_ABI). */
-#define DAM_ABI_VERSION 23
+#define DAM_ABI_VERSION 24
 const char* dam_arch(void);
 int dam_abi_version(void);
 
@@ -740,6 +740,64 @@ int dam_loudness_window_power(const double* e, int n_tracks, int channels, int n
 int dam_loudness_curve_stats(const double* power, int n_tracks, int n_windows, double* out, void* stream);
 int dam_loudness_profile_error(const double* ref_lufs, const double* cand_lufs, int n_variants, int n_stems,
                                int n_windows, double* err, double* active, void* stream);
+
+/* ---------------------------------------------------------------------------------
+ * Band spectrum (long-term average spectrum, LTAS, in fractional-octave bands) of gain-ramped stem sums, and the
+ * spectral-balance error built on it -- the tonal counterpart of the loudness profile of evaluation.py:39-53.  Neither the
+ * mix nor its STFT is written.  Every entry is stateless, allocates nothing, does not synchronise with the host, uses no
+ * atomics and is hipGraph-capturable.  tests/_spectrum_ref.py restates the definition in numpy float64.
+ *   Mix signal.  Mix r of n_mixes, stems s = 0 .. n_stems-1 of `channels` (1 or 2), sample p in [0, n_samples):
+ *     element (r, s, p, c) is x[r*mix_stride + s*stem_stride + p*sample_stride + c*channel_stride] (element strides,
+ *     float32 or float64 by x_is_f64; mix_stride = 0: every mix reads the same stems; n_stems = 1 with mix_stride the
+ *     track stride: n_mixes independent tracks);
+ *     m_s[p]  = ((double)a + (double)b) * 0.5 for the two channels a, b, or (double)a for one channel;
+ *     xm_r[p] = (float)( sum_s m_s[p] * g[r][s][min(p / (n_samples / n_gains), n_gains-1)] ), the sum in double in ascending
+ *     s, every product its own rounding (no fused multiply-add) -- the gain index and the float64 product of
+ *     dam_gain_ramp_apply and dam_loudness_block_energy_batch.  gains: device float64 [n_mixes][n_stems][n_gains] or NULL;
+ *     NULL means every gain is exactly 1.0 (the products are skipped: m * 1.0 == m).
+ *   Frames are the front-end's (dam_stft_complex_f32, torch.stft(center=True, pad_mode='reflect')): T = 1 + n_samples / hop,
+ *     frame_t[j] = xm[reflect(t*hop - n_fft/2 + j)] * w[j] in float32, j in [0, n_fft), w = `window` (device float32
+ *     [n_fft], the periodic Hann table), twiddles as dam_stft_fill_twiddles_host fills them.  n_fft a power of two
+ *     64 .. 16384, hop >= 1, n_samples > n_fft/2.
+ *   Band power.  X_t = the float32 FFT of frame_t, bins k = 0 .. n_fft/2 (imaginary parts of bins 0 and n_fft/2 taken as 0),
+ *     P[r][b] = ( sum_t sum_{k = edges[b]}^{edges[b+1]-1} c_k * ((double)re^2 + (double)im^2) ) / (double)T,
+ *     c_k = 1 for k = 0 and k = n_fft/2, else 2: one band over all bins is (n_fft / T) * sum_t sum_j frame_t[j]^2 (Parseval).
+ *     edges: device int32 [n_bands + 1], 0 <= edges[0] < ... < edges[n_bands] <= n_fft/2 + 1, 1 <= n_bands <=
+ *     dam_spectrum_max_bands() (64).  The table lives on the device, so its CONTENT is the caller's to check
+ *     (spectrum.py does, on the host copy it uploads); the kernel clamps every edge to [0, n_fft/2 + 1], so a bad table
+ *     gives wrong numbers, never an access out of bounds.
+ *     Order of the float64 additions: one workgroup owns F = dam_spectrum_frames_per_block() consecutive frames
+ *     [i F, (i+1) F) of one mix; lane l of its 256 keeps one running sum per bin l, l + 256, ... over those frames in
+ *     ascending t; bins are then folded into a band by 64 lanes (lane q adds bins edges[b] + q, + 64, ... ascending, then an
+ *     xor-butterfly over the 64 partials, distances 1, 2, .. 32); a second kernel adds a mix's workgroup partials in
+ *     ascending i and divides by T.  The order depends on (n_samples, n_fft, hop, edges) only: a row is bitwise
+ *     reproducible and does not depend on the other rows of the call or on how many there are.
+ *     power: device float64 [n_mixes][n_bands].  workspace: dam_spectrum_workspace_bytes(n_mixes, n_samples, hop, n_bands)
+ *     bytes, 8-byte aligned.  n_mixes <= 65535.
+ *     Argument errors (NULL x / window / twiddles / edges / power / workspace; a non-positive count; channels not 1 or 2;
+ *     n_fft not a power of two in 64 .. 16384; hop < 1; n_samples <= n_fft/2; gains with n_gains < 1 or > n_samples;
+ *     n_bands outside 1 .. dam_spectrum_max_bands(); more than 65535 mixes) return DAM_ERR_BAD_ARG before any launch.
+ *   dam_spectrum_balance_error: ref_power [B], cand_power [V][B] (device float64), B <= dam_spectrum_max_bands().  For a
+ *     spectrum P: tot = sum_b P[b] (ascending b), L[b] = 10 log10(P[b] / tot).  Band b of candidate v is KEPT iff
+ *     ref[b] >= DAM_SPECTRUM_GATE * tot_ref and cand[v][b] >= DAM_SPECTRUM_GATE * tot_cand (a gate on powers, -70 dB under
+ *     the total: no decision hangs on a log10);
+ *       err[v] = (sum over kept b, ascending, of |L_cand[b] - L_ref[b]|) / n_kept,   NaN when n_kept = 0;
+ *     n_kept[v] (device int32) = the number of kept bands.  Level-independent by construction: a common gain on all stems
+ *     leaves every L[b] unchanged.  A spectrum that is zero everywhere passes the gate with 0 >= 0 and yields NaN.
+ *     One 64-lane workgroup per candidate; err [V] float64.
+ * Parity with any other analyser's band definitions (IEC 61260 filter skirts, A/K weighting) is not claimed: bands are
+ * sums of FFT bins between edges computed in spectrum.band_edges.
+ * --------------------------------------------------------------------------------- */
+#define DAM_SPECTRUM_GATE 0x1.ad7f29abcaf48p-24 /* 1e-7 = 10^(-70 / 10) */
+int dam_spectrum_frames_per_block(void);
+int dam_spectrum_max_bands(void);
+int64_t dam_spectrum_workspace_bytes(int n_mixes, int64_t n_samples, int hop, int n_bands);
+int dam_spectrum_band_power(const void* x, int x_is_f64, int n_mixes, int n_stems, int channels, int64_t n_samples,
+                            int64_t mix_stride, int64_t stem_stride, int64_t sample_stride, int64_t channel_stride,
+                            const double* gains, int n_gains, const float* window, const float* twiddles, int n_fft, int hop,
+                            const int32_t* edges, int n_bands, double* power, void* workspace, void* stream);
+int dam_spectrum_balance_error(const double* ref_power, const double* cand_power, int n_variants, int n_bands, double* err,
+                               int32_t* n_kept, void* stream);
 
 /* ---------------------------------------------------------------------------------
  * Stem input layout: x [B][C][HW] (C <= 16 planes, the reference's [B,S,F,T] feature stack) -> y [B][HW][16] with
