@@ -12,7 +12,7 @@ LIB_PATH = os.environ.get('DAM_LIB_PATH') or os.path.join(_HERE, 'libdam_hip.so'
 # include/dam_hip.h: bumped whenever a C signature changes (together with dam_abi_version() in csrc/dam_api.hip and
 # DAM_ABI_VERSION in the header).  libdam_hip.so is git-ignored and travels prebuilt: a stale one would read device pointers
 # as streams, so lib() refuses it instead of launching.
-EXPECTED_ABI = 24
+EXPECTED_ABI = 25
 
 _STATUS = {0: 'DAM_OK', -1: 'DAM_ERR_BAD_ARG', -2: 'DAM_ERR_UNSUPPORTED', -3: 'DAM_ERR_LAUNCH',
            -4: 'DAM_ERR_WORKSPACE'}
@@ -121,6 +121,11 @@ SIGNATURES = {
     'dam_spectrum_band_power': (c_i, [c_p, c_i, c_i, c_i, c_i, c_i64, c_i64, c_i64, c_i64, c_i64, c_p, c_i, c_p, c_p, c_i, c_i,
                                       c_p, c_i, c_p, c_p, c_p]),
     'dam_spectrum_balance_error': (c_i, [c_p, c_p, c_i, c_i, c_p, c_p, c_p]),
+    'dam_gainfit_tile_samples': (c_i64, []),
+    'dam_gainfit_workspace_bytes': (c_i64, [c_i, c_i64, c_i]),
+    'dam_gainfit_moments': (c_i, [c_p, c_i, c_i, c_i, c_i64, c_i64, c_i64, c_i64, c_p, c_i, c_i64, c_i64, c_i, c_p, c_p, c_p]),
+    'dam_gainfit_solve': (c_i, [c_p, c_i, c_i, c_i, c_d, c_p, c_p, c_p, c_p]),
+    'dam_gainfit_gain_error': (c_i, [c_p, c_p, c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_p]),
 }
 
 

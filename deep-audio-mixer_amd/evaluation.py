@@ -26,6 +26,12 @@ the loudness errors only see level): every variant's long-term average spectrum 
 reference mix's, each relative to its own total (spectrum.band_power_mix / balance_error_device) -- '*_spec_error' beside
 every '*_error', in dB -- and 'ltas', the two spectra themselves.  Two mixes of equal loudness error, one of them
 bass-heavy, differ here; scaling every stem by a common gain changes neither figure.
+
+``gain_fit=True`` asks the direct question the three axes only circle: what gains did the reference mix use, and how far
+are a variant's gains from them?  The reference stems' sum is fitted with the raw stems by windowed least squares over the
+windows of the model's own gain ramp (gainfit.fit_gains): 'oracle_gains', 'oracle_residual' (the share of the reference no
+gain-only mixer explains) and a '*_gain_error' beside every '*_error' -- the mean distance in dB from the fitted gains,
+stem by stem and window by window, relative to each window's mean over the stems (gainfit.gain_error_device).
 """
 import os
 from collections import OrderedDict
@@ -34,7 +40,7 @@ from statistics import mean
 import numpy as np
 import torch
 
-from . import inference_utils, spectrum, staging
+from . import gainfit, inference_utils, ops, spectrum, staging
 from .loudness import Meter, curve_stats_device, normalize_loudness, profile_error_device
 from .models.baselines.mean_loudness_model import MeanLoudnessModel
 from .models.baselines.random_model import RandomModel
@@ -117,6 +123,17 @@ class LoudnessEvaluator:
         edges, centres = spectrum.band_edges(self.sr, o['n_fft'], o['fraction'], o['f_lo'], o['f_hi'])
         return o['n_fft'], hop, edges, centres
 
+    GAIN_FIT_DEFAULTS = {'pool': 0, 'ridge': 0.0}
+
+    def _gain_fit_args(self, gain_fit):
+        """``gain_fit`` as the whole-song methods take it (True, or a dict with any of pool, ridge) -> (pool, ridge)."""
+        given = {} if gain_fit is True else dict(gain_fit)
+        unknown = set(given) - set(self.GAIN_FIT_DEFAULTS)
+        if unknown:
+            raise ValueError('gain_fit: unknown keys %s (expected any of %s)' % (sorted(unknown), sorted(self.GAIN_FIT_DEFAULTS)))
+        o = dict(self.GAIN_FIT_DEFAULTS, **given)
+        return ops.gainfit_check_solve_args(o['pool'], o['ridge'])
+
     def evaluate_spectrum_batch(self, stems, gains=None, **spectral):
         """Band powers of the stem sum (long-term average spectrum in fractional-octave bands at the evaluator's rate),
         measured as ``sum of stem * gain ramp`` where gains are given, without that sum being written.  stems as
@@ -167,7 +184,7 @@ class LoudnessEvaluator:
 
     def process_song_tracks(self, loaded_tracks: dict, reference_tracks: dict, song_name: str, n_random_samples: int = 5,
                             chunk_length: int = 2, write_wavs_to_disk=False, results_dir='./experiment',
-                            ceiling_dbtp=None, dynamics=False, limiter=None, spectral=False) -> dict:
+                            ceiling_dbtp=None, dynamics=False, limiter=None, spectral=False, gain_fit=False) -> dict:
         """evaluation.py:77-116 on stems already in memory ({name: ndarray [channels, n]} each): the loudness profile of
         ``reference_tracks`` against the profiles of ``loaded_tracks`` summed as they are ('sum_error'), normalised to the
         training set's mean loudness ('loudnorm_error'), mixed by the model ('mix_error') and scaled by random gains
@@ -186,7 +203,14 @@ class LoudnessEvaluator:
         (the mean over the draws) -- the spectral-balance error in dB of every variant's stem sum against the reference
         stems' sum, measured from the gains the variant already passes to the meter (the draws in one call) -- and 'ltas'
         {'centres': [Hz], 'reference': [dB re total], 'mix': [...]}.  Nothing else depends on it; the lengths may differ
-        (a long-term AVERAGE spectrum)."""
+        (a long-term AVERAGE spectrum).
+        gain_fit (True, or a dict with any of pool, ridge; defaults 0, 0.0 -- gainfit.solve explains them): the stats gain,
+        after any dynamics and spectral keys, 'sum_gain_error' (unit gains), 'loudnorm_gain_error', 'mix_gain_error' (the
+        model's smoothed gains), 'random_gain_error' (the mean over the draws) -- each variant's distance in dB from the gains
+        that best rebuild the float64 sum of the reference stems from ``loaded_tracks``, one per stem and window of the
+        model's gain ramp, relative to each window's mean over the stems -- 'oracle_gains' {name: [windows]}, those fitted
+        gains (NaN where a stem is silent), and 'oracle_residual' [windows], the share of the reference's energy they leave
+        unexplained.  Nothing else depends on it.  The reference mix and the stems must be of one length."""
         if self.d is None or self.mix_model is None or self.mean_loudness_model is None:
             raise ValueError('process_song needs the dataset, d_mean_loudness and mix_model constructor arguments')
         stems = [t for t in self.d.get_tracklist() if t != 'mix']
@@ -194,6 +218,10 @@ class LoudnessEvaluator:
             raise ValueError('the dataset tracklist and the evaluator keys must both be %s' % (self.random_model.tracklist,))
         if dynamics and np.asarray(reference_tracks[self.keys[0]]).shape[-1] != np.asarray(loaded_tracks[self.keys[0]]).shape[-1]:
             raise ValueError('dynamics=True compares window by window: the reference mix and the stems differ in length')
+        if gain_fit:
+            fit_pool, fit_ridge = self._gain_fit_args(gain_fit)
+            if np.asarray(reference_tracks[self.keys[0]]).shape[-1] != np.asarray(loaded_tracks[self.keys[0]]).shape[-1]:
+                raise ValueError('gain_fit fits sample by sample: the reference mix and the stems differ in length')
         stats = {'song_name': song_name}
 
         def write(identifier, pcm, gains=None):
@@ -216,6 +244,10 @@ class LoudnessEvaluator:
                 return spectrum.band_power_mix(stem_pcm.transpose(1, 2), g, n_fft=n_fft, hop=hop, edges=edges)
             reference_spec = band_power(reference_pcm)
             drawn_gains = []
+        if gain_fit:                                        # the fit's target: the float64 sum of the reference stems, [channels, n]
+            fit_target = ops.mixdown_peak_normalize(reference_pcm, torch.ones((len(self.keys), 1), dtype=torch.float64,
+                                                                              device=reference_pcm.device), normalize=False)
+            candidates_fit = []                             # loudnorm, then the draws: [stems] each
         del reference_pcm
 
         def error(profile):
@@ -241,6 +273,8 @@ class LoudnessEvaluator:
             candidates_st.append(self.evaluate_short_term_batch(pcm, loudnorm_gains))
         if spectral:
             candidates_spec.append(band_power(pcm, loudnorm_gains))
+        if gain_fit:
+            candidates_fit.append(loudnorm_gains.reshape(-1))
         stats['mix_error'] = error(self._profile([float(v) for v in mix_lufs]))
         write('mix', pcm, mixer.gains[1])
         if dynamics:
@@ -257,6 +291,8 @@ class LoudnessEvaluator:
                 candidates_st.append(self.evaluate_short_term_batch(pcm, g))
             if spectral:
                 drawn_gains.append(g)
+            if gain_fit:
+                candidates_fit.append(g)
         stats['random_error'] = mean(random_errors)
         stats['smooth_gains'] = {name: list(gains[1, i]) for i, name in enumerate(self.keys)}
         if dynamics:                                        # one launch for every variant, one copy to the host
@@ -277,30 +313,47 @@ class LoudnessEvaluator:
             stats['random_spec_error'] = mean(host[3:n_var])
             stats['ltas'] = {'centres': centres.tolist(), 'reference': host[n_var:n_var + n_bands],
                              'mix': host[n_var + n_bands:]}
+        if gain_fit:                                        # one launch for every variant, one copy to the host
+            n_stems, W = len(self.keys), mixer.n_proc
+            fitted, residual, _ = gainfit.fit_gains(pcm.transpose(1, 2), fit_target.transpose(0, 1), W, pool=fit_pool,
+                                                    ridge=fit_ridge)
+            constant = torch.stack(candidates_fit).unsqueeze(-1).expand(-1, -1, W)         # loudnorm, draws: [.., stems, W]
+            cand = torch.cat([torch.ones((1, n_stems, W), dtype=torch.float64, device=pcm.device), constant[:1],
+                              mixer.gains[1].unsqueeze(0), constant[1:]])
+            fit_errors = gainfit.gain_error_device(fitted, cand)[0]
+            host = torch.cat([fit_errors, fitted.reshape(-1), residual]).cpu().tolist()
+            n_var = cand.shape[0]
+            stats['sum_gain_error'], stats['loudnorm_gain_error'], stats['mix_gain_error'] = host[:3]
+            stats['random_gain_error'] = mean(host[3:n_var]) if n_var > 3 else float('nan')
+            stats['oracle_gains'] = {name: host[n_var + i * W:n_var + (i + 1) * W] for i, name in enumerate(self.keys)}
+            stats['oracle_residual'] = host[n_var + n_stems * W:]
         return stats
 
     def process_song(self, base_dir: str, song_name: str, n_random_samples: int = 5, chunk_length: int = 2,
                      write_wavs_to_disk=False, results_dir='./experiment', ceiling_dbtp=None, dynamics=False, limiter=None,
-                     spectral=False) -> dict:
+                     spectral=False, gain_fit=False) -> dict:
         """evaluation.py:77-116: the reference mix from ``base_dir/manual_gain_mixes``, the stems from ``base_dir/test``."""
         from .data.dataset_utils import load_tracks_musdb18
         reference_tracks = load_tracks_musdb18(os.path.join(base_dir, 'manual_gain_mixes'), song_name, tracklist=self.keys,
                                                sr=self.sr)
         loaded_tracks = load_tracks_musdb18(os.path.join(base_dir, 'test'), song_name, tracklist=self.keys, sr=self.sr)
         return self.process_song_tracks(loaded_tracks, reference_tracks, song_name, n_random_samples, chunk_length,
-                                        write_wavs_to_disk, results_dir, ceiling_dbtp, dynamics, limiter, spectral)
+                                        write_wavs_to_disk, results_dir, ceiling_dbtp, dynamics, limiter, spectral,
+                                        **({'gain_fit': gain_fit} if gain_fit else {}))
 
     def process_songlist(self, base_dir, songlist, n_random_samples: int = 5, chunk_length: int = 2,
                          write_wavs_to_disk=False, results_dir='./experiment', ceiling_dbtp=None, dynamics=False, limiter=None,
-                         spectral=False):
+                         spectral=False, gain_fit=False):
         """evaluation.py:118-144 without the spreadsheet: (rows, means) -- one stats dict per song and the mean of every
         error over the songs (the sheet's last row); with ``dynamics`` the four '*_st_error' keys too, with ``spectral``
-        the four '*_spec_error' keys."""
+        the four '*_spec_error' keys, with ``gain_fit`` the four '*_gain_error' keys (a song whose figure is NaN -- nothing
+        to compare -- is left out of that mean; the mean is NaN if every song's is)."""
         keys = ['sum_error', 'random_error', 'loudnorm_error', 'mix_error']
         if dynamics:
             keys += ['sum_st_error', 'random_st_error', 'loudnorm_st_error', 'mix_st_error']
         if spectral:
             keys += ['sum_spec_error', 'random_spec_error', 'loudnorm_spec_error', 'mix_spec_error']
+        fit_keys = ['sum_gain_error', 'random_gain_error', 'loudnorm_gain_error', 'mix_gain_error'] if gain_fit else []
         rows = []
         for i, song_name in enumerate(songlist):
             print('{}/{}: {}'.format(i + 1, len(songlist), song_name))
@@ -308,6 +361,12 @@ class LoudnessEvaluator:
             extra = {} if limiter is None or limiter is False else {'limiter': limiter}
             if spectral:
                 extra['spectral'] = spectral
+            if gain_fit:
+                extra['gain_fit'] = gain_fit
             rows.append(self.process_song(base_dir, song_name, n_random_samples, chunk_length, write_wavs_to_disk,
                                           results_dir, ceiling_dbtp, dynamics, **extra))
-        return rows, {key: mean(row[key] for row in rows) for key in keys}
+        means = {key: mean(row[key] for row in rows) for key in keys}
+        for key in fit_keys:
+            finite = [row[key] for row in rows if row[key] == row[key]]
+            means[key] = mean(finite) if finite else float('nan')
+        return rows, means

@@ -1024,6 +1024,145 @@ def spectrum_balance_error(ref_power, cand_power, err_out=None, n_kept_out=None)
     return err_out, n_kept_out
 
 
+# ----------------------------------------------------------------------------- gain fit and gain error
+GAINFIT_MAX_STEMS = 8                  # DAM_GAINFIT_MAX_STEMS
+
+
+def gainfit_geometry():
+    """(samples of one workgroup tile, largest number of stems) of dam_gainfit_moments; the tile is asked of the library."""
+    return _lib.lib().dam_gainfit_tile_samples(), GAINFIT_MAX_STEMS
+
+
+def gainfit_check_shapes(stems_shape, mix_shape, n_windows):
+    """The host-side argument rules of gainfit_moments on shapes alone -> (S, n, channels, W); ValueError / TypeError
+    otherwise.  No tensor and no library is touched."""
+    if len(stems_shape) != 3:
+        raise ValueError('gainfit_moments: stems must be [stems, samples, channels], got shape %s' % (tuple(stems_shape),))
+    S, n, ch = stems_shape
+    if not 1 <= S <= GAINFIT_MAX_STEMS:
+        raise ValueError('gainfit_moments: 1..%d stems expected, got %d' % (GAINFIT_MAX_STEMS, S))
+    if ch not in (1, 2):
+        raise ValueError('gainfit_moments: 1 or 2 channels expected, got %d' % ch)
+    if tuple(mix_shape) != (n, ch):
+        raise ValueError('gainfit_moments: the mix must be [samples, channels] = [%d, %d] as the stems are, got shape %s'
+                         % (n, ch, tuple(mix_shape)))
+    if not isinstance(n_windows, numbers.Integral) or isinstance(n_windows, bool):
+        raise TypeError('gainfit_moments: n_windows must be an integer')
+    if not 1 <= n_windows <= n:
+        raise ValueError('gainfit_moments: between one window and one window per sample expected (%d samples), got %d'
+                         % (n, n_windows))
+    return S, n, ch, int(n_windows)
+
+
+def gainfit_check_solve_args(pool, ridge):
+    """pool, ridge as gainfit_solve takes them -> (int, float); TypeError / ValueError otherwise."""
+    if not isinstance(pool, numbers.Integral) or isinstance(pool, bool):
+        raise TypeError('gainfit_solve: pool must be an integer')
+    if not isinstance(ridge, numbers.Real) or isinstance(ridge, bool):
+        raise TypeError('gainfit_solve: ridge must be a real number')
+    if pool < 0 or pool > 0x7fffffff or not float(ridge) >= 0.0:
+        raise ValueError('gainfit_solve: pool >= 0 and ridge >= 0 expected, got %r and %r' % (pool, ridge))
+    return int(pool), float(ridge)
+
+
+def gainfit_moments(stems, mix, n_windows, out=None, workspace=None):
+    """stems: CUDA float32 / float64 [S, samples, channels] with any strides (planar [S, channels, n] storage is passed as
+    ``pcm.transpose(1, 2)``, no copy); mix: CUDA float32 / float64 [samples, channels] with any strides, its dtype
+    independent of the stems' -> the moment matrices of (stems, mix) per window, float64 [W, S + 1, S + 1]
+    (include/dam_hip.h: dam_gainfit_moments states the definition and the order of the additions).  workspace: optional
+    float64 tensor of dam_gainfit_workspace_bytes / 8 elements.  No host synchronisation, hipGraph-capturable."""
+    _lib.require_cuda(stems, mix, out, workspace)
+    xk, yk = _audio_kind(stems, 'stems'), _audio_kind(mix, 'mix')
+    S, n, ch, W = gainfit_check_shapes(stems.shape, mix.shape, n_windows)
+    dev = stems.device
+    if mix.device != dev:
+        raise ValueError('gainfit_moments: the stems and the mix must be on one device')
+    if out is None:
+        out = torch.empty((W, S + 1, S + 1), dtype=torch.float64, device=dev)
+    elif tuple(out.shape) != (W, S + 1, S + 1) or out.dtype != torch.float64 or not out.is_contiguous():
+        raise ValueError('gainfit_moments: out must be a contiguous float64 [%d, %d, %d] tensor' % (W, S + 1, S + 1))
+    L = _lib.lib()
+    need = L.dam_gainfit_workspace_bytes(W, n, S) // 8
+    if workspace is None:
+        workspace = torch.empty(need, dtype=torch.float64, device=dev)
+    elif workspace.dtype != torch.float64 or workspace.numel() < need or not workspace.is_contiguous():
+        raise ValueError('gainfit_moments: workspace must be a contiguous float64 tensor of at least %d elements' % need)
+    with torch.cuda.device(dev):
+        _lib.check(L.dam_gainfit_moments(_lib.ptr(stems), xk, S, ch, n, stems.stride(0), stems.stride(1), stems.stride(2),
+                                         _lib.ptr(mix), yk, mix.stride(0), mix.stride(1), W, _lib.ptr(out),
+                                         _lib.ptr(workspace), _lib.stream()), 'dam_gainfit_moments')
+    return out
+
+
+def gainfit_solve(moments, pool=0, ridge=0.0, gains_out=None, residual_out=None, status_out=None):
+    """moments: CUDA float64 [W, S + 1, S + 1] (gainfit_moments) -> (gains float64 [S, W], residual float64 [W], status int32
+    [W]): the least-squares gains of every window over the moments of windows w - pool .. w + pool, NaN for a stem that is
+    silent there (include/dam_hip.h: dam_gainfit_solve).  status: the number of fitted stems, 0 for a silent target, -1 for
+    a rank-deficient window (then ``ridge`` > 0 helps)."""
+    _lib.require_cuda(moments, gains_out, residual_out, status_out)
+    pool, ridge = gainfit_check_solve_args(pool, ridge)
+    if moments.dtype != torch.float64:
+        raise TypeError('gainfit_solve: float64 moments expected')
+    if moments.dim() != 3 or moments.shape[1] != moments.shape[2] or not 2 <= moments.shape[1] <= GAINFIT_MAX_STEMS + 1 \
+            or moments.shape[0] < 1:
+        raise ValueError('gainfit_solve: moments must be [windows, S + 1, S + 1] with 1..%d stems, got shape %s'
+                         % (GAINFIT_MAX_STEMS, tuple(moments.shape)))
+    moments = moments.contiguous()
+    W, S = moments.shape[0], moments.shape[1] - 1
+    dev = moments.device
+    if gains_out is None:
+        gains_out = torch.empty((S, W), dtype=torch.float64, device=dev)
+    if residual_out is None:
+        residual_out = torch.empty(W, dtype=torch.float64, device=dev)
+    if status_out is None:
+        status_out = torch.empty(W, dtype=torch.int32, device=dev)
+    for o, dt, shape in ((gains_out, torch.float64, (S, W)), (residual_out, torch.float64, (W,)), (status_out, torch.int32, (W,))):
+        if o.dtype != dt or tuple(o.shape) != shape or not o.is_contiguous():
+            raise ValueError('gainfit_solve: outputs must be contiguous float64 [%d, %d], float64 [%d] and int32 [%d] tensors'
+                             % (S, W, W, W))
+    with torch.cuda.device(dev):
+        _lib.check(_lib.lib().dam_gainfit_solve(_lib.ptr(moments), W, S, pool, ridge, _lib.ptr(gains_out),
+                                                _lib.ptr(residual_out), _lib.ptr(status_out), _lib.stream()),
+                   'dam_gainfit_solve')
+    return gains_out, residual_out, status_out
+
+
+def gainfit_gain_error(fit, cand, err_out=None, err_stem_out=None, n_kept_out=None):
+    """fit: CUDA float64 [S, W]; cand: [V, S, W] or [V, S, 1] (a constant gain per stem), or one variant without the leading
+    axis -> (err float64 [V], err_stem float64 [V, S], n_kept int32 [V]): the mean over windows and stems of
+    |d - the window's mean d|, d = 20 log10(cand / fit), over the entries where both gains are finite and positive and the
+    windows that keep at least two stems; NaN where nothing is kept (include/dam_hip.h: dam_gainfit_gain_error)."""
+    _lib.require_cuda(fit, cand, err_out, err_stem_out, n_kept_out)
+    if cand.dim() == 2:
+        cand = cand.unsqueeze(0)
+    if fit.dtype != torch.float64 or cand.dtype != torch.float64:
+        raise TypeError('gainfit_gain_error: float64 gains expected')
+    if fit.dim() != 2 or cand.dim() != 3 or cand.shape[1] != fit.shape[0] or cand.shape[2] not in (1, fit.shape[1]):
+        raise ValueError('gainfit_gain_error: [S, W] and [V, S, W or 1] expected, got %s and %s'
+                         % (tuple(fit.shape), tuple(cand.shape)))
+    S, W = fit.shape
+    V, n_cand = cand.shape[0], cand.shape[2]
+    if V < 1 or W < 1 or not 1 <= S <= GAINFIT_MAX_STEMS:
+        raise ValueError('gainfit_gain_error: at least one variant and window and 1..%d stems expected' % GAINFIT_MAX_STEMS)
+    fit, cand = fit.contiguous(), cand.contiguous()
+    dev = fit.device
+    if err_out is None:
+        err_out = torch.empty(V, dtype=torch.float64, device=dev)
+    if err_stem_out is None:
+        err_stem_out = torch.empty((V, S), dtype=torch.float64, device=dev)
+    if n_kept_out is None:
+        n_kept_out = torch.empty(V, dtype=torch.int32, device=dev)
+    for o, dt, count in ((err_out, torch.float64, V), (err_stem_out, torch.float64, V * S), (n_kept_out, torch.int32, V)):
+        if o.dtype != dt or o.numel() != count or not o.is_contiguous():
+            raise ValueError('gainfit_gain_error: outputs must be contiguous float64 [%d], float64 [%d, %d] and int32 [%d] tensors'
+                             % (V, V, S, V))
+    with torch.cuda.device(dev):
+        _lib.check(_lib.lib().dam_gainfit_gain_error(_lib.ptr(fit), _lib.ptr(cand), V, S, W, n_cand, _lib.ptr(err_out),
+                                                     _lib.ptr(err_stem_out), _lib.ptr(n_kept_out), _lib.stream()),
+                   'dam_gainfit_gain_error')
+    return err_out, err_stem_out, n_kept_out
+
+
 # ----------------------------------------------------------------------------- dropout
 _dropout_counters = {}
 

@@ -55,7 +55,7 @@ struct dam_bn_bwd_sums; /* defined in the BatchNorm section */
 /* Library / build identification ("gfx950").  DAM_ABI_VERSION is bumped whenever a signature below changes; a binding
  * compares dam_abi_version() of the library it loaded with the version it was written against and refuses a stale one
  * (deep-audio-mixer_amd/_lib.py: EXPECTED_ABI). */
-#define DAM_ABI_VERSION 24
+#define DAM_ABI_VERSION 25
 const char* dam_arch(void);
 int dam_abi_version(void);
 
@@ -798,6 +798,69 @@ int dam_spectrum_band_power(const void* x, int x_is_f64, int n_mixes, int n_stem
                             const int32_t* edges, int n_bands, double* power, void* workspace, void* stream);
 int dam_spectrum_balance_error(const double* ref_power, const double* cand_power, int n_variants, int n_bands, double* err,
                                int32_t* n_kept, void* stream);
+
+/* ---------------------------------------------------------------------------------
+ * Gain fit: the per-stem gains a reference mix used, by windowed least squares "stems x gains ~ reference mix", the share
+ * of the reference such gains cannot explain, and the distance in dB of candidate gain curves from the fitted ones.  Every
+ * entry is stateless, allocates nothing, does not synchronise with the host, uses no atomics and is hipGraph-capturable.
+ * tests/_gainfit_ref.py restates the definitions in numpy float64.
+ *   Signals.  Stems s = 0 .. S-1, 1 <= S <= DAM_GAINFIT_MAX_STEMS, of `channels` (1 or 2), samples p in [0, n_samples):
+ *     element (s, p, c) is x[s*stem_stride + p*sample_stride + c*channel_stride] (element strides, float32 or float64 by
+ *     x_is_f64).  The target y is one track of the same length and channel count: element (p, c) is
+ *     y[p*y_sample_stride + c*y_channel_stride], float32 or float64 by y_is_f64, independently of x.
+ *     Window of a sample: w(p) = min(p / (n_samples / W), W-1) in integer division -- the gain index of dam_gain_ramp_apply,
+ *     so window w of the fit is gain w of the mixer.  1 <= W <= n_samples.  With seg = n_samples / W, window w starts at
+ *     w*seg and holds seg samples, the last one n_samples - (W-1)*seg.
+ *   dam_gainfit_moments: the symmetric moment matrix of the S+1 signals u = (x_0 .. x_{S-1}, y) of every window,
+ *       M[w][i][j] = sum over p in window w, c of (double)u_i * (double)u_j,
+ *     device float64 [W][S+1][S+1], both triangles written from one computation of each pair (exactly symmetric).
+ *     Every addend enters its sum through one fused multiply-add, acc = fma(u_i, u_j, acc): for float32 inputs the
+ *     product is exact in float64 either way, so only the additions round.
+ *     Order of the additions, for a window of L samples (q = p - window start, 0 <= q < L): workgroup t of the window owns
+ *     the T = dam_gainfit_tile_samples() samples q in [t T, min((t+1) T, L)); lane l of its 256 adds the samples
+ *     q = t T + l, + 256, ... in ascending q, channel 0 before channel 1, to a running sum that starts at +0.0 (a lane
+ *     without a sample keeps +0.0); the 64 lanes of a wave are folded by an xor-butterfly, distances 1, 2, .. 32
+ *     (v = v + v[lane ^ m]); the four waves are added as ((w0 + w1) + w2) + w3; a second kernel adds the window's
+ *     ceil(L / T) tile sums in ascending t, starting from the first.  The order depends on (L, channels, S) only -- not on
+ *     W, on the window's index or on the alignment of its first sample: the same samples passed as a call of their own
+ *     with W = 1 give the same bits.
+ *     workspace: dam_gainfit_workspace_bytes(W, n_samples, S) bytes, 8-byte aligned (one record of (S+1)(S+2)/2 doubles
+ *     per tile).  More than 2^31 - 1 tiles in all: DAM_ERR_UNSUPPORTED.
+ *   dam_gainfit_solve: moments [W][S+1][S+1] -> gains [S][W] (the mixer's layout), residual [W] (device float64),
+ *     status [W] (device int32).  pool = h >= 0, ridge >= 0.  For window w:
+ *       A = sum of M[v], v = max(0, w-h) .. min(W-1, w+h) ascending (starting from the first); G = A[:S,:S], b = A[:S,S],
+ *       Y = A[S][S].  Stem s is ACTIVE iff G_ss > 0 and G_ss >= DAM_GAINFIT_GATE * Y.
+ *       Y == 0 or no active stem: every gain NaN, residual NaN, status 0.
+ *       Otherwise, on the active stems in ascending order: d_s = sqrt(G_ss), R_ij = G_ij / (d_i * d_j) + ridge * [i == j];
+ *       Cholesky R = L L^T in float64, column by column (pivot_j = R_jj less L_jk^2, k < j, one by one in ascending k); a pivot that is
+ *       not > DAM_GAINFIT_PIVOT makes the window rank-deficient: every gain NaN, residual NaN, status -1.
+ *       Else R h = (b_s / d_s) by forward and back substitution; active stems get g_s = h_s / d_s, inactive stems NaN;
+ *       status = the number of active stems; with g of inactive stems taken as 0,
+ *       residual = max(0, (Y - 2 (b . g) + g . (G g)) / Y), every dot product in ascending index from +0.0.
+ *     One 64-lane workgroup per window; the elimination itself runs on one lane.
+ *   dam_gainfit_gain_error: fit [S][W], cand [V][S][n_cand] (device float64), n_cand = W or 1 (a constant per stem).
+ *       d[v][s][w] = 20 log10(cand / fit); an entry is KEPT iff both values are finite and > 0 (a negative fitted gain is
+ *       inverted polarity, not a level).  A window with at least two kept stems contributes |d - mu| for each of them,
+ *       mu = (sum of its kept d, ascending s) / their number; a window with fewer contributes nothing: a common gain on
+ *       all stems of a window is a master fader, not a balance decision.
+ *       err[v] = (sum of all contributions, windows ascending, stems ascending within a window) / their number,
+ *       err_stem[v][s] = the same over stem s alone (windows ascending), n_kept[v] (device int32) = the number of
+ *       contributions; NaN where that number is 0.  One 64-lane workgroup per variant.
+ *   Argument errors (a NULL pointer; S outside 1 .. DAM_GAINFIT_MAX_STEMS; channels not 1 or 2; a non-positive count; W outside
+ *     1 .. n_samples; negative pool or ridge, or a NaN ridge; n_cand not W or 1) return DAM_ERR_BAD_ARG before any launch.
+ * --------------------------------------------------------------------------------- */
+#define DAM_GAINFIT_MAX_STEMS 8
+#define DAM_GAINFIT_GATE 0x1.5798ee2308c3ap-27 /* 1e-8: a stem 80 dB under the target's energy is not fitted */
+#define DAM_GAINFIT_PIVOT 0x1p-40
+int64_t dam_gainfit_tile_samples(void);
+int64_t dam_gainfit_workspace_bytes(int n_windows, int64_t n_samples, int n_stems);
+int dam_gainfit_moments(const void* x, int x_is_f64, int n_stems, int channels, int64_t n_samples, int64_t stem_stride,
+                        int64_t sample_stride, int64_t channel_stride, const void* y, int y_is_f64, int64_t y_sample_stride,
+                        int64_t y_channel_stride, int n_windows, double* moments, void* workspace, void* stream);
+int dam_gainfit_solve(const double* moments, int n_windows, int n_stems, int pool, double ridge, double* gains,
+                      double* residual, int32_t* status, void* stream);
+int dam_gainfit_gain_error(const double* fit, const double* cand, int n_variants, int n_stems, int n_windows, int n_cand,
+                           double* err, double* err_stem, int32_t* n_kept, void* stream);
 
 /* ---------------------------------------------------------------------------------
  * Stem input layout: x [B][C][HW] (C <= 16 planes, the reference's [B,S,F,T] feature stack) -> y [B][HW][16] with
