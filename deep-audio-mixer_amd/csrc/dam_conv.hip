@@ -295,6 +295,7 @@ int launch_conv(const ConvGeo& g, size_t lds, const float* X, const float* Wp, c
         hipLaunchKernelGGL(splitk_reduce_kernel, dim3(blocks), dim3(256), 0, st, splitk_ws, g.ksplit, n4, g.N / 4, bias, res, res_mask, g.relu_out, Y);
         DAM_CHECK_LAUNCH();
     }
+    conv_last_launch = ConvLaunchNote{CONV_FAM_TILE, MB, NB, 0, 0, 0, 0, 0, 0, 0, 0, g.ksplit, 1};
     return DAM_OK;
 }
 
@@ -546,6 +547,7 @@ int launch_conv1x1(const ConvGeo& g, const float* X, const float* Wp, const floa
     hipLaunchKernelGGL((conv1x1_direct_kernel<NB, NCHMAX>), dim3((unsigned)cdiv(units, 4), (unsigned)(g.N / 16 / NB)), dim3(256), 0, st,
                        g, X, reinterpret_cast<const float4*>(Wp), bias, Y, res, res_mask, segs, (int)units);
     DAM_CHECK_LAUNCH();
+    conv_last_launch = ConvLaunchNote{CONV_FAM_1X1, 0, NB, NCHMAX, 0, 0, 0, 0, 0, 0, 0, 1, 1};
     return DAM_OK;
 }
 
@@ -581,6 +583,18 @@ extern "C" int dam_conv1x1_pair_f32(const float* x1, const float* w1_packed, int
     return DAM_OK;
 }
 
+namespace dam {
+thread_local ConvLaunchNote conv_last_launch{};
+}
+
+extern "C" int dam_conv_last_launch(int* out16_host) {
+    if (!out16_host) return DAM_ERR_BAD_ARG;
+    const dam::ConvLaunchNote& n = dam::conv_last_launch;
+    const int v[16] = {n.family, n.MB, n.NB, n.NCH, n.T33, n.LW, n.EPI, n.SO, n.PU, n.STATS, n.KS, n.ksplit, n.ranges, 0, 0, 0};
+    for (int i = 0; i < 16; ++i) out16_host[i] = v[i];
+    return DAM_OK;
+}
+
 // Generic tap-grid convolution (see dam_hip.h).  The host wrapper derives the patch geometry and picks the tile.
 extern "C" int64_t dam_conv_batch_bytes(void) { return (int64_t)sizeof(dam::ConvBatch); }
 
@@ -607,6 +621,7 @@ extern "C" int dam_conv2d_tapgrid_f32(const float* x, int B, int H, int W, int C
                                       const dam_bn_bwd_sums* bn_bwd, float* workspace, int64_t workspace_floats,
                                       void* batch, void* stream) {
     using namespace dam;
+    conv_last_launch = ConvLaunchNote{};
     if (bn_parts_host) *bn_parts_host = 0;
     BnBwdEpi bwd{};
     if (bn_bwd && bn_bwd->x) {
@@ -695,7 +710,11 @@ extern "C" int dam_conv2d_tapgrid_f32(const float* x, int B, int H, int W, int C
                     rc2 = conv_pipe_try(g2, h_hi - h_lo, x, w_packed, bias, in_scale, in_shift, y, res, res_mask, workspace, nullptr,
                                         nullptr, BnBwdEpi{}, st);
                 }
-                if (rc2 == DAM_OK) return DAM_OK;
+                if (rc2 == DAM_OK) {
+                    conv_last_launch.family = CONV_FAM_PIPE_RANGES;      // (tile parameters: those of the last range's launch)
+                    conv_last_launch.ranges = done;
+                    return DAM_OK;
+                }
                 if (rc2 != DAM_ERR_UNSUPPORTED || done > 1) return rc2 == DAM_ERR_UNSUPPORTED ? DAM_ERR_LAUNCH : rc2;   // a later range cannot fail where the first fitted
             }
         }
@@ -778,6 +797,7 @@ extern "C" int dam_conv2d_tapgrid_f32(const float* x, int B, int H, int W, int C
         ConvLaunchRec& r = cb->rec[cb->n++];
         r.g = g; r.MB = MB; r.NB = NB; r.lds = lds; r.X = x; r.Wp = w_packed; r.bias = bias; r.sc = in_scale; r.sh = in_shift;
         r.res = res; r.res_mask = res_mask; r.Y = y; r.ws = workspace;
+        conv_last_launch = ConvLaunchNote{CONV_FAM_TILE_BATCH, MB, NB, 0, 0, 0, 0, 0, 0, 0, 0, 1, 1};
         return DAM_OK;
     }
 #define DAM_CONV_CASE(M_, N_) \

@@ -48,6 +48,15 @@ struct StripGeo {
     unsigned wo_magic;       // floor(2^32 / Wo) + 1: p / Wo == umulhi(p, wo_magic) for p < 2^22 (scalar-ALU division)
 };
 
+// What the last dam_conv2d_tapgrid_f32 call of this thread launched (dam_conv_last_launch, include/dam_hip.h): a host variable
+// written beside the launch sites, read by tests that must know which kernel family and instantiation they exercised.
+enum ConvFamily { CONV_FAM_NONE = 0, CONV_FAM_STRIP = 1, CONV_FAM_PIPE = 2, CONV_FAM_PIPE_RANGES = 3, CONV_FAM_TILE = 4,
+                  CONV_FAM_TILE_BATCH = 5, CONV_FAM_1X1 = 6 };
+struct ConvLaunchNote {
+    int family, MB, NB, NCH, T33, LW, EPI, SO, PU, STATS, KS, ksplit, ranges;
+};
+extern thread_local ConvLaunchNote conv_last_launch;     // dam_conv.hip
+
 // dam_conv_strip.hip
 int conv_strip_try(ConvGeo& g, int h_lo, int h_hi, const float* X, const float* Wp, const float* bias, float* Y,
                    const float* res, const float* res_mask, float* stats, int* stats_parts,

@@ -588,6 +588,7 @@ int launch_pipe(const ConvGeo& g, size_t lds, const float* X, const float* Wp, c
     if (mode == 2) DAM_PIPE_LAUNCH(2); else if (mode == 1) DAM_PIPE_LAUNCH(1); else DAM_PIPE_LAUNCH(0);
 #undef DAM_PIPE_LAUNCH
     DAM_CHECK_LAUNCH();
+    conv_last_launch = ConvLaunchNote{CONV_FAM_PIPE, MB, NB, 0, 0, 0, 0, 0, PU, mode, KS, 1, 1};
     return DAM_OK;
 }
 

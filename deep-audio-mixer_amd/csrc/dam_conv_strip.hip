@@ -1151,6 +1151,7 @@ static int launch_strip(ConvGeo& g, StripGeo& sg, size_t lds, const float* X, co
     hipLaunchKernelGGL((conv_strip_kernel<MB, NB, NCH, T33, LW, EPI, SO>), grid, dim3(SO ? 512 : STRIP_THREADS), lds, st, g, sg, X, reinterpret_cast<const float4*>(Wp), bias,
                        Y, res, res_mask, stats, in_scale, in_shift, bwd);
     DAM_CHECK_LAUNCH();
+    conv_last_launch = ConvLaunchNote{CONV_FAM_STRIP, MB, NB, NCH, T33, LW, EPI, SO, 0, 0, 0, 1, 1};
     return DAM_OK;
 }
 

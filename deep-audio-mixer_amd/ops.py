@@ -1,6 +1,7 @@
 """Thin Python wrappers over the C ABI (include/dam_hip.h): shape checks, output allocation through
 torch's caching allocator, launch on the current torch stream.  No arithmetic happens here and
 there is no CPU fallback."""
+import collections
 import ctypes
 import numbers
 import os
@@ -79,11 +80,12 @@ def _tapgrid(x, B, H, W, C, in_nchw, wp, k_chunks, n_out, bias, in_scale, in_shi
 
 
 def conv2d_fwd(x, wp, n_out, kh, kw, stride=1, pad=0, dil=1, bias=None, in_scale=None, in_shift=None,
-               relu_in=False, in_nchw=False, bn_partial=None, bn=None, res=None, relu_out=False, finalize=True):
+               relu_in=False, in_nchw=False, bn_partial=None, bn=None, res=None, relu_out=False, finalize=True, out=None):
     """x: NHWC [B,H,W,C] (C % 16 == 0), or NCHW [B,C,H,W] with C <= 16 if in_nchw.  Returns NHWC
     [B,Ho,Wo,n_out] with n_out rounded up to a multiple of 16 (extra channels are zero).
     res (same shape as the result) is added, relu_out applies max(., 0) last: with an eval-mode BatchNorm folded into
-    the weights and `bias`, one launch is relu(bn(conv(x)) [+ shortcut])."""
+    the weights and `bias`, one launch is relu(bn(conv(x)) [+ shortcut]).
+    out: the result tensor to write (contiguous float32 [B,Ho,Wo,n16] on x's device) instead of a fresh one."""
     _lib.require_cuda(x, wp)
     _f32c(x, 'x'), _f32c(bias, 'bias'), _f32c(in_scale, 'in_scale'), _f32c(in_shift, 'in_shift'), _f32c(res, 'res')
     if in_nchw:
@@ -96,7 +98,12 @@ def conv2d_fwd(x, wp, n_out, kh, kw, stride=1, pad=0, dil=1, bias=None, in_scale
     Ho, Wo = conv_out_size(H, kh, stride, pad, dil), conv_out_size(W, kw, stride, pad, dil)
     if Ho <= 0 or Wo <= 0:
         raise ValueError('convolution output would be empty')
-    y = torch.empty((B, Ho, Wo, n16), dtype=torch.float32, device=x.device)
+    if out is None:
+        y = torch.empty((B, Ho, Wo, n16), dtype=torch.float32, device=x.device)
+    else:
+        if out.dtype != torch.float32 or not out.is_contiguous() or tuple(out.shape) != (B, Ho, Wo, n16) or out.device != x.device:
+            raise ValueError('out must be a contiguous float32 tensor of shape %s on %s' % ((B, Ho, Wo, n16), x.device))
+        y = out
     parts = _tapgrid(x, B, H, W, C, in_nchw, wp, k_chunks, n16, bias, in_scale, in_shift, relu_in, y, Ho, Wo, Ho, Wo,
                      1, 0, 0, stride, kh, kw, -pad, dil, -pad, dil, 0, kw, 1, res=res, bn_partial=bn_partial,
                      relu_out=relu_out)
@@ -108,6 +115,18 @@ def conv2d_fwd(x, wp, n_out, kh, kw, stride=1, pad=0, dil=1, bias=None, in_scale
     if bn_partial is not None:
         return y, parts          # parts == 0: the launch could not produce the statistics
     return y
+
+
+CONV_FAMILIES = ('none', 'strip', 'pipe', 'pipe_ranges', 'tile', 'tile_batch', '1x1')
+ConvLaunch = collections.namedtuple('ConvLaunch', 'family MB NB NCH T33 LW EPI SO PU STATS KS ksplit ranges')
+
+
+def conv_last_launch():
+    """Which kernel the last tap-grid convolution call of this thread launched (dam_conv_last_launch): the family by name and
+    the template parameters of the instantiation; fields that do not belong to the family are 0.  Host-side only."""
+    v = (ctypes.c_int * 16)()
+    _lib.check(_lib.lib().dam_conv_last_launch(v), 'dam_conv_last_launch')
+    return ConvLaunch(CONV_FAMILIES[v[0]], *v[1:13])
 
 
 def _dgrad_axis(parity, pad, dil, k, stride):

@@ -55,7 +55,7 @@ struct dam_bn_bwd_sums; /* defined in the BatchNorm section */
 /* Library / build identification ("gfx950").  DAM_ABI_VERSION is bumped whenever a signature below changes; a binding
  * compares dam_abi_version() of the library it loaded with the version it was written against and refuses a stale one
  * (deep-audio-mixer_amd/_lib.py: EXPECTED_ABI). */
-#define DAM_ABI_VERSION 25
+#define DAM_ABI_VERSION 26
 const char* dam_arch(void);
 int dam_abi_version(void);
 
@@ -294,6 +294,21 @@ int dam_conv_s2_pair_fwd_f32(const float* x, const float* w_packed, const float*
 int64_t dam_conv_batch_bytes(void);
 int dam_conv_batch_init(void* batch);
 int dam_conv_batch_flush(void* batch, void* stream);
+
+/* Which kernel the last dam_conv2d_tapgrid_f32 call of the CALLING THREAD launched (ABI 26): the entry point falls back from
+ * kernel to kernel without telling, so a test that means to exercise one family asks here.  A host variable written beside the
+ * launch sites -- no device work, nothing synchronised.  out16_host (host memory, 16 ints) receives
+ *   [0] family: 0 none (no call yet; after a call that FAILED the record is unspecified), 1 row-ring strip kernel, 2 loader-wave (pipe) kernel,
+ *       3 the pipe kernel on column ranges, 4 tile kernel, 5 tile kernel recorded into a batch (launched by the flush), 6 direct 1x1
+ *   [1] MB  [2] NB                 M / N tile in 64-pixel / 16-channel blocks (1x1: NB only)
+ *   [3] NCH                        strip: resident K chunks; 1x1: chunk slots (NCHMAX)
+ *   [4] T33 [5] LW [6] EPI [7] SO  strip: compile-time 3x3 / stride-1 grid, wide-row loader, statistics epilogue, self-overlapped
+ *                                  form and its write-out variant (0: ping-pong form)
+ *   [8] PU  [9] STATS [10] KS      pipe: items per loader thread, statistics mode, K split over the wave pairs
+ *   [11] ksplit                    tile: split-K factor (> 1: splitk_reduce_kernel wrote the result)
+ *   [12] ranges                    column ranges launched (family 3; the tile fields are those of the last range), else 1
+ *   [13..15] 0 */
+int dam_conv_last_launch(int* out16_host);
 
 /* Weight gradient of the same convolutions (autograd of nn.Conv2d reached from loss.backward(),
  * model_trainer.py:36):  dw[n][k][kh][kw] = sum_{b,oh,ow} dy[b,oh,ow,n] * f(x[b, oh*stride+kh*dil-pad, ow*stride+kw*dil-pad, k])

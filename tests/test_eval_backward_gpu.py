@@ -11,6 +11,7 @@ import torch
 
 from _inputs import model_input
 from _model_check import best_over_seeds
+from _randomize import _randomize, _running_stats
 from oracle import models_ref
 
 pytestmark = pytest.mark.gpu
@@ -29,11 +30,6 @@ def dam(dam_lib):
 
 def _rel(got, want):
     return float((got.detach().double().cpu() - want.detach().double()).norm() / (want.detach().double().norm() + 1e-300))
-
-
-def _running_stats(C, gen):
-    """Non-trivial running statistics: mean in [-2, 2], var in [0.1, 10]."""
-    return 4 * torch.rand(C, generator=gen) - 2, 10 ** (2 * torch.rand(C, generator=gen) - 1)
 
 
 def _sign_bytes(mask):
@@ -141,23 +137,6 @@ def test_bn_backward_eval_exact(dam, B, H, W, C):
 
 
 # ---------------------------------------------------------------------------------------------------------------- blocks
-def _randomize(module, gen):
-    """Parameters as tests/test_blocks_gpu.py, plus running statistics: mean in [-0.5, 0.5] (the blocks' inputs are of order 1)
-    and var in [0.1, 10]."""
-    with torch.no_grad():
-        for m in module.modules():
-            if isinstance(m, torch.nn.BatchNorm2d):
-                m.weight.copy_(1.0 + 0.1 * torch.randn(m.weight.shape, generator=gen))
-                m.bias.copy_(0.1 * torch.randn(m.bias.shape, generator=gen))
-                rm, rv = _running_stats(m.num_features, gen)
-                m.running_mean.copy_(0.25 * rm), m.running_var.copy_(rv)
-            elif isinstance(m, torch.nn.Conv2d):
-                m.weight.copy_(torch.randn(m.weight.shape, generator=gen) * (2.0 / (m.weight[0].numel())) ** 0.5)
-                if m.bias is not None:
-                    m.bias.copy_(0.1 * torch.randn(m.bias.shape, generator=gen))
-    return module
-
-
 def _a1_mask(ops, out):
     saved = out.grad_fn.saved_tensors
     c1, sc1, sh1 = saved[5], saved[12], saved[13]
