@@ -62,6 +62,15 @@ struct DirectJobs { DirectJob job[WD_MAX_JOBS]; int njobs; };
 
 namespace {
 
+// What the last dam_conv2d_wgrad_f32 call of this thread committed to (dam_wgrad_last_launch, include/dam_hip.h): a host variable
+// written where a launcher has passed its last refusal, read by tests that must know which instantiation they exercised.
+enum WgradFamily { WGRAD_FAM_NONE = 0, WGRAD_FAM_ROWS = 1, WGRAD_FAM_ROWS_S2 = 2, WGRAD_FAM_DIRECT = 3, WGRAD_FAM_TILE = 4 };
+enum WgradIssue { WGRAD_REDUCED_NOW = 0, WGRAD_REDUCTION_QUEUED = 1, WGRAD_LAUNCH_RECORDED = 2 };
+struct WgradLaunchNote {
+    int family, TNB, TKB, STEPS, KP, GPP, GPPD, HV, NL, TA, TB, nx, nsplit, spi_tmw, rps, issued;
+};
+thread_local WgradLaunchNote wgrad_last_launch{};
+
 typedef float v4f __attribute__((ext_vector_type(4)));
 typedef int v4i __attribute__((ext_vector_type(4)));
 
@@ -756,6 +765,8 @@ int launch_wgrad_rows(int B, int H, int W, int C, const float* X, const float* d
     const int nsplit = B * g.spi;
     if ((int64_t)nsplit * nx * NBLK * 256 > ws_floats) return DAM_ERR_WORKSPACE;
     if (!raise_lds_limit<&wgrad_rows_kernel<TNB, TKB, STEPS, KP, GPP, HV, NL>>(160 * 1024)) return DAM_ERR_LAUNCH;
+    wgrad_last_launch = WgradLaunchNote{WGRAD_FAM_ROWS, TNB, TKB, STEPS, KP, GPP, 0, HV, NL, 0, 0, nx, nsplit, g.spi, g.rps,
+                                        queue ? WGRAD_REDUCTION_QUEUED : WGRAD_REDUCED_NOW};
     hipLaunchKernelGGL((wgrad_rows_kernel<TNB, TKB, STEPS, KP, GPP, HV, NL>), dim3(nx, nsplit), dim3((256 + 64 * NL)), lds, st, g, X, dY, in_scale,
                        in_shift, relu_in, partial);
     DAM_CHECK_LAUNCH();
@@ -1051,6 +1062,8 @@ int launch_wgrad_rows_s2(int B, int H, int W, int C, int Ho, int Wo, int N, cons
     const int nsplit = B * g.spi;
     if ((int64_t)nsplit * nx * NBLK * 256 > ws_floats) return DAM_ERR_WORKSPACE;
     if (!raise_lds_limit<&wgrad_rows_s2_kernel<TNB, STEPS, KP, GPPX, GPPD, HV>>(160 * 1024)) return DAM_ERR_LAUNCH;
+    wgrad_last_launch = WgradLaunchNote{WGRAD_FAM_ROWS_S2, TNB, 1, STEPS, KP, GPPX, GPPD, HV, RW_LOADERS, 0, 0, nx, nsplit, g.spi, g.rps,
+                                        queue ? WGRAD_REDUCTION_QUEUED : WGRAD_REDUCED_NOW};
     hipLaunchKernelGGL((wgrad_rows_s2_kernel<TNB, STEPS, KP, GPPX, GPPD, HV>), dim3(nx, nsplit), dim3(RW_THREADS), lds, st, g, X, dY,
                        partial);
     DAM_CHECK_LAUNCH();
@@ -1231,8 +1244,11 @@ int launch_wgrad_direct(int B, int H, int W, int C, int Ho, int Wo, int N, int s
         j.X = X; j.dY = dY; j.partial = partial; j.rows = rows; j.Ho = Ho; j.Wo = Wo; j.H = H; j.W = W; j.C = C; j.N = N; j.s = s;
         j.pad = pad; j.dil = dil; j.tiles_k = tiles_k; j.nx = nx; j.nsplit = nsplit; j.wg0 = 0;
         p.dw[i] = dw; p.n_real[i] = n_real; p.k_real[i] = k_real;
+        wgrad_last_launch = WgradLaunchNote{WGRAD_FAM_DIRECT, TNB, TKB, 0, 0, 0, 0, 0, 0, KH, KW, nx, nsplit, 0, 0, WGRAD_LAUNCH_RECORDED};
         return DAM_OK;
     }
+    wgrad_last_launch = WgradLaunchNote{WGRAD_FAM_DIRECT, TNB, TKB, 0, 0, 0, 0, 0, 0, KH, KW, nx, nsplit, 0, 0,
+                                        queue ? WGRAD_REDUCTION_QUEUED : WGRAD_REDUCED_NOW};
     hipLaunchKernelGGL((wgrad_direct_kernel<TNB, TKB, KH, KW>), dim3(nx, nsplit), dim3(256), 0, st, X, dY, rows, Ho, Wo, H, W, C,
                        N, s, pad, dil, tiles_k, partial);
     DAM_CHECK_LAUNCH();
@@ -1242,7 +1258,7 @@ int launch_wgrad_direct(int B, int H, int W, int C, int Ho, int Wo, int N, int s
 // One launch of the tile kernel for `njobs` weight gradients of geometry g (blockIdx.z = job), then their slab reductions.
 template <int TNB, int TKB, int TA, int TB>
 int launch_wgrad_jobs(WgradGeo g, const WgradJobs& jobs, int njobs, int64_t ws_floats, float* const* dw, const int* n_real,
-                      const int* k_real, void* queue, hipStream_t st) {
+                      const int* k_real, void* queue, hipStream_t st, bool note = false) {
     constexpr int NBLK = TNB * TKB * TA * TB;
     const int nx = g.tiles_n * g.tiles_k * g.tap_groups;
     size_t lds = (size_t)TKB * g.PR * g.PWT * 64 + (size_t)TNB * g.TMW * 64;
@@ -1274,6 +1290,9 @@ int launch_wgrad_jobs(WgradGeo g, const WgradJobs& jobs, int njobs, int64_t ws_f
     g.nsplit = nsplit;
     if (lds > 160 * 1024) return DAM_ERR_UNSUPPORTED;
     if (lds > 64 * 1024 && !raise_lds_limit<&wgrad_kernel<TNB, TKB, TA, TB>>(160 * 1024)) return DAM_ERR_LAUNCH;
+    if (note)                                // (not for the recorded launches of a flush: the record belongs to the last CALL)
+        wgrad_last_launch = WgradLaunchNote{WGRAD_FAM_TILE, TNB, TKB, 0, 0, 0, 0, 0, 0, TA, TB, nx, nsplit, g.TMW, 0,
+                                            queue ? WGRAD_REDUCTION_QUEUED : WGRAD_REDUCED_NOW};
     hipLaunchKernelGGL((wgrad_kernel<TNB, TKB, TA, TB>), dim3(nx, nsplit, njobs), dim3(256), lds, st, g, jobs);
     DAM_CHECK_LAUNCH();
     for (int i = 0; i < njobs; ++i) {
@@ -1321,12 +1340,14 @@ int launch_wgrad(WgradGeo& g, const float* X, const float* dY, const float* sc, 
         p.jobs.X[i] = X; p.jobs.dY[i] = dY; p.jobs.sc[i] = sc; p.jobs.sh[i] = sh; p.jobs.partial[i] = partial;
         p.jobs.relu_in[i] = relu_in;
         p.dw[i] = dw; p.ws_floats[i] = ws_floats; p.n_real[i] = n_real; p.k_real[i] = k_real;
+        wgrad_last_launch = WgradLaunchNote{WGRAD_FAM_TILE, TNB, TKB, 0, 0, 0, 0, 0, 0, TA, TB, g.tiles_n * g.tiles_k * g.tap_groups, 0,
+                                            g.TMW, 0, WGRAD_LAUNCH_RECORDED};
         return DAM_OK;
     }
     WgradJobs jobs;
     memset(&jobs, 0, sizeof(jobs));
     jobs.X[0] = X; jobs.dY[0] = dY; jobs.sc[0] = sc; jobs.sh[0] = sh; jobs.partial[0] = partial; jobs.relu_in[0] = relu_in;
-    return launch_wgrad_jobs<TNB, TKB, TA, TB>(g, jobs, 1, ws_floats, &dw, &n_real, &k_real, queue, st);
+    return launch_wgrad_jobs<TNB, TKB, TA, TB>(g, jobs, 1, ws_floats, &dw, &n_real, &k_real, queue, st, true);
 }
 
 }  // namespace
@@ -1371,6 +1392,15 @@ extern "C" int dam_wgrad_queue_flush(void* queue, void* stream) {
     return dam::reduce_flush(q->batch, (hipStream_t)stream);
 }
 
+extern "C" int dam_wgrad_last_launch(int* out16_host) {
+    if (!out16_host) return DAM_ERR_BAD_ARG;
+    const dam::WgradLaunchNote& n = dam::wgrad_last_launch;
+    const int v[16] = {n.family, n.TNB, n.TKB, n.STEPS, n.KP, n.GPP, n.GPPD, n.HV, n.NL, n.TA, n.TB, n.nx, n.nsplit, n.spi_tmw, n.rps,
+                       n.issued};
+    for (int i = 0; i < 16; ++i) out16_host[i] = v[i];
+    return DAM_OK;
+}
+
 extern "C" int64_t dam_conv2d_wgrad_workspace_floats(int n_out, int c_in, int kh, int kw) {
     if (n_out <= 0 || c_in <= 0 || kh <= 0 || kw <= 0) return 0;
     // enough for ~512 workgroup slabs of the largest tile, and at least 4 splits of the whole gradient
@@ -1384,12 +1414,14 @@ extern "C" int dam_conv2d_wgrad_f32(const float* x, int B, int H, int W, int C, 
                                     int n_out, int kh, int kw, int stride, int pad, int dil, float* dw, int c_real,
                                     float* workspace, int64_t workspace_floats, void* reduce_queue, void* stream) {
     using namespace dam;
+    wgrad_last_launch = WgradLaunchNote{};
     if (!x || !dy || !dw || !workspace || B <= 0 || H <= 0 || W <= 0 || C <= 0 || Ho <= 0 || Wo <= 0) return DAM_ERR_BAD_ARG;
     if (c_real < 0 || c_real > C) return DAM_ERR_BAD_ARG;
     const int k_real = c_real ? c_real : C;         // dw rows kept: the real input channels (the stem's zero-padded planes drop out)
     if (n_chan % 16 || n_out > n_chan || (stride != 1 && stride != 2)) return DAM_ERR_UNSUPPORTED;
     if (in_nchw ? C > 16 : C % 16) return DAM_ERR_UNSUPPORTED;
     if (in_scale && !in_shift) return DAM_ERR_BAD_ARG;
+    if (in_nchw && in_scale) return DAM_ERR_UNSUPPORTED;        // the NCHW loader (stage_patch) applies no affine: the first layer reads raw features
     hipStream_t st = (hipStream_t)stream;
     if (kh == 3 && kw == 3 && stride == 1 && pad == 1 && dil == 1 && !in_nchw && Ho == H && Wo == W && C == n_chan) {
         // row-streaming kernel for the shapes of the ResNet stages; anything else takes the tile kernel below

@@ -386,6 +386,23 @@ def conv2d_wgrad(x, dy, n_out, kh, kw, stride=1, pad=0, dil=1, in_scale=None, in
     return out
 
 
+WGRAD_FAMILIES = ('none', 'rows', 'rows_s2', 'direct', 'tile')
+WgradLaunch = collections.namedtuple('WgradLaunch', 'family TNB TKB STEPS KP GPP GPPD HV NL TA TB nx nsplit spi rps TMW issued')
+
+
+def wgrad_last_launch():
+    """Which kernel the last conv2d_wgrad call of this thread committed to (dam_wgrad_last_launch): the family by name, the
+    template parameters of the instantiation (rows_s2: GPP is GPPX; direct: TA, TB are KH, KW), the grid (nx, nsplit), strips per
+    image and rows per strip (row kernels) or pixels per tile (tile kernel), and how it was issued (0 launched and reduced now,
+    1 launched with the reduction queued, 2 the launch itself recorded for a batched launch at the flush); fields that do not
+    belong to the family are 0.  Host-side only."""
+    v = (ctypes.c_int * 16)()
+    _lib.check(_lib.lib().dam_wgrad_last_launch(v), 'dam_wgrad_last_launch')
+    fam = WGRAD_FAMILIES[v[0]]
+    rows = fam in ('rows', 'rows_s2')
+    return WgradLaunch(fam, *v[1:13], v[13] if rows else 0, v[14] if rows else 0, v[13] if fam == 'tile' else 0, v[15])
+
+
 def nchw_to_nhwc16(x):
     """[B,C,H,W] float32 (C <= 16) -> NHWC [B,H,W,16], channels C..15 zero."""
     _lib.require_cuda(x)

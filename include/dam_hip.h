@@ -55,7 +55,7 @@ struct dam_bn_bwd_sums; /* defined in the BatchNorm section */
 /* Library / build identification ("gfx950").  DAM_ABI_VERSION is bumped whenever a signature below changes; a binding
  * compares dam_abi_version() of the library it loaded with the version it was written against and refuses a stale one
  * (deep-audio-mixer_amd/_lib.py: EXPECTED_ABI). */
-#define DAM_ABI_VERSION 26
+#define DAM_ABI_VERSION 27
 const char* dam_arch(void);
 int dam_abi_version(void);
 
@@ -312,7 +312,9 @@ int dam_conv_last_launch(int* out16_host);
 
 /* Weight gradient of the same convolutions (autograd of nn.Conv2d reached from loss.backward(),
  * model_trainer.py:36):  dw[n][k][kh][kw] = sum_{b,oh,ow} dy[b,oh,ow,n] * f(x[b, oh*stride+kh*dil-pad, ow*stride+kw*dil-pad, k])
- *   x  : as for dam_conv2d_tapgrid_f32 (NHWC, or in_nchw planes for the first layer), same fused f()
+ *   x  : as for dam_conv2d_tapgrid_f32 (NHWC, or in_nchw planes for the first layer), same fused f() -- for NHWC input
+ *        only: in_nchw together with in_scale is DAM_ERR_UNSUPPORTED (the loader of the NCHW planes applies no affine, and
+ *        the first layer reads raw features)
  *   dy : NHWC [B][Ho][Wo][n_chan], n_chan % 16 == 0; only the first n_out channels are real
  *   dw : torch layout [n_out][c_real][kh][kw], fully overwritten; c_real <= C is the number of REAL input channels
  *        (0 = C): the zero-padded planes of the re-laid stem input (dam_nchw_to_nhwc16_f32) drop out, so the result can
@@ -351,6 +353,27 @@ int dam_wgrad_queue_flush(void* queue, void* stream);
  *   Contract while on: x, dy, in_scale / in_shift of a queued call must stay valid and unmodified until the flush as well
  *   (not only its workspace and dw).  Switching needs an empty queue (DAM_ERR_BAD_ARG otherwise). */
 int dam_wgrad_queue_set_batching(void* queue, int on);
+
+/* Which kernel the last dam_conv2d_wgrad_f32 call of the CALLING THREAD committed to (ABI 27): the entry point picks between four
+ * kernel families with 29 instantiations by row width and channel counts and falls through to the tile kernel without
+ * telling, so a test that means to exercise one instantiation asks here (as dam_conv_last_launch for the forward kernels).  A host
+ * variable: reset to "none" at the entry of every call, written where the dispatcher has passed an instantiation's last refusal --
+ * no device work, no kernel argument, nothing synchronised.  out16_host (host memory, 16 ints) receives
+ *   [0] family: 0 none (no call yet, or the call failed before committing), 1 row-streaming kernel (3x3 / stride 1), 2 row-streaming
+ *       kernel on column-parity planes (3x3 / stride 2), 3 direct kernel, 4 tile kernel
+ *   [1] TNB [2] TKB                output / input channel blocks of the workgroup's tile (family 2: TKB = 1)
+ *   [3] STEPS [4] KP               row kernels: MFMA steps per wave and row part, planes per loader wave
+ *   [5] GPP (family 2: GPPX) [6] GPPD   row kernels: 1 KB pieces per X row plane; family 2 also per dY row plane
+ *   [7] HV [8] NL                  row kernels: row parts per compute wave's row (1 or 2), loader waves
+ *   [9] TA [10] TB                 tile kernel: kernel rows / columns per tap group; direct kernel: KH / KW
+ *   [11] nx [12] nsplit            grid: channel (x tap group) tiles, pixel splits = slabs.  With [15] == 2 the split is decided when
+ *                                  the recorded launch runs: 0 for the tile kernel, the direct kernel's upper bound
+ *   [13] [14]                      row kernels: strips per image, output rows per strip; tile kernel: pixels per tile (TMW), 0
+ *   [15] how it was issued: 0 launched and reduced now, 1 launched, the reduction queued, 2 the launch itself recorded in the
+ *        batching queue (it runs with others of its kind at dam_wgrad_queue_flush or when the queue makes room; a recorded
+ *        tile launch has its LDS, workspace and LDS-limit refusals still ahead of it: they are returned by the call that runs it)
+ * Fields foreign to the family are 0. */
+int dam_wgrad_last_launch(int* out16_host);
 
 /* Diagnostic builds of the library only (libdam_hip_diag.so: dam_conv_strip.hip compiled with -DDAM_STRIP_DIAG_TAGS): the row-ring
  * convolution's loader waves tag every geometry-table entry with the tile it describes and its compute waves check the tag of every

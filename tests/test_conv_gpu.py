@@ -139,18 +139,43 @@ def test_full_resolution_layer1(ops):
     close(ops.conv2d_wgrad(nhwc(x).cuda(), nhwc(dy).cuda(), 16, 3, 3, 1, 1, 1), want_dw, 1e-4)
 
 
+def wgrad_ran(ops, family, *inst):
+    """The kernel the last conv2d_wgrad call committed to (ops.wgrad_last_launch()): rows <TNB, TKB, STEPS, HV, NL>,
+    rows_s2 <STEPS, HV>, direct <TNB, TKB, K>, tile <TNB, TKB, TA, TB>.  Every instantiation: tests/test_wgrad_kernels_gpu.py."""
+    rec = ops.wgrad_last_launch()
+    got = {'rows': (rec.TNB, rec.TKB, rec.STEPS, rec.HV, rec.NL), 'rows_s2': (rec.STEPS, rec.HV), 'direct': (rec.TNB, rec.TKB, rec.TA),
+           'tile': (rec.TNB, rec.TKB, rec.TA, rec.TB)}.get(rec.family)
+    assert (rec.family, got) == (family, inst) and rec.issued == 0, rec
+    return rec
+
+
+# row width -> the instantiation of the stride-1 row kernel whose window holds it (16 channels / from 32 channels on)
+ROW_KERNEL_16 = {127: (1, 1, 33, 1, 8), 130: (1, 1, 33, 1, 8), 215: (1, 1, 28, 2, 8), 216: (1, 1, 28, 2, 8)}
+ROW_KERNEL_32 = {9: (2, 1, 3, 1, 8), 17: (2, 1, 5, 1, 4), 31: (2, 1, 9, 1, 8), 33: (2, 1, 9, 1, 8), 54: (2, 1, 14, 1, 8),
+                 65: (2, 1, 17, 1, 8), 66: (2, 1, 17, 1, 8), 108: (2, 1, 14, 2, 8)}
+
+
 @pytest.mark.parametrize('B,C,H,W', [(2, 16, 23, 130), (1, 16, 9, 127), (2, 32, 21, 65), (1, 64, 19, 33), (3, 32, 4, 66),
                                      (1, 64, 37, 31), (1, 16, 9, 216), (2, 32, 7, 108), (1, 64, 11, 54), (1, 16, 3, 213),
-                                     (8, 16, 165, 130), (2, 96, 33, 17), (1, 128, 65, 9), (2, 256, 33, 5)])
+                                     (8, 16, 165, 130), (2, 96, 33, 17), (1, 128, 65, 9), (2, 256, 33, 5), (1, 16, 3, 215)])
 def test_wgrad_row_streaming_shapes(ops, B, C, H, W):
     """3x3 / stride 1 / pad 1 weight gradient at the widths of the ResNet stages (row-streaming kernel), ragged strips.
     (8, 16, 165, 130): 32 strips of 5 or 6 rows per image -- last slots of ONE row, which the one-block tile splits over its four
-    waves by MFMA steps; 17-pixel rows: the four-loader-wave instantiation; 5-pixel rows: the tile kernel with a 176-pixel tile."""
+    waves by MFMA steps; 17-pixel rows: the four-loader-wave instantiation; 5-pixel rows: the tile kernel with a 176-pixel tile.
+    (1, 16, 3, 213): W = 213 lies in neither 16-channel window (127..130, 215..222), so this is the one-block TILE kernel; the
+    strip shorter than a slot on the half-row instantiation is (1, 16, 3, 215)."""
     g = torch.Generator().manual_seed(B * 1000 + C + H + W)
     x = torch.randn(B, C, H, W, generator=g)
     dy = torch.randn(B, C, H, W, generator=g)
     want = torch.nn.grad.conv2d_weight(x.double(), (C, C, 3, 3), dy.double(), 1, 1)
     got = ops.conv2d_wgrad(nhwc(x).cuda(), nhwc(dy).cuda(), C, 3, 3, 1, 1, 1)
+    inst = (ROW_KERNEL_16 if C == 16 else ROW_KERNEL_32).get(W)
+    if inst:
+        wgrad_ran(ops, 'rows', *inst)
+    else:
+        assert W in (213, 5), 'name the kernel that rows of %d pixels at %d channels take (ROW_KERNEL_16 / ROW_KERNEL_32)' % (W, C)
+        rec = wgrad_ran(ops, 'tile', *((1, 1, 3, 3) if C == 16 else (2, 2, 3, 3)))
+        assert rec.TMW == {213: 128, 5: 176}[W], rec
     assert got.shape == (C, C, 3, 3)
     close(got, want, 5e-5)
 
@@ -162,29 +187,50 @@ def test_wgrad_row_streaming_shapes(ops, B, C, H, W):
 def test_wgrad_strided_row_streaming_shapes(ops, B, Ci, Co, H, W):
     """3x3 / stride 2 / pad 1 weight gradient of the down-sampling convolutions (row-streaming kernel with column-parity
     planes): odd and even heights and widths (bottom padding row / right padding column present or not), ragged strips,
-    strips of a single slot, the widths of the ResNet stages at 130 and 216 frames."""
+    strips of a single slot, the widths of the ResNet stages at 130 and 216 frames.  Output rows of 9 and 5 pixels (the last four
+    shapes) are kept off the row kernel by the dispatcher (Wo > 14): they run the tile kernel."""
     g = torch.Generator().manual_seed(B * 1000 + Ci + H + W)
     x = torch.randn(B, Ci, H, W, generator=g)
     Ho, Wo = (H - 1) // 2 + 1, (W - 1) // 2 + 1
     dy = torch.randn(B, Co, Ho, Wo, generator=g)
     want = torch.nn.grad.conv2d_weight(x.double(), (Co, Ci, 3, 3), dy.double(), 2, 1)
     got = ops.conv2d_wgrad(nhwc(x).cuda(), nhwc(dy).cuda(), Co, 3, 3, 2, 1, 1)
+    if Wo < 15:
+        # (33 output rows of 9 pixels: the patch of a two-block tile is past the tile kernel's 72 KB rule at either tile size)
+        wgrad_ran(ops, 'tile', *((1, 1, 3, 3) if (H, W) == (65, 17) else (2, 2, 3, 3)))
+    else:
+        inst = {65: (9, 2), 33: (9, 1), 17: (5, 1), 54: (7, 2), 27: (7, 1)}.get(Wo)
+        assert inst, 'name the stride-2 row instantiation (or other kernel) that output rows of %d pixels take' % Wo
+        wgrad_ran(ops, 'rows_s2', *inst)
     assert got.shape == (Co, Ci, 3, 3)
     close(got, want, 5e-5)
 
 
 @pytest.mark.parametrize('B,Ci,Co,H,W,k,s,p', [(2, 16, 32, 41, 65, 3, 2, 1), (1, 32, 64, 33, 34, 3, 2, 1), (2, 96, 96, 9, 17, 3, 1, 1),
                                               (1, 16, 32, 9, 216, 3, 2, 1), (1, 16, 16, 21, 40, 3, 2, 1),
-                                              (2, 16, 32, 41, 65, 1, 2, 0), (1, 64, 96, 21, 33, 1, 2, 0), (1, 48, 48, 20, 30, 3, 1, 1)])
+                                              (2, 16, 32, 41, 65, 1, 2, 0), (1, 64, 96, 21, 33, 1, 2, 0), (1, 48, 48, 20, 30, 3, 1, 1),
+                                              (2, 16, 32, 41, 45, 3, 2, 1), (1, 32, 64, 33, 38, 3, 2, 1), (2, 32, 48, 20, 46, 3, 2, 1),
+                                              (1, 48, 64, 21, 33, 1, 2, 0), (1, 64, 48, 21, 33, 1, 2, 0)])
 def test_wgrad_direct_kernel_shapes(ops, B, Ci, Co, H, W, k, s, p):
-    """Weight gradient without LDS staging: strided 3x3, narrow-row 3x3 and 1x1 shortcut shapes (ragged row ends, padding
-    columns and rows, odd channel-block counts)."""
+    """Weight gradient without LDS staging: strided 3x3 and 1x1 shortcut shapes (ragged row ends, padding columns and rows, odd
+    channel-block counts).  The direct kernel takes a strided 3x3 layer only where no stride-2 row window holds its output
+    width (Wo = 108, 20, 23, 19 here) and no stride-1 layer at all: the first three shapes run the two row kernels, (1, 48, 48,
+    20, 30) the tile kernel.  <2,2> needs even block counts on both sides ((1, 64, 96, ...): 4 and 6 blocks), an odd input
+    count gives <2,1>, an odd output count <1,1>."""
     g = torch.Generator().manual_seed(Ci + Co + H + W + k)
     x = torch.randn(B, Ci, H, W, generator=g)
     Ho, Wo = (H + 2 * p - k) // s + 1, (W + 2 * p - k) // s + 1
     dy = torch.randn(B, Co, Ho, Wo, generator=g)
     want = torch.nn.grad.conv2d_weight(x.double(), (Co, Ci, k, k), dy.double(), s, p)
     got = ops.conv2d_wgrad(nhwc(x).cuda(), nhwc(dy).cuda(), Co, k, k, s, p, 1)
+    if s == 1:
+        wgrad_ran(ops, *(('rows', 2, 1, 5, 1, 4) if Ci == 96 else ('tile', 2, 2, 3, 3)))
+    elif k == 3 and Wo in (33, 17):
+        wgrad_ran(ops, 'rows_s2', *{33: (9, 1), 17: (5, 1)}[Wo])
+    else:
+        assert k == 1 or Wo in (108, 20, 23, 19), 'output rows of %d pixels: inside a stride-2 row window?' % Wo
+        tn = 2 if Co // 16 % 2 == 0 else 1
+        wgrad_ran(ops, 'direct', tn, 2 if k == 1 and tn == 2 and Ci // 16 % 2 == 0 else 1, k)
     assert got.shape == (Co, Ci, k, k)
     close(got, want, 5e-5)
 
