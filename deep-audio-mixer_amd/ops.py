@@ -141,7 +141,7 @@ def _dgrad_axis(parity, pad, dil, k, stride):
 
 
 def conv2d_dgrad(dy, wpt, n_in, H, W, kh, kw, stride=1, pad=0, dil=1, res=None, res_mask=None, accumulate_into=None,
-                 bn_bwd=None, res_mask_bits=None, pair_1x1=None, _s2_sums=None):
+                 bn_bwd=None, res_mask_bits=None, pair_1x1=None, _s2_sums=None, out=None):
     """dy: NHWC [B,Ho,Wo,Cout]; wpt packed with transpose=True.  Returns dx NHWC [B,H,W,n_in16]
     (+ res * (res_mask > 0) if given).  With accumulate_into=dx0 the result is added to dx0 in place.
     bn_bwd=(x, save_mean, save_invstd, mask_scale, mask_shift[, mask_bits]) (stride 1; 3x3 / stride 2 / pad 1 with the mask_bits
@@ -149,8 +149,15 @@ def conv2d_dgrad(dy, wpt, n_in, H, W, kh, kw, stride=1, pad=0, dil=1, res=None, 
     mask_bits and scale = shift = None, relu(bn(x) + shortcut) whose sign bytes they are); returns
     (dx, partials) where partials = (records, count) for bn_backward(partials=) when the launch could also take that
     BatchNorm's two backward sums from its epilogue, else None (stride 1; with a residual only when its mask is also given
-    as the sign bytes of bn_apply, res_mask_bits -- the float res_mask serves the launches that cannot use them)."""
+    as the sign bytes of bn_apply, res_mask_bits -- the float res_mask serves the launches that cannot use them).
+    out: the result tensor to write (contiguous float32 [B,H,W,n_in16] on dy's device) instead of a fresh one."""
     _lib.require_cuda(dy, wpt)
+    if out is not None:
+        want = (dy.shape[0], H, W, (n_in + 15) // 16 * 16)
+        if accumulate_into is not None:
+            raise ValueError('out and accumulate_into exclude each other')
+        if out.dtype != torch.float32 or not out.is_contiguous() or tuple(out.shape) != want or out.device != dy.device:
+            raise ValueError('out must be a contiguous float32 tensor of shape %s on %s' % (want, dy.device))
     if bn_bwd is not None and stride == 2:
         # the strided form: the upstream BatchNorm is a residual block's bn2 (mask = the sign bytes of the block output); only the
         # one-launch kernels of the thin stages take its sums, (dx, None) otherwise
@@ -163,7 +170,7 @@ def conv2d_dgrad(dy, wpt, n_in, H, W, kh, kw, stride=1, pad=0, dil=1, res=None, 
             raise ValueError('bn_bwd: x has the shape of the data gradient')
         rec = torch.empty(_lib.lib().dam_bn_workspace_floats(n16), dtype=torch.float32, device=dy.device)
         epi = _lib.BnBwdSums(_lib.ptr(xb), _lib.ptr(mean), _lib.ptr(invstd), None, None, None, _lib.ptr(up_bits))
-        got = conv2d_dgrad(dy, wpt, n_in, H, W, kh, kw, stride, pad, dil, pair_1x1=pair_1x1, _s2_sums=(epi, rec))
+        got = conv2d_dgrad(dy, wpt, n_in, H, W, kh, kw, stride, pad, dil, pair_1x1=pair_1x1, _s2_sums=(epi, rec), out=out)
         return got if isinstance(got, tuple) else (got, None)
     if bn_bwd is not None:
         if stride != 1 or accumulate_into is not None:
@@ -180,7 +187,7 @@ def conv2d_dgrad(dy, wpt, n_in, H, W, kh, kw, stride=1, pad=0, dil=1, res=None, 
         n16 = (n_in + 15) // 16 * 16
         if tuple(xb.shape) != (B, H, W, n16):
             raise ValueError('bn_bwd: x has the shape of the data gradient')
-        dx = torch.empty((B, H, W, n16), dtype=torch.float32, device=dy.device)
+        dx = out if out is not None else torch.empty((B, H, W, n16), dtype=torch.float32, device=dy.device)
         rec = torch.empty(_lib.lib().dam_bn_workspace_floats(n16), dtype=torch.float32, device=dy.device)
         epi = _lib.BnBwdSums(_lib.ptr(xb), _lib.ptr(mean), _lib.ptr(invstd), _lib.ptr(msc), _lib.ptr(msh), _lib.ptr(res_mask_bits),
                              _lib.ptr(up_bits))
@@ -193,7 +200,7 @@ def conv2d_dgrad(dy, wpt, n_in, H, W, kh, kw, stride=1, pad=0, dil=1, res=None, 
     if accumulate_into is not None:
         dx, res, res_mask = accumulate_into, accumulate_into, None
     else:
-        dx = torch.empty((B, H, W, n16), dtype=torch.float32, device=dy.device)
+        dx = out if out is not None else torch.empty((B, H, W, n16), dtype=torch.float32, device=dy.device)
     if stride == 1:
         _tapgrid(dy, B, Ho, Wo, Co, False, wpt, Co // 16, n16, None, None, None, False, dx, H, W, H, W, 1, 0, 0, 1,
                  kh, kw, pad, -dil, pad, -dil, 0, kw, 1, res, res_mask)

@@ -319,7 +319,8 @@ def test_bn_stats_against_float64(ops):
 def test_loader_wave_tile_kernel(ops, B, C, H, W, s, monkeypatch):
     """conv_pipe_kernel (thick 3x3 stages): every tile of its rule, few persistent workgroups (each walks many units, so the
     chunk stream crosses unit and image boundaries), the fused input affine, the residual epilogue -- and the tile kernel on
-    the same inputs (DAM_NO_PIPE) as a second witness."""
+    the same inputs (DAM_NO_PIPE) as a second witness.  (At 96 channels DAM_TILE=1x4 does not divide the six blocks: the tile
+    kernel answers there too -- ops.conv_last_launch(); tests/test_conv_training_epilogue_gpu.py names the launch of every case.)"""
     g = torch.Generator().manual_seed(C + W)
     x = torch.randn(B, C, H, W, generator=g)
     w = torch.randn(C, C, 3, 3, generator=g) / (C * 9) ** 0.5
@@ -396,7 +397,10 @@ def test_dgrad_bn_backward_sums_epilogue(ops, B, C, H, W):
     """conv2d_dgrad(bn_bwd=...): the data gradient is bitwise the plain one, and the records it leaves are the two sums of
     the BatchNorm backward pass of relu(bn(x)) -- checked against float64 and through bn_backward(partials=) against the
     separate pass.  Both kernels that have the epilogue are covered (row-ring kernel: 16 / 32 channels; loader-wave tile kernel:
-    thick layers); a thick layer whose tiles would leave more than 1024 records returns partials None (last case)."""
+    thick layers); a thick layer whose tiles would leave more than 1024 records returns partials None (last case).  By the launch
+    record these shapes reach strip EPI 1 in the self-overlapped and the wide-row form at 16 and 32 channels and pipe STATS 2 on
+    three of its eleven instantiations; tests/test_conv_training_epilogue_gpu.py names the launch of every case and lists the
+    instantiations it requires and those no call reaches, with the sums against float64 sums of the float64 reference gradient."""
     g = torch.Generator().manual_seed(B * 100 + C + H + W)
     dy = torch.randn(B, H, W, C, generator=g).cuda()
     w = torch.randn(C, C, 3, 3, generator=g) / (3 * C ** 0.5)
