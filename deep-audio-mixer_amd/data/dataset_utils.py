@@ -316,9 +316,37 @@ def _load(path, sr):
     return a[:, 0].copy() if a.shape[1] == 1 else a.T.copy()   # mono=False: [n] for mono files, else [channels, n]
 
 
-def load_tracks(base_dir, song_name, tracklist=('bass', 'drums', 'vocals', 'other', 'mix'), sr=44100) -> dict:
+def align_tracks_to_mix(tracks, max_lag):
+    """{track: ndarray [channels, n] or [n]} with a 'mix' entry -> the same dict with every stem shifted by its lag against
+    the mix (zeros shifted in), the mix untouched: the lag is the peak of the plain cross-correlation within +-max_lag
+    samples (a stem that is a component of the mix peaks at its own offset whatever its spectrum), estimated and removed
+    on the GPU (align.estimate_lag / align.shift_tracks; a silent stem stays where it is).  For a dataset's own mix file, which need not start where its stems do.  All tracks must share one shape;
+    needs a GPU -- there is no CPU fallback."""
+    import torch
+    from .. import align
+    if 'mix' not in tracks:
+        raise ValueError("align_to_mix needs the 'mix' track in the tracklist")
+    names = [t for t in tracks if t != 'mix']
+    mix = np.asarray(tracks['mix'])
+    if not names or any(np.asarray(tracks[t]).shape != mix.shape or np.asarray(tracks[t]).dtype != mix.dtype for t in names):
+        raise ValueError('align_to_mix: the stems and the mix must share one shape and dtype, got %s'
+                         % {t: np.asarray(a).shape for t, a in tracks.items()})
+    dev = torch.device('cuda')
+    stems = torch.from_numpy(np.stack([np.asarray(tracks[t]).reshape(-1, mix.shape[-1]) for t in names])).to(dev)   # [S, C, n]
+    target = torch.from_numpy(mix.reshape(-1, mix.shape[-1])).to(dev)
+    lag = align.estimate_lag(stems.transpose(1, 2), target.transpose(0, 1), max_lag, weighting='plain')[0]
+    shifted = align.shift_tracks(stems.transpose(1, 2), lag).transpose(1, 2).cpu().numpy()
+    out = dict(tracks)
+    for i, t in enumerate(names):
+        out[t] = np.ascontiguousarray(shifted[i].reshape(mix.shape))
+    return out
+
+
+def load_tracks(base_dir, song_name, tracklist=('bass', 'drums', 'vocals', 'other', 'mix'), sr=44100, align_to_mix=None) -> dict:
     """data/dataset_utils.py:53-68, MedleyDB layout: {track: float32 ndarray[channels, n]} (what
-    ``librosa.load(path, sr=sr, mono=False)`` returns for files already at `sr`)."""
+    ``librosa.load(path, sr=sr, mono=False)`` returns for files already at `sr`).  align_to_mix: None, or the largest lag in
+    samples within which every stem is moved onto the loaded 'mix' (align_tracks_to_mix) -- MedleyDB's mixes are bounces of
+    their own, not the sum of the stem files."""
     out = {}
     for track in tracklist:
         if track == 'mix':
@@ -327,13 +355,16 @@ def load_tracks(base_dir, song_name, tracklist=('bass', 'drums', 'vocals', 'othe
             p = os.path.join(base_dir, song_name, '{}_STEMS_JOINED'.format(song_name),
                              '{}_STEM_{}.wav'.format(song_name, track.upper()))
         out[track] = _load(p, sr)
-    return out
+    return out if align_to_mix is None else align_tracks_to_mix(out, align_to_mix)
 
 
-def load_tracks_musdb18(base_dir, song_name, tracklist=('bass', 'drums', 'vocals', 'other', 'mix'), sr=44100) -> dict:
-    """data/dataset_utils.py:71-83, MUSDB18-HQ layout: {song}/{bass,drums,vocals,other,mixture}.wav."""
-    return {track: _load(os.path.join(base_dir, song_name, '{}.wav'.format('mixture' if track == 'mix' else track)), sr)
-            for track in tracklist}
+def load_tracks_musdb18(base_dir, song_name, tracklist=('bass', 'drums', 'vocals', 'other', 'mix'), sr=44100,
+                        align_to_mix=None) -> dict:
+    """data/dataset_utils.py:71-83, MUSDB18-HQ layout: {song}/{bass,drums,vocals,other,mixture}.wav.  align_to_mix: as
+    load_tracks takes it."""
+    out = {track: _load(os.path.join(base_dir, song_name, '{}.wav'.format('mixture' if track == 'mix' else track)), sr)
+           for track in tracklist}
+    return out if align_to_mix is None else align_tracks_to_mix(out, align_to_mix)
 
 
 # ---- WAV encoding (stands in for soundfile.write) -------------------------------------------------------------------

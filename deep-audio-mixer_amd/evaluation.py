@@ -40,7 +40,7 @@ from statistics import mean
 import numpy as np
 import torch
 
-from . import gainfit, inference_utils, ops, spectrum, staging
+from . import align, gainfit, inference_utils, ops, spectrum, staging
 from .loudness import Meter, curve_stats_device, normalize_loudness, profile_error_device
 from .models.baselines.mean_loudness_model import MeanLoudnessModel
 from .models.baselines.random_model import RandomModel
@@ -123,16 +123,24 @@ class LoudnessEvaluator:
         edges, centres = spectrum.band_edges(self.sr, o['n_fft'], o['fraction'], o['f_lo'], o['f_hi'])
         return o['n_fft'], hop, edges, centres
 
-    GAIN_FIT_DEFAULTS = {'pool': 0, 'ridge': 0.0}
+    GAIN_FIT_DEFAULTS = {'pool': 0, 'ridge': 0.0, 'align': None}
 
     def _gain_fit_args(self, gain_fit):
-        """``gain_fit`` as the whole-song methods take it (True, or a dict with any of pool, ridge) -> (pool, ridge)."""
+        """``gain_fit`` as the whole-song methods take it (True, or a dict with any of pool, ridge, align) -> (pool, ridge);
+        _gain_fit_align gives its align."""
         given = {} if gain_fit is True else dict(gain_fit)
         unknown = set(given) - set(self.GAIN_FIT_DEFAULTS)
         if unknown:
             raise ValueError('gain_fit: unknown keys %s (expected any of %s)' % (sorted(unknown), sorted(self.GAIN_FIT_DEFAULTS)))
         o = dict(self.GAIN_FIT_DEFAULTS, **given)
         return ops.gainfit_check_solve_args(o['pool'], o['ridge'])
+
+    def _gain_fit_align(self, gain_fit):
+        """-> None, or the largest lag in samples the stems are searched for against the reference (the 'align' key)."""
+        max_lag = None if gain_fit is True else dict(gain_fit).get('align')
+        if max_lag is not None:
+            ops.align_check_shapes((1, 1, 1), None, max_lag)
+        return max_lag
 
     def evaluate_spectrum_batch(self, stems, gains=None, **spectral):
         """Band powers of the stem sum (long-term average spectrum in fractional-octave bands at the evaluator's rate),
@@ -210,7 +218,14 @@ class LoudnessEvaluator:
         that best rebuild the float64 sum of the reference stems from ``loaded_tracks``, one per stem and window of the
         model's gain ramp, relative to each window's mean over the stems -- 'oracle_gains' {name: [windows]}, those fitted
         gains (NaN where a stem is silent), and 'oracle_residual' [windows], the share of the reference's energy they leave
-        unexplained.  Nothing else depends on it.  The reference mix and the stems must be of one length."""
+        unexplained.  Nothing else depends on it.  The reference mix and the stems must be of one length.
+        gain_fit={'align': max_lag_samples} is for a reference that is not aligned with ``loaded_tracks`` (a mix that did not
+        come out of this package): every stem's lag against the reference within +-max_lag is estimated on the device
+        (align.estimate_lag with the plain weighting: a stem that is a component of the reference peaks at its own offset
+        whatever its spectrum, where the PHAT weighting loses a near-sinusoidal stem) and the stems are shifted by it before
+        the fit; the stats gain 'oracle_lag' {name: samples, positive where the reference is late} and 'oracle_lag_peak'
+        {name: the normalised correlation at that lag, 0 .. 1, NaN for a silent stem}.  Absent (the default), nothing is
+        estimated and no key is added."""
         if self.d is None or self.mix_model is None or self.mean_loudness_model is None:
             raise ValueError('process_song needs the dataset, d_mean_loudness and mix_model constructor arguments')
         stems = [t for t in self.d.get_tracklist() if t != 'mix']
@@ -219,7 +234,7 @@ class LoudnessEvaluator:
         if dynamics and np.asarray(reference_tracks[self.keys[0]]).shape[-1] != np.asarray(loaded_tracks[self.keys[0]]).shape[-1]:
             raise ValueError('dynamics=True compares window by window: the reference mix and the stems differ in length')
         if gain_fit:
-            fit_pool, fit_ridge = self._gain_fit_args(gain_fit)
+            (fit_pool, fit_ridge), fit_align = self._gain_fit_args(gain_fit), self._gain_fit_align(gain_fit)
             if np.asarray(reference_tracks[self.keys[0]]).shape[-1] != np.asarray(loaded_tracks[self.keys[0]]).shape[-1]:
                 raise ValueError('gain_fit fits sample by sample: the reference mix and the stems differ in length')
         stats = {'song_name': song_name}
@@ -315,18 +330,27 @@ class LoudnessEvaluator:
                              'mix': host[n_var + n_bands:]}
         if gain_fit:                                        # one launch for every variant, one copy to the host
             n_stems, W = len(self.keys), mixer.n_proc
-            fitted, residual, _ = gainfit.fit_gains(pcm.transpose(1, 2), fit_target.transpose(0, 1), W, pool=fit_pool,
-                                                    ridge=fit_ridge)
+            fit_stems = pcm.transpose(1, 2)
+            if fit_align is not None:                       # the raw stems moved onto the reference; the lags stay on the device
+                stem_lag, _, stem_lag_peak, _, _ = align.estimate_lag(fit_stems, fit_target.transpose(0, 1), fit_align,
+                                                                      weighting='plain')
+                fit_stems = align.shift_tracks(fit_stems, stem_lag)
+            fitted, residual, _ = gainfit.fit_gains(fit_stems, fit_target.transpose(0, 1), W, pool=fit_pool, ridge=fit_ridge)
             constant = torch.stack(candidates_fit).unsqueeze(-1).expand(-1, -1, W)         # loudnorm, draws: [.., stems, W]
             cand = torch.cat([torch.ones((1, n_stems, W), dtype=torch.float64, device=pcm.device), constant[:1],
                               mixer.gains[1].unsqueeze(0), constant[1:]])
             fit_errors = gainfit.gain_error_device(fitted, cand)[0]
-            host = torch.cat([fit_errors, fitted.reshape(-1), residual]).cpu().tolist()
+            tail = [stem_lag.to(torch.float64), stem_lag_peak] if fit_align is not None else []
+            host = torch.cat([fit_errors, fitted.reshape(-1), residual] + tail).cpu().tolist()
             n_var = cand.shape[0]
             stats['sum_gain_error'], stats['loudnorm_gain_error'], stats['mix_gain_error'] = host[:3]
             stats['random_gain_error'] = mean(host[3:n_var]) if n_var > 3 else float('nan')
             stats['oracle_gains'] = {name: host[n_var + i * W:n_var + (i + 1) * W] for i, name in enumerate(self.keys)}
-            stats['oracle_residual'] = host[n_var + n_stems * W:]
+            stats['oracle_residual'] = host[n_var + n_stems * W:n_var + n_stems * W + W]
+            if fit_align is not None:
+                lags = host[n_var + n_stems * W + W:]
+                stats['oracle_lag'] = {name: int(lags[i]) for i, name in enumerate(self.keys)}
+                stats['oracle_lag_peak'] = dict(zip(self.keys, lags[n_stems:]))
         return stats
 
     def process_song(self, base_dir: str, song_name: str, n_random_samples: int = 5, chunk_length: int = 2,

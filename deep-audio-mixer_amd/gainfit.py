@@ -40,11 +40,18 @@ def solve(moment_matrices, *, pool=0, ridge=0.0):
     return ops.gainfit_solve(moment_matrices, pool, ridge)
 
 
-def fit_gains(stems, mix, n_windows, *, pool=0, ridge=0.0):
+def fit_gains(stems, mix, n_windows, *, pool=0, ridge=0.0, align=None, align_weighting='phat'):
     """``solve(moments(stems, mix, n_windows), pool=pool, ridge=ridge)`` -> (gains [S, W], residual [W], status [W]): the
-    gains the mix used, in the mixer's layout.  Nothing comes to the host; hipGraph-capturable."""
+    gains the mix used, in the mixer's layout.  Nothing comes to the host; hipGraph-capturable.
+    align: None (the stems and the mix are taken as aligned), or ``max_lag`` in samples: the lag of every stem against the
+    mix is estimated within +-max_lag (align.estimate_lag with ``align_weighting``: 'phat', or 'plain' for near-sinusoidal
+    stems, which PHAT loses), the stems are shifted by it on the device and the shifted stems are fitted -- for a mix that
+    is not the sum of these very arrays.  The lags themselves are ``align.estimate_lag``'s to report."""
     ops.gainfit_check_shapes(tuple(stems.shape), tuple(mix.shape), n_windows)
     pool, ridge = ops.gainfit_check_solve_args(pool, ridge)
+    if align is not None:
+        ops.align_check_shapes(tuple(stems.shape), tuple(mix.shape), align, align_weighting)
+        stems = ops.align_shift(stems, ops.align_estimate(stems, mix, align, align_weighting)[0])
     return ops.gainfit_solve(ops.gainfit_moments(stems, mix, n_windows), pool, ridge)
 
 

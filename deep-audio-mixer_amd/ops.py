@@ -1206,6 +1206,115 @@ def gainfit_gain_error(fit, cand, err_out=None, err_stem_out=None, n_kept_out=No
     return err_out, err_stem_out, n_kept_out
 
 
+# ----------------------------------------------------------------------------- alignment
+ALIGN_MAX_STEMS = 8
+ALIGN_WEIGHTINGS = {'plain': 0, 'phat': 1}      # DAM_ALIGN_PLAIN, DAM_ALIGN_PHAT
+ALIGN_MAX_LAG = 4096                            # dam_align_max_lag(); align_geometry() asks the library
+
+
+def align_geometry(max_lag=None):
+    """(largest max_lag, frames one workgroup owns) of dam_align_estimate, asked of the library; with ``max_lag`` also the
+    frame length N and the hop H = N / 2 for it: (cap, F, N, H)."""
+    L = _lib.lib()
+    cap, F = L.dam_align_max_lag(), L.dam_align_frames_per_block()
+    if max_lag is None:
+        return cap, F
+    N = L.dam_align_fft_size(int(max_lag))
+    if N <= 0:
+        raise ValueError('align: max_lag must be 1..%d, got %r' % (cap, max_lag))
+    return cap, F, N, N // 2
+
+
+def align_check_shapes(stems_shape, mix_shape, max_lag, weighting='phat'):
+    """The host-side argument rules of align_estimate on shapes alone -> (S, n, channels, L, weighting code); ValueError /
+    TypeError otherwise.  No tensor and no library is touched."""
+    if len(stems_shape) != 3:
+        raise ValueError('align: stems must be [stems, samples, channels], got shape %s' % (tuple(stems_shape),))
+    S, n, ch = stems_shape
+    if not 1 <= S <= ALIGN_MAX_STEMS:
+        raise ValueError('align: 1..%d stems expected, got %d' % (ALIGN_MAX_STEMS, S))
+    if ch not in (1, 2):
+        raise ValueError('align: 1 or 2 channels expected, got %d' % ch)
+    if n < 1:
+        raise ValueError('align: at least one sample expected')
+    if mix_shape is not None and tuple(mix_shape) != (n, ch):
+        raise ValueError('align: the mix must be [samples, channels] = [%d, %d] as the stems are, got shape %s'
+                         % (n, ch, tuple(mix_shape)))
+    if not isinstance(max_lag, numbers.Integral) or isinstance(max_lag, bool):
+        raise TypeError('align: max_lag must be an integer')
+    if not 1 <= max_lag <= ALIGN_MAX_LAG:
+        raise ValueError('align: max_lag must be 1..%d samples, got %d' % (ALIGN_MAX_LAG, max_lag))
+    if weighting not in ALIGN_WEIGHTINGS:
+        raise ValueError('align: unknown weighting %r (expected one of %s)' % (weighting, sorted(ALIGN_WEIGHTINGS)))
+    return S, n, ch, int(max_lag), ALIGN_WEIGHTINGS[weighting]
+
+
+def align_estimate(stems, mix, max_lag, weighting='phat', twiddles=None, want_curve=False, workspace=None):
+    """stems: CUDA float32 / float64 [S, samples, channels] with any strides; mix: CUDA float32 / float64 [samples, channels]
+    with any strides, its dtype independent of the stems' -> (lag int32 [S], frac float64 [S], peak float64 [S], sign int32
+    [S], status int32 [S], curve float64 [S, 2 max_lag + 1] or None): the lag of the largest |cross-correlation| of every stem
+    with the mix within +-max_lag samples (include/dam_hip.h: dam_align_estimate states the definitions and the order of the
+    additions).  twiddles: the float32 table of features._get_tables for dam_align_fft_size(max_lag), fetched when None.
+    workspace: optional float64 tensor of dam_align_workspace_bytes / 8 elements.  No host synchronisation,
+    hipGraph-capturable (once the table is resident: a first call outside the capture uploads it)."""
+    _lib.require_cuda(stems, mix, twiddles, workspace)
+    xk, yk = _audio_kind(stems, 'stems'), _audio_kind(mix, 'mix')
+    S, n, ch, Lg, wcode = align_check_shapes(stems.shape, mix.shape, max_lag, weighting)
+    dev = stems.device
+    if mix.device != dev:
+        raise ValueError('align_estimate: the stems and the mix must be on one device')
+    L = _lib.lib()
+    N = L.dam_align_fft_size(Lg)
+    if twiddles is None:
+        from . import features
+        twiddles = features._get_tables(dev, N)[1]
+    if twiddles.dtype != torch.float32 or twiddles.numel() != 2 * N or not twiddles.is_contiguous():
+        raise ValueError('align_estimate: twiddles must be a contiguous float32 tensor of %d elements' % (2 * N))
+    need = L.dam_align_workspace_bytes(S, n, Lg) // 8
+    if workspace is None:
+        workspace = torch.empty(need, dtype=torch.float64, device=dev)
+    elif workspace.dtype != torch.float64 or workspace.numel() < need or not workspace.is_contiguous():
+        raise ValueError('align_estimate: workspace must be a contiguous float64 tensor of at least %d elements' % need)
+    lag = torch.empty(S, dtype=torch.int32, device=dev)
+    sign = torch.empty(S, dtype=torch.int32, device=dev)
+    status = torch.empty(S, dtype=torch.int32, device=dev)
+    frac = torch.empty(S, dtype=torch.float64, device=dev)
+    peak = torch.empty(S, dtype=torch.float64, device=dev)
+    curve = torch.empty((S, 2 * Lg + 1), dtype=torch.float64, device=dev) if want_curve else None
+    with torch.cuda.device(dev):
+        _lib.check(L.dam_align_estimate(_lib.ptr(stems), xk, S, ch, n, stems.stride(0), stems.stride(1), stems.stride(2),
+                                        _lib.ptr(mix), yk, mix.stride(0), mix.stride(1), Lg, wcode, _lib.ptr(twiddles),
+                                        _lib.ptr(lag), _lib.ptr(frac), _lib.ptr(peak), _lib.ptr(sign), _lib.ptr(status),
+                                        _lib.ptr(curve), _lib.ptr(workspace), _lib.stream()), 'dam_align_estimate')
+    return lag, frac, peak, sign, status, curve
+
+
+def align_shift(stems, lag, out=None):
+    """stems: CUDA float32 / float64 [S, samples, channels] with any strides; lag: CUDA int32 [S] (read on the device) ->
+    out[s, p] = stems[s, p - lag[s]], 0 outside the stem: the stems' dtype, and their layout where that is dense (planar
+    storage stays planar), contiguous otherwise.  out: optional tensor of that shape and dtype that does not overlap the
+    stems.  No host synchronisation, hipGraph-capturable."""
+    _lib.require_cuda(stems, lag, out)
+    xk = _audio_kind(stems, 'stems')
+    S, n, ch, _, _ = align_check_shapes(stems.shape, None, 1)
+    if lag.dtype != torch.int32 or tuple(lag.shape) != (S,) or not lag.is_contiguous():
+        raise ValueError('align_shift: lag must be a contiguous int32 [%d] tensor' % S)
+    if lag.device != stems.device:
+        raise ValueError('align_shift: the stems and the lags must be on one device')
+    if out is None:
+        if stems.transpose(1, 2).is_contiguous():
+            out = torch.empty((S, ch, n), dtype=stems.dtype, device=stems.device).transpose(1, 2)
+        else:
+            out = torch.empty((S, n, ch), dtype=stems.dtype, device=stems.device)
+    elif tuple(out.shape) != (S, n, ch) or out.dtype != stems.dtype or out.device != stems.device:
+        raise ValueError('align_shift: out must be a %s [%d, %d, %d] tensor on the stems\' device' % (stems.dtype, S, n, ch))
+    with torch.cuda.device(stems.device):
+        _lib.check(_lib.lib().dam_align_shift(_lib.ptr(stems), xk, S, ch, n, stems.stride(0), stems.stride(1), stems.stride(2),
+                                              _lib.ptr(lag), _lib.ptr(out), out.stride(0), out.stride(1), out.stride(2),
+                                              _lib.stream()), 'dam_align_shift')
+    return out
+
+
 # ----------------------------------------------------------------------------- dropout
 _dropout_counters = {}
 

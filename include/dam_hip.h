@@ -55,7 +55,7 @@ struct dam_bn_bwd_sums; /* defined in the BatchNorm section */
 /* Library / build identification ("gfx950").  DAM_ABI_VERSION is bumped whenever a signature below changes; a binding
  * compares dam_abi_version() of the library it loaded with the version it was written against and refuses a stale one
  * (deep-audio-mixer_amd/_lib.py: EXPECTED_ABI). */
-#define DAM_ABI_VERSION 27
+#define DAM_ABI_VERSION 28
 const char* dam_arch(void);
 int dam_abi_version(void);
 
@@ -899,6 +899,71 @@ int dam_gainfit_solve(const double* moments, int n_windows, int n_stems, int poo
                       double* residual, int32_t* status, void* stream);
 int dam_gainfit_gain_error(const double* fit, const double* cand, int n_variants, int n_stems, int n_windows, int n_cand,
                            double* err, double* err_stem, int32_t* n_kept, void* stream);
+
+/* ---------------------------------------------------------------------------------
+ * Alignment (ABI 28): the time offset of every stem against a mix by block cross-correlation, and the sample shift that removes
+ * it -- what the gain fit above needs before it can be trusted on a mix that is not the sum of the same arrays (a dataset's
+ * own mix file, a bounce with plug-in delay, a file trimmed by hand).  Every entry is stateless, allocates nothing, does not
+ * synchronise with the host, uses no atomics and is hipGraph-capturable.  tests/_align_ref.py restates the definitions in
+ * numpy float64.
+ *   Signals.  Stems s = 0 .. S-1, 1 <= S <= 8, and one mix y, of `channels` (1 or 2) and n = n_samples samples, addressed as
+ *     dam_gainfit_moments addresses them (element strides, float32 or float64, the mix independently of the stems).
+ *     Mono signal: a_s[p] = (float)(((double)l + (double)r) * 0.5) for the two channels l, r, or (float) of the single
+ *     channel; y[p] likewise for the mix.  A sample outside [0, n) is 0.
+ *   Cross-correlation.  R_s[l] = sum_p a_s[p] * y[p + l], l in [-L, L], L = max_lag, 1 <= L <= dam_align_max_lag() (4096).
+ *     A positive lag means the mix is late: y[q] = a[q - d] peaks at l = d.
+ *   Framing.  N = dam_align_fft_size(L) = max(64, 4 * 2^ceil(log2 L)), H = N/2, T = ceil(n / H) frames.  Frame t of a stem
+ *     holds a[t H + j] at j in [0, H) and zeros above; frame t of the mix holds y[t H - N/4 + j] at j in [0, N).  No window.
+ *     A'_t, Y'_t = the float32 FFTs of the frames (twiddles as dam_stft_fill_twiddles_host(N) fills them), bins k = 0 .. N/2,
+ *     the imaginary parts of bins 0 and N/2 taken as 0;
+ *       C_s[k] = sum_t conj(A'_t[k]) * Y'_t[k]   in float64:
+ *       re += (double)Ar (double)Yr + (double)Ai (double)Yi,  im += (double)Ar (double)Yi - (double)Ai (double)Yr.
+ *     With this placement the circular correlation of a frame pair has no wrap-around for lags in [-N/4, N/4], so the sum
+ *     over the frames is the LINEAR correlation: irfft(C_s)[l + N/4] = R_s[l], whatever n is and however it is cut.
+ *     Energies: E_a = sum_p (double)a[p]^2, E_y likewise (every sample once: the stem frame's H samples, the mix frame's
+ *     samples j in [N/4, N/4 + H)).
+ *     Order of the float64 additions: one workgroup owns F = dam_align_frames_per_block() consecutive frames [i F, (i+1) F)
+ *     of one (stem, mix) pair; lane l of its 256 keeps one running sum per bin l, l + 256, ... over those frames in
+ *     ascending t (bin N/2 on lane 0), and one running sum per energy over the sample pairs (2m, 2m + 1) of its frames,
+ *     m = l, l + 256, ..., frames ascending; the energies' 64 lanes of a wave are folded by an xor-butterfly, distances
+ *     1, 2, .. 32, the four waves added as ((w0 + w1) + w2) + w3; a second kernel adds a pair's workgroup records in
+ *     ascending i, starting from the first.  The order depends on (n, L) only: a pair is bitwise reproducible and does not
+ *     depend on the other stems of the call or on how many there are.
+ *   Weighting.  DAM_ALIGN_PLAIN: c = R_s.  DAM_ALIGN_PHAT: c = irfft(C_s[k] / (|C_s[k]| + DAM_ALIGN_PHAT_FLOOR * mean_k |C_s[k]|)),
+ *     the mean over the N/2 + 1 bins (lane sums ascending, butterfly, four waves, as above).  The floor is smooth on
+ *     purpose: no bin is switched on or off by a comparison.  The inverse transform is the float32 LDS FFT on the weighted
+ *     spectrum scaled to unit peak magnitude, scaled back in float64.
+ *   Estimate, per stem.  l* = argmax_l |c[l]|; ties go to the smallest |l|, then to the negative lag.  sign = the sign of
+ *     c[l*] (-1: inverted polarity).  frac = 0.5 (y0 - y2) / (y0 - 2 y1 + y2) of y = |c| at l* - 1, l*, l* + 1; 0 at
+ *     |l*| = L and where y0 - 2 y1 + y2 is not negative.  peak = |c[l*]| / sqrt(E_a E_y) for PLAIN, |c[l*]| for PHAT.
+ *     status = 1; status = 0 for a silent stem or mix (E = 0) or a cross-spectrum that is zero in every bin: lag 0, frac 0,
+ *     sign 0, peak NaN, curve 0.
+ *   dam_align_estimate: lag, sign, status device int32 [S]; frac, peak device float64 [S]; curve: NULL or device float64
+ *     [S][2 L + 1], c[l] at index l + L.  workspace: dam_align_workspace_bytes(S, n, L) bytes, 8-byte aligned.  Three launches
+ *     (cross spectrum, reduce, finish).  More than 2^31 - 1 frames: DAM_ERR_UNSUPPORTED.
+ *   dam_align_shift: out[s][p][c] = x[s][p - lag[s]][c], 0 where p - lag[s] is outside [0, n).  lag: DEVICE int32 [S] -- what
+ *     dam_align_estimate wrote, so estimate -> shift -> fit needs no host round trip; + lag makes a stem as late as the mix is.
+ *     x and out: float32 or float64 alike (x_is_f64), each with its own element strides; they must not overlap.
+ *   Argument errors (a NULL pointer other than curve; S outside 1 .. 8; channels not 1 or 2; max_lag outside
+ *     1 .. dam_align_max_lag(); non-positive n; an unknown weighting) return DAM_ERR_BAD_ARG before any launch;
+ *     dam_align_fft_size and dam_align_workspace_bytes return 0 for them.
+ * Not covered: offsets beyond dam_align_max_lag() (a decimated coarse stage would come first), drift and varispeed, and
+ * sub-sample shifting (frac is reported, not applied).
+ * --------------------------------------------------------------------------------- */
+#define DAM_ALIGN_PLAIN 0
+#define DAM_ALIGN_PHAT 1
+#define DAM_ALIGN_PHAT_FLOOR 0x1.47ae147ae147bp-7 /* 1e-2 */
+int dam_align_max_lag(void);
+int dam_align_frames_per_block(void);
+int dam_align_fft_size(int max_lag);
+int64_t dam_align_workspace_bytes(int n_stems, int64_t n_samples, int max_lag);
+int dam_align_estimate(const void* x, int x_is_f64, int n_stems, int channels, int64_t n_samples, int64_t stem_stride,
+                       int64_t sample_stride, int64_t channel_stride, const void* y, int y_is_f64, int64_t y_sample_stride,
+                       int64_t y_channel_stride, int max_lag, int weighting, const float* twiddles, int32_t* lag, double* frac,
+                       double* peak, int32_t* sign, int32_t* status, double* curve, void* workspace, void* stream);
+int dam_align_shift(const void* x, int x_is_f64, int n_stems, int channels, int64_t n_samples, int64_t stem_stride,
+                    int64_t sample_stride, int64_t channel_stride, const int32_t* lag, void* out, int64_t out_stem_stride,
+                    int64_t out_sample_stride, int64_t out_channel_stride, void* stream);
 
 /* ---------------------------------------------------------------------------------
  * Stem input layout: x [B][C][HW] (C <= 16 planes, the reference's [B,S,F,T] feature stack) -> y [B][HW][16] with
