@@ -23,7 +23,7 @@
 //     with the same kernel.
 #include <cstdlib>
 #include "dam_common.h"
-#include "dam_conv_geo.h"
+#include "dam_conv_plan.h"
 #include "dam_conv_stage.h"
 
 namespace dam {
@@ -282,32 +282,14 @@ int launch_conv_pack(const ConvGeoPack& pk, size_t lds, const float* X, const fl
     return DAM_OK;
 }
 
-template <int MB, int NB>
-int launch_conv(const ConvGeo& g, size_t lds, const float* X, const float* Wp, const float* bias, const float* sc,
-                const float* sh, float* Y, const float* res, const float* res_mask, float* splitk_ws, hipStream_t st) {
-    ConvGeoPack pk;
-    pk.g[0] = g; pk.n = 1; pk.B = g.B;
-    const int rc = launch_conv_pack<MB, NB>(pk, lds, X, Wp, bias, sc, sh, Y, res, res_mask, splitk_ws, st);
-    if (rc != DAM_OK) return rc;
-    if (g.ksplit > 1) {
-        const int64_t n4 = (int64_t)g.B * g.OHt * g.OWt * g.N / 4;
-        const int blocks = (int)(cdiv(n4, 256) < 2048 ? cdiv(n4, 256) : 2048);
-        hipLaunchKernelGGL(splitk_reduce_kernel, dim3(blocks), dim3(256), 0, st, splitk_ws, g.ksplit, n4, g.N / 4, bias, res, res_mask, g.relu_out, Y);
-        DAM_CHECK_LAUNCH();
-    }
-    conv_last_launch = ConvLaunchNote{CONV_FAM_TILE, MB, NB, 0, 0, 0, 0, 0, 0, 0, 0, g.ksplit, 1};
-    return DAM_OK;
-}
-
-// Caller-owned batch of tile-kernel launches (include/dam_hip.h: dam_conv_batch_*): dam_conv2d_tapgrid_f32 records a launch that
-// would take conv_igemm_kernel without split-K instead of making it; the flush packs consecutive records that differ only in
-// geometry into one launch.
+// A tile-kernel launch: the plan's geometry, tile <MB, NB> and LDS bytes with the call's operands.  Caller-owned batch of them
+// (include/dam_hip.h: dam_conv_batch_*): dam_conv2d_tapgrid_f32 records a launch whose plan is the tile kernel without split-K
+// instead of making it; the flush packs consecutive records that differ only in geometry into one launch.
 struct ConvLaunchRec {
     ConvGeo g;
     int MB, NB;
     size_t lds;
-    const float *X, *Wp, *bias, *sc, *sh, *res, *res_mask;
-    float *Y, *ws;
+    ConvOperands a;
 };
 constexpr int CONV_BATCH_MAX = 8;
 constexpr unsigned CONV_BATCH_MAGIC = 0x43424154u;      // "CBAT"
@@ -317,15 +299,35 @@ struct ConvBatch {
     ConvLaunchRec rec[CONV_BATCH_MAX];
 };
 
+// Every instantiation of conv_igemm_kernel, by tile <MB, NB>.
 int conv_pack_dispatch(const ConvGeoPack& pk, const ConvLaunchRec& r, hipStream_t st) {
-#define DAM_CONV_PCASE(M_, N_) \
-    if (r.MB == M_ && r.NB == N_) return launch_conv_pack<M_, N_>(pk, r.lds, r.X, r.Wp, r.bias, r.sc, r.sh, r.Y, r.res, r.res_mask, r.ws, st)
+#define DAM_CONV_PCASE(M_, N_)                                                                                                \
+    if (r.MB == M_ && r.NB == N_)                                                                                             \
+        return launch_conv_pack<M_, N_>(pk, r.lds, r.a.x, r.a.w_packed, r.a.bias, r.a.in_scale, r.a.in_shift, r.a.y, r.a.res, \
+                                        r.a.res_mask, r.a.workspace, st)
     DAM_CONV_PCASE(4, 4); DAM_CONV_PCASE(4, 2); DAM_CONV_PCASE(4, 1);
     DAM_CONV_PCASE(4, 3); DAM_CONV_PCASE(2, 3); DAM_CONV_PCASE(1, 3);
     DAM_CONV_PCASE(2, 4); DAM_CONV_PCASE(2, 2); DAM_CONV_PCASE(2, 1);
     DAM_CONV_PCASE(1, 4); DAM_CONV_PCASE(1, 2); DAM_CONV_PCASE(1, 1);
 #undef DAM_CONV_PCASE
     return DAM_ERR_UNSUPPORTED;
+}
+
+// The tile kernel for one geometry; with split-K the reduction that writes the result (bias, residual, ReLU there).
+int launch_tile(const ConvLaunchPlan& p, const ConvOperands& a, hipStream_t st) {
+    const ConvGeo& g = p.g;
+    ConvGeoPack pk;
+    pk.g[0] = g; pk.n = 1; pk.B = g.B;
+    const int rc = conv_pack_dispatch(pk, ConvLaunchRec{g, p.note.MB, p.note.NB, p.lds, a}, st);
+    if (rc != DAM_OK) return rc;
+    if (g.ksplit > 1) {
+        const int64_t n4 = (int64_t)g.B * g.OHt * g.OWt * g.N / 4;
+        const int blocks = (int)(cdiv(n4, 256) < 2048 ? cdiv(n4, 256) : 2048);
+        hipLaunchKernelGGL(splitk_reduce_kernel, dim3(blocks), dim3(256), 0, st, a.workspace, g.ksplit, n4, g.N / 4, a.bias, a.res, a.res_mask,
+                           g.relu_out, a.y);
+        DAM_CHECK_LAUNCH();
+    }
+    return DAM_OK;
 }
 
 int conv_batch_flush(ConvBatch& b, hipStream_t st) {
@@ -338,8 +340,9 @@ int conv_batch_flush(ConvBatch& b, hipStream_t st) {
         int k = i;
         while (k < b.n && pk.n < GEO_PACK_MAX) {
             const ConvLaunchRec& q = b.rec[k];
-            if (q.MB != r.MB || q.NB != r.NB || q.X != r.X || q.Wp != r.Wp || q.bias != r.bias || q.sc != r.sc || q.sh != r.sh ||
-                q.Y != r.Y || q.res != r.res || q.res_mask != r.res_mask || q.g.B != r.g.B)
+            if (q.MB != r.MB || q.NB != r.NB || q.a.x != r.a.x || q.a.w_packed != r.a.w_packed || q.a.bias != r.a.bias ||
+                q.a.in_scale != r.a.in_scale || q.a.in_shift != r.a.in_shift || q.a.y != r.a.y || q.a.res != r.a.res ||
+                q.a.res_mask != r.a.res_mask || q.g.B != r.g.B)
                 break;
             pk.g[pk.n++] = q.g;
             lds = q.lds > lds ? q.lds : lds;
@@ -539,16 +542,21 @@ __global__ __launch_bounds__(256) void conv1x1_pair_kernel(const float* __restri
 }
 
 template <int NB, int NCHMAX>
-int launch_conv1x1(const ConvGeo& g, const float* X, const float* Wp, const float* bias, float* Y, const float* res,
-                   const float* res_mask, hipStream_t st) {
+int launch_1x1_as(const ConvGeo& g, const ConvOperands& a, hipStream_t st) {
     const int segs = (int)cdiv(g.Wo, 16);
-    const int64_t units = (int64_t)g.B * g.Ho * segs;
-    if (units >= (1ll << 30)) return DAM_ERR_UNSUPPORTED;
+    const int64_t units = (int64_t)g.B * g.Ho * segs;       // (< 2^30: plan_1x1)
     hipLaunchKernelGGL((conv1x1_direct_kernel<NB, NCHMAX>), dim3((unsigned)cdiv(units, 4), (unsigned)(g.N / 16 / NB)), dim3(256), 0, st,
-                       g, X, reinterpret_cast<const float4*>(Wp), bias, Y, res, res_mask, segs, (int)units);
+                       g, a.x, reinterpret_cast<const float4*>(a.w_packed), a.bias, a.y, a.res, a.res_mask, segs, (int)units);
     DAM_CHECK_LAUNCH();
-    conv_last_launch = ConvLaunchNote{CONV_FAM_1X1, 0, NB, NCHMAX, 0, 0, 0, 0, 0, 0, 0, 1, 1};
     return DAM_OK;
+}
+
+// Every instantiation of conv1x1_direct_kernel, by <NB, chunk slots>.
+int launch_1x1(const ConvLaunchPlan& p, const ConvOperands& a, hipStream_t st) {
+#define DAM_1X1_CASE(N_, C_) if (p.note.NB == N_ && p.note.NCH == C_) return launch_1x1_as<N_, C_>(p.g, a, st)
+    DAM_1X1_CASE(2, 2); DAM_1X1_CASE(1, 2); DAM_1X1_CASE(2, 4); DAM_1X1_CASE(1, 4); DAM_1X1_CASE(2, 8); DAM_1X1_CASE(1, 8);
+#undef DAM_1X1_CASE
+    return DAM_ERR_UNSUPPORTED;
 }
 
 }  // namespace
@@ -583,19 +591,6 @@ extern "C" int dam_conv1x1_pair_f32(const float* x1, const float* w1_packed, int
     return DAM_OK;
 }
 
-namespace dam {
-thread_local ConvLaunchNote conv_last_launch{};
-}
-
-extern "C" int dam_conv_last_launch(int* out16_host) {
-    if (!out16_host) return DAM_ERR_BAD_ARG;
-    const dam::ConvLaunchNote& n = dam::conv_last_launch;
-    const int v[16] = {n.family, n.MB, n.NB, n.NCH, n.T33, n.LW, n.EPI, n.SO, n.PU, n.STATS, n.KS, n.ksplit, n.ranges, 0, 0, 0};
-    for (int i = 0; i < 16; ++i) out16_host[i] = v[i];
-    return DAM_OK;
-}
-
-// Generic tap-grid convolution (see dam_hip.h).  The host wrapper derives the patch geometry and picks the tile.
 extern "C" int64_t dam_conv_batch_bytes(void) { return (int64_t)sizeof(dam::ConvBatch); }
 
 extern "C" int dam_conv_batch_init(void* batch) {
@@ -612,123 +607,47 @@ extern "C" int dam_conv_batch_flush(void* batch, void* stream) {
     return dam::conv_batch_flush(*b, (hipStream_t)stream);
 }
 
-extern "C" int dam_conv2d_tapgrid_f32(const float* x, int B, int H, int W, int C, int in_nchw, const float* w_packed,
-                                      int k_chunks, int n_out, const float* bias, const float* in_scale,
-                                      const float* in_shift, int relu_in, int relu_out, float* y, int OHt, int OWt, int Ho, int Wo,
-                                      int out_stride, int out_off_h, int out_off_w, int in_stride, int nA, int nB,
-                                      int off_h, int step_h, int off_w, int step_w, int wt_base, int wt_sa, int wt_sb,
-                                      const float* res, const float* res_mask, float* bn_partial, int* bn_parts_host,
-                                      const dam_bn_bwd_sums* bn_bwd, float* workspace, int64_t workspace_floats,
-                                      void* batch, void* stream) {
-    using namespace dam;
-    conv_last_launch = ConvLaunchNote{};
-    if (bn_parts_host) *bn_parts_host = 0;
-    BnBwdEpi bwd{};
-    if (bn_bwd && bn_bwd->x) {
-        if (!bn_partial || !bn_parts_host || !bn_bwd->mean || !bn_bwd->invstd) return DAM_ERR_BAD_ARG;
-        if (bn_bwd->mask_bits ? (bn_bwd->mask_scale || bn_bwd->mask_shift || !res) : (!bn_bwd->mask_scale || !bn_bwd->mask_shift))
-            return DAM_ERR_BAD_ARG;
-        if (res && (!bn_bwd->res_mask_bits || !res_mask)) return DAM_ERR_BAD_ARG;      // bytes for the kernels that can, floats for the rest
-        bwd = BnBwdEpi{bn_bwd->x, bn_bwd->mean, bn_bwd->invstd, bn_bwd->mask_scale, bn_bwd->mask_shift, bn_bwd->res_mask_bits,
-                       bn_bwd->mask_bits};
-    }
-    if (!x || !w_packed || !y || B <= 0 || H <= 0 || W <= 0 || C <= 0 || Ho <= 0 || Wo <= 0 || nA <= 0 || nB <= 0)
-        return DAM_ERR_BAD_ARG;
-    if (n_out % 16 || (in_stride != 1 && in_stride != 2) || out_stride < 1) return DAM_ERR_UNSUPPORTED;
-    if (in_nchw ? (C > 16 || k_chunks != 1) : (C % 16 || k_chunks != C / 16)) return DAM_ERR_UNSUPPORTED;
-    if (in_scale && !in_shift) return DAM_ERR_BAD_ARG;
-    if (B > 65535) return DAM_ERR_UNSUPPORTED;
-    ConvGeo g;
-    g.B = B; g.H = H; g.W = W; g.C = C; g.Ho = Ho; g.Wo = Wo; g.N = n_out; g.OHt = OHt; g.OWt = OWt;
-    g.os = out_stride; g.oo_h = out_off_h; g.oo_w = out_off_w; g.s = in_stride; g.nA = nA; g.nB = nB;
-    g.off_h = off_h; g.step_h = step_h; g.off_w = off_w; g.step_w = step_w;
-    g.wt_base = wt_base; g.wt_sa = wt_sa; g.wt_sb = wt_sb;
-    g.in_nchw = in_nchw; g.relu_in = relu_in; g.relu_out = relu_out != 0; g.nchunks = k_chunks; g.NBtot = n_out / 16;
-    g.epi_bwd = 0;
-    const int h_lo = off_h + (step_h < 0 ? (nA - 1) * step_h : 0), h_hi = off_h + (step_h > 0 ? (nA - 1) * step_h : 0);
-    const int w_lo = off_w + (step_w < 0 ? (nB - 1) * step_w : 0), w_hi = off_w + (step_w > 0 ? (nB - 1) * step_w : 0);
-    g.r0 = h_lo; g.c0 = w_lo;
-    g.PWin = (Wo - 1) * in_stride + (w_hi - w_lo) + 1;
-    g.PWs = (int)cdiv(g.PWin, in_stride);
-    g.PWT = g.PWs * in_stride;
+// ---------------------------------------------------------------------------------------------------------------- the plan
+namespace dam {
 
-    hipStream_t st = (hipStream_t)stream;
+ConvGeo conv_base_geo(const ConvRequest& rq) {
+    ConvGeo g;
+    g.B = rq.B; g.H = rq.H; g.W = rq.W; g.C = rq.C; g.Ho = rq.Ho; g.Wo = rq.Wo; g.N = rq.n_out; g.OHt = rq.OHt; g.OWt = rq.OWt;
+    g.os = rq.out_stride; g.oo_h = rq.out_off_h; g.oo_w = rq.out_off_w; g.s = rq.in_stride; g.nA = rq.nA; g.nB = rq.nB;
+    g.off_h = rq.off_h; g.step_h = rq.step_h; g.off_w = rq.off_w; g.step_w = rq.step_w;
+    g.wt_base = rq.wt_base; g.wt_sa = rq.wt_sa; g.wt_sb = rq.wt_sb;
+    g.in_nchw = rq.in_nchw; g.relu_in = rq.relu_in; g.relu_out = rq.relu_out != 0; g.nchunks = rq.k_chunks; g.NBtot = rq.n_out / 16;
+    g.epi_bwd = 0;
+    g.r0 = rq.off_h + (rq.step_h < 0 ? (rq.nA - 1) * rq.step_h : 0);
+    g.c0 = rq.off_w + (rq.step_w < 0 ? (rq.nB - 1) * rq.step_w : 0);
+    g.PWin = (rq.Wo - 1) * rq.in_stride + tap_span(rq.nB, rq.step_w) + 1;
+    g.PWs = (int)cdiv(g.PWin, rq.in_stride);
+    g.PWT = g.PWs * rq.in_stride;
     g.PR = 0; g.CG = 1; g.tiles_m = 0; g.ksplit = 1; g.gps = 1 << 30;
-    // single tap (1x1 shortcut convolutions, forward and data gradient): direct kernel, nothing staged
-    if (nA == 1 && nB == 1 && !in_nchw && !in_scale && k_chunks <= 8 &&
-        (int64_t)B * H * W * C * 4 < (1ll << 31) && (int64_t)B * OHt * OWt * n_out * 4 < (1ll << 62)) {
-        const int nblk = n_out / 16;
-        if (k_chunks <= 2) return nblk % 2 == 0 ? launch_conv1x1<2, 2>(g, x, w_packed, bias, y, res, res_mask, st)
-                                                : launch_conv1x1<1, 2>(g, x, w_packed, bias, y, res, res_mask, st);
-        if (k_chunks <= 4) return nblk % 2 == 0 ? launch_conv1x1<2, 4>(g, x, w_packed, bias, y, res, res_mask, st)
-                                                : launch_conv1x1<1, 4>(g, x, w_packed, bias, y, res, res_mask, st);
-        return nblk % 2 == 0 ? launch_conv1x1<2, 8>(g, x, w_packed, bias, y, res, res_mask, st)
-                             : launch_conv1x1<1, 8>(g, x, w_packed, bias, y, res, res_mask, st);
-    }
-    // persistent strip variant (LDS row ring fed by loader waves, optional fused BatchNorm statistics) when the layer fits it
-    if (!in_nchw) {
-        int parts = 0;
-        const int rc = conv_strip_try(g, h_lo, h_hi, x, w_packed, bias, y, res, res_mask, bn_partial, &parts,
-                                      in_scale, in_shift, bwd, st);
-        if (rc == DAM_OK) {
-            if (bn_partial && bn_parts_host) *bn_parts_host = parts;
-            return DAM_OK;
-        }
-        if (rc != DAM_ERR_UNSUPPORTED) return rc;
-        if (bn_partial) {       // maybe only the statistics did not fit: retry without them
-            const int rc2 = conv_strip_try(g, h_lo, h_hi, x, w_packed, bias, y, res, res_mask, nullptr, nullptr, in_scale, in_shift,
-                                           BnBwdEpi{}, st);
-            if (rc2 == DAM_OK) return DAM_OK;
-            if (rc2 != DAM_ERR_UNSUPPORTED) return rc2;
-        }
-    }
-    // thick 3x3 layers: the persistent variant whose patches are staged chunk by chunk by loader waves beside the MFMAs
-    // (DAM_NO_PIPE: diagnostic switch for the A/B in tools/pipe_ab.sh)
-    if (!getenv("DAM_NO_PIPE")) {
-        int parts = 0;
-        const int rc = conv_pipe_try(g, h_hi - h_lo, x, w_packed, bias, in_scale, in_shift, y, res, res_mask, workspace,
-                                     (bwd.x && res) ? nullptr : bn_partial, &parts, (bwd.x && res) ? BnBwdEpi{} : bwd, st);
-        if (rc == DAM_OK && bn_partial && bn_parts_host) *bn_parts_host = parts;
-        if (rc != DAM_ERR_UNSUPPORTED) return rc;
-        // Too wide for its patch buffers (the strided 16 -> 32 convolution on 1025x130: 131 input columns x 5 rows): the same
-        // kernel on 2-4 column ranges of the output, one launch each -- a range is just another output sub-grid of this entry
-        // point's geometry (width, output column offset, input column offset).  Not with an epilogue that leaves records.
-        if (nA == 3 && nB == 3 && !in_nchw && !bn_partial) {
-            for (int ns = 2; ns <= 4; ++ns) {
-                const int wd0 = (int)cdiv(Wo, ns);
-                if (wd0 < 16) break;
-                int rc2 = DAM_OK, done = 0;
-                for (int ow0 = 0; ow0 < Wo && rc2 == DAM_OK; ow0 += wd0, ++done) {
-                    ConvGeo g2 = g;
-                    g2.Wo = Wo - ow0 < wd0 ? Wo - ow0 : wd0;
-                    g2.oo_w = out_off_w + ow0 * out_stride;
-                    g2.off_w = off_w + ow0 * in_stride;
-                    g2.c0 = w_lo + ow0 * in_stride;
-                    g2.PWin = (g2.Wo - 1) * in_stride + (w_hi - w_lo) + 1;
-                    g2.PWs = (int)cdiv(g2.PWin, in_stride);
-                    g2.PWT = g2.PWs * in_stride;
-                    rc2 = conv_pipe_try(g2, h_hi - h_lo, x, w_packed, bias, in_scale, in_shift, y, res, res_mask, workspace, nullptr,
-                                        nullptr, BnBwdEpi{}, st);
-                }
-                if (rc2 == DAM_OK) {
-                    conv_last_launch.family = CONV_FAM_PIPE_RANGES;      // (tile parameters: those of the last range's launch)
-                    conv_last_launch.ranges = done;
-                    return DAM_OK;
-                }
-                if (rc2 != DAM_ERR_UNSUPPORTED || done > 1) return rc2 == DAM_ERR_UNSUPPORTED ? DAM_ERR_LAUNCH : rc2;   // a later range cannot fail where the first fitted
-            }
-        }
-    }
-    // tile choice.  With a workspace: keep big tiles (weights are streamed per workgroup: FLOPs per weight byte grow with
-    // the tile) and get the workgroup count from split-K over channel groups; otherwise shrink tiles to fill the chip.
+    return g;
+}
+
+// Single tap (1x1 shortcut convolutions, forward and data gradient): direct kernel, nothing staged.  <NB, chunk slots>.
+int plan_1x1(const ConvGeo& g, ConvLaunchPlan& p) {
+    if ((int64_t)g.B * g.Ho * cdiv(g.Wo, 16) >= (1ll << 30)) return DAM_ERR_UNSUPPORTED;
+    p.note = ConvLaunchNote{CONV_FAM_1X1, 0, g.N / 16 % 2 == 0 ? 2 : 1, g.nchunks <= 2 ? 2 : (g.nchunks <= 4 ? 4 : 8), 0, 0, 0, 0, 0, 0, 0, 1, 1};
+    p.g = g; p.lds = 0; p.stats = 0;
+    return DAM_OK;
+}
+
+// conv_igemm_kernel: tile <MB, NB>, channel group, split-K.  With a workspace: keep big tiles (weights are streamed per
+// workgroup: FLOPs per weight byte grow with the tile) and get the workgroup count from split-K over channel groups; otherwise
+// shrink tiles to fill the chip.
+int plan_tile(const ConvRequest& rq, const ConvGeo& g_in, ConvLaunchPlan& p) {
+    ConvGeo g = g_in;
+    const int B = g.B, Ho = g.Ho, Wo = g.Wo, k_chunks = g.nchunks;
     const int64_t npix = (int64_t)Ho * Wo;
-    const int nblk = n_out / 16;
+    const int nblk = g.N / 16;
     // NB must divide the block count.  Three-block tiles for the 48-channel layers of the scalar models (models/model_scalar_2s.py:
     // 64-77: the 7x7 data gradient 64 -> 48 ran the one-block tile, every LDS operand feeding ONE MFMA group: 371 us = 0.50 of peak; three-block tiles: 312 us, C2 5.267 -> 5.198 ms)
     int MB = 4, NB = nblk % 4 == 0 ? 4 : (nblk % 3 == 0 ? 3 : (nblk % 2 == 0 ? 2 : 1));
     auto wgs = [&](int mb, int nb) { return cdiv(npix, 64 * mb) * cdiv(nblk, nb) * B; };
-    const bool can_split = workspace && out_stride == 1 && Ho == OHt && Wo == OWt && out_off_h == 0 && out_off_w == 0 &&
-                           k_chunks >= 4;
+    const bool can_split = rq.workspace && g.os == 1 && Ho == g.OHt && Wo == g.OWt && g.oo_h == 0 && g.oo_w == 0 && k_chunks >= 4;
     bool split = can_split;
     if (split) {
         // enough workgroups without splitting: the tile with the smallest makespan.  Every CU works through
@@ -761,7 +680,7 @@ extern "C" int dam_conv2d_tapgrid_f32(const float* x, int B, int H, int W, int C
         const int tm = 64 * mb;
         int rows_out = (int)((tm + Wo - 2) / Wo + 1);
         if (rows_out > Ho) rows_out = Ho;
-        return (rows_out - 1) * in_stride + (h_hi - h_lo) + 1;
+        return (rows_out - 1) * g.s + tap_span(g.nA, g.step_h) + 1;
     };
     for (;;) {
         g.PR = patch_rows(MB);
@@ -776,36 +695,193 @@ extern "C" int dam_conv2d_tapgrid_f32(const float* x, int B, int H, int W, int C
     g.tiles_m = (int)cdiv(npix, 64 * MB);
     if (split) {
         const int ngroups = k_chunks / CG;
-        const int64_t w = wgs(MB, NB), out_elems = (int64_t)B * OHt * OWt * n_out;
+        const int64_t w = wgs(MB, NB), out_elems = (int64_t)B * g.OHt * g.OWt * g.N;
         int ksplit = (int)cdiv(512, w);
         if (ksplit > 8) ksplit = 8;
         if (ksplit > ngroups) ksplit = ngroups;
-        while (ksplit > 1 && ksplit * out_elems > workspace_floats) --ksplit;
+        while (ksplit > 1 && ksplit * out_elems > rq.workspace_floats) --ksplit;
         if (ksplit > 1) {
             g.gps = (int)cdiv(ngroups, ksplit);
             g.ksplit = (int)cdiv(ngroups, g.gps);
         }
     }
-    const size_t lds = (size_t)CG * g.PR * g.PWT * 64;
-    if (batch && g.ksplit == 1) {       // recorded, launched (packed with its siblings) by dam_conv_batch_flush
+    p.note = ConvLaunchNote{CONV_FAM_TILE, MB, NB, 0, 0, 0, 0, 0, 0, 0, 0, g.ksplit, 1};
+    p.g = g; p.lds = (size_t)CG * g.PR * g.PWT * 64; p.stats = 0;
+    return DAM_OK;
+}
+
+// The pipe kernel on 2, 3, then 4 column ranges of the output, one launch each: a range is just another output sub-grid of the
+// entry point's geometry (width, output column offset, input column offset).  For layers too wide for the kernel's patch buffers
+// (the strided 16 -> 32 convolution on 1025x130: 131 input columns x 5 rows).  DAM_ERR_UNSUPPORTED: no range count fits.
+static int plan_pipe_ranges(const ConvRequest& rq, const ConvGeo& g, ConvPlan& plan) {
+    for (int ns = 2; ns <= CONV_RANGES_MAX; ++ns) {
+        const int wd0 = (int)cdiv(g.Wo, ns);
+        if (wd0 < 16) break;
+        int rc = DAM_OK, done = 0, none = 0;
+        for (int ow0 = 0; ow0 < g.Wo && rc == DAM_OK; ow0 += wd0, ++done) {
+            ConvGeo g2 = g;
+            g2.Wo = g.Wo - ow0 < wd0 ? g.Wo - ow0 : wd0;
+            g2.oo_w = g.oo_w + ow0 * g.os;
+            g2.off_w = g.off_w + ow0 * g.s;
+            g2.c0 = g.c0 + ow0 * g.s;
+            g2.PWin = (g2.Wo - 1) * g.s + tap_span(g.nB, g.step_w) + 1;
+            g2.PWs = (int)cdiv(g2.PWin, g.s);
+            g2.PWT = g2.PWs * g.s;
+            rc = plan_pipe(g2, rq.in_scale, 0, plan.range[done], &none);
+        }
+        if (rc == DAM_OK) {
+            static_cast<ConvLaunchPlan&>(plan) = plan.range[done - 1];      // (tile parameters: those of the last range's launch)
+            plan.note.family = CONV_FAM_PIPE_RANGES;
+            plan.note.ranges = plan.ranges = done;
+            plan.range_w = wd0;
+            return DAM_OK;
+        }
+        if (done > 1) return DAM_ERR_LAUNCH;      // a later range cannot fail where the first fitted
+    }
+    return DAM_ERR_UNSUPPORTED;
+}
+
+int plan_conv(const ConvRequest& rq, ConvPlan& plan) {
+    plan.bn_records = 0; plan.ranges = 1; plan.range_w = rq.Wo;
+    if (rq.bn_bwd) {
+        if (!rq.bn_partial) return DAM_ERR_BAD_ARG;
+        if (rq.bwd_mask_bits ? (rq.bwd_mask_scale || !rq.res) : !rq.bwd_mask_scale) return DAM_ERR_BAD_ARG;
+        if (rq.res && (!rq.bwd_res_mask_bits || !rq.res_mask)) return DAM_ERR_BAD_ARG;      // bytes for the kernels that can, floats for the rest
+    }
+    if (rq.B <= 0 || rq.H <= 0 || rq.W <= 0 || rq.C <= 0 || rq.Ho <= 0 || rq.Wo <= 0 || rq.nA <= 0 || rq.nB <= 0) return DAM_ERR_BAD_ARG;
+    if (rq.n_out % 16 || (rq.in_stride != 1 && rq.in_stride != 2) || rq.out_stride < 1) return DAM_ERR_UNSUPPORTED;
+    if (rq.in_nchw ? (rq.C > 16 || rq.k_chunks != 1) : (rq.C % 16 || rq.k_chunks != rq.C / 16)) return DAM_ERR_UNSUPPORTED;
+    if (rq.in_scale && !rq.in_shift) return DAM_ERR_BAD_ARG;
+    if (rq.B > 65535) return DAM_ERR_UNSUPPORTED;
+    const ConvGeo g = conv_base_geo(rq);
+    // 1. single tap: the direct kernel; a layer that qualifies stays there (its refusal is the call's)
+    if (rq.nA == 1 && rq.nB == 1 && !rq.in_nchw && !rq.in_scale && rq.k_chunks <= 8 &&
+        (int64_t)rq.B * rq.H * rq.W * rq.C * 4 < (1ll << 31) && (int64_t)rq.B * rq.OHt * rq.OWt * rq.n_out * 4 < (1ll << 62))
+        return plan_1x1(g, plan);
+    // 2. / 3. persistent strip kernel (LDS row ring fed by loader waves) with the statistics / sums the call asks for; refused
+    // with them, maybe only they did not fit: without (the call then reports no records)
+    if (!rq.in_nchw) {
+        int rc = plan_strip(rq, g, rq.bn_bwd ? 2 : (rq.bn_partial ? 1 : 0), plan, &plan.bn_records);
+        if (rc == DAM_ERR_UNSUPPORTED && rq.bn_partial) rc = plan_strip(rq, g, 0, plan, &plan.bn_records);
+        if (rc != DAM_ERR_UNSUPPORTED) return rc;
+    }
+    // 4. / 5. thick 3x3 layers: the persistent kernel whose patches are staged chunk by chunk by loader waves beside the MFMAs (its
+    // sums epilogue has no residual form), then the same kernel on column ranges -- not with an epilogue that leaves records
+    // (DAM_NO_PIPE: diagnostic switch for the A/B in tools/pipe_ab.sh)
+    if (!getenv("DAM_NO_PIPE")) {
+        const int stats = rq.bn_bwd ? (rq.res ? 0 : 2) : (rq.bn_partial ? 1 : 0);
+        int rc = plan_pipe(g, rq.in_scale, stats, plan, &plan.bn_records);
+        if (rc == DAM_ERR_UNSUPPORTED && rq.nA == 3 && rq.nB == 3 && !rq.in_nchw && !rq.bn_partial) rc = plan_pipe_ranges(rq, g, plan);
+        if (rc != DAM_ERR_UNSUPPORTED) return rc;
+    }
+    // 6. the tile kernel; without split-K a caller's batch records the launch
+    const int rc = plan_tile(rq, g, plan);
+    if (rc == DAM_OK && rq.batch && plan.g.ksplit == 1) plan.note.family = CONV_FAM_TILE_BATCH;
+    return rc;
+}
+
+namespace {
+
+int launch_plan(const ConvPlan& plan, const ConvOperands& a, void* batch, hipStream_t st) {
+    switch (plan.note.family) {
+    case CONV_FAM_1X1: return launch_1x1(plan, a, st);
+    case CONV_FAM_STRIP: return launch_strip(plan, a, st);
+    case CONV_FAM_PIPE: return launch_pipe(plan, a, st);
+    case CONV_FAM_PIPE_RANGES:
+        for (int i = 0; i < plan.ranges; ++i) {
+            const int rc = launch_pipe(plan.range[i], a, st);
+            if (rc != DAM_OK) return rc;
+        }
+        return DAM_OK;
+    case CONV_FAM_TILE: return launch_tile(plan, a, st);
+    case CONV_FAM_TILE_BATCH: {     // recorded, launched (packed with its siblings) by dam_conv_batch_flush
         ConvBatch* cb = static_cast<ConvBatch*>(batch);
         if (cb->magic != CONV_BATCH_MAGIC) return DAM_ERR_BAD_ARG;
         if (cb->n == CONV_BATCH_MAX) {
             const int rc = conv_batch_flush(*cb, st);
             if (rc != DAM_OK) return rc;
         }
-        ConvLaunchRec& r = cb->rec[cb->n++];
-        r.g = g; r.MB = MB; r.NB = NB; r.lds = lds; r.X = x; r.Wp = w_packed; r.bias = bias; r.sc = in_scale; r.sh = in_shift;
-        r.res = res; r.res_mask = res_mask; r.Y = y; r.ws = workspace;
-        conv_last_launch = ConvLaunchNote{CONV_FAM_TILE_BATCH, MB, NB, 0, 0, 0, 0, 0, 0, 0, 0, 1, 1};
+        cb->rec[cb->n++] = ConvLaunchRec{plan.g, plan.note.MB, plan.note.NB, plan.lds, a};
         return DAM_OK;
     }
-#define DAM_CONV_CASE(M_, N_) \
-    if (MB == M_ && NB == N_) return launch_conv<M_, N_>(g, lds, x, w_packed, bias, in_scale, in_shift, y, res, res_mask, workspace, st)
-    DAM_CONV_CASE(4, 4); DAM_CONV_CASE(4, 2); DAM_CONV_CASE(4, 1);
-    DAM_CONV_CASE(4, 3); DAM_CONV_CASE(2, 3); DAM_CONV_CASE(1, 3);
-    DAM_CONV_CASE(2, 4); DAM_CONV_CASE(2, 2); DAM_CONV_CASE(2, 1);
-    DAM_CONV_CASE(1, 4); DAM_CONV_CASE(1, 2); DAM_CONV_CASE(1, 1);
-#undef DAM_CONV_CASE
+    }
     return DAM_ERR_UNSUPPORTED;
+}
+
+void request_operands(ConvRequest& rq, unsigned has, int64_t workspace_floats) {
+    rq.bias = has & DAM_CONV_HAS_BIAS; rq.in_scale = has & DAM_CONV_HAS_IN_SCALE; rq.in_shift = has & DAM_CONV_HAS_IN_SHIFT;
+    rq.res = has & DAM_CONV_HAS_RES; rq.res_mask = has & DAM_CONV_HAS_RES_MASK; rq.bn_partial = has & DAM_CONV_HAS_BN_PARTIAL;
+    rq.workspace = has & DAM_CONV_HAS_WORKSPACE; rq.batch = has & DAM_CONV_HAS_BATCH;
+    rq.bn_bwd = has & DAM_CONV_HAS_BN_BWD; rq.bwd_mask_bits = has & DAM_CONV_HAS_BWD_MASK_BITS;
+    rq.bwd_res_mask_bits = has & DAM_CONV_HAS_BWD_RES_MASK_BITS; rq.bwd_mask_scale = has & DAM_CONV_HAS_BWD_MASK_SCALE;
+    rq.workspace_floats = workspace_floats;
+}
+
+void note_ints(const ConvLaunchNote& n, int* out16) {
+    const int v[16] = {n.family, n.MB, n.NB, n.NCH, n.T33, n.LW, n.EPI, n.SO, n.PU, n.STATS, n.KS, n.ksplit, n.ranges, 0, 0, 0};
+    for (int i = 0; i < 16; ++i) out16[i] = v[i];
+}
+
+}  // namespace
+
+thread_local ConvLaunchNote conv_last_launch{};
+
+}  // namespace dam
+
+extern "C" int dam_conv_last_launch(int* out16_host) {
+    if (!out16_host) return DAM_ERR_BAD_ARG;
+    dam::note_ints(dam::conv_last_launch, out16_host);
+    return DAM_OK;
+}
+
+// Plan only (see dam_hip.h): host arithmetic, no device work.
+extern "C" int dam_conv2d_tapgrid_plan(int B, int H, int W, int C, int in_nchw, int k_chunks, int n_out, int relu_in, int relu_out,
+                                       int OHt, int OWt, int Ho, int Wo, int out_stride, int out_off_h, int out_off_w, int in_stride,
+                                       int nA, int nB, int off_h, int step_h, int off_w, int step_w, int wt_base, int wt_sa,
+                                       int wt_sb, unsigned operands, int64_t workspace_floats, int* out16_host, int* bn_parts_host) {
+    using namespace dam;
+    if (!out16_host || !bn_parts_host) return DAM_ERR_BAD_ARG;
+    ConvRequest rq{B, H, W, C, in_nchw, k_chunks, n_out, relu_in, relu_out, OHt, OWt, Ho, Wo, out_stride, out_off_h, out_off_w, in_stride,
+                   nA, nB, off_h, step_h, off_w, step_w, wt_base, wt_sa, wt_sb};
+    request_operands(rq, operands, workspace_floats);
+    ConvPlan plan;
+    plan.note = ConvLaunchNote{};
+    const int rc = plan_conv(rq, plan);
+    note_ints(rc == DAM_OK ? plan.note : ConvLaunchNote{}, out16_host);
+    *bn_parts_host = rc == DAM_OK ? plan.bn_records : 0;
+    return rc;
+}
+
+// Generic tap-grid convolution (see dam_hip.h): validate the pointers, build the request, plan, launch what the plan says.
+extern "C" int dam_conv2d_tapgrid_f32(const float* x, int B, int H, int W, int C, int in_nchw, const float* w_packed,
+                                      int k_chunks, int n_out, const float* bias, const float* in_scale,
+                                      const float* in_shift, int relu_in, int relu_out, float* y, int OHt, int OWt, int Ho, int Wo,
+                                      int out_stride, int out_off_h, int out_off_w, int in_stride, int nA, int nB,
+                                      int off_h, int step_h, int off_w, int step_w, int wt_base, int wt_sa, int wt_sb,
+                                      const float* res, const float* res_mask, float* bn_partial, int* bn_parts_host,
+                                      const dam_bn_bwd_sums* bn_bwd, float* workspace, int64_t workspace_floats,
+                                      void* batch, void* stream) {
+    using namespace dam;
+    conv_last_launch = ConvLaunchNote{};
+    if (bn_parts_host) *bn_parts_host = 0;
+    if (!x || !w_packed || !y) return DAM_ERR_BAD_ARG;
+    const dam_bn_bwd_sums* s = bn_bwd && bn_bwd->x ? bn_bwd : nullptr;
+    if (s && (!bn_parts_host || !s->mean || !s->invstd || !s->mask_scale != !s->mask_shift)) return DAM_ERR_BAD_ARG;
+    ConvRequest rq{B, H, W, C, in_nchw, k_chunks, n_out, relu_in, relu_out, OHt, OWt, Ho, Wo, out_stride, out_off_h, out_off_w, in_stride,
+                   nA, nB, off_h, step_h, off_w, step_w, wt_base, wt_sa, wt_sb};
+    request_operands(rq, (bias ? DAM_CONV_HAS_BIAS : 0) | (in_scale ? DAM_CONV_HAS_IN_SCALE : 0) | (in_shift ? DAM_CONV_HAS_IN_SHIFT : 0) |
+                         (res ? DAM_CONV_HAS_RES : 0) | (res_mask ? DAM_CONV_HAS_RES_MASK : 0) | (bn_partial ? DAM_CONV_HAS_BN_PARTIAL : 0) |
+                         (workspace ? DAM_CONV_HAS_WORKSPACE : 0) | (batch ? DAM_CONV_HAS_BATCH : 0) | (s ? DAM_CONV_HAS_BN_BWD : 0) |
+                         (s && s->mask_bits ? DAM_CONV_HAS_BWD_MASK_BITS : 0) | (s && s->res_mask_bits ? DAM_CONV_HAS_BWD_RES_MASK_BITS : 0) |
+                         (s && s->mask_scale ? DAM_CONV_HAS_BWD_MASK_SCALE : 0), workspace_floats);
+    ConvPlan plan;
+    int rc = plan_conv(rq, plan);
+    if (rc != DAM_OK) return rc;
+    const ConvOperands a{x, w_packed, bias, in_scale, in_shift, res, res_mask, y, bn_partial, workspace,
+                         s ? BnBwdEpi{s->x, s->mean, s->invstd, s->mask_scale, s->mask_shift, s->res_mask_bits, s->mask_bits} : BnBwdEpi{}};
+    rc = launch_plan(plan, a, batch, (hipStream_t)stream);
+    if (rc != DAM_OK) return rc;
+    conv_last_launch = plan.note;
+    if (bn_partial && bn_parts_host) *bn_parts_host = plan.bn_records;
+    return DAM_OK;
 }

@@ -48,24 +48,14 @@ struct StripGeo {
     unsigned wo_magic;       // floor(2^32 / Wo) + 1: p / Wo == umulhi(p, wo_magic) for p < 2^22 (scalar-ALU division)
 };
 
-// What the last dam_conv2d_tapgrid_f32 call of this thread launched (dam_conv_last_launch, include/dam_hip.h): a host variable
-// written beside the launch sites, read by tests that must know which kernel family and instantiation they exercised.
+// Kernel family and template parameters of a launch: the plan's name for it (dam_conv_plan.h), and what the last
+// dam_conv2d_tapgrid_f32 call of this thread launched (dam_conv_last_launch, include/dam_hip.h) -- the plan's note, copied once by
+// the entry point, for tests that must know which instantiation they exercised.
 enum ConvFamily { CONV_FAM_NONE = 0, CONV_FAM_STRIP = 1, CONV_FAM_PIPE = 2, CONV_FAM_PIPE_RANGES = 3, CONV_FAM_TILE = 4,
                   CONV_FAM_TILE_BATCH = 5, CONV_FAM_1X1 = 6 };
 struct ConvLaunchNote {
     int family, MB, NB, NCH, T33, LW, EPI, SO, PU, STATS, KS, ksplit, ranges;
 };
 extern thread_local ConvLaunchNote conv_last_launch;     // dam_conv.hip
-
-// dam_conv_strip.hip
-int conv_strip_try(ConvGeo& g, int h_lo, int h_hi, const float* X, const float* Wp, const float* bias, float* Y,
-                   const float* res, const float* res_mask, float* stats, int* stats_parts,
-                   const float* in_scale, const float* in_shift, const BnBwdEpi& bwd, hipStream_t st);
-
-// dam_conv_pipe.hip: the persistent tile kernel with loader waves (thick 3x3 layers); picks its own tile;
-// DAM_ERR_UNSUPPORTED = the caller falls back to conv_igemm_kernel
-int conv_pipe_try(ConvGeo g, int row_span, const float* X, const float* Wp, const float* bias, const float* sc, const float* sh,
-                  float* Y, const float* res, const float* res_mask, float* workspace, float* stats, int* stats_parts,
-                  const BnBwdEpi& bwd, hipStream_t st);
 
 }  // namespace dam

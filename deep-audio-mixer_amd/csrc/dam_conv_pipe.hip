@@ -25,7 +25,7 @@
 #include <climits>
 #include <cstdlib>
 #include "dam_common.h"
-#include "dam_conv_geo.h"
+#include "dam_conv_plan.h"
 #include "dam_conv_stage.h"
 
 namespace dam {
@@ -562,47 +562,49 @@ int pipe_slots(size_t lds) {
     return cached;
 }
 
-template <int MB, int NB, int PU, int KS>
-int launch_pipe(const ConvGeo& g, size_t lds, const float* X, const float* Wp, const float* bias, const float* sc, const float* sh,
-                float* Y, const float* res, const float* res_mask, float* workspace, float* stats, int* stats_parts,
-                const BnBwdEpi& bwd, hipStream_t st) {
+template <int MB, int NB, int PU, int STATS, int KS>
+int launch_pipe_as(const ConvLaunchPlan& p, const ConvOperands& a, hipStream_t st) {
+    const ConvGeo& g = p.g;
     const int nunits = g.tiles_m * (g.N / 16 / NB) * g.B;
-    // statistics records: one per (image tile, wave), each unit fills its own channels of it
-    int mode = 0;
-    if (stats) {
-        const int64_t parts = (int64_t)g.B * g.tiles_m * (4 / KS);
-        mode = bwd.x ? 2 : 1;
-        // (one record per WORKGROUP, accumulated over its units, was measured slower: C3 step 4.456 -> 4.483 ms, the 1 x 4 tile's
-        // launches with an epilogue 61.9 / 73.8 us against 52.6 us without -- profiles/r04_pipe_stats_acc_ab.txt)
-        if (parts > (bwd.x ? BN_BWD_RECORDS_MAX : BN_RECORDS_MAX)) { stats = nullptr; mode = 0; }   // the caller runs the separate pass
-        else if (stats_parts) *stats_parts = (int)parts;
-    }
-    if (bwd.x) res = mode == 2 ? bwd.x : nullptr;               // the sums epilogue reads x through the residual operand
-    int wgs = mode == 2 ? pipe_slots<MB, NB, PU, 2, KS>(lds) : (mode == 1 ? pipe_slots<MB, NB, PU, 1, KS>(lds) : pipe_slots<MB, NB, PU, 0, KS>(lds));
+    int wgs = pipe_slots<MB, NB, PU, STATS, KS>(p.lds);
     if (const char* e = getenv("DAM_PIPE_WGS")) wgs = atoi(e);          // diagnostic
     if (wgs < 1) wgs = 1;
     if (wgs > nunits) wgs = nunits;
-#define DAM_PIPE_LAUNCH(S_)                                                                                                 \
-    hipLaunchKernelGGL((conv_pipe_kernel<MB, NB, PU, S_, KS>), dim3((unsigned)wgs), dim3(PIPE_THREADS), lds, st, g, nunits, X,  \
-                       reinterpret_cast<const float4*>(Wp), bias, sc, sh, Y, res, res_mask, workspace, stats, bwd)
-    if (mode == 2) DAM_PIPE_LAUNCH(2); else if (mode == 1) DAM_PIPE_LAUNCH(1); else DAM_PIPE_LAUNCH(0);
-#undef DAM_PIPE_LAUNCH
+    // (the sums epilogue reads the BatchNorm's input x through the residual operand)
+    hipLaunchKernelGGL((conv_pipe_kernel<MB, NB, PU, STATS, KS>), dim3((unsigned)wgs), dim3(PIPE_THREADS), p.lds, st, g, nunits, a.x,
+                       reinterpret_cast<const float4*>(a.w_packed), a.bias, a.in_scale, a.in_shift, a.y, STATS == 2 ? a.bwd.x : a.res,
+                       a.res_mask, a.workspace, STATS ? a.bn_partial : nullptr, STATS == 2 ? a.bwd : BnBwdEpi{});
     DAM_CHECK_LAUNCH();
-    conv_last_launch = ConvLaunchNote{CONV_FAM_PIPE, MB, NB, 0, 0, 0, 0, 0, PU, mode, KS, 1, 1};
     return DAM_OK;
 }
 
 }  // namespace
 
-// Returns DAM_ERR_UNSUPPORTED when the layer does not fit this variant (the caller goes on to conv_igemm_kernel).
-// g: set up by dam_conv2d_tapgrid_f32 up to the tile-independent part (patch columns PWin / PWs / PWT, tap grid);
-// row_span = h_hi - h_lo of the tap grid.  The tile is chosen here: no split-K -- small tiles give this kernel its
-// workgroups, their patches are staged beside the MFMAs and cost the matrix pipe nothing.
-int conv_pipe_try(ConvGeo g, int row_span, const float* X, const float* Wp, const float* bias, const float* sc, const float* sh,
-                  float* Y, const float* res, const float* res_mask, float* workspace, float* stats, int* stats_parts,
-                  const BnBwdEpi& bwd, hipStream_t st) {
-    if (bwd.x && (res || !stats)) return DAM_ERR_BAD_ARG;
-    if (g.nA != 3 || g.nB != 3 || g.in_nchw) return DAM_ERR_UNSUPPORTED;     // (16-channel stride-1 layers never get here: row-ring kernel)
+// Every instantiation of conv_pipe_kernel, by the plan's note <MB, NB, PU, STATS, KS>: the five tiles with loader depth 5 and 8
+// and the K split <1, 1, 3, 2>, each with the three statistics modes.
+int launch_pipe(const ConvLaunchPlan& p, const ConvOperands& a, hipStream_t st) {
+    const ConvLaunchNote& n = p.note;
+#define DAM_PIPE_INST(M_, N_, U_, K_)                                                                                      \
+    if (n.MB == M_ && n.NB == N_ && n.PU == U_ && n.KS == K_)                                                              \
+        return n.STATS == 2 ? launch_pipe_as<M_, N_, U_, 2, K_>(p, a, st)                                                  \
+                            : (n.STATS == 1 ? launch_pipe_as<M_, N_, U_, 1, K_>(p, a, st) : launch_pipe_as<M_, N_, U_, 0, K_>(p, a, st))
+#define DAM_PIPE_TILE(M_, N_) DAM_PIPE_INST(M_, N_, 5, 1); DAM_PIPE_INST(M_, N_, 8, 1)
+    DAM_PIPE_INST(1, 1, 3, 2);
+    DAM_PIPE_TILE(1, 4); DAM_PIPE_TILE(2, 2); DAM_PIPE_TILE(1, 2); DAM_PIPE_TILE(2, 1); DAM_PIPE_TILE(1, 1);
+#undef DAM_PIPE_TILE
+#undef DAM_PIPE_INST
+    return DAM_ERR_UNSUPPORTED;
+}
+
+// The pipe kernel's eligibility (3x3 NHWC layers whose patch fits the loader waves and the stage buffers), tile, K split, loader
+// depth and statistics mode.  g: the base geometry (patch columns, tap grid) -- of the whole output or of one column range.  No
+// split-K over channel groups: small tiles give this kernel its workgroups, their patches are staged beside the MFMAs and cost
+// the matrix pipe nothing.  stats: 0 none, 1 forward statistics, 2 BatchNorm-backward sums; *records: record count.
+int plan_pipe(const ConvGeo& g_in, bool in_scale, int stats, ConvLaunchPlan& p, int* records) {
+    ConvGeo g = g_in;
+    *records = 0;
+    const int row_span = tap_span(g.nA, g.step_h);
+    if (g.nA != 3 || g.nB != 3 || g.in_nchw) return DAM_ERR_UNSUPPORTED;     // (16-channel stride-1 layers get here only past the row-ring kernel's widths)
     if ((size_t)g.H * g.W * g.C * 4 >= ((size_t)1 << 30)) return DAM_ERR_UNSUPPORTED;      // offsets of the range-checked loads
     const int64_t npix = (int64_t)g.Ho * g.Wo;
     const int nblk = g.N / 16;
@@ -629,9 +631,12 @@ int conv_pipe_try(ConvGeo g, int row_span, const float* X, const float* Wp, cons
         if (units >= 384) { MB = mb; NB = nb; break; }
         if (units > most) { most = units; MB = mb; NB = nb; }
     }
-    if (const char* e = getenv("DAM_TILE")) {          // diagnostic: "MBxNB"
+    if (const char* e = getenv("DAM_TILE")) {          // diagnostic: "MBxNB", one of the five tiles
         MB = e[0] - '0'; NB = e[2] - '0';
         if (MB < 1 || NB < 1 || !fits(MB, NB)) return DAM_ERR_UNSUPPORTED;
+        bool known = false;
+        for (int i = 0; i < 5; ++i) known = known || (cand[i][0] == MB && cand[i][1] == NB);
+        if (!known) return DAM_ERR_UNSUPPORTED;
     }
     if (!MB) return DAM_ERR_UNSUPPORTED;
     // K split over the wave pairs (kernel comment): for one-block tiles that leave the chip fewer than three units per CU
@@ -648,17 +653,19 @@ int conv_pipe_try(ConvGeo g, int row_span, const float* X, const float* Wp, cons
     g.tiles_m = (int)cdiv(npix, upx);
     g.CG = 1; g.ksplit = 1; g.gps = g.nchunks;
     // stage buffer 0 (padded to PIPE_BUF1), stage buffer 1, scale / shift tables, the dump zone, the K halves' hand-over
-    const size_t lds = PIPE_BUF1 + (size_t)KS * g.PR * g.PWT * 64 + (sc ? (size_t)2 * g.C * 4 : 0) + PIPE_LT * 16 +
-                       (KS == 2 ? (size_t)2 * MB * NB * 1024 : 0);
-    const bool big = g.PR * g.PWin * 4 * KS > PIPE_LT * 5; // items per loader thread: 5 or 8
-    if (KS == 2) return launch_pipe<1, 1, 3, 2>(g, lds, X, Wp, bias, sc, sh, Y, res, res_mask, workspace, stats, stats_parts, bwd, st);
-#define DAM_PIPE_CASE(M_, N_)                                                                                              \
-    if (MB == M_ && NB == N_)                                                                                              \
-        return big ? launch_pipe<M_, N_, 8, 1>(g, lds, X, Wp, bias, sc, sh, Y, res, res_mask, workspace, stats, stats_parts, bwd, st) \
-                   : launch_pipe<M_, N_, 5, 1>(g, lds, X, Wp, bias, sc, sh, Y, res, res_mask, workspace, stats, stats_parts, bwd, st)
-    DAM_PIPE_CASE(1, 4); DAM_PIPE_CASE(2, 2); DAM_PIPE_CASE(1, 2); DAM_PIPE_CASE(2, 1); DAM_PIPE_CASE(1, 1);
-#undef DAM_PIPE_CASE
-    return DAM_ERR_UNSUPPORTED;
+    p.lds = PIPE_BUF1 + (size_t)KS * g.PR * g.PWT * 64 + (in_scale ? (size_t)2 * g.C * 4 : 0) + PIPE_LT * 16 +
+            (KS == 2 ? (size_t)2 * MB * NB * 1024 : 0);
+    const bool big = g.PR * g.PWin * 4 * KS > PIPE_LT * 5; // items per loader thread: 5 or 8 (3 with the K split)
+    // statistics records: one per (image tile, wave), each unit fills its own channels of it.  Too many for the workspace: the
+    // launch goes without them and the caller runs the separate pass.
+    // (one record per WORKGROUP, accumulated over its units, was measured slower: C3 step 4.456 -> 4.483 ms, the 1 x 4 tile's
+    // launches with an epilogue 61.9 / 73.8 us against 52.6 us without -- profiles/r04_pipe_stats_acc_ab.txt)
+    const int64_t parts = (int64_t)g.B * g.tiles_m * (4 / KS);
+    if (stats && parts > (stats == 2 ? BN_BWD_RECORDS_MAX : BN_RECORDS_MAX)) stats = 0;
+    if (stats) *records = (int)parts;
+    p.note = ConvLaunchNote{CONV_FAM_PIPE, MB, NB, 0, 0, 0, 0, 0, KS == 2 ? 3 : (big ? 8 : 5), stats, KS, 1, 1};
+    p.g = g; p.stats = stats;
+    return DAM_OK;
 }
 
 }  // namespace dam

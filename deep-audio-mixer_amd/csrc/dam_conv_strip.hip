@@ -24,7 +24,7 @@
 #include <algorithm>
 #include <cstdint>
 #include "dam_common.h"
-#include "dam_conv_geo.h"
+#include "dam_conv_plan.h"
 
 namespace dam {
 namespace {
@@ -1141,28 +1141,57 @@ __global__ __launch_bounds__(SO ? 512 : STRIP_THREADS, 1) void conv_strip_kernel
 
 }  // namespace
 
-// Returns DAM_OK if launched, DAM_ERR_UNSUPPORTED if the layer does not fit this variant (caller falls back).
-template <int MB, int NB, int NCH, bool T33, bool LW = false, int EPI = 0, int SO = 0>
-static int launch_strip(ConvGeo& g, StripGeo& sg, size_t lds, const float* X, const float* Wp, const float* bias, float* Y,
-                        const float* res, const float* res_mask, float* stats, const float* in_scale, const float* in_shift,
-                        const BnBwdEpi& bwd, hipStream_t st) {
-    if (lds > 64 * 1024 && !raise_lds_limit<&conv_strip_kernel<MB, NB, NCH, T33, LW, EPI, SO>>(160 * 1024)) return DAM_ERR_LAUNCH;
-    dim3 grid((unsigned)sg.strips, (unsigned)cdiv(g.N / 16, NB), (unsigned)g.B);
-    hipLaunchKernelGGL((conv_strip_kernel<MB, NB, NCH, T33, LW, EPI, SO>), grid, dim3(SO ? 512 : STRIP_THREADS), lds, st, g, sg, X, reinterpret_cast<const float4*>(Wp), bias,
-                       Y, res, res_mask, stats, in_scale, in_shift, bwd);
+template <int MB, int NB, int NCH, bool T33, bool LW, int EPI, int SO>
+static int launch_strip_as(const ConvLaunchPlan& p, const ConvOperands& a, hipStream_t st) {
+    if (p.lds > 64 * 1024 && !raise_lds_limit<&conv_strip_kernel<MB, NB, NCH, T33, LW, EPI, SO>>(160 * 1024)) return DAM_ERR_LAUNCH;
+    // the sums epilogue reads the BatchNorm's input through the residual operand, a real residual's mask as sign bytes
+    const bool sums = p.stats == 2;
+    const float* res = sums && !a.res ? a.bwd.x : a.res;
+    const float* res_mask = sums && a.res ? reinterpret_cast<const float*>(a.bwd.res_bits) : a.res_mask;
+    dim3 grid((unsigned)p.sg.strips, (unsigned)cdiv(p.g.N / 16, NB), (unsigned)p.g.B);
+    hipLaunchKernelGGL((conv_strip_kernel<MB, NB, NCH, T33, LW, EPI, SO>), grid, dim3(SO ? 512 : STRIP_THREADS), p.lds, st, p.g, p.sg, a.x,
+                       reinterpret_cast<const float4*>(a.w_packed), a.bias, a.y, res, res_mask, p.stats ? a.bn_partial : nullptr, a.in_scale,
+                       a.in_shift, sums ? a.bwd : BnBwdEpi{});
     DAM_CHECK_LAUNCH();
-    conv_last_launch = ConvLaunchNote{CONV_FAM_STRIP, MB, NB, NCH, T33, LW, EPI, SO, 0, 0, 0, 1, 1};
     return DAM_OK;
 }
 
-int conv_strip_try(ConvGeo& g_in, int h_lo, int h_hi, const float* X, const float* Wp, const float* bias, float* Y,
-                   const float* res, const float* res_mask, float* stats, int* stats_parts,
-                   const float* in_scale, const float* in_shift, const BnBwdEpi& bwd, hipStream_t st) {
-    if (bwd.x && !stats) return DAM_ERR_BAD_ARG;
-    if (bwd.x && res && !bwd.res_bits) return DAM_ERR_UNSUPPORTED;     // with a residual the sums need its mask as sign bytes
+// Every instantiation of conv_strip_kernel, by the plan's note <MB, NB, NCH, T33, LW, EPI, SO> (plan_strip names no other).
+int launch_strip(const ConvLaunchPlan& p, const ConvOperands& a, hipStream_t st) {
+    const ConvLaunchNote& n = p.note;
+#define DAM_STRIP_INST(M_, N_, C_, T_, L_, E_, S_)                                                                             \
+    if (n.MB == M_ && n.NB == N_ && n.NCH == C_ && n.T33 == T_ && n.LW == L_ && n.EPI == E_ && n.SO == S_)                     \
+        return launch_strip_as<M_, N_, C_, T_, L_, E_, S_>(p, a, st)
+#define DAM_STRIP_PAIR(T_, L_, E_, S_) DAM_STRIP_INST(4, 1, 1, T_, L_, E_, S_); DAM_STRIP_INST(2, 2, 2, T_, L_, E_, S_)     /* 16 ch <4, 1>, 32 ch <2, 2> */
+#define DAM_STRIP_TILE(M_, N_)                                                                                               \
+    DAM_STRIP_INST(M_, N_, 1, true, false, 0, 0); DAM_STRIP_INST(M_, N_, 2, true, false, 0, 0);                                 \
+    DAM_STRIP_INST(M_, N_, 1, false, false, 0, 0); DAM_STRIP_INST(M_, N_, 2, false, false, 0, 0)
+    // self-overlapped form: write-out variants 1 plain, 2 statistics, 3 bias / ReLU, 4 residual, 5 masked residual; the sums
+    DAM_STRIP_PAIR(true, false, 0, 1); DAM_STRIP_PAIR(true, false, 0, 2); DAM_STRIP_PAIR(true, false, 0, 3);
+    DAM_STRIP_PAIR(true, false, 0, 4); DAM_STRIP_PAIR(true, false, 0, 5); DAM_STRIP_PAIR(true, false, 1, 1);
+    DAM_STRIP_INST(4, 1, 1, true, false, 2, 1); DAM_STRIP_INST(4, 1, 1, true, false, 3, 1);
+    // ping-pong form with the sums epilogue (residual + sums: 16 channels only), ordinary and wide rows
+    DAM_STRIP_PAIR(true, false, 1, 0); DAM_STRIP_PAIR(true, true, 1, 0);
+    DAM_STRIP_INST(4, 1, 1, true, false, 2, 0); DAM_STRIP_INST(4, 1, 1, true, true, 2, 0);
+    DAM_STRIP_INST(4, 1, 1, true, false, 3, 0); DAM_STRIP_INST(4, 1, 1, true, true, 3, 0);
+    // ping-pong form, wide-row loader; then every tile x chunk count x tap grid
+    DAM_STRIP_PAIR(true, true, 0, 0); DAM_STRIP_PAIR(false, true, 0, 0);
+    DAM_STRIP_TILE(4, 2); DAM_STRIP_TILE(4, 1); DAM_STRIP_TILE(2, 2); DAM_STRIP_TILE(2, 1);
+#undef DAM_STRIP_TILE
+#undef DAM_STRIP_PAIR
+#undef DAM_STRIP_INST
+    return DAM_ERR_UNSUPPORTED;
+}
+
+// The strip kernel's eligibility, tile, ring and strip count, and which instantiation writes the result out.  stats: 0 none,
+// 1 forward statistics, 2 BatchNorm-backward sums (with rq.res: through the residual epilogue).  *records: record count.
+int plan_strip(const ConvRequest& rq, const ConvGeo& g_in, int stats, ConvLaunchPlan& p, int* records) {
+    const bool sums = stats == 2, res = rq.res, bias = rq.bias;
+    *records = 0;
+    if (sums && res && !rq.bwd_res_mask_bits) return DAM_ERR_UNSUPPORTED;     // with a residual the sums need its mask as sign bytes
     ConvGeo g = g_in;                 // the caller's copy stays as it is for the tile kernel
-    g.epi_bwd = bwd.x ? (res ? (bwd.mask_bits ? 3 : 2) : 1) : 0;
-    if (bwd.x && bwd.mask_bits && !res) return DAM_ERR_UNSUPPORTED;    // byte-masked sums exist with the residual epilogue only
+    g.epi_bwd = sums ? (res ? (rq.bwd_mask_bits ? 3 : 2) : 1) : 0;
+    if (sums && rq.bwd_mask_bits && !res) return DAM_ERR_UNSUPPORTED;    // byte-masked sums exist with the residual epilogue only
     if (g.nB == 3 && g.step_w < 0) {  // same taps walked left to right: column step becomes +1, weight taps are re-indexed
         g.off_w += 2 * g.step_w; g.step_w = -g.step_w;
         g.wt_base += 2 * g.wt_sb; g.wt_sb = -g.wt_sb;
@@ -1174,7 +1203,7 @@ int conv_strip_try(ConvGeo& g_in, int h_lo, int h_hi, const float* X, const floa
     const int NB = nblk % 2 == 0 ? 2 : 1;
     if (stats && cdiv(nblk, NB) != 1) return DAM_ERR_UNSUPPORTED;        // statistics need all channels in one workgroup
     StripGeo sg;
-    sg.RH = h_hi - h_lo + 1;
+    sg.RH = tap_span(g.nA, g.step_h) + 1;
     sg.w_taps = 9;                                                         // canonical [a*3+b] order in LDS
     const size_t w_bytes = (size_t)9 * g.nchunks * NB * 1024;      // resident packed weights of the N tile
     if (w_bytes > 48 * 1024) return DAM_ERR_UNSUPPORTED;                    // thick layers: tile kernel (weights from L2)
@@ -1226,72 +1255,37 @@ int conv_strip_try(ConvGeo& g_in, int h_lo, int h_hi, const float* X, const floa
     if (g.Wo > 1024 || g.Wo < 16) return DAM_ERR_UNSUPPORTED;   // scalar pixel decode: 16 consecutive pixels span <= 2 output rows
     sg.wo_magic = (unsigned)((1ull << 32) / (unsigned)g.Wo) + 1u;
     sg.ring_off = sg.NR * 64;           // keeps (row + ring_off) non-negative for row >= -64*NR
-    if (stats_parts) *stats_parts = sg.strips * g.B;
     if (stats && (int64_t)sg.strips * g.B > 1024) return DAM_ERR_UNSUPPORTED;
     if (lds < (size_t)8 * NB * 16 * 3 * sizeof(float)) lds = (size_t)8 * NB * 16 * 3 * sizeof(float);
     // 3x3 taps, stride 1, unit column step: compile-time item grid with immediate operand offsets
     const bool t33 = g.nA == 3 && g.nB == 3 && g.s == 1 && g.step_w == 1;
-#define DAM_STRIP_ARGS g, sg, lds, X, Wp, bias, Y, (bwd.x && !res ? bwd.x : res), (bwd.x && res ? reinterpret_cast<const float*>(bwd.res_bits) : res_mask), stats, in_scale, in_shift, bwd, st
+    // the two tiles that exist with the wide-row loader, the sums epilogue and the self-overlapped form
+    const bool tile16 = g.nchunks == 1 && MB == 4 && NB == 1, tile32 = g.nchunks == 2 && MB == 2 && NB == 2;
     // Self-overlapped form (template comment of the kernel) for the 3x3 / stride-1 shapes of the 16- and 32-channel stages at
-    // ordinary row widths; the ping-pong form takes every other shape.  The write-out variant is compile time.
+    // ordinary row widths; the ping-pong form takes every other shape.  The write-out variant is compile time: 1 plain (and the
+    // sums), 2 statistics, 3 bias / ReLU, 4 residual, 5 masked residual; a combination none of them spells (0) goes on to the
+    // ping-pong form -- with the geometry tables' LDS still counted.
+    int so = 0;
     const int rows_out_so = std::min(g.Ho, (64 * MB + g.Wo - 2) / g.Wo + 1), rows_tile_so = (rows_out_so - 1) * g.s + sg.RH;
-    if (t33 && !wide && rows_tile_so * g.nchunks <= 8 * (g.nchunks == 1 ? 1 : 2) &&
-        ((g.nchunks == 1 && MB == 4 && NB == 1) || (g.nchunks == 2 && MB == 2 && NB == 2))) {
-        const bool c16 = g.nchunks == 1;
+    if (t33 && !wide && rows_tile_so * g.nchunks <= 8 * (g.nchunks == 1 ? 1 : 2) && (tile16 || tile32)) {
         lds += 2048;                        // geometry tables: 4 compute waves x 4 buffers x 8 ints x <= 4 pixel blocks
-#define DAM_SO_CASE(E_, S_)                                                                                              \
-    return c16 ? launch_strip<4, 1, 1, true, false, E_, S_>(DAM_STRIP_ARGS) : launch_strip<2, 2, 2, true, false, E_, S_>(DAM_STRIP_ARGS)
-        if (bwd.x && res) {
-            if (c16) {
-                if (bwd.mask_bits) return launch_strip<4, 1, 1, true, false, 3, 1>(DAM_STRIP_ARGS);
-                return launch_strip<4, 1, 1, true, false, 2, 1>(DAM_STRIP_ARGS);
-            }
-        } else if (bwd.x) {
-            DAM_SO_CASE(1, 1);
-        } else if (stats) {
-            if (!bias && !res && !g.relu_out) DAM_SO_CASE(0, 2);
-        } else if (res && res_mask) {
-            if (!bias && !g.relu_out) DAM_SO_CASE(0, 5);
-        } else if (res) {
-            DAM_SO_CASE(0, 4);
-        } else if (bias || g.relu_out) {
-            DAM_SO_CASE(0, 3);
-        } else {
-            DAM_SO_CASE(0, 1);
-        }
-#undef DAM_SO_CASE
+        if (sums && res) so = tile16 ? 1 : 0;
+        else if (sums) so = 1;
+        else if (stats) so = !bias && !res && !g.relu_out ? 2 : 0;
+        else if (res && rq.res_mask) so = !bias && !g.relu_out ? 5 : 0;
+        else if (res) so = 4;
+        else so = bias || g.relu_out ? 3 : 1;
     }
-    if (bwd.x && res) { // residual + upstream sums: the 16-channel full-resolution data gradient only (stem <- first block)
-        if (!t33 || g.nchunks != 1 || MB != 4 || NB != 1) return DAM_ERR_UNSUPPORTED;
-        if (bwd.mask_bits)
-            return wide ? launch_strip<4, 1, 1, true, true, 3>(DAM_STRIP_ARGS) : launch_strip<4, 1, 1, true, false, 3>(DAM_STRIP_ARGS);
-        return wide ? launch_strip<4, 1, 1, true, true, 2>(DAM_STRIP_ARGS) : launch_strip<4, 1, 1, true, false, 2>(DAM_STRIP_ARGS);
+    if (!so) {
+        // ping-pong form.  Residual + upstream sums: the 16-channel full-resolution data gradient only (stem <- first block);
+        // sums: the 3x3 / stride-1 data gradients of the 16- and 32-channel stages only; wide rows: <4, 1> at 16, <2, 2> at 32 channels
+        if (sums && !(t33 && (tile16 || (tile32 && !res)))) return DAM_ERR_UNSUPPORTED;
+        if (wide && !(tile16 || tile32)) return DAM_ERR_UNSUPPORTED;
     }
-    if (bwd.x) {        // sums epilogue: the 3x3 / stride-1 data gradients of the 16- and 32-channel stages only
-        if (!t33) return DAM_ERR_UNSUPPORTED;
-        if (g.nchunks == 1 && MB == 4 && NB == 1)
-            return wide ? launch_strip<4, 1, 1, true, true, 1>(DAM_STRIP_ARGS) : launch_strip<4, 1, 1, true, false, 1>(DAM_STRIP_ARGS);
-        if (g.nchunks == 2 && MB == 2 && NB == 2)
-            return wide ? launch_strip<2, 2, 2, true, true, 1>(DAM_STRIP_ARGS) : launch_strip<2, 2, 2, true, false, 1>(DAM_STRIP_ARGS);
-        return DAM_ERR_UNSUPPORTED;
-    }
-#define DAM_STRIP_CASE(M_, N_)                                                                                           \
-    if (MB == M_ && NB == N_) {                                                                                             \
-        if (t33) return g.nchunks == 1 ? launch_strip<M_, N_, 1, true>(DAM_STRIP_ARGS) : launch_strip<M_, N_, 2, true>(DAM_STRIP_ARGS); \
-        return g.nchunks == 1 ? launch_strip<M_, N_, 1, false>(DAM_STRIP_ARGS) : launch_strip<M_, N_, 2, false>(DAM_STRIP_ARGS); \
-    }
-    if (wide) {         // 16 ch: <4, 1>, 32 ch: <2, 2> only
-        if (g.nchunks == 1 && MB == 4 && NB == 1)
-            return t33 ? launch_strip<4, 1, 1, true, true>(DAM_STRIP_ARGS) : launch_strip<4, 1, 1, false, true>(DAM_STRIP_ARGS);
-        if (g.nchunks == 2 && MB == 2 && NB == 2)
-            return t33 ? launch_strip<2, 2, 2, true, true>(DAM_STRIP_ARGS) : launch_strip<2, 2, 2, false, true>(DAM_STRIP_ARGS);
-        return DAM_ERR_UNSUPPORTED;
-    }
-    DAM_STRIP_CASE(4, 2); DAM_STRIP_CASE(4, 1);
-    DAM_STRIP_CASE(2, 2); DAM_STRIP_CASE(2, 1);
-#undef DAM_STRIP_CASE
-#undef DAM_STRIP_ARGS
-    return DAM_ERR_UNSUPPORTED;
+    p.note = ConvLaunchNote{CONV_FAM_STRIP, MB, NB, g.nchunks, t33, wide, g.epi_bwd, so, 0, 0, 0, 1, 1};
+    p.g = g; p.sg = sg; p.lds = lds; p.stats = stats;
+    if (stats) *records = sg.strips * g.B;
+    return DAM_OK;
 }
 
 }  // namespace dam

@@ -59,24 +59,77 @@ def _bn_fin_struct(bn, out4):
                       _lib.ptr(out4[0]), _lib.ptr(out4[1]), _lib.ptr(out4[2]), _lib.ptr(out4[3]))
 
 
-def _tapgrid(x, B, H, W, C, in_nchw, wp, k_chunks, n_out, bias, in_scale, in_shift, relu_in, y, OHt, OWt, Ho, Wo,
-             out_stride, oo_h, oo_w, in_stride, nA, nB, off_h, step_h, off_w, step_w, wt_base, wt_sa, wt_sb,
-             res=None, res_mask=None, bn_partial=None, relu_out=False, batch=None, bn_bwd=None):
+# The scalar arguments of dam_conv2d_tapgrid_f32 / dam_conv2d_tapgrid_plan (all but relu_in / relu_out), in the header's order
+TapGrid = collections.namedtuple('TapGrid', 'B H W C in_nchw k_chunks n_out OHt OWt Ho Wo out_stride oo_h oo_w in_stride nA nB '
+                                            'off_h step_h off_w step_w wt_base wt_sa wt_sb')
+# dam_conv2d_tapgrid_plan's `operands` bits (include/dam_hip.h: DAM_CONV_HAS_*)
+_HAS = dict(bias=0x001, in_scale=0x002, in_shift=0x004, res=0x008, res_mask=0x010, bn_partial=0x020, bn_bwd=0x040,
+            bwd_mask_bits=0x080, bwd_res_mask_bits=0x100, bwd_mask_scale=0x200, workspace=0x400, batch=0x800)
+
+
+def _given(v):
+    """An optional operand of a plan call: a tensor or True stands for "given", None or False for "absent"."""
+    return v is not None and v is not False
+
+
+def _fwd_grid(x_shape, n_out, kh, kw, stride, pad, dil, in_nchw):
+    """Tap grid of a forward convolution of an input of x_shape (NHWC, or NCHW if in_nchw)."""
+    if in_nchw:
+        B, C, H, W = x_shape
+        k_chunks = 1
+    else:
+        B, H, W, C = x_shape
+        k_chunks = C // 16
+    Ho, Wo = conv_out_size(H, kh, stride, pad, dil), conv_out_size(W, kw, stride, pad, dil)
+    if Ho <= 0 or Wo <= 0:
+        raise ValueError('convolution output would be empty')
+    return TapGrid(B, H, W, C, 1 if in_nchw else 0, k_chunks, (n_out + 15) // 16 * 16, Ho, Wo, Ho, Wo, 1, 0, 0, stride, kh, kw,
+                   -pad, dil, -pad, dil, 0, kw, 1)
+
+
+def _dgrad_grid(dy_shape, n_in, H, W, kh, kw, stride, pad, dil, ph=0, pw=0):
+    """Tap grid of the data gradient [B, H, W, n_in16] of a convolution with output dy_shape, output parity class (ph, pw) -- the
+    whole gradient at stride 1; None for a class that has no pixels or receives no taps."""
+    B, Ho, Wo, Co = dy_shape
+    ah, aw = _dgrad_axis(ph, pad, dil, kh, stride), _dgrad_axis(pw, pad, dil, kw, stride)
+    nh, nw = (H - ph + stride - 1) // stride, (W - pw + stride - 1) // stride
+    if nh <= 0 or nw <= 0 or ah is None or aw is None:
+        return None
+    return TapGrid(B, Ho, Wo, Co, 0, Co // 16, (n_in + 15) // 16 * 16, H, W, nh, nw, stride, ph, pw, 1, ah[0], aw[0],
+                   ah[3], ah[4], aw[3], aw[4], ah[1] * kw + aw[1], ah[2] * kw, aw[2])
+
+
+def _splitk_floats(g):
+    """Split-K scratch of a tap-grid call: the host code only splits when no tile shape gives 400 workgroups, i.e. for outputs
+    below 400 * 64 px * 64 ch = 1.64 M floats, and then at most 8 ways (dam_conv.hip) -- never more than 13.1 M floats."""
+    return min(8 * g.B * g.OHt * g.OWt * g.n_out, 8 * 400 * 64 * 64)
+
+
+def _tapgrid(g, x, wp, y, bias=None, in_scale=None, in_shift=None, relu_in=False, res=None, res_mask=None, bn_partial=None,
+             relu_out=False, batch=None, bn_bwd=None):
+    """dam_conv2d_tapgrid_f32 on the tap grid g -> the record count left in bn_partial."""
     parts = ctypes.c_int(0)
-    # split-K scratch: the host code only splits when no tile shape gives 400 workgroups, i.e. for outputs below
-    # 400 * 64 px * 64 ch = 1.64 M floats, and then at most 8 ways (dam_conv.hip) -- never more than 13.1 M floats
-    ws = _workspace(y.device, min(8 * y.numel(), 8 * 400 * 64 * 64))
+    ws = _workspace(y.device, _splitk_floats(g))
     st = _lib.lib().dam_conv2d_tapgrid_f32(
-        _lib.ptr(x), B, H, W, C, 1 if in_nchw else 0, _lib.ptr(wp), k_chunks, n_out, _lib.ptr(bias),
-        _lib.ptr(in_scale), _lib.ptr(in_shift), 1 if relu_in else 0, 1 if relu_out else 0, _lib.ptr(y), OHt, OWt, Ho, Wo,
-        out_stride,
-        oo_h, oo_w, in_stride, nA, nB, off_h, step_h, off_w, step_w, wt_base, wt_sa, wt_sb, _lib.ptr(res),
-        _lib.ptr(res_mask), _lib.ptr(bn_partial), ctypes.byref(parts) if bn_partial is not None else None,
-        ctypes.byref(bn_bwd) if bn_bwd is not None else None,
-        _lib.ptr(ws), ws.numel(),
-        ctypes.addressof(batch) if batch is not None else None, _lib.stream())
+        _lib.ptr(x), *g[:5], _lib.ptr(wp), g.k_chunks, g.n_out, _lib.ptr(bias), _lib.ptr(in_scale), _lib.ptr(in_shift),
+        1 if relu_in else 0, 1 if relu_out else 0, _lib.ptr(y), *g[7:], _lib.ptr(res), _lib.ptr(res_mask), _lib.ptr(bn_partial),
+        ctypes.byref(parts) if bn_partial is not None else None, ctypes.byref(bn_bwd) if bn_bwd is not None else None,
+        _lib.ptr(ws), ws.numel(), ctypes.addressof(batch) if batch is not None else None, _lib.stream())
     _lib.check(st, 'dam_conv2d_tapgrid_f32')
     return parts.value
+
+
+def _tapgrid_plan(g, relu_in=False, relu_out=False, **given):
+    """dam_conv2d_tapgrid_plan on the tap grid g with the operands named in `given` (keys of _HAS) -> (ConvLaunch, record count):
+    what _tapgrid with those operands would launch and report.  Host arithmetic in the library; no tensor, no GPU."""
+    has = _HAS['workspace']
+    for name, v in given.items():
+        has |= _HAS[name] if _given(v) else 0
+    rec, parts = (ctypes.c_int * 16)(), ctypes.c_int(0)
+    st = _lib.lib().dam_conv2d_tapgrid_plan(*g[:7], 1 if relu_in else 0, 1 if relu_out else 0, *g[7:], has, _splitk_floats(g),
+                                            rec, ctypes.byref(parts))
+    _lib.check(st, 'dam_conv2d_tapgrid_plan')
+    return ConvLaunch(CONV_FAMILIES[rec[0]], *rec[1:13]), parts.value
 
 
 def conv2d_fwd(x, wp, n_out, kh, kw, stride=1, pad=0, dil=1, bias=None, in_scale=None, in_shift=None,
@@ -88,25 +141,15 @@ def conv2d_fwd(x, wp, n_out, kh, kw, stride=1, pad=0, dil=1, bias=None, in_scale
     out: the result tensor to write (contiguous float32 [B,Ho,Wo,n16] on x's device) instead of a fresh one."""
     _lib.require_cuda(x, wp)
     _f32c(x, 'x'), _f32c(bias, 'bias'), _f32c(in_scale, 'in_scale'), _f32c(in_shift, 'in_shift'), _f32c(res, 'res')
-    if in_nchw:
-        B, C, H, W = x.shape
-        k_chunks = 1
-    else:
-        B, H, W, C = x.shape
-        k_chunks = C // 16
-    n16 = (n_out + 15) // 16 * 16
-    Ho, Wo = conv_out_size(H, kh, stride, pad, dil), conv_out_size(W, kw, stride, pad, dil)
-    if Ho <= 0 or Wo <= 0:
-        raise ValueError('convolution output would be empty')
+    g = _fwd_grid(x.shape, n_out, kh, kw, stride, pad, dil, in_nchw)
+    B, Ho, Wo, n16 = g.B, g.Ho, g.Wo, g.n_out
     if out is None:
         y = torch.empty((B, Ho, Wo, n16), dtype=torch.float32, device=x.device)
     else:
         if out.dtype != torch.float32 or not out.is_contiguous() or tuple(out.shape) != (B, Ho, Wo, n16) or out.device != x.device:
             raise ValueError('out must be a contiguous float32 tensor of shape %s on %s' % ((B, Ho, Wo, n16), x.device))
         y = out
-    parts = _tapgrid(x, B, H, W, C, in_nchw, wp, k_chunks, n16, bias, in_scale, in_shift, relu_in, y, Ho, Wo, Ho, Wo,
-                     1, 0, 0, stride, kh, kw, -pad, dil, -pad, dil, 0, kw, 1, res=res, bn_partial=bn_partial,
-                     relu_out=relu_out)
+    parts = _tapgrid(g, x, wp, y, bias, in_scale, in_shift, relu_in, res=res, bn_partial=bn_partial, relu_out=relu_out)
     if bn is not None and bn_partial is not None:
         # two-launch form: merge the records with the finalize kernel
         out4 = bn_finalize(bn_partial, parts, *bn) if parts > 0 and finalize else None
@@ -127,6 +170,40 @@ def conv_last_launch():
     v = (ctypes.c_int * 16)()
     _lib.check(_lib.lib().dam_conv_last_launch(v), 'dam_conv_last_launch')
     return ConvLaunch(CONV_FAMILIES[v[0]], *v[1:13])
+
+
+def conv2d_fwd_plan(x_shape, n_out, kh, kw, stride=1, pad=0, dil=1, bias=None, in_scale=None, in_shift=None, relu_in=False,
+                    in_nchw=False, bn_partial=None, res=None, relu_out=False, parts=False):
+    """What conv2d_fwd would launch for an input of x_shape, as conv_last_launch() would report it after the call -- decided by
+    host arithmetic in the library (dam_conv2d_tapgrid_plan): no tensors, no GPU.  The keywords mean what they mean to
+    conv2d_fwd; an optional operand is given as True (or as the tensor) / None.  parts=True: -> (ConvLaunch, record count the call
+    would return for bn_partial)."""
+    rec, n = _tapgrid_plan(_fwd_grid(tuple(x_shape), n_out, kh, kw, stride, pad, dil, in_nchw), relu_in, relu_out, bias=bias,
+                           in_scale=in_scale, in_shift=in_shift, res=res, bn_partial=bn_partial)
+    return (rec, n) if parts else rec
+
+
+def _dgrad_operands(res, res_mask, bn_bwd, res_mask_bits):
+    """Which optional operands a stride-1 conv2d_dgrad hands to the tap-grid call (keys of _HAS)."""
+    given = dict(res=res, res_mask=res_mask)
+    if bn_bwd is not None:
+        given.update(bn_partial=True, bn_bwd=True, bwd_mask_scale=bn_bwd[3], bwd_mask_bits=bn_bwd[5] if len(bn_bwd) > 5 else None,
+                     bwd_res_mask_bits=res_mask_bits)
+    return given
+
+
+def conv2d_dgrad_plan(dy_shape, n_in, H, W, kh, kw, stride=1, pad=0, dil=1, res=None, res_mask=None, accumulate_into=None,
+                      bn_bwd=None, res_mask_bits=None, parts=False):
+    """What a stride-1 conv2d_dgrad would launch for a gradient of dy_shape, as conv_last_launch() would report it (see
+    conv2d_fwd_plan).  bn_bwd: the tuple conv2d_dgrad takes, its entries True (or tensors) / None.  parts=True: -> (ConvLaunch,
+    record count of the sums; 0 = conv2d_dgrad returns no partials)."""
+    if stride != 1:
+        raise ValueError('conv2d_dgrad_plan: stride-1 data gradients only')
+    if _given(accumulate_into):
+        res, res_mask = True, None
+    rec, n = _tapgrid_plan(_dgrad_grid(tuple(dy_shape), n_in, H, W, kh, kw, 1, pad, dil),
+                           **_dgrad_operands(res, res_mask, bn_bwd, res_mask_bits))
+    return (rec, n) if parts else rec
 
 
 def _dgrad_axis(parity, pad, dil, k, stride):
@@ -191,8 +268,8 @@ def conv2d_dgrad(dy, wpt, n_in, H, W, kh, kw, stride=1, pad=0, dil=1, res=None, 
         rec = torch.empty(_lib.lib().dam_bn_workspace_floats(n16), dtype=torch.float32, device=dy.device)
         epi = _lib.BnBwdSums(_lib.ptr(xb), _lib.ptr(mean), _lib.ptr(invstd), _lib.ptr(msc), _lib.ptr(msh), _lib.ptr(res_mask_bits),
                              _lib.ptr(up_bits))
-        parts = _tapgrid(dy, B, Ho, Wo, Co, False, wpt, Co // 16, n16, None, None, None, False, dx, H, W, H, W, 1, 0, 0, 1,
-                         kh, kw, pad, -dil, pad, -dil, 0, kw, 1, res, res_mask, bn_partial=rec, bn_bwd=epi)
+        parts = _tapgrid(_dgrad_grid(dy.shape, n_in, H, W, kh, kw, 1, pad, dil), dy, wpt, dx, res=res, res_mask=res_mask,
+                         bn_partial=rec, bn_bwd=epi)
         return dx, ((rec, parts) if parts > 0 else None)
     _f32c(dy, 'dy'), _f32c(res, 'res'), _f32c(res_mask, 'res_mask')
     B, Ho, Wo, Co = dy.shape
@@ -202,8 +279,7 @@ def conv2d_dgrad(dy, wpt, n_in, H, W, kh, kw, stride=1, pad=0, dil=1, res=None, 
     else:
         dx = out if out is not None else torch.empty((B, H, W, n16), dtype=torch.float32, device=dy.device)
     if stride == 1:
-        _tapgrid(dy, B, Ho, Wo, Co, False, wpt, Co // 16, n16, None, None, None, False, dx, H, W, H, W, 1, 0, 0, 1,
-                 kh, kw, pad, -dil, pad, -dil, 0, kw, 1, res, res_mask)
+        _tapgrid(_dgrad_grid(dy.shape, n_in, H, W, kh, kw, 1, pad, dil), dy, wpt, dx, res=res, res_mask=res_mask)
         return dx
     # pair_1x1=(dy2, wpt2): a SECOND operator's data gradient into the same dx -- a 1x1 / stride-`stride` / pad-0 convolution of the
     # same input (a down-sampling block's shortcut beside its conv1): its one tap lands on the pixels of this operator's single-tap
@@ -247,20 +323,17 @@ def conv2d_dgrad(dy, wpt, n_in, H, W, kh, kw, stride=1, pad=0, dil=1, res=None, 
     try:
         for ph in range(stride):
             for pw in range(stride):
-                ah, aw = _dgrad_axis(ph, pad, dil, kh, stride), _dgrad_axis(pw, pad, dil, kw, stride)
-                nh, nw = (H - ph + stride - 1) // stride, (W - pw + stride - 1) // stride
-                if nh <= 0 or nw <= 0 or ah is None or aw is None:
+                g = _dgrad_grid(dy.shape, n_in, H, W, kh, kw, stride, pad, dil, ph, pw)
+                if g is None:
                     continue
                 if pair_1x1 is not None and ph == 0 and pw == 0:
-                    if nh != Ho or nw != Wo:
+                    if g.Ho != Ho or g.Wo != Wo:
                         raise ValueError('pair_1x1: class (0, 0) does not cover the gradient\'s pixels')
-                    _lib.check(_lib.lib().dam_conv1x1_pair_f32(_lib.ptr(dy), _lib.ptr(wpt), ah[1] * kw + aw[1], _lib.ptr(pair_1x1[0]),
+                    _lib.check(_lib.lib().dam_conv1x1_pair_f32(_lib.ptr(dy), _lib.ptr(wpt), g.wt_base, _lib.ptr(pair_1x1[0]),
                                                                _lib.ptr(pair_1x1[1]), 0, B, Ho, Wo, Co, n16, _lib.ptr(dx), H, W, stride,
                                                                0, 0, _lib.stream()), 'dam_conv1x1_pair_f32')
                     continue
-                _tapgrid(dy, B, Ho, Wo, Co, False, wpt, Co // 16, n16, None, None, None, False, dx, H, W, nh, nw,
-                         stride, ph, pw, 1, ah[0], aw[0], ah[3], ah[4], aw[3], aw[4], ah[1] * kw + aw[1],
-                         ah[2] * kw, aw[2], res, res_mask, batch=batch)
+                _tapgrid(g, dy, wpt, dx, res=res, res_mask=res_mask, batch=batch)
         _lib.check(_lib.lib().dam_conv_batch_flush(ctypes.addressof(batch), _lib.stream()), 'dam_conv_batch_flush')
     except Exception:
         _lib.lib().dam_conv_batch_init(ctypes.addressof(batch))      # drop what a failed call left recorded

@@ -55,7 +55,7 @@ struct dam_bn_bwd_sums; /* defined in the BatchNorm section */
 /* Library / build identification ("gfx950").  DAM_ABI_VERSION is bumped whenever a signature below changes; a binding
  * compares dam_abi_version() of the library it loaded with the version it was written against and refuses a stale one
  * (deep-audio-mixer_amd/_lib.py: EXPECTED_ABI). */
-#define DAM_ABI_VERSION 28
+#define DAM_ABI_VERSION 29
 const char* dam_arch(void);
 int dam_abi_version(void);
 
@@ -236,7 +236,10 @@ int dam_conv_pack_weights_multi_f32(const int64_t* desc_dev, int n_tensors, int6
  * output dy feeds the backward pass of y = relu(bn(x)); if it can, it also writes that pass's two per-channel sums as records
  * [*bn_parts_host][n_out][2] into bn_partial (then hand them to dam_bn_backward_f32 as partials_given); 0 records = not produced.
  * workspace (optional): scratch for split-K over the input channels (used for small-spatial, wide layers; at most
- * 8 * B*OHt*OWt*n_out floats are used, fewer if less is given); partial slabs are summed in a fixed order. */
+ * 8 * B*OHt*OWt*n_out floats are used, fewer if less is given); partial slabs are summed in a fixed order.
+ * Which kernel a call gets (1x1 direct, row-ring strip, loader-wave pipe, pipe on column ranges, tile) is decided by host
+ * arithmetic on the scalar arguments and on which optional operands are given: dam_conv2d_tapgrid_plan below answers it without
+ * launching, on a machine without a GPU too. */
 int dam_conv2d_tapgrid_f32(const float* x, int B, int H, int W, int C, int in_nchw, const float* w_packed,
                            int k_chunks, int n_out, const float* bias, const float* in_scale,
                            const float* in_shift, int relu_in, int relu_out, float* y, int OHt, int OWt, int Ho, int Wo,
@@ -295,9 +298,34 @@ int64_t dam_conv_batch_bytes(void);
 int dam_conv_batch_init(void* batch);
 int dam_conv_batch_flush(void* batch, void* stream);
 
+/* The plan of a dam_conv2d_tapgrid_f32 call without the call (ABI 29): the same scalar arguments, `operands` = which optional
+ * operands the call would be given (DAM_CONV_HAS_* below; the BWD bits describe *bn_bwd and count only with DAM_CONV_HAS_BN_BWD,
+ * i.e. bn_bwd->x set) and workspace_floats.  Writes the 16 ints of dam_conv_last_launch that the call would leave into out16_host
+ * and the record count it would store in *bn_parts_host into bn_parts_host (both HOST memory, both required), and returns what
+ * the call would return wherever that does not depend on the device or on a pointer's value: DAM_OK, DAM_ERR_BAD_ARG,
+ * DAM_ERR_UNSUPPORTED, and DAM_ERR_LAUNCH for a layer whose column ranges fit only in part.  Host arithmetic only: no device
+ * work, no GPU needed.  The diagnostic switches DAM_NO_PIPE, DAM_TILE and DAM_PIPE_KS are read as by the call (DAM_PIPE_WGS
+ * only sizes a grid and is not part of the plan). */
+#define DAM_CONV_HAS_BIAS 0x001u
+#define DAM_CONV_HAS_IN_SCALE 0x002u
+#define DAM_CONV_HAS_IN_SHIFT 0x004u
+#define DAM_CONV_HAS_RES 0x008u
+#define DAM_CONV_HAS_RES_MASK 0x010u
+#define DAM_CONV_HAS_BN_PARTIAL 0x020u
+#define DAM_CONV_HAS_BN_BWD 0x040u
+#define DAM_CONV_HAS_BWD_MASK_BITS 0x080u
+#define DAM_CONV_HAS_BWD_RES_MASK_BITS 0x100u
+#define DAM_CONV_HAS_BWD_MASK_SCALE 0x200u     /* mask_scale and mask_shift */
+#define DAM_CONV_HAS_WORKSPACE 0x400u
+#define DAM_CONV_HAS_BATCH 0x800u
+int dam_conv2d_tapgrid_plan(int B, int H, int W, int C, int in_nchw, int k_chunks, int n_out, int relu_in, int relu_out,
+                            int OHt, int OWt, int Ho, int Wo, int out_stride, int out_off_h, int out_off_w, int in_stride,
+                            int nA, int nB, int off_h, int step_h, int off_w, int step_w, int wt_base, int wt_sa, int wt_sb,
+                            unsigned operands, int64_t workspace_floats, int* out16_host, int* bn_parts_host);
+
 /* Which kernel the last dam_conv2d_tapgrid_f32 call of the CALLING THREAD launched (ABI 26): the entry point falls back from
- * kernel to kernel without telling, so a test that means to exercise one family asks here.  A host variable written beside the
- * launch sites -- no device work, nothing synchronised.  out16_host (host memory, 16 ints) receives
+ * kernel to kernel without telling, so a test that means to exercise one family asks here.  A host variable, the plan's record
+ * copied after a successful launch -- no device work, nothing synchronised.  out16_host (host memory, 16 ints) receives
  *   [0] family: 0 none (no call yet; after a call that FAILED the record is unspecified), 1 row-ring strip kernel, 2 loader-wave (pipe) kernel,
  *       3 the pipe kernel on column ranges, 4 tile kernel, 5 tile kernel recorded into a batch (launched by the flush), 6 direct 1x1
  *   [1] MB  [2] NB                 M / N tile in 64-pixel / 16-channel blocks (1x1: NB only)

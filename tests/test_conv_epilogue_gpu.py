@@ -154,7 +154,10 @@ def _launch(ops, c, epi, xd, wp, bias_d, res_d, monkeypatch):
         y = ops.conv2d_fwd(xd, wp, c.Co, c.k, c.k, c.s, c.p, c.d, bias=bias_d if use_bias else None, in_nchw=c.nchw,
                            res=res_d if use_res else None, relu_out=relu, out=out)
         rec = ops.conv_last_launch()
+        plan = ops.conv2d_fwd_plan(xd.shape, c.Co, c.k, c.k, c.s, c.p, c.d, bias=bias_d if use_bias else None, in_nchw=c.nchw,
+                                   res=res_d if use_res else None, relu_out=relu, parts=True)
     assert y is out
+    assert plan == (rec, 0), '%s %s: launched %s, planned %s' % (c.id, epi, rec, plan)
     SEEN[(c.id, epi)] = rec
     want = expected(c, use_res)
     got = {k: getattr(rec, k) for k in want}

@@ -571,6 +571,8 @@ def _fwd_call(ops, c, form, dev, with_stats, check=True):
     else:
         y = ops.conv2d_fwd(dev['x'], dev['wp'], c.Co, c.k, c.k, c.s, c.p, c.d, out=out, **kw)
     rec = ops.conv_last_launch()
+    plan = ops.conv2d_fwd_plan(dev['x'].shape, c.Co, c.k, c.k, c.s, c.p, c.d, bn_partial=with_stats, parts=True, **kw)
+    assert plan == (rec, parts), '%s %s: launched %s with %d records, planned %s' % (c.id, form, rec, parts, plan)
     assert y is out
     if with_stats and check:
         _assert_record(c, form, rec, parts > 0)
@@ -704,6 +706,8 @@ def _dgrad_call(ops, c, form, dev):
     got = ops.conv2d_dgrad(dev['dy'], dev['wpt'], c.Ci, c.H, c.W, c.k, c.k, 1, c.p, c.d, out=out, **kw)
     rec = ops.conv_last_launch()
     dx, partials = got if isinstance(got, tuple) else (got, None)
+    plan = ops.conv2d_dgrad_plan(dev['dy'].shape, c.Ci, c.H, c.W, c.k, c.k, 1, c.p, c.d, parts=True, **kw)
+    assert plan == (rec, partials[1] if partials else 0), '%s %s: launched %s with %s, planned %s' % (c.id, form, rec, partials and partials[1], plan)
     assert dx is out
     return buf, partials, rec
 
