@@ -110,14 +110,23 @@ __global__ __launch_bounds__(WAVE) void gainfit_reduce_kernel(const double* __re
 
 __device__ __forceinline__ double gf_nan() { return __longlong_as_double(0x7ff8000000000000ll); }
 
+// One workgroup per (group, window): blockIdx.x = group * W + w.  A group is one run of W windows with its own moments
+// [W][S+1][S+1], gains [S][W], residual / target / status [W]; windows are pooled within their group only.  dam_gainfit_solve is
+// the call with one group and no target.
 __global__ __launch_bounds__(WAVE) void gainfit_solve_kernel(const double* __restrict__ moments, int W, int S, int pool,
                                                              double ridge, double* __restrict__ gains,
-                                                             double* __restrict__ residual, int* __restrict__ status) {
+                                                             double* __restrict__ residual, double* __restrict__ target,
+                                                             int* __restrict__ status) {
     __shared__ double A[GF_MAX_U * GF_MAX_U];
     __shared__ double R[GF_MAX_S * GF_MAX_S];         // the normalised matrix, then its Cholesky factor (lower triangle)
     __shared__ double d[GF_MAX_S], hv[GF_MAX_S], gv[GF_MAX_S];
     __shared__ int idx[GF_MAX_S];
-    const int w = blockIdx.x, U = S + 1, UU = U * U;
+    const int w = (int)(blockIdx.x % (unsigned)W), U = S + 1, UU = U * U;
+    const int64_t group = blockIdx.x / (unsigned)W;
+    moments += group * W * UU;
+    gains += group * S * W;
+    residual += group * W;
+    status += group * W;
     const int64_t v0 = (int64_t)w - pool > 0 ? (int64_t)w - pool : 0;
     const int64_t v1 = (int64_t)w + pool < W - 1 ? (int64_t)w + pool : W - 1;
     for (int e = threadIdx.x; e < UU; e += WAVE) {
@@ -184,6 +193,7 @@ __global__ __launch_bounds__(WAVE) void gainfit_solve_kernel(const double* __res
         residual[w] = gf_nan();
     }
     status[w] = st;
+    if (target) target[group * W + w] = Y;
 }
 
 // Lane j of the 64 takes window c0 + j of a run of 64 and leaves its contributions in LDS; lane s < S then adds stem s's, and
@@ -325,7 +335,19 @@ extern "C" int dam_gainfit_solve(const double* moments, int n_windows, int n_ste
     if (!moments || !gains || !residual || !status) return DAM_ERR_BAD_ARG;
     if (n_windows < 1 || n_stems < 1 || n_stems > GF_MAX_S || pool < 0 || !(ridge >= 0.0)) return DAM_ERR_BAD_ARG;
     hipLaunchKernelGGL(gainfit_solve_kernel, dim3((unsigned)n_windows), dim3(WAVE), 0, (hipStream_t)stream, moments, n_windows,
-                       n_stems, pool, ridge, gains, residual, status);
+                       n_stems, pool, ridge, gains, residual, (double*)nullptr, status);
+    DAM_CHECK_LAUNCH();
+    return DAM_OK;
+}
+
+extern "C" int dam_bandfit_solve_grouped(const double* moments, int n_groups, int n_windows, int n_stems, int pool, double ridge,
+                                         double* gains, double* residual, double* target, int32_t* status, void* stream) {
+    using namespace dam;
+    if (!moments || !gains || !residual || !target || !status) return DAM_ERR_BAD_ARG;
+    if (n_groups < 1 || n_windows < 1 || n_stems < 1 || n_stems > GF_MAX_S || pool < 0 || !(ridge >= 0.0)) return DAM_ERR_BAD_ARG;
+    if ((int64_t)n_groups * n_windows > 0x7fffffff) return DAM_ERR_UNSUPPORTED;
+    hipLaunchKernelGGL(gainfit_solve_kernel, dim3((unsigned)((int64_t)n_groups * n_windows)), dim3(WAVE), 0, (hipStream_t)stream,
+                       moments, n_windows, n_stems, pool, ridge, gains, residual, target, status);
     DAM_CHECK_LAUNCH();
     return DAM_OK;
 }

@@ -32,6 +32,12 @@ are a variant's gains from them?  The reference stems' sum is fitted with the ra
 windows of the model's own gain ramp (gainfit.fit_gains): 'oracle_gains', 'oracle_residual' (the share of the reference no
 gain-only mixer explains) and a '*_gain_error' beside every '*_error' -- the mean distance in dB from the fitted gains,
 stem by stem and window by window, relative to each window's mean over the stems (gainfit.gain_error_device).
+
+``band_fit=True`` asks what that residual is made of -- a human mix is mostly gain plus EQ per stem: the same fit per
+fractional-octave band of the STFT (gainfit.fit_band_gains): 'oracle_band_gains' (the reference's EQ curve per stem),
+'oracle_band_residual_total' (what per-band gains still leave unexplained: its distance in dB from 'oracle_residual' is the
+headroom of a band-gain mixer over a gain-only one) and a '*_band_gain_error' beside every '*_gain_error' -- how far a
+variant's broadband gains sit from the band-wise optimum.
 """
 import os
 from collections import OrderedDict
@@ -142,6 +148,26 @@ class LoudnessEvaluator:
             ops.align_check_shapes((1, 1, 1), None, max_lag)
         return max_lag
 
+    BAND_FIT_DEFAULTS = {'n_fft': 4096, 'hop': None, 'fraction': 3, 'f_lo': 25.0, 'f_hi': 20000.0, 'pool': 0, 'ridge': 0.0,
+                         'align': None}                    # hop None: n_fft / 2
+
+    def _band_fit_args(self, band_fit):
+        """``band_fit`` as the whole-song methods take it (True, or a dict with any of n_fft, hop, fraction, f_lo, f_hi, pool,
+        ridge, align) -> a dict of n_fft, hop, edges, centres (spectrum.band_edges at the evaluator's rate), pool, ridge, align."""
+        given = {} if band_fit is True else dict(band_fit)
+        unknown = set(given) - set(self.BAND_FIT_DEFAULTS)
+        if unknown:
+            raise ValueError('band_fit: unknown keys %s (expected any of %s)' % (sorted(unknown), sorted(self.BAND_FIT_DEFAULTS)))
+        o = dict(self.BAND_FIT_DEFAULTS, **given)
+        hop = o['n_fft'] // 2 if o['hop'] is None else o['hop']
+        # (the shapes are placeholders: what is checked here is n_fft, hop and the number of bands)
+        edges, centres = spectrum.band_edges(self.sr, o['n_fft'], o['fraction'], o['f_lo'], o['f_hi'])
+        n_fft, hop = ops.gainfit_band_check_shapes((1, o['n_fft'], 1), (o['n_fft'], 1), 1, o['n_fft'], hop, len(centres))[4:]
+        pool, ridge = ops.gainfit_check_solve_args(o['pool'], o['ridge'])
+        if o['align'] is not None:
+            ops.align_check_shapes((1, 1, 1), None, o['align'])
+        return {'n_fft': n_fft, 'hop': hop, 'edges': edges, 'centres': centres, 'pool': pool, 'ridge': ridge, 'align': o['align']}
+
     def evaluate_spectrum_batch(self, stems, gains=None, **spectral):
         """Band powers of the stem sum (long-term average spectrum in fractional-octave bands at the evaluator's rate),
         measured as ``sum of stem * gain ramp`` where gains are given, without that sum being written.  stems as
@@ -192,7 +218,7 @@ class LoudnessEvaluator:
 
     def process_song_tracks(self, loaded_tracks: dict, reference_tracks: dict, song_name: str, n_random_samples: int = 5,
                             chunk_length: int = 2, write_wavs_to_disk=False, results_dir='./experiment',
-                            ceiling_dbtp=None, dynamics=False, limiter=None, spectral=False, gain_fit=False) -> dict:
+                            ceiling_dbtp=None, dynamics=False, limiter=None, spectral=False, gain_fit=False, band_fit=False) -> dict:
         """evaluation.py:77-116 on stems already in memory ({name: ndarray [channels, n]} each): the loudness profile of
         ``reference_tracks`` against the profiles of ``loaded_tracks`` summed as they are ('sum_error'), normalised to the
         training set's mean loudness ('loudnorm_error'), mixed by the model ('mix_error') and scaled by random gains
@@ -225,7 +251,17 @@ class LoudnessEvaluator:
         whatever its spectrum, where the PHAT weighting loses a near-sinusoidal stem) and the stems are shifted by it before
         the fit; the stats gain 'oracle_lag' {name: samples, positive where the reference is late} and 'oracle_lag_peak'
         {name: the normalised correlation at that lag, 0 .. 1, NaN for a silent stem}.  Absent (the default), nothing is
-        estimated and no key is added."""
+        estimated and no key is added.
+        band_fit (True, or a dict with any of n_fft, hop, fraction, f_lo, f_hi, pool, ridge, align; BAND_FIT_DEFAULTS): the
+        same fit taken per frequency band (gainfit.fit_band_gains on the same target, fractional-octave bands at the
+        evaluator's rate).  The stats gain, after any gain_fit keys, 'oracle_band_centres' [bands] in Hz, 'oracle_band_gains'
+        {name: [bands][windows]} -- the reference's EQ curve per stem --, 'oracle_band_residual' [bands][windows],
+        'oracle_band_residual_total' [windows] -- the share of the reference that per-band gains leave unexplained: its
+        distance in dB from 'oracle_residual' is the headroom of a band-gain mixer over a gain-only one -- and
+        'sum_band_gain_error', 'loudnorm_band_gain_error', 'mix_band_gain_error', 'random_band_gain_error': each variant's
+        broadband gains against the band-wise optimum, the gain error over every (band, window) with the variant's curve
+        repeated over the bands.  'align' is gain_fit's; where both ask for the same lag the stems are aligned once.  It needs
+        no gain_fit, changes no other key and comes to the host in the same copy.  The lengths must agree."""
         if self.d is None or self.mix_model is None or self.mean_loudness_model is None:
             raise ValueError('process_song needs the dataset, d_mean_loudness and mix_model constructor arguments')
         stems = [t for t in self.d.get_tracklist() if t != 'mix']
@@ -233,6 +269,10 @@ class LoudnessEvaluator:
             raise ValueError('the dataset tracklist and the evaluator keys must both be %s' % (self.random_model.tracklist,))
         if dynamics and np.asarray(reference_tracks[self.keys[0]]).shape[-1] != np.asarray(loaded_tracks[self.keys[0]]).shape[-1]:
             raise ValueError('dynamics=True compares window by window: the reference mix and the stems differ in length')
+        if band_fit:
+            band = self._band_fit_args(band_fit)
+            if np.asarray(reference_tracks[self.keys[0]]).shape[-1] != np.asarray(loaded_tracks[self.keys[0]]).shape[-1]:
+                raise ValueError('band_fit fits frame by frame: the reference mix and the stems differ in length')
         if gain_fit:
             (fit_pool, fit_ridge), fit_align = self._gain_fit_args(gain_fit), self._gain_fit_align(gain_fit)
             if np.asarray(reference_tracks[self.keys[0]]).shape[-1] != np.asarray(loaded_tracks[self.keys[0]]).shape[-1]:
@@ -259,7 +299,7 @@ class LoudnessEvaluator:
                 return spectrum.band_power_mix(stem_pcm.transpose(1, 2), g, n_fft=n_fft, hop=hop, edges=edges)
             reference_spec = band_power(reference_pcm)
             drawn_gains = []
-        if gain_fit:                                        # the fit's target: the float64 sum of the reference stems, [channels, n]
+        if gain_fit or band_fit:                            # the fit's target: the float64 sum of the reference stems, [channels, n]
             fit_target = ops.mixdown_peak_normalize(reference_pcm, torch.ones((len(self.keys), 1), dtype=torch.float64,
                                                                               device=reference_pcm.device), normalize=False)
             candidates_fit = []                             # loudnorm, then the draws: [stems] each
@@ -288,7 +328,7 @@ class LoudnessEvaluator:
             candidates_st.append(self.evaluate_short_term_batch(pcm, loudnorm_gains))
         if spectral:
             candidates_spec.append(band_power(pcm, loudnorm_gains))
-        if gain_fit:
+        if gain_fit or band_fit:
             candidates_fit.append(loudnorm_gains.reshape(-1))
         stats['mix_error'] = error(self._profile([float(v) for v in mix_lufs]))
         write('mix', pcm, mixer.gains[1])
@@ -306,7 +346,7 @@ class LoudnessEvaluator:
                 candidates_st.append(self.evaluate_short_term_batch(pcm, g))
             if spectral:
                 drawn_gains.append(g)
-            if gain_fit:
+            if gain_fit or band_fit:
                 candidates_fit.append(g)
         stats['random_error'] = mean(random_errors)
         stats['smooth_gains'] = {name: list(gains[1, i]) for i, name in enumerate(self.keys)}
@@ -328,34 +368,72 @@ class LoudnessEvaluator:
             stats['random_spec_error'] = mean(host[3:n_var])
             stats['ltas'] = {'centres': centres.tolist(), 'reference': host[n_var:n_var + n_bands],
                              'mix': host[n_var + n_bands:]}
-        if gain_fit:                                        # one launch for every variant, one copy to the host
+        if gain_fit or band_fit:                            # one launch for every variant and fit, one copy to the host
             n_stems, W = len(self.keys), mixer.n_proc
-            fit_stems = pcm.transpose(1, 2)
-            if fit_align is not None:                       # the raw stems moved onto the reference; the lags stay on the device
-                stem_lag, _, stem_lag_peak, _, _ = align.estimate_lag(fit_stems, fit_target.transpose(0, 1), fit_align,
-                                                                      weighting='plain')
-                fit_stems = align.shift_tracks(fit_stems, stem_lag)
-            fitted, residual, _ = gainfit.fit_gains(fit_stems, fit_target.transpose(0, 1), W, pool=fit_pool, ridge=fit_ridge)
+            raw_stems, target = pcm.transpose(1, 2), fit_target.transpose(0, 1)
+            aligned = {}                                    # max_lag -> (shifted stems, lag, peak): a lag asked for twice is estimated once
+
+            def on_reference(max_lag):                      # the raw stems moved onto the reference; the lags stay on the device
+                if max_lag not in aligned:
+                    lag, _, peak, _, _ = align.estimate_lag(raw_stems, target, max_lag, weighting='plain')
+                    aligned[max_lag] = (align.shift_tracks(raw_stems, lag), lag, peak)
+                return aligned[max_lag]
             constant = torch.stack(candidates_fit).unsqueeze(-1).expand(-1, -1, W)         # loudnorm, draws: [.., stems, W]
             cand = torch.cat([torch.ones((1, n_stems, W), dtype=torch.float64, device=pcm.device), constant[:1],
                               mixer.gains[1].unsqueeze(0), constant[1:]])
-            fit_errors = gainfit.gain_error_device(fitted, cand)[0]
-            tail = [stem_lag.to(torch.float64), stem_lag_peak] if fit_align is not None else []
-            host = torch.cat([fit_errors, fitted.reshape(-1), residual] + tail).cpu().tolist()
             n_var = cand.shape[0]
-            stats['sum_gain_error'], stats['loudnorm_gain_error'], stats['mix_gain_error'] = host[:3]
-            stats['random_gain_error'] = mean(host[3:n_var]) if n_var > 3 else float('nan')
-            stats['oracle_gains'] = {name: host[n_var + i * W:n_var + (i + 1) * W] for i, name in enumerate(self.keys)}
-            stats['oracle_residual'] = host[n_var + n_stems * W:n_var + n_stems * W + W]
-            if fit_align is not None:
-                lags = host[n_var + n_stems * W + W:]
-                stats['oracle_lag'] = {name: int(lags[i]) for i, name in enumerate(self.keys)}
-                stats['oracle_lag_peak'] = dict(zip(self.keys, lags[n_stems:]))
+            parts = []
+            if gain_fit:
+                fit_stems = raw_stems
+                if fit_align is not None:
+                    fit_stems, stem_lag, stem_lag_peak = on_reference(fit_align)
+                fitted, residual, _ = gainfit.fit_gains(fit_stems, target, W, pool=fit_pool, ridge=fit_ridge)
+                fit_errors = gainfit.gain_error_device(fitted, cand)[0]
+                parts += [fit_errors, fitted.reshape(-1), residual]
+                if fit_align is not None:
+                    parts += [stem_lag.to(torch.float64), stem_lag_peak]
+            if band_fit:
+                band_stems = raw_stems if band['align'] is None else on_reference(band['align'])[0]
+                band_gains, band_residual, band_target, band_status = gainfit.fit_band_gains(
+                    band_stems, target, W, n_fft=band['n_fft'], hop=band['hop'], edges=band['edges'], pool=band['pool'],
+                    ridge=band['ridge'])
+                n_bands = band_gains.shape[0]
+                # every (band, window) is a window of the gain error: fitted [S][B W], the candidates' curves repeated over the bands
+                band_errors = gainfit.gain_error_device(
+                    band_gains.permute(1, 0, 2).reshape(n_stems, n_bands * W),
+                    cand.unsqueeze(2).expand(-1, -1, n_bands, -1).reshape(n_var, n_stems, n_bands * W))[0]
+                parts += [band_errors, band_gains.reshape(-1), band_residual.reshape(-1),
+                          gainfit.band_residual_total(band_residual, band_target, band_status)]
+            host = torch.cat(parts).cpu().tolist()
+            at = 0
+
+            def take(count):
+                nonlocal at
+                at += count
+                return host[at - count:at]
+            if gain_fit:
+                errors = take(n_var)
+                stats['sum_gain_error'], stats['loudnorm_gain_error'], stats['mix_gain_error'] = errors[:3]
+                stats['random_gain_error'] = mean(errors[3:]) if n_var > 3 else float('nan')
+                stats['oracle_gains'] = {name: take(W) for name in self.keys}
+                stats['oracle_residual'] = take(W)
+                if fit_align is not None:
+                    stats['oracle_lag'] = {name: int(v) for name, v in zip(self.keys, take(n_stems))}
+                    stats['oracle_lag_peak'] = dict(zip(self.keys, take(n_stems)))
+            if band_fit:
+                errors = take(n_var)
+                stats['sum_band_gain_error'], stats['loudnorm_band_gain_error'], stats['mix_band_gain_error'] = errors[:3]
+                stats['random_band_gain_error'] = mean(errors[3:]) if n_var > 3 else float('nan')
+                stats['oracle_band_centres'] = np.asarray(band['centres'], dtype=np.float64)
+                per_band = [[take(W) for _ in self.keys] for _ in range(n_bands)]
+                stats['oracle_band_gains'] = {name: [per_band[b][i] for b in range(n_bands)] for i, name in enumerate(self.keys)}
+                stats['oracle_band_residual'] = [take(W) for _ in range(n_bands)]
+                stats['oracle_band_residual_total'] = take(W)
         return stats
 
     def process_song(self, base_dir: str, song_name: str, n_random_samples: int = 5, chunk_length: int = 2,
                      write_wavs_to_disk=False, results_dir='./experiment', ceiling_dbtp=None, dynamics=False, limiter=None,
-                     spectral=False, gain_fit=False) -> dict:
+                     spectral=False, gain_fit=False, band_fit=False) -> dict:
         """evaluation.py:77-116: the reference mix from ``base_dir/manual_gain_mixes``, the stems from ``base_dir/test``."""
         from .data.dataset_utils import load_tracks_musdb18
         reference_tracks = load_tracks_musdb18(os.path.join(base_dir, 'manual_gain_mixes'), song_name, tracklist=self.keys,
@@ -363,21 +441,25 @@ class LoudnessEvaluator:
         loaded_tracks = load_tracks_musdb18(os.path.join(base_dir, 'test'), song_name, tracklist=self.keys, sr=self.sr)
         return self.process_song_tracks(loaded_tracks, reference_tracks, song_name, n_random_samples, chunk_length,
                                         write_wavs_to_disk, results_dir, ceiling_dbtp, dynamics, limiter, spectral,
-                                        **({'gain_fit': gain_fit} if gain_fit else {}))
+                                        **({'gain_fit': gain_fit} if gain_fit else {}),
+                                        **({'band_fit': band_fit} if band_fit else {}))
 
     def process_songlist(self, base_dir, songlist, n_random_samples: int = 5, chunk_length: int = 2,
                          write_wavs_to_disk=False, results_dir='./experiment', ceiling_dbtp=None, dynamics=False, limiter=None,
-                         spectral=False, gain_fit=False):
+                         spectral=False, gain_fit=False, band_fit=False):
         """evaluation.py:118-144 without the spreadsheet: (rows, means) -- one stats dict per song and the mean of every
         error over the songs (the sheet's last row); with ``dynamics`` the four '*_st_error' keys too, with ``spectral``
         the four '*_spec_error' keys, with ``gain_fit`` the four '*_gain_error' keys (a song whose figure is NaN -- nothing
-        to compare -- is left out of that mean; the mean is NaN if every song's is)."""
+        to compare -- is left out of that mean; the mean is NaN if every song's is), with ``band_fit`` the four
+        '*_band_gain_error' keys in the same way."""
         keys = ['sum_error', 'random_error', 'loudnorm_error', 'mix_error']
         if dynamics:
             keys += ['sum_st_error', 'random_st_error', 'loudnorm_st_error', 'mix_st_error']
         if spectral:
             keys += ['sum_spec_error', 'random_spec_error', 'loudnorm_spec_error', 'mix_spec_error']
         fit_keys = ['sum_gain_error', 'random_gain_error', 'loudnorm_gain_error', 'mix_gain_error'] if gain_fit else []
+        if band_fit:
+            fit_keys += ['sum_band_gain_error', 'random_band_gain_error', 'loudnorm_band_gain_error', 'mix_band_gain_error']
         rows = []
         for i, song_name in enumerate(songlist):
             print('{}/{}: {}'.format(i + 1, len(songlist), song_name))
@@ -387,6 +469,8 @@ class LoudnessEvaluator:
                 extra['spectral'] = spectral
             if gain_fit:
                 extra['gain_fit'] = gain_fit
+            if band_fit:
+                extra['band_fit'] = band_fit
             rows.append(self.process_song(base_dir, song_name, n_random_samples, chunk_length, write_wavs_to_disk,
                                           results_dir, ceiling_dbtp, dynamics, **extra))
         means = {key: mean(row[key] for row in rows) for key in keys}

@@ -15,7 +15,7 @@ CUDA tensors and raise otherwise -- there is no CPU fallback.
 import numpy as np
 import torch
 
-from . import ops
+from . import features, ops, spectrum
 
 
 def moments(stems, mix, n_windows):
@@ -61,6 +61,63 @@ def gain_error_device(fit, cand):
     positive, the mean of |d - the window's mean d| over the windows that keep at least two stems; NaN where none does.
     One launch for all candidates, nothing comes to the host."""
     return ops.gainfit_gain_error(fit, cand)
+
+
+def _band_args(stems, mix, n_windows, n_fft, hop, edges):
+    """Everything band_moments checks on the host, before anything is launched -> (n_fft, hop, host edge table)."""
+    n_fft, hop = ops.gainfit_band_check_shapes(tuple(stems.shape), tuple(mix.shape), n_windows, n_fft, hop)[4:]
+    table = spectrum.check_edges(edges, n_fft)
+    ops.gainfit_band_check_shapes(tuple(stems.shape), tuple(mix.shape), n_windows, n_fft, hop, table.size - 1)
+    return n_fft, hop, table
+
+
+def _band_moments(stems, mix, n_windows, n_fft, hop, table):
+    ops._lib.require_cuda(stems, mix)
+    dev_edges = spectrum._device_edges(table, n_fft, stems.device)      # resident after the first call, as the tables below
+    win, tw = features._get_tables(stems.device, n_fft)
+    return ops.gainfit_band_moments(stems, mix, n_windows, win, tw, n_fft, hop, dev_edges)
+
+
+def band_moments(stems, mix, n_windows, *, n_fft=4096, hop=None, edges):
+    """stems, mix, n_windows as ``moments`` takes them; edges: a host table of bin edges, ``spectrum.band_edges(...)[0]``
+    (strictly ascending within 0 .. n_fft/2 + 1, at most ops.GAINFIT_BAND_MAX_BANDS bands); hop defaults to n_fft / 2.
+    -> CUDA float64 [B, W, S + 1, S + 1]: for every band and window the sums, over the band's bins, the window's frames and
+    the channels, of Re(conj(U_i) U_j) of the S + 1 signals' STFTs (frames and window exactly those of features.stft, every
+    channel transformed on its own), exactly symmetric.  Window w holds the frames whose centre sample has gain index w in
+    the mixer's ramp; every window must own a frame.  Frames reach n_fft / 2 samples over a window's borders: a gain step in
+    the mix is smeared over one frame.  A cell depends on its own band, frames and signals only (bitwise).  No host
+    synchronisation once the tables are resident; hipGraph-capturable then."""
+    n_fft, hop, table = _band_args(stems, mix, n_windows, n_fft, hop, edges)
+    return _band_moments(stems, mix, n_windows, n_fft, hop, table)
+
+
+def solve_bands(moment_matrices, *, pool=0, ridge=0.0):
+    """moments [B, W, S + 1, S + 1] -> (gains float64 [B, S, W], residual float64 [B, W], target float64 [B, W], status int32
+    [B, W]), all on the device: ``solve`` on every band of its own (windows are pooled within a band), and ``target``, the
+    mix's energy in the band and (pooled) window -- what ``band_residual_total`` weighs the residuals by."""
+    pool, ridge = ops.gainfit_check_solve_args(pool, ridge)
+    ops.gainfit_check_grouped_shape(tuple(moment_matrices.shape))
+    return ops.gainfit_solve_grouped(moment_matrices, pool, ridge)
+
+
+def fit_band_gains(stems, mix, n_windows, *, n_fft=4096, hop=None, edges, pool=0, ridge=0.0, align=None, align_weighting='phat'):
+    """``solve_bands(band_moments(stems, mix, n_windows, ...), pool=pool, ridge=ridge)`` -> (gains [B, S, W], residual [B, W],
+    target [B, W], status [B, W]): the gain every stem had in every band and window of the mix -- its EQ curve per stem.
+    align: as ``fit_gains`` takes it; the stems are shifted by the estimated lags first, exactly as there."""
+    n_fft, hop, table = _band_args(stems, mix, n_windows, n_fft, hop, edges)
+    pool, ridge = ops.gainfit_check_solve_args(pool, ridge)
+    if align is not None:
+        ops.align_check_shapes(tuple(stems.shape), tuple(mix.shape), align, align_weighting)
+        stems = ops.align_shift(stems, ops.align_estimate(stems, mix, align, align_weighting)[0])
+    return ops.gainfit_solve_grouped(_band_moments(stems, mix, n_windows, n_fft, hop, table), pool, ridge)
+
+
+def band_residual_total(residual, target, status):
+    """residual, target, status [B, W] of ``solve_bands`` -> CUDA float64 [W]: the share of the mix's energy the band-wise
+    gains leave unexplained in every window (a band that could not be fitted counts as unexplained, a silent band adds
+    nothing; NaN where the mix is silent in every band) -- the counterpart of ``solve``'s broadband residual; the difference
+    of the two in dB is what per-band gains explain beyond scalar gains."""
+    return ops.gainfit_band_summary(residual, target, status)
 
 
 def residual_db(residual):

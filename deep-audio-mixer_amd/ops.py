@@ -1279,6 +1279,147 @@ def gainfit_gain_error(fit, cand, err_out=None, err_stem_out=None, n_kept_out=No
     return err_out, err_stem_out, n_kept_out
 
 
+# ----------------------------------------------------------------------------- band gain fit
+GAINFIT_BAND_MAX_BANDS = 64            # dam_spectrum_max_bands()
+
+
+def gainfit_band_frame_windows(n, n_windows, hop):
+    """[first frame of window w] for w = 0 .. W (the last entry is the frame count T = 1 + n / hop): window w of the band fit
+    owns the frames whose centre sample has gain index w in the mixer's ramp (include/dam_hip.h: Window of a frame)."""
+    seg, T = n // n_windows, 1 + n // hop
+    return [0] + [min(T, -(-(w * seg) // hop)) for w in range(1, n_windows)] + [T]
+
+
+def gainfit_band_check_shapes(stems_shape, mix_shape, n_windows, n_fft, hop, n_bands=None):
+    """The host-side argument rules of gainfit_band_moments on shapes alone -> (S, n, channels, W, n_fft, hop); ValueError /
+    TypeError otherwise.  hop None: n_fft / 2.  No tensor and no library is touched."""
+    S, n, ch, W = gainfit_check_shapes(stems_shape, mix_shape, n_windows)
+    if not isinstance(n_fft, numbers.Integral) or isinstance(n_fft, bool) or \
+            (hop is not None and (not isinstance(hop, numbers.Integral) or isinstance(hop, bool))):
+        raise TypeError('gainfit_band_moments: n_fft and hop must be integers')
+    n_fft = int(n_fft)
+    hop = n_fft // 2 if hop is None else int(hop)
+    if n_fft < 64 or n_fft > 16384 or n_fft & (n_fft - 1):
+        raise ValueError('gainfit_band_moments: n_fft must be a power of two from 64 to 16384')
+    if hop < 1:
+        raise ValueError('gainfit_band_moments: hop must be positive')
+    if n <= n_fft // 2:
+        raise ValueError('gainfit_band_moments: reflect padding needs more than n_fft / 2 samples (got %d)' % n)
+    if 1 + n // hop > 0x7fffffff // 2:
+        raise ValueError('gainfit_band_moments: too many frames')
+    first = gainfit_band_frame_windows(n, W, hop)
+    empty = [w for w in range(W) if first[w + 1] <= first[w]]
+    if empty:
+        raise ValueError('gainfit_band_moments: window %d of %d owns no frame (%d samples, hop %d): fewer windows or a '
+                         'smaller hop' % (empty[0], W, n, hop))
+    if n_bands is not None and not 1 <= n_bands <= GAINFIT_BAND_MAX_BANDS:
+        raise ValueError('gainfit_band_moments: 1..%d bands expected, got %d' % (GAINFIT_BAND_MAX_BANDS, n_bands))
+    return S, n, ch, W, n_fft, hop
+
+
+def gainfit_band_moments(stems, mix, n_windows, window, twiddles, n_fft, hop, edges, out=None, workspace=None, slab_bytes=0):
+    """stems, mix as gainfit_moments takes them; window, twiddles: the float32 tables of features._get_tables for ``n_fft``;
+    edges: CUDA int32 [B + 1] (content unchecked here, as in spectrum_band_power) -> the moment matrices of (stems, mix) over
+    the STFT bins of every band and the frames of every window, float64 [B, W, S + 1, S + 1] (include/dam_hip.h:
+    dam_bandfit_moments states the definition and the order of the additions).  slab_bytes: the spectra the workspace
+    holds at a time (0: the library's default); it changes no bit of the result.  workspace: optional float64 tensor of
+    dam_bandfit_workspace_bytes / 8 elements.  No host synchronisation, hipGraph-capturable."""
+    _lib.require_cuda(stems, mix, window, twiddles, edges, out, workspace)
+    xk, yk = _audio_kind(stems, 'stems'), _audio_kind(mix, 'mix')
+    if edges.dtype != torch.int32 or edges.dim() != 1 or not edges.is_contiguous():
+        raise TypeError('gainfit_band_moments: edges must be a contiguous int32 [bands + 1] tensor')
+    B = edges.numel() - 1
+    S, n, ch, W, n_fft, hop = gainfit_band_check_shapes(stems.shape, mix.shape, n_windows, n_fft, hop, B)
+    if not isinstance(slab_bytes, numbers.Integral) or slab_bytes < 0:
+        raise ValueError('gainfit_band_moments: slab_bytes must be a non-negative integer')
+    for t, what, count in ((window, 'window', n_fft), (twiddles, 'twiddles', 2 * n_fft)):
+        if t.dtype != torch.float32 or t.numel() != count or not t.is_contiguous():
+            raise ValueError('gainfit_band_moments: %s must be a contiguous float32 tensor of %d elements' % (what, count))
+    dev = stems.device
+    if mix.device != dev:
+        raise ValueError('gainfit_band_moments: the stems and the mix must be on one device')
+    shape = (B, W, S + 1, S + 1)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float64, device=dev)
+    elif tuple(out.shape) != shape or out.dtype != torch.float64 or not out.is_contiguous():
+        raise ValueError('gainfit_band_moments: out must be a contiguous float64 %s tensor' % (shape,))
+    L = _lib.lib()
+    need = L.dam_bandfit_workspace_bytes(W, n, S, ch, n_fft, hop, B, int(slab_bytes))
+    if need <= 0:
+        raise ValueError('gainfit_band_moments: the library refuses these arguments')
+    need = (need + 7) // 8
+    if workspace is None:
+        workspace = torch.empty(need, dtype=torch.float64, device=dev)
+    elif workspace.dtype != torch.float64 or workspace.numel() < need or not workspace.is_contiguous():
+        raise ValueError('gainfit_band_moments: workspace must be a contiguous float64 tensor of at least %d elements' % need)
+    with torch.cuda.device(dev):
+        _lib.check(L.dam_bandfit_moments(_lib.ptr(stems), xk, S, ch, n, stems.stride(0), stems.stride(1), stems.stride(2),
+                                              _lib.ptr(mix), yk, mix.stride(0), mix.stride(1), _lib.ptr(window),
+                                              _lib.ptr(twiddles), n_fft, hop, _lib.ptr(edges), B, W, int(slab_bytes),
+                                              _lib.ptr(out), _lib.ptr(workspace), _lib.stream()), 'dam_bandfit_moments')
+    return out
+
+
+def gainfit_check_grouped_shape(moments_shape):
+    """[G, W, S + 1, S + 1] as gainfit_solve_grouped takes it -> (G, W, S); ValueError otherwise."""
+    shape = tuple(moments_shape)
+    if len(shape) != 4 or shape[2] != shape[3] or not 2 <= shape[2] <= GAINFIT_MAX_STEMS + 1 or shape[0] < 1 or shape[1] < 1:
+        raise ValueError('gainfit_solve_grouped: moments must be [groups, windows, S + 1, S + 1] with 1..%d stems, got shape %s'
+                         % (GAINFIT_MAX_STEMS, shape))
+    return shape[0], shape[1], shape[2] - 1
+
+
+def gainfit_solve_grouped(moments, pool=0, ridge=0.0, gains_out=None, residual_out=None, target_out=None, status_out=None):
+    """moments: CUDA float64 [G, W, S + 1, S + 1] -> (gains float64 [G, S, W], residual float64 [G, W], target float64 [G, W],
+    status int32 [G, W]): gainfit_solve on every group (band) of its own -- windows are pooled within a group only -- and
+    ``target``, the mix's energy in the pooled matrix the residual was divided by (include/dam_hip.h:
+    dam_bandfit_solve_grouped).  One launch."""
+    _lib.require_cuda(moments, gains_out, residual_out, target_out, status_out)
+    pool, ridge = gainfit_check_solve_args(pool, ridge)
+    if moments.dtype != torch.float64:
+        raise TypeError('gainfit_solve_grouped: float64 moments expected')
+    G, W, S = gainfit_check_grouped_shape(moments.shape)
+    moments = moments.contiguous()
+    dev = moments.device
+    outs = []
+    for o, dt, shape in ((gains_out, torch.float64, (G, S, W)), (residual_out, torch.float64, (G, W)),
+                         (target_out, torch.float64, (G, W)), (status_out, torch.int32, (G, W))):
+        if o is None:
+            o = torch.empty(shape, dtype=dt, device=dev)
+        elif o.dtype != dt or tuple(o.shape) != shape or not o.is_contiguous():
+            raise ValueError('gainfit_solve_grouped: outputs must be contiguous float64 [%d, %d, %d], float64 [%d, %d] twice and '
+                             'int32 [%d, %d] tensors' % (G, S, W, G, W, G, W))
+        outs.append(o)
+    with torch.cuda.device(dev):
+        _lib.check(_lib.lib().dam_bandfit_solve_grouped(_lib.ptr(moments), G, W, S, pool, ridge, _lib.ptr(outs[0]),
+                                                        _lib.ptr(outs[1]), _lib.ptr(outs[2]), _lib.ptr(outs[3]), _lib.stream()),
+                   'dam_bandfit_solve_grouped')
+    return tuple(outs)
+
+
+def gainfit_band_summary(residual, target, status, out=None):
+    """residual, target CUDA float64 [G, W], status int32 [G, W] (gainfit_solve_grouped) -> total float64 [W]: the share of the
+    mix's energy the band-wise gains leave unexplained in every window, NaN where the mix is silent in every band
+    (include/dam_hip.h: dam_bandfit_summary)."""
+    _lib.require_cuda(residual, target, status, out)
+    if residual.dtype != torch.float64 or target.dtype != torch.float64 or status.dtype != torch.int32:
+        raise TypeError('gainfit_band_summary: float64 residual and target and int32 status expected')
+    if residual.dim() != 2 or residual.shape[0] < 1 or residual.shape[1] < 1 or target.shape != residual.shape \
+            or status.shape != residual.shape:
+        raise ValueError('gainfit_band_summary: three [groups, windows] tensors expected, got %s, %s and %s'
+                         % (tuple(residual.shape), tuple(target.shape), tuple(status.shape)))
+    residual, target, status = residual.contiguous(), target.contiguous(), status.contiguous()
+    G, W = residual.shape
+    if out is None:
+        out = torch.empty(W, dtype=torch.float64, device=residual.device)
+    elif out.dtype != torch.float64 or tuple(out.shape) != (W,) or not out.is_contiguous():
+        raise ValueError('gainfit_band_summary: out must be a contiguous float64 [%d] tensor' % W)
+    with torch.cuda.device(residual.device):
+        _lib.check(_lib.lib().dam_bandfit_summary(_lib.ptr(residual), _lib.ptr(target), _lib.ptr(status), G, W,
+                                                       _lib.ptr(out), _lib.stream()), 'dam_bandfit_summary')
+    return out
+
+
 # ----------------------------------------------------------------------------- alignment
 ALIGN_MAX_STEMS = 8
 ALIGN_WEIGHTINGS = {'plain': 0, 'phat': 1}      # DAM_ALIGN_PLAIN, DAM_ALIGN_PHAT

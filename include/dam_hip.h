@@ -55,7 +55,7 @@ struct dam_bn_bwd_sums; /* defined in the BatchNorm section */
 /* Library / build identification ("gfx950").  DAM_ABI_VERSION is bumped whenever a signature below changes; a binding
  * compares dam_abi_version() of the library it loaded with the version it was written against and refuses a stale one
  * (deep-audio-mixer_amd/_lib.py: EXPECTED_ABI). */
-#define DAM_ABI_VERSION 29
+#define DAM_ABI_VERSION 30
 const char* dam_arch(void);
 int dam_abi_version(void);
 
@@ -927,6 +927,81 @@ int dam_gainfit_solve(const double* moments, int n_windows, int n_stems, int poo
                       double* residual, int32_t* status, void* stream);
 int dam_gainfit_gain_error(const double* fit, const double* cand, int n_variants, int n_stems, int n_windows, int n_cand,
                            double* err, double* err_stem, int32_t* n_kept, void* stream);
+
+/* ---------------------------------------------------------------------------------
+ * Band gain fit (ABI 30): the gain fit above taken per frequency band -- the same least squares over the STFT bins of a band
+ * and the frames of a window, which gives the per-stem, per-band gains a reference mix used (its EQ curve per stem), and the
+ * share of the reference that per-band gains leave unexplained.  Every entry is stateless, allocates nothing, does not
+ * synchronise with the host, uses no atomics and is hipGraph-capturable.  tests/_bandfit_ref.py restates the definitions in
+ * numpy float64.
+ *   Signals.  Stems s = 0 .. S-1, 1 <= S <= DAM_GAINFIT_MAX_STEMS, and one mix y, of `channels` (1 or 2) and n = n_samples
+ *     samples, addressed exactly as dam_gainfit_moments addresses them (element strides, float32 or float64, the mix
+ *     independently of the stems).  u = (x_0 .. x_{S-1}, y).
+ *   Transforms.  Every channel of every signal is transformed on its own (no mono down-mix: the time-domain fit sums over the
+ *     channels too).  U_i[c][t][k] = the front-end's float32 STFT of channel c of u_i, with the conventions of
+ *     dam_stft_complex_f32 for a mono track without a gain: a float64 sample is rounded to float32 first, center = True with
+ *     reflect padding, frame_t[j] = u[reflect(t*hop - n_fft/2 + j)] * w[j] in float32, w = `window` (device float32 [n_fft], the
+ *     periodic Hann table), twiddles as dam_stft_fill_twiddles_host fills them, T = 1 + n / hop frames, n_fft a power of two
+ *     64 .. 16384, hop >= 1, n > n_fft/2, bins k = 0 .. n_fft/2 with the imaginary parts of bins 0 and n_fft/2 taken as 0.
+ *   Window of a frame.  w(t) = min(min(t*hop, n-1) / (n / W), W-1) in integer division: the gain index, in
+ *     dam_gain_ramp_apply, of the frame's centre sample -- window w of this fit is gain w of the mixer, as in the time-domain
+ *     fit.  1 <= W <= n, and every window must own at least one frame (DAM_ERR_BAD_ARG otherwise).  A frame reaches n_fft/2
+ *     samples to either side of its centre, so frames straddle the window borders: a gain step in the reference is smeared
+ *     over one frame, and the fitted gains of the two windows at a step are each pulled towards the other's.
+ *   Bands.  edges as dam_spectrum_band_power takes it: device int32 [B + 1], 0 <= edges[0] < ... < edges[B] <= n_fft/2 + 1,
+ *     1 <= B <= dam_spectrum_max_bands(); band b is the bins edges[b] .. edges[b+1]-1.  The CONTENT is the caller's to check
+ *     (gainfit.py does, on the host copy it uploads); the kernel clamps every edge to [0, n_fft/2 + 1].
+ *   dam_bandfit_moments:
+ *       M[b][w][i][j] = sum over t with w(t) = w, k in band b, c of  c_k * ( (double)Re U_i (double)Re U_j + (double)Im U_i (double)Im U_j ),
+ *     c_k = 1 for k = 0 and k = n_fft/2, else 2 (as in the band spectrum; the real part of conj(U_i) U_j: the gains are real).
+ *     device float64 [B][W][S+1][S+1], both triangles written from one computation of each pair (exactly symmetric).  One band
+ *     over all bins is the time-domain moment of the windowed frames times n_fft (Parseval), about n_fft * sum(w^2) / hop
+ *     times dam_gainfit_moments' value.
+ *     Every element (t, k, c) enters the sum of pair (i, j) through two fused multiply-adds, acc = fma(c_k Re U_i, Re U_j, acc),
+ *     then acc = fma(c_k Im U_i, Im U_j, acc); the float32 values are converted to float64 first and c_k U_i is exact.
+ *     Order of the additions, for the cell (b, w) of nb bins and nf frames: its E = nf * nb elements are numbered
+ *     q = (t - first frame) * nb + (k - edges[b]); tile r owns q in [r D, min((r+1) D, E)), D = dam_bandfit_tile_elements();
+ *     lane l of the tile's 256 adds q = r D + l, + 256, ... in ascending q, channel 0 before channel 1, to a running sum that
+ *     starts at +0.0; the 64 lanes of a wave are folded by an xor-butterfly, distances 1, 2, .. 32; the four waves are added as
+ *     ((w0 + w1) + w2) + w3; a second kernel adds the cell's ceil(E / D) tile sums in ascending r, starting from the first.  The
+ *     order depends on (nf, nb, channels) only, and an entry (i, j) on signals i and j only: a cell does not depend on the
+ *     other bands of the table, on the other windows, on the other stems or on how the call is cut into slabs (bitwise).
+ *     Stages and workspace.  The spectra are written to the workspace ([signal][channel][frame][bin] float2) and read back once;
+ *     those of a whole song do not fit (about 0.85 GB for four minutes of four stereo stems and a mix at 4096 / 2048), so the
+ *     entry walks the windows in slabs: as many whole windows as hold at most slab_bytes of spectra (at least one window), four
+ *     launches per slab (transform of the stems, of the mix, moments, reduce), no synchronisation between them.  slab_bytes = 0
+ *     means DAM_BANDFIT_SLAB_BYTES (128 MiB: half the last-level cache, so that a slab's spectra can still be there
+ *     when the moment kernel reads them).  workspace: dam_bandfit_workspace_bytes(the same arguments) bytes, 8-byte
+ *     aligned: the slab's spectra and one record of (S+1)(S+2)/2 doubles per tile; 0 for arguments the entry refuses.
+ *     A cell of more than 2^31 - 1 elements, or more than 2^30 - 1 frames: DAM_ERR_UNSUPPORTED.
+ *   dam_bandfit_solve_grouped: moments [G][W][S+1][S+1] -> gains [G][S][W], residual [G][W], target [G][W] (device float64),
+ *     status [G][W] (device int32): every group g (a band) is dam_gainfit_solve on moments[g], bit for bit -- one kernel serves
+ *     both -- so windows are pooled over w-pool .. w+pool OF THE SAME GROUP only.  target[g][w] = Y, the mix's energy in the
+ *     pooled matrix the residual was divided by (written for every cell, whatever its status).
+ *   dam_bandfit_summary: residual, target, status [G][W] -> total [W] (device float64).  For window w, in ascending b from
+ *     +0.0: a cell with Y = target[b][w] > 0 adds num = num + r * Y (a product, then a sum) and den = den + Y, where
+ *     r = residual[b][w] if status[b][w] > 0 and 1 otherwise (status -1, or 0 with Y > 0: nothing is explained there); a cell
+ *     with Y = 0 adds nothing.  total[w] = num / den, NaN if den = 0: the share of the mix's energy that per-band gains leave
+ *     unexplained, the counterpart of dam_gainfit_solve's broadband residual[w]; the difference of the two in dB is what
+ *     per-band gains explain beyond scalar gains.  One lane per window.
+ *   Argument errors (a NULL pointer; S outside 1 .. DAM_GAINFIT_MAX_STEMS; channels not 1 or 2; n_fft not a power of two in
+ *     64 .. 16384; hop < 1; n <= n_fft/2; W outside 1 .. n; a window without a frame; B outside 1 .. dam_spectrum_max_bands();
+ *     a negative slab_bytes; a non-positive count; negative pool or ridge, or a NaN ridge) return DAM_ERR_BAD_ARG before any launch.
+ * Not covered: complex (phase-shifting) band gains, and rendering the fitted band gains to audio.
+ * --------------------------------------------------------------------------------- */
+#define DAM_BANDFIT_SLAB_BYTES 134217728
+int64_t dam_bandfit_tile_elements(void);
+int64_t dam_bandfit_workspace_bytes(int n_windows, int64_t n_samples, int n_stems, int channels, int n_fft, int hop,
+                                         int n_bands, int64_t slab_bytes);
+int dam_bandfit_moments(const void* x, int x_is_f64, int n_stems, int channels, int64_t n_samples, int64_t stem_stride,
+                             int64_t sample_stride, int64_t channel_stride, const void* y, int y_is_f64, int64_t y_sample_stride,
+                             int64_t y_channel_stride, const float* window, const float* twiddles, int n_fft, int hop,
+                             const int32_t* edges, int n_bands, int n_windows, int64_t slab_bytes, double* moments,
+                             void* workspace, void* stream);
+int dam_bandfit_solve_grouped(const double* moments, int n_groups, int n_windows, int n_stems, int pool, double ridge,
+                              double* gains, double* residual, double* target, int32_t* status, void* stream);
+int dam_bandfit_summary(const double* residual, const double* target, const int32_t* status, int n_groups, int n_windows,
+                             double* total, void* stream);
 
 /* ---------------------------------------------------------------------------------
  * Alignment (ABI 28): the time offset of every stem against a mix by block cross-correlation, and the sample shift that removes
