@@ -566,6 +566,7 @@ extern "C" int dam_conv1x1_pair_f32(const float* x1, const float* w1_packed, int
                                     int tap2, int B, int H, int W, int C, int n_out, float* y, int OHt, int OWt, int out_stride,
                                     int out_off_h, int out_off_w, void* stream) {
     using namespace dam;
+    s2_last_launch = S2LaunchNote{};
     if (!x1 || !w1_packed || !x2 || !w2_packed || !y || B <= 0 || H <= 0 || W <= 0 || tap1 < 0 || tap2 < 0 || out_stride < 1)
         return DAM_ERR_BAD_ARG;
     if (C % 16 || n_out % 16 || C <= 0 || n_out <= 0) return DAM_ERR_UNSUPPORTED;
@@ -578,9 +579,13 @@ extern "C" int dam_conv1x1_pair_f32(const float* x1, const float* w1_packed, int
     const int nblk = n_out / 16, nch = C / 16;
     hipStream_t st = (hipStream_t)stream;
 #define DAM_PAIR_GO(NB_, R_, BOTH_)                                                                                           \
-    hipLaunchKernelGGL((conv1x1_pair_kernel<NB_, R_, BOTH_>), dim3((unsigned)cdiv(units, 4), (unsigned)(nblk / NB_)), dim3(256), 0, st, x1, \
-                       reinterpret_cast<const float4*>(w1_packed), tap1, x2, reinterpret_cast<const float4*>(w2_packed), tap2, B, H, W, \
-                       C, n_out, y, OHt, OWt, out_stride, out_off_h, out_off_w, segs, (int)units)
+    do {                                                                                                                      \
+        hipLaunchKernelGGL((conv1x1_pair_kernel<NB_, R_, BOTH_>), dim3((unsigned)cdiv(units, 4), (unsigned)(nblk / NB_)), dim3(256), 0, st, \
+                           x1, reinterpret_cast<const float4*>(w1_packed), tap1, x2, reinterpret_cast<const float4*>(w2_packed), tap2, B, \
+                           H, W, C, n_out, y, OHt, OWt, out_stride, out_off_h, out_off_w, segs, (int)units);                      \
+        note_nb = NB_; note_r = R_; note_both = BOTH_;                                                                        \
+    } while (0)
+    int note_nb = 0, note_r = 0, note_both = 0;
     if (nblk % 2 == 0) {
         if (nch <= 2) DAM_PAIR_GO(2, 2, true); else if (nch <= 4) DAM_PAIR_GO(2, 4, true); else DAM_PAIR_GO(2, 4, false);
     } else {
@@ -588,6 +593,9 @@ extern "C" int dam_conv1x1_pair_f32(const float* x1, const float* w1_packed, int
     }
 #undef DAM_PAIR_GO
     DAM_CHECK_LAUNCH();
+    // a wave takes exactly one (image, row, 16-pixel segment) unit of NB channel blocks
+    s2_last_launch = S2LaunchNote{S2_ENTRY_PAIR_1X1, S2_FAM_PAIR_1X1, note_nb, nch, 0, note_r, note_both, 0,
+                                  (int)(cdiv(units, 4) * (nblk / note_nb)), (int)units, 1, 1, 0};
     return DAM_OK;
 }
 

@@ -17,6 +17,9 @@
 #include "dam_common.h"
 
 namespace dam {
+
+thread_local S2LaunchNote s2_last_launch{};
+
 namespace {
 
 typedef float v4f __attribute__((ext_vector_type(4)));
@@ -303,6 +306,10 @@ int launch_conv_s2_pair(const float* x, const float* wp, const float* wp2, int B
                            reinterpret_cast<const float4*>(wp), reinterpret_cast<const float4*>(wp2), Hd, Wd, H, W, y, ys, p1, p2, (int)px,
                            (int)units);
     DAM_CHECK_LAUNCH();
+    int n_xcd = 1;
+    const int rounds = s2_resident_rounds(units, wgs, WAVES, &n_xcd);
+    s2_last_launch = S2LaunchNote{S2_ENTRY_PAIR_FWD, S2_FAM_RESIDENT, NB, NCH, 1, WAVES, 1, stats ? 1 : 0, (int)wgs, (int)units, rounds, n_xcd,
+                                  stats ? (int)wgs : 0};
     return DAM_OK;
 }
 
@@ -505,6 +512,9 @@ int launch_conv_s2_pair_stream(const float* x, const float* wp, const float* wp2
     if (stats) DAM_CS2S_GO(true); else DAM_CS2S_GO(false);
 #undef DAM_CS2S_GO
     DAM_CHECK_LAUNCH();
+    // a wave takes exactly one (16 pixels, 16 channels) unit; group g of 64 pixels runs on XCD g % 8
+    s2_last_launch = S2LaunchNote{S2_ENTRY_PAIR_FWD, S2_FAM_STREAM_LDS, NB, NCH, 1, 4, 1, stats ? 1 : 0, (int)grid.x, (int)(cdiv(px, 16) * NB), 1, 8,
+                                  stats ? (int)groups : 0};
     return DAM_OK;
 }
 
@@ -516,6 +526,7 @@ extern "C" int dam_conv_s2_pair_fwd_f32(const float* x, const float* w_packed, c
                                         int Co, float* y, float* ysc, float* partial, float* partial_sc, int* parts_host,
                                         void* stream) {
     using namespace dam;
+    s2_last_launch = S2LaunchNote{};
     if (!x || !w_packed || !wsc_packed || !y || !ysc || B <= 0 || H <= 0 || W <= 0) return DAM_ERR_BAD_ARG;
     if ((partial != nullptr) != (partial_sc != nullptr)) return DAM_ERR_BAD_ARG;
     if (partial && !parts_host) return DAM_ERR_BAD_ARG;
@@ -526,4 +537,13 @@ extern "C" int dam_conv_s2_pair_fwd_f32(const float* x, const float* w_packed, c
     if (Ci % 32 == 0 && Co % 16 == 0)
         return launch_conv_s2_pair_stream(x, w_packed, wsc_packed, B, H, W, Ci, Co, y, ysc, partial, partial_sc, parts_host, st);
     return DAM_ERR_UNSUPPORTED;
+}
+
+extern "C" int dam_s2_last_launch(int* out16_host) {
+    if (!out16_host) return DAM_ERR_BAD_ARG;
+    const dam::S2LaunchNote& n = dam::s2_last_launch;
+    const int v[16] = {n.entry, n.family, n.NB, n.NCH, n.MB, n.WAVES, n.pair, n.sums, n.workgroups, n.units, n.rounds, n.n_xcd, n.records,
+                       0, 0, 0};
+    for (int i = 0; i < 16; ++i) out16_host[i] = v[i];
+    return DAM_OK;
 }

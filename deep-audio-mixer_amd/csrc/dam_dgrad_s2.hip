@@ -309,6 +309,10 @@ int launch_dgrad_s2(const float* dc, const float* wpt, const float* ds, const fl
 #undef DAM_S2_GO
     if (parts_host) *parts_host = sums.u ? (int)wgs : 0;
     DAM_CHECK_LAUNCH();
+    int n_xcd = 1;
+    const int rounds = s2_resident_rounds(units, wgs, WAVES, &n_xcd);
+    s2_last_launch = S2LaunchNote{S2_ENTRY_DGRAD, S2_FAM_RESIDENT, NB, NCH, MB, WAVES, ds ? 1 : 0, sums.u ? 1 : 0, (int)wgs, (int)units, rounds,
+                                  n_xcd, sums.u ? (int)wgs : 0};
     return DAM_OK;
 }
 
@@ -541,6 +545,8 @@ int launch_dgrad_s2_stream(const float* dc, const float* wpt, const float* ds, c
             hipLaunchKernelGGL((dgrad_s2_stream_lds_kernel<false>), grid_l, block_l, 0, st, dc, reinterpret_cast<const float4*>(wpt),
                                (const float*)nullptr, (const float4*)nullptr, Hd, Wd, dx, H, W, (int)px, NCH, NB);
         DAM_CHECK_LAUNCH();
+        // a wave takes exactly one unit; group g of 64 pixels runs on XCD g % 8
+        s2_last_launch = S2LaunchNote{S2_ENTRY_DGRAD, S2_FAM_STREAM_LDS, NB, NCH, 1, 4, ds ? 1 : 0, 0, (int)grid_l.x, (int)units, 1, 8, 0};
         return DAM_OK;
     }
     const dim3 grid((unsigned)cdiv(units, 4)), block(256);
@@ -551,6 +557,7 @@ int launch_dgrad_s2_stream(const float* dc, const float* wpt, const float* ds, c
         hipLaunchKernelGGL((dgrad_s2_stream_kernel<false>), grid, block, 0, st, dc, reinterpret_cast<const float4*>(wpt),
                            (const float*)nullptr, (const float4*)nullptr, Hd, Wd, dx, H, W, (int)px, NCH, NB, (int)units);
     DAM_CHECK_LAUNCH();
+    s2_last_launch = S2LaunchNote{S2_ENTRY_DGRAD, S2_FAM_STREAM, NB, NCH, 2, 4, ds ? 1 : 0, 0, (int)grid.x, (int)units, 1, 1, 0};
     return DAM_OK;
 }
 
@@ -562,6 +569,7 @@ extern "C" int dam_dgrad_s2_3x3_f32(const float* dy, const float* w_packed_t, co
                                     int B, int Hd, int Wd, int Co, int Ci, float* dx, int H, int W, const dam_bn_bwd_sums* bn_bwd,
                                     float* bn_partial, int* bn_parts_host, void* stream) {
     using namespace dam;
+    s2_last_launch = S2LaunchNote{};
     if (!dy || !w_packed_t || !dx || B <= 0 || Hd <= 0 || Wd <= 0 || H <= 0 || W <= 0) return DAM_ERR_BAD_ARG;
     if ((dy_pair != nullptr) != (w_pair_packed_t != nullptr)) return DAM_ERR_BAD_ARG;
     if (Hd != (H + 1) / 2 || Wd != (W + 1) / 2) return DAM_ERR_BAD_ARG;             // 3x3 / stride 2 / pad 1 geometry

@@ -218,7 +218,7 @@ def _dgrad_axis(parity, pad, dil, k, stride):
 
 
 def conv2d_dgrad(dy, wpt, n_in, H, W, kh, kw, stride=1, pad=0, dil=1, res=None, res_mask=None, accumulate_into=None,
-                 bn_bwd=None, res_mask_bits=None, pair_1x1=None, _s2_sums=None, out=None):
+                 bn_bwd=None, res_mask_bits=None, pair_1x1=None, _s2_sums=None, out=None, records=None):
     """dy: NHWC [B,Ho,Wo,Cout]; wpt packed with transpose=True.  Returns dx NHWC [B,H,W,n_in16]
     (+ res * (res_mask > 0) if given).  With accumulate_into=dx0 the result is added to dx0 in place.
     bn_bwd=(x, save_mean, save_invstd, mask_scale, mask_shift[, mask_bits]) (stride 1; 3x3 / stride 2 / pad 1 with the mask_bits
@@ -227,8 +227,16 @@ def conv2d_dgrad(dy, wpt, n_in, H, W, kh, kw, stride=1, pad=0, dil=1, res=None, 
     (dx, partials) where partials = (records, count) for bn_backward(partials=) when the launch could also take that
     BatchNorm's two backward sums from its epilogue, else None (stride 1; with a residual only when its mask is also given
     as the sign bytes of bn_apply, res_mask_bits -- the float res_mask serves the launches that cannot use them).
-    out: the result tensor to write (contiguous float32 [B,H,W,n_in16] on dy's device) instead of a fresh one."""
+    out: the result tensor to write (contiguous float32 [B,H,W,n_in16] on dy's device) instead of a fresh one.
+    records (the strided bn_bwd form only): the record buffer to write (contiguous float32, at least
+    dam_bn_workspace_floats(n_in16) elements, on dy's device) instead of a fresh one."""
     _lib.require_cuda(dy, wpt)
+    if records is not None:
+        need = _lib.lib().dam_bn_workspace_floats((n_in + 15) // 16 * 16)
+        if bn_bwd is None or stride != 2:
+            raise ValueError('records: only with bn_bwd at stride 2')
+        if records.dtype != torch.float32 or not records.is_contiguous() or records.numel() < need or records.device != dy.device:
+            raise ValueError('records must be a contiguous float32 tensor of at least %d elements on %s' % (need, dy.device))
     if out is not None:
         want = (dy.shape[0], H, W, (n_in + 15) // 16 * 16)
         if accumulate_into is not None:
@@ -245,7 +253,7 @@ def conv2d_dgrad(dy, wpt, n_in, H, W, kh, kw, stride=1, pad=0, dil=1, res=None, 
         n16 = (n_in + 15) // 16 * 16
         if tuple(xb.shape) != (dy.shape[0], H, W, n16):
             raise ValueError('bn_bwd: x has the shape of the data gradient')
-        rec = torch.empty(_lib.lib().dam_bn_workspace_floats(n16), dtype=torch.float32, device=dy.device)
+        rec = records if records is not None else torch.empty(_lib.lib().dam_bn_workspace_floats(n16), dtype=torch.float32, device=dy.device)
         epi = _lib.BnBwdSums(_lib.ptr(xb), _lib.ptr(mean), _lib.ptr(invstd), None, None, None, _lib.ptr(up_bits))
         got = conv2d_dgrad(dy, wpt, n_in, H, W, kh, kw, stride, pad, dil, pair_1x1=pair_1x1, _s2_sums=(epi, rec), out=out)
         return got if isinstance(got, tuple) else (got, None)
@@ -483,6 +491,21 @@ def wgrad_last_launch():
     return WgradLaunch(fam, *v[1:13], v[13] if rows else 0, v[14] if rows else 0, v[13] if fam == 'tile' else 0, v[15])
 
 
+S2_ENTRIES = ('none', 'pair_fwd', 'dgrad_s2', 'pair_1x1')
+S2_FAMILIES = ('none', 'resident', 'stream_lds', 'stream', 'pair_1x1')
+S2Launch = collections.namedtuple('S2Launch', 'entry family NB NCH MB WAVES pair sums workgroups units rounds n_xcd records')
+
+
+def s2_last_launch():
+    """Which kernel the last conv_s2_pair_fwd / strided conv2d_dgrad call of this thread launched (dam_s2_last_launch): the entry
+    point and the kernel family by name, the template parameters of the instantiation (1x1 pair: WAVES is R, pair is BOTH), the
+    grid, the wave units, the largest number of units one wave takes (rounds), the XCD split and the records written; entry
+    'none' after a call that was refused.  Host-side only."""
+    v = (ctypes.c_int * 16)()
+    _lib.check(_lib.lib().dam_s2_last_launch(v), 'dam_s2_last_launch')
+    return S2Launch(S2_ENTRIES[v[0]], S2_FAMILIES[v[1]], *v[2:13])
+
+
 def nchw_to_nhwc16(x):
     """[B,C,H,W] float32 (C <= 16) -> NHWC [B,H,W,16], channels C..15 zero."""
     _lib.require_cuda(x)
@@ -563,22 +586,40 @@ def bn_stats_pair(xa, bn_a, xb, bn_b):
     return tuple(outs[0]), tuple(outs[1])
 
 
-def conv_s2_pair_fwd(x, wp, wp_sc, n_out, stats=True):
+def conv_s2_pair_fwd(x, wp, wp_sc, n_out, stats=True, out=None, records=None):
     """conv1 (3x3 / stride 2 / pad 1) and the 1x1 / stride-2 shortcut convolution of one NHWC input in one launch:
-    (c1, cs, (records1, records_sc, parts) or None), or None when the layer is not one dam_conv_s2_pair_fwd_f32 takes."""
+    (c1, cs, (records1, records_sc, parts) or None), or None when the layer is not one dam_conv_s2_pair_fwd_f32 takes.
+    out=(c1, cs): the result tensors to write (contiguous float32 [B,Hd,Wd,n_out16] on x's device) instead of fresh ones;
+    records=(p1, p2) (with stats): the record buffers to write (contiguous float32, at least dam_bn_workspace_floats(n_out16)
+    elements each, on x's device) instead of fresh ones."""
     _lib.require_cuda(x, wp, wp_sc)
     _f32c(x, 'x')
     B, H, W, C = x.shape
     n16 = (n_out + 15) // 16 * 16
     Hd, Wd = (H + 1) // 2, (W + 1) // 2
-    c1 = torch.empty((B, Hd, Wd, n16), dtype=torch.float32, device=x.device)
-    cs = torch.empty_like(c1)
+    if out is not None:
+        want = (B, Hd, Wd, n16)
+        if len(out) != 2 or any(t.dtype != torch.float32 or not t.is_contiguous() or tuple(t.shape) != want or t.device != x.device
+                                for t in out):
+            raise ValueError('out must be two contiguous float32 tensors of shape %s on %s' % (want, x.device))
+        c1, cs = out
+    else:
+        c1 = torch.empty((B, Hd, Wd, n16), dtype=torch.float32, device=x.device)
+        cs = torch.empty_like(c1)
     p1 = p2 = None
     parts = ctypes.c_int(0)
+    if records is not None and not stats:
+        raise ValueError('records: only with stats')
     if stats:
         n = _lib.lib().dam_bn_workspace_floats(n16)
-        p1 = torch.empty(n, dtype=torch.float32, device=x.device)
-        p2 = torch.empty(n, dtype=torch.float32, device=x.device)
+        if records is not None:
+            if len(records) != 2 or any(t.dtype != torch.float32 or not t.is_contiguous() or t.numel() < n or t.device != x.device
+                                        for t in records):
+                raise ValueError('records must be two contiguous float32 tensors of at least %d elements on %s' % (n, x.device))
+            p1, p2 = records
+        else:
+            p1 = torch.empty(n, dtype=torch.float32, device=x.device)
+            p2 = torch.empty(n, dtype=torch.float32, device=x.device)
     st = _lib.lib().dam_conv_s2_pair_fwd_f32(_lib.ptr(x), _lib.ptr(wp), _lib.ptr(wp_sc), B, H, W, C, n16, _lib.ptr(c1), _lib.ptr(cs),
                                              _lib.ptr(p1), _lib.ptr(p2), ctypes.byref(parts), _lib.stream())
     if st == -2:                                       # DAM_ERR_UNSUPPORTED

@@ -55,7 +55,7 @@ struct dam_bn_bwd_sums; /* defined in the BatchNorm section */
 /* Library / build identification ("gfx950").  DAM_ABI_VERSION is bumped whenever a signature below changes; a binding
  * compares dam_abi_version() of the library it loaded with the version it was written against and refuses a stale one
  * (deep-audio-mixer_amd/_lib.py: EXPECTED_ABI). */
-#define DAM_ABI_VERSION 30
+#define DAM_ABI_VERSION 31
 const char* dam_arch(void);
 int dam_abi_version(void);
 
@@ -287,6 +287,35 @@ int dam_dgrad_s2_3x3_f32(const float* dy, const float* w_packed_t, const float* 
  * dam_bn_stats_pair_f32. */
 int dam_conv_s2_pair_fwd_f32(const float* x, const float* w_packed, const float* wsc_packed, int B, int H, int W, int Ci, int Co,
                              float* y, float* ysc, float* partial, float* partial_sc, int* parts_host, void* stream);
+
+/* Which kernel the last call of the CALLING THREAD to one of the three entry points above (dam_conv1x1_pair_f32,
+ * dam_dgrad_s2_3x3_f32, dam_conv_s2_pair_fwd_f32) launched (ABI 31): each picks between kernels and template instantiations by
+ * channel counts, pixel count, the device's CU count and an occupancy answer without telling, so a test that means to exercise one
+ * instantiation, or the unit loop of a persistent kernel, asks here (as dam_wgrad_last_launch for the weight gradient).  A host
+ * variable: reset to "none" at the entry of every call of the three, written after the launch was made -- no device work, no kernel
+ * argument, nothing synchronised; the choice of kernel is unchanged.  out16_host (host memory, 16 ints) receives
+ *   [0] entry: 0 none (no call yet, or the call was refused or failed), 1 dam_conv_s2_pair_fwd_f32, 2 dam_dgrad_s2_3x3_f32,
+ *       3 dam_conv1x1_pair_f32
+ *   [1] family: 1 persistent kernel with the weight images resident in LDS, 2 streaming kernel with a chunk's weight fragments
+ *       staged in LDS per workgroup (one 16-pixel block per wave), 3 streaming kernel with the fragments straight from L2 (two
+ *       pixel blocks per wave; data gradient only), 4 the 1x1 pair kernel
+ *   [2] NB                         16-channel blocks of the OUTPUT (forward: Co / 16, data gradient: Ci / 16; 1x1 pair: blocks per
+ *                                  workgroup, 1 or 2)
+ *   [3] NCH                        16-channel chunks of the INPUT (forward: Ci / 16, data gradient: Co / 16, 1x1 pair: C / 16)
+ *   [4] MB                         16-pixel blocks per wave unit (1x1 pair: 0)
+ *   [5] WAVES                      waves per workgroup; 1x1 pair: R, the chunk slots per operand and round
+ *   [6] pair                       data gradient: dy_pair given; forward: 1; 1x1 pair: BOTH (all chunks of both operands in one round)
+ *   [7] sums                       forward: statistics records written; data gradient: the BatchNorm-backward sums written
+ *   [8] workgroups                 of the grid (streaming kernels: including the surplus ones that leave at once)
+ *   [9] units                      wave units of the launch (16 * MB pixels; streaming kernels: x one channel block; 1x1 pair: (image,
+ *                                  row, 16-pixel segment))
+ *   [10] rounds                    the largest number of units one wave takes: the persistent kernels' loop count, from the same
+ *                                  arithmetic as the kernel's (per_xcd, ustride); 1 for the others
+ *   [11] n_xcd                     persistent kernels: 8 when the grid is a multiple of 8 (every XCD takes a contiguous eighth of the
+ *                                  units), else 1; streaming kernels with LDS staging: 8 (group g on XCD g % 8); else 1
+ *   [12] records                   the count stored in *parts_host / *bn_parts_host
+ *   [13..15] 0 */
+int dam_s2_last_launch(int* out16_host);
 
 /* Sibling launches in one.  The parity classes of a strided data gradient are up to four small launches over the same
  * tensors, weights and tile that differ only in their tap grid.  With a batch (caller-owned HOST memory of

@@ -608,7 +608,10 @@ def test_strided_dgrad_one_launch(ops, monkeypatch, B, Ci, Co, H, W, pair):
     """dam_dgrad_s2_3x3_f32: the data gradient of a 3x3 / stride-2 / pad-1 convolution's input -- all four output parity classes
     from one read of dy, optionally + the 1x1 / stride-2 shortcut's gradient at the (even, even) pixels -- against
     torch.nn.grad.conv2d_input in float64, odd and even sizes, ragged pixel segments, and bit for bit the same as ... no: within
-    float32 summation order of the parity-class launches it replaces (DAM_NO_DGRAD_S2)."""
+    float32 summation order of the parity-class launches it replaces (DAM_NO_DGRAD_S2).
+    What these shapes reach (ops.s2_last_launch()): the persistent kernels at one unit per wave, except (8, 16, 32, 1025, 130)
+    (three rounds); stream_lds for the wide shapes, the two-block streaming kernel for (2, 64, 96, 513, 130).  The unit loop of
+    every instantiation, guard bands and the launch record: tests/test_s2_kernels_gpu.py."""
     g = torch.Generator().manual_seed(B * 100 + H + W + pair)
     Hd, Wd = (H + 1) // 2, (W + 1) // 2
     w = torch.randn(Co, Ci, 3, 3, generator=g) / (Ci * 9) ** 0.5
@@ -640,7 +643,9 @@ def test_downsampling_pair_forward_one_launch(ops, B, Ci, Co, H, W):
     """dam_conv_s2_pair_fwd_f32: a down-sampling block's conv1 (3x3 / stride 2 / pad 1) and its 1x1 / stride-2 shortcut convolution
     from one read of x, with the BatchNorm statistics records of both outputs -- against torch's conv2d in float64, odd and even
     sizes, units that straddle rows and images; the records merged (dam_bn_finalize_pair_f32) against the float64 mean / variance of
-    the float64 outputs, and their pixel counts against the tensor's."""
+    the float64 outputs, and their pixel counts against the tensor's.
+    (The two full-size shapes go round the unit loop 3 to 9 times, every other resident shape once; inputs far from zero mean,
+    every instantiation at one and several rounds, the record limit of the streaming form: tests/test_s2_kernels_gpu.py.)"""
     g = torch.Generator().manual_seed(B * 1000 + H + W)
     x = torch.randn(B, Ci, H, W, generator=g) + 0.3 * torch.randn(1, Ci, 1, 1, generator=g)
     w = torch.randn(Co, Ci, 3, 3, generator=g) / (Ci * 9) ** 0.5
@@ -680,7 +685,9 @@ def test_downsampling_pair_forward_one_launch(ops, B, Ci, Co, H, W):
 def test_strided_dgrad_takes_the_upstream_batchnorm_sums(ops, B, Ci, Co, H, W):
     """dam_dgrad_s2_3x3_f32 with bn_bwd: dx reaches y = relu(bn(u) + shortcut) of the block in front; the launch also leaves
     sum(dz) and sum(dz * uhat), dz = dx * (y > 0), per channel -- against float64 sums over the dx it wrote; the wide layers
-    (weights streamed) report "not produced"."""
+    (weights streamed) report "not produced".
+    (Every shape here is one unit per wave; the sums across the units of a looping wave, against the float64 reference dx:
+    tests/test_s2_kernels_gpu.py.)"""
     g = torch.Generator().manual_seed(B * 10 + H + W)
     Hd, Wd = (H + 1) // 2, (W + 1) // 2
     w = torch.randn(Co, Ci, 3, 3, generator=g) / (Ci * 9) ** 0.5

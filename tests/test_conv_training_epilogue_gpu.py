@@ -46,7 +46,8 @@ Unreachable from conv2d_fwd / conv2d_dgrad (named here instead of being dropped)
   * strip EPI 2 / 3 at 32 channels: not instantiated (`if (bwd.x && res) { if (c16) ...`, `nchunks != 1 -> UNSUPPORTED`): the entry
     point's second conv_strip_try runs SO 5 / the ping-pong write-out with the FLOAT mask and reports no records (test_retreat_backward_sums).
   * strip statistics with more than one channel workgroup (cdiv(nblk, NB) != 1) and with more than 1024 records: retreats, below.
-  * strided data gradients (parity classes, dam_dgrad_s2_3x3_f32) and dam_conv_s2_pair_fwd_f32: other entry points, out of scope;
+  * strided data gradients (parity classes, dam_dgrad_s2_3x3_f32) and dam_conv_s2_pair_fwd_f32: other entry points, with a launch
+    record and a table of their own in tests/test_s2_kernels_gpu.py;
     so the run-time tap grid of the strip is reached by the masked residual through dilated layers only.
   * pipe STATS 1 / 2 on column ranges: the entry point runs ranges only without bn_partial (`!bn_partial`): a statistics call on
     such a shape takes conv_igemm_kernel and reports parts == 0 (test_retreat_statistics_on_column_ranges).
