@@ -17,26 +17,12 @@
 //   * a second kernel sums the slabs in a fixed order (deterministic, no float atomics) and writes
 //     torch's [O][I][KH][KW] layout.
 #include <string.h>
+#include <type_traits>
 #include "dam_common.h"
 #include "dam_conv_stage.h"
+#include "dam_wgrad_plan.h"
 
 namespace dam {
-
-struct WgradGeo {
-    int B, H, W, C;          // input tensor
-    int Ho, Wo, N;           // dY tensor [B][Ho][Wo][N]
-    int s;                   // conv stride (1 or 2)
-    int KH, KW;              // full kernel
-    int off_h, step_h, off_w, step_w;   // tap (kh,kw) reads input (oh*s + off_h + kh*step_h, ...)
-    int r0, c0;
-    int PR, PWin, PWs, PWT;
-    int nchunks;             // ceil(C/16) (1 if in_nchw)
-    int nblk;                // N/16
-    int tiles_n, tiles_k, tap_groups;
-    int tiles_m, total_tiles, nsplit;
-    int in_nchw, relu_in;
-    int TMW;                 // pixels per tile (a multiple of 16, <= 256): 4 waves x TMW/4 pixels
-};
 
 // Weight gradients of ONE geometry batched into one launch of the tile kernel (blockIdx.z = job): the three equal convolutions of
 // a deep ResNet stage (models/model_resnet.py:14-21 at 256 / 128 channels) are 20-28 us launches of which ~13 us are launch and
@@ -51,24 +37,14 @@ struct WgradJobs {
     int relu_in[WG_MAX_JOBS];             // per job (with sc): a block's conv2 reads relu(bn1(c1)), its conv1 the plain block input
 };
 
-// Jobs of a batched launch of the direct kernel (see wgrad_direct_batch_kernel): each with its own geometry and grid share.
+// Jobs of a batched launch of the direct kernel (see wgrad_direct_batch_kernel; DirectJob: dam_wgrad_plan.h).
 constexpr int WD_MAX_JOBS = 8;
-struct DirectJob {
-    const float* X; const float* dY; float* partial;
-    int rows, Ho, Wo, H, W, C, N, s, pad, dil, tiles_k;
-    int nx, nsplit, wg0;                     // the job's (nx, nsplit) grid and its first workgroup in the flat launch
-};
 struct DirectJobs { DirectJob job[WD_MAX_JOBS]; int njobs; };
 
 namespace {
 
 // What the last dam_conv2d_wgrad_f32 call of this thread committed to (dam_wgrad_last_launch, include/dam_hip.h): a host variable
-// written where a launcher has passed its last refusal, read by tests that must know which instantiation they exercised.
-enum WgradFamily { WGRAD_FAM_NONE = 0, WGRAD_FAM_ROWS = 1, WGRAD_FAM_ROWS_S2 = 2, WGRAD_FAM_DIRECT = 3, WGRAD_FAM_TILE = 4 };
-enum WgradIssue { WGRAD_REDUCED_NOW = 0, WGRAD_REDUCTION_QUEUED = 1, WGRAD_LAUNCH_RECORDED = 2 };
-struct WgradLaunchNote {
-    int family, TNB, TKB, STEPS, KP, GPP, GPPD, HV, NL, TA, TB, nx, nsplit, spi_tmw, rps, issued;
-};
+// written from the plan where a launcher has passed its last refusal, read by tests that must know which instantiation they exercised.
 thread_local WgradLaunchNote wgrad_last_launch{};
 
 typedef float v4f __attribute__((ext_vector_type(4)));
@@ -312,25 +288,22 @@ __global__ __launch_bounds__(256) void wgrad_reduce_batch_kernel(const ReduceBat
 }
 
 // Host side of a caller-owned queue of deferred reductions (include/dam_hip.h: dam_wgrad_queue_*).
-struct WgradQueue;
 // tile-kernel launches of one geometry recorded, not yet launched (dam_wgrad_queue_set_batching)
 struct PendingTile {
     int njobs;                               // 0: nothing pending
-    int sig;                                 // the instantiation: TNB | TKB << 4 | TA << 8 | TB << 12
+    WgradLaunchNote note;                    // the instantiation (as planned for every job)
     WgradGeo g;                              // shared geometry, nsplit = 0 (decided at launch from the number of jobs)
     WgradJobs jobs;
     float* dw[WG_MAX_JOBS];
     int64_t ws_floats[WG_MAX_JOBS];
-    int n_real[WG_MAX_JOBS], k_real[WG_MAX_JOBS];
-    int (*launch)(WgradQueue*, hipStream_t);
+    WgradReduce red[WG_MAX_JOBS];
 };
 // direct-kernel launches of one instantiation recorded, not yet launched (any geometry: every job carries its own)
 struct PendingDirect {
-    int sig;                                 // TNB | TKB << 4 | KH << 8 | KW << 12
+    WgradLaunchNote note;                    // the instantiation
     DirectJobs jobs;                         // jobs.njobs == 0: nothing pending
     float* dw[WD_MAX_JOBS];
-    int n_real[WD_MAX_JOBS], k_real[WD_MAX_JOBS];
-    int (*launch)(WgradQueue*, hipStream_t);
+    WgradReduce red[WD_MAX_JOBS];
 };
 struct WgradQueue {
     unsigned magic;
@@ -353,12 +326,11 @@ int reduce_flush(ReduceBatch& b, hipStream_t st) {
 
 // The slab reduction of one weight gradient: launched now (queue == nullptr) or appended to the caller's queue (its slabs
 // must then stay untouched until dam_wgrad_queue_flush).
-int reduce_submit(void* queue, const float* partial, float* dw, int nsplit, int nx, int TNB, int TKB, int TA, int TB, int n_real,
-                  int k_real, int KH, int KW, int tap_groups, int tiles_k, hipStream_t st) {
+int reduce_submit(void* queue, const float* partial, float* dw, int nsplit, int nx, const WgradReduce& r, hipStream_t st) {
     ReduceJob j;
-    j.partial = partial; j.dw = dw; j.nsplit = nsplit; j.nx = nx; j.TNB = TNB; j.TKB = TKB; j.TA = TA; j.TB = TB;
-    j.n_real = n_real; j.k_real = k_real; j.KH = KH; j.KW = KW; j.tap_groups = tap_groups; j.tiles_k = tiles_k;
-    const int64_t per_split4 = (int64_t)nx * TNB * TKB * TA * TB * 64;
+    j.partial = partial; j.dw = dw; j.nsplit = nsplit; j.nx = nx; j.TNB = r.TNB; j.TKB = r.TKB; j.TA = r.TA; j.TB = r.TB;
+    j.n_real = r.n_real; j.k_real = r.k_real; j.KH = r.KH; j.KW = r.KW; j.tap_groups = r.tap_groups; j.tiles_k = r.tiles_k;
+    const int64_t per_split4 = (int64_t)nx * r.TNB * r.TKB * r.TA * r.TB * 64;
     if (nsplit >= 64) {
         j.sl = 32;
         j.blocks = (int)(cdiv(per_split4, 8) < 4096 ? cdiv(per_split4, 8) : 4096);
@@ -399,13 +371,6 @@ int reduce_submit(void* queue, const float* partial, float* dw, int nsplit, int 
 //     (a streaming MFMA wave owns the SIMD's vector issue port, see dam_conv_strip.hip).
 //   * Loader waves: scalar plane arithmetic, buffer_load with per-lane column offsets computed once, ds_write with the
 //     column mask in EXEC.  Two slots ahead in two register sets (a slot is ~4 us of MFMAs, about the HBM latency under load).
-struct RowsGeo {
-    int B, H, W, C;          // C channels per pixel in X and in dY
-    int P4;                  // ring row pitch in cells: roundup4(W + 2)
-    int rps, spi;            // output rows per strip (multiple of 4), strips per image
-    int tiles_k;             // in-channel tiles
-    int gpp;                 // 1 KB pieces per row plane
-};
 // Diagnostic build only (-DDAM_WGR_STAMPS, tools/wgr_stamps_probe.py; results are wrong): instead of its slab a workgroup leaves
 // s_memtime stamps of compute wave 0 and loader wave 0, [role][32] of (tag << 56 | time): 1 start, 2 first rows staged,
 // 5 end of a slot's MFMAs / commits, 7 behind the slot's barrier, 8 end.
@@ -418,8 +383,6 @@ struct RowsGeo {
 #else
 #define DAM_WSTAMP(tag) do { } while (0)
 #endif
-constexpr int RW_LOADERS = 8;                 // loader waves (waves 4..11)
-constexpr int RW_THREADS = 256 + 64 * RW_LOADERS, RW_GUARD = 64, RW_TAIL = 1280;   // (tail: the step-split last slot prefetches up to 1 KB past a row)
 // v % d for the two ring sizes (scalar multiply-shift, v < 30000)
 template <int D> __device__ __forceinline__ int rw_mod(int v) { return D == 10 ? v - ((v * 52429) >> 19) * 10 : v - ((v * 43691) >> 18) * 6; }
 
@@ -726,53 +689,6 @@ __global__ __launch_bounds__(256 + 64 * NL) void wgrad_rows_kernel(const RowsGeo
 
 #undef DAM_RW_ZERO
 
-template <int TNB, int TKB, int STEPS, int KP, int GPP, int HV = 1, int NL = 8>
-int launch_wgrad_rows(int B, int H, int W, int C, const float* X, const float* dY, const float* in_scale, const float* in_shift,
-                      int relu_in, float* partial, int64_t ws_floats, float* dw, int n_real, int k_real, void* queue,
-                      hipStream_t st) {
-    constexpr int NBLK = TNB * TKB * 9;
-    RowsGeo g;
-    g.B = B; g.H = H; g.W = W; g.C = C;
-    constexpr int RPS = 4 / HV, NRX = 2 * RPS + 2, NRD = 2 * RPS;
-    g.P4 = ((W + 2 + 4 * HV - 1) / (4 * HV)) * (4 * HV);
-    if (g.P4 != STEPS * 4 * HV) return DAM_ERR_UNSUPPORTED;
-    g.gpp = (g.P4 * 64 + 1023) / 1024;
-    if (g.gpp > GPP || (RPS * (TKB + TNB) + NL - 1) / NL > KP) return DAM_ERR_UNSUPPORTED;
-    const int nblk = C / 16;
-    if (nblk % TNB || nblk % TKB || H >= 8000) return DAM_ERR_UNSUPPORTED;
-    const int tiles_n = nblk / TNB;
-    g.tiles_k = nblk / TKB;
-    const int nx = tiles_n * g.tiles_k;
-    const size_t rowb = (size_t)g.P4 * 64;
-    size_t lds = RW_GUARD + (size_t)TKB * NRX * rowb + (size_t)TNB * NRD * rowb + RW_TAIL;
-    if (lds < (size_t)NBLK * 1024) lds = (size_t)NBLK * 1024;
-    if (lds > 160 * 1024) return DAM_ERR_UNSUPPORTED;
-    // Strips: as many workgroups as the chip holds at once and no more (a strip that has to wait for a CU doubles the
-    // launch: 96 channels on 8 images gave 288 workgroups on 256 CUs, 63 us).  One workgroup per CU when whole strips per
-    // image fill >= 80 % of the CUs that way; otherwise size for two co-resident workgroups per CU (the register file
-    // holds two of these 8-wave workgroups, the narrow stages' rings leave the LDS for both): 432 workgroups, 50 us.
-    // Measured both ways: where one per CU already fills the chip, two cost 15 % (more slabs, shared pipe).
-    auto strips = [&](int per_cu) { const int w = 256 * per_cu / (nx * B); return w > 0 ? w : 1; };
-    int spi = strips(1);
-    if (nx * B * spi < 205 && lds * 2 <= 160 * 1024) spi = strips(2);
-    if (spi > (int)cdiv(H, RPS)) spi = (int)cdiv(H, RPS);
-    if (spi > H) spi = H;
-    for (;; --spi) {                              // (rows in spi nearly equal parts, see the kernel)
-        g.spi = spi;
-        g.rps = (int)cdiv(H, spi);
-        if ((int64_t)B * g.spi * nx * NBLK * 256 <= ws_floats || spi == 1) break;
-    }
-    const int nsplit = B * g.spi;
-    if ((int64_t)nsplit * nx * NBLK * 256 > ws_floats) return DAM_ERR_WORKSPACE;
-    if (!raise_lds_limit<&wgrad_rows_kernel<TNB, TKB, STEPS, KP, GPP, HV, NL>>(160 * 1024)) return DAM_ERR_LAUNCH;
-    wgrad_last_launch = WgradLaunchNote{WGRAD_FAM_ROWS, TNB, TKB, STEPS, KP, GPP, 0, HV, NL, 0, 0, nx, nsplit, g.spi, g.rps,
-                                        queue ? WGRAD_REDUCTION_QUEUED : WGRAD_REDUCED_NOW};
-    hipLaunchKernelGGL((wgrad_rows_kernel<TNB, TKB, STEPS, KP, GPP, HV, NL>), dim3(nx, nsplit), dim3((256 + 64 * NL)), lds, st, g, X, dY, in_scale,
-                       in_shift, relu_in, partial);
-    DAM_CHECK_LAUNCH();
-    return reduce_submit(queue, partial, dw, nsplit, nx, TNB, TKB, 3, 3, n_real, k_real, 3, 3, 1, g.tiles_k, st);
-}
-
 // ---------------------------------------------------------------------------------------------------------------------
 // Row-streaming variant for 3x3 / stride 2 / pad 1 (the first convolution of a down-sampling block,
 // models/model_resnet.py:18-21 of the reference): the same workgroup shape, rings, slabs and reduce kernel as
@@ -784,12 +700,6 @@ int launch_wgrad_rows(int B, int H, int W, int C, const float* X, const float* d
 //   * Output row r reads X rows 2r-1, 2r, 2r+1.  A slot of RPS output rows brings in the 2*RPS rows 2r, 2r+1 of its output
 //     rows (row 2*r_begin-1 comes with slot 0), so the X ring holds 2*RPS+1 rows in use + 2*RPS being written.
 //   * one 16-channel chunk of X per workgroup (TKB = 1): the ring of two chunks does not fit beside the dY ring.
-struct RowsS2Geo {
-    int B, H, W, C;          // X
-    int Ho, Wo, N;           // dY
-    int rps, spi;            // output rows per strip (multiple of the slot's rows), strips per image
-    int tiles_k;             // in-channel tiles (= chunks)
-};
 template <> __device__ __forceinline__ int rw_mod<18>(int v) { return v - ((v * 58255) >> 20) * 18; }     // v < 36000
 
 // HV as in wgrad_rows_kernel; GPPX / GPPD: 1 KB pieces per X row plane (both parities) / dY row plane; KP planes per loader wave
@@ -1027,49 +937,6 @@ __global__ __launch_bounds__(RW_THREADS) void wgrad_rows_s2_kernel(const RowsS2G
     for (int e = tid; e < NBLK * 64; e += RW_THREADS) out[e] = reinterpret_cast<const float4*>(red)[e];
 }
 
-template <int TNB, int STEPS, int KP, int GPPX, int GPPD, int HV>
-int launch_wgrad_rows_s2(int B, int H, int W, int C, int Ho, int Wo, int N, const float* X, const float* dY, float* partial,
-                         int64_t ws_floats, float* dw, int n_real, int k_real, void* queue, hipStream_t st) {
-    constexpr int NBLK = TNB * 9;
-    constexpr int RPS = 4 / HV, NRX = 4 * RPS + 2, NRD = 2 * RPS, P4 = STEPS * 4 * HV;
-    static_assert(NRX == 18 || NRX == 10, "ring sizes with a multiply-shift modulo");
-    static_assert((2 * RPS + RPS * TNB + RW_LOADERS - 1) / RW_LOADERS <= KP, "planes per loader wave");
-    static_assert(2 * P4 * 64 <= GPPX * 1024 && P4 * 64 <= GPPD * 1024, "pieces per plane");
-    if (Ho != (H - 1) / 2 + 1 || Wo != (W - 1) / 2 + 1) return DAM_ERR_UNSUPPORTED;
-    if (((Wo + 1 + 4 * HV - 1) / (4 * HV)) * (4 * HV) != P4) return DAM_ERR_UNSUPPORTED;
-    const int nblk = N / 16;
-    if (nblk % TNB || C % 16 || H >= 8000) return DAM_ERR_UNSUPPORTED;
-    if ((int64_t)H * W * C * 4 >= (1ll << 31) || (int64_t)Ho * Wo * N * 4 >= (1ll << 31)) return DAM_ERR_UNSUPPORTED;
-    RowsS2Geo g;
-    g.B = B; g.H = H; g.W = W; g.C = C; g.Ho = Ho; g.Wo = Wo; g.N = N;
-    const int tiles_n = nblk / TNB;
-    g.tiles_k = C / 16;
-    const int nx = tiles_n * g.tiles_k;
-    size_t lds = RW_GUARD + (size_t)NRX * 2 * P4 * 64 + (size_t)TNB * NRD * P4 * 64 + RW_TAIL;
-    if (lds < (size_t)NBLK * 1024) lds = (size_t)NBLK * 1024;
-    if (lds > 160 * 1024) return DAM_ERR_UNSUPPORTED;
-    // strips as in launch_wgrad_rows: fill the chip once
-    auto strips = [&](int per_cu) { const int w = 256 * per_cu / (nx * B); return w > 0 ? w : 1; };
-    int spi = strips(1);
-    if (nx * B * spi < 205 && lds * 2 <= 160 * 1024) spi = strips(2);
-    if (spi > (int)cdiv(Ho, RPS)) spi = (int)cdiv(Ho, RPS);
-    if (spi > Ho) spi = Ho;
-    for (;; --spi) {                              // (rows in spi nearly equal parts, see the kernel)
-        g.spi = spi;
-        g.rps = (int)cdiv(Ho, spi);
-        if ((int64_t)B * g.spi * nx * NBLK * 256 <= ws_floats || spi == 1) break;
-    }
-    const int nsplit = B * g.spi;
-    if ((int64_t)nsplit * nx * NBLK * 256 > ws_floats) return DAM_ERR_WORKSPACE;
-    if (!raise_lds_limit<&wgrad_rows_s2_kernel<TNB, STEPS, KP, GPPX, GPPD, HV>>(160 * 1024)) return DAM_ERR_LAUNCH;
-    wgrad_last_launch = WgradLaunchNote{WGRAD_FAM_ROWS_S2, TNB, 1, STEPS, KP, GPPX, GPPD, HV, RW_LOADERS, 0, 0, nx, nsplit, g.spi, g.rps,
-                                        queue ? WGRAD_REDUCTION_QUEUED : WGRAD_REDUCED_NOW};
-    hipLaunchKernelGGL((wgrad_rows_s2_kernel<TNB, STEPS, KP, GPPX, GPPD, HV>), dim3(nx, nsplit), dim3(RW_THREADS), lds, st, g, X, dY,
-                       partial);
-    DAM_CHECK_LAUNCH();
-    return reduce_submit(queue, partial, dw, nsplit, nx, TNB, 1, 3, 3, n_real, k_real, 3, 3, 1, g.tiles_k, st);
-}
-
 // ---------------------------------------------------------------------------------------------------------------------
 // Direct variant: nothing goes through LDS.  dW[n][k][a][b] = sum over output pixels of dY[p][n] * X[s*p + tap][k]; a
 // wave walks whole output rows, lane = (pixel 4t + kq, channel j), both MFMA operands are buffer loads (dword per lane,
@@ -1180,7 +1047,77 @@ __global__ __launch_bounds__(256) void wgrad_direct_batch_kernel(const DirectJob
                                         li % j.nx, li / j.nx, j.nx, j.nsplit);
 }
 
-template <int TNB, int TKB, int KH, int KW>
+// ---------------------------------------------------------------------------------------------------------------------
+// Launch from the plan (dam_wgrad_plan.h).  Nothing is decided here: a launcher holds the table from the note's template parameters
+// to the instantiation -- generated from the plan header's instantiation lists, so a kernel exists exactly for the rows of those
+// lists --, the LDS limit, the queue logic, the launch and the slab reduction.
+
+// f(integral_constant<int, I>) for the row I of an N-row instantiation list that `match` picks; DAM_ERR_LAUNCH: the note names none
+template <int N, int I = 0, class Match, class F>
+int with_inst(Match match, F f) {
+    if constexpr (I == N) return DAM_ERR_LAUNCH;
+    else return match(I) ? f(std::integral_constant<int, I>()) : with_inst<N, I + 1>(match, f);
+}
+bool same_inst(const WgradLaunchNote& a, const WgradLaunchNote& b) { return a.TNB == b.TNB && a.TKB == b.TKB && a.TA == b.TA && a.TB == b.TB; }
+
+// The one write of the record: where a launcher has passed its last refusal, before it launches (or records the launch).
+void commit(const WgradPlan& p) { wgrad_last_launch = p.note; }
+
+int launch_rows(const WgradPlan& p, const WgradOperands& a, void* queue, hipStream_t st) {
+    const WgradLaunchNote& n = p.note;
+    auto match = [&](int i) {
+        const RowsInst& t = ROWS_INST[i];
+        return n.TNB == t.TNB && n.TKB == t.TKB && n.STEPS == t.STEPS && n.KP == t.KP && n.GPP == t.GPP && n.HV == t.HV && n.NL == t.NL;
+    };
+    return with_inst<ROWS_INST_N>(match, [&](auto I) -> int {
+        constexpr RowsInst t = ROWS_INST[I];
+        if (!raise_lds_limit<&wgrad_rows_kernel<t.TNB, t.TKB, t.STEPS, t.KP, t.GPP, t.HV, t.NL>>(160 * 1024)) return DAM_ERR_LAUNCH;
+        commit(p);
+        hipLaunchKernelGGL((wgrad_rows_kernel<t.TNB, t.TKB, t.STEPS, t.KP, t.GPP, t.HV, t.NL>), dim3(p.nx, p.nsplit), dim3(256 + 64 * t.NL),
+                           p.lds, st, p.rows, a.x, a.dy, a.in_scale, a.in_shift, p.relu_in, a.workspace);
+        DAM_CHECK_LAUNCH();
+        return reduce_submit(queue, a.workspace, a.dw, p.nsplit, p.nx, p.red, st);
+    });
+}
+
+int launch_rows_s2(const WgradPlan& p, const WgradOperands& a, void* queue, hipStream_t st) {
+    const WgradLaunchNote& n = p.note;
+    auto match = [&](int i) {
+        const RowsS2Inst& t = ROWS_S2_INST[i];
+        return n.TNB == t.TNB && n.STEPS == t.STEPS && n.KP == t.KP && n.GPP == t.GPPX && n.GPPD == t.GPPD && n.HV == t.HV;
+    };
+    return with_inst<ROWS_S2_INST_N>(match, [&](auto I) -> int {
+        constexpr RowsS2Inst t = ROWS_S2_INST[I];
+        constexpr int RPS = 4 / t.HV, NRX = 4 * RPS + 2, P4 = t.STEPS * 4 * t.HV;
+        static_assert(NRX == 18 || NRX == 10, "ring sizes with a multiply-shift modulo");
+        static_assert((2 * RPS + RPS * t.TNB + RW_LOADERS - 1) / RW_LOADERS <= t.KP, "planes per loader wave");
+        static_assert(2 * P4 * 64 <= t.GPPX * 1024 && P4 * 64 <= t.GPPD * 1024, "pieces per plane");
+        if (!raise_lds_limit<&wgrad_rows_s2_kernel<t.TNB, t.STEPS, t.KP, t.GPPX, t.GPPD, t.HV>>(160 * 1024)) return DAM_ERR_LAUNCH;
+        commit(p);
+        hipLaunchKernelGGL((wgrad_rows_s2_kernel<t.TNB, t.STEPS, t.KP, t.GPPX, t.GPPD, t.HV>), dim3(p.nx, p.nsplit), dim3(RW_THREADS), p.lds,
+                           st, p.rows_s2, a.x, a.dy, a.workspace);
+        DAM_CHECK_LAUNCH();
+        return reduce_submit(queue, a.workspace, a.dw, p.nsplit, p.nx, p.red, st);
+    });
+}
+
+// The direct kernel of the note's instantiation: job j alone on its own (nx, nsplit) grid, or (batch given) the batch's flat grid.
+int launch_direct_kernel(const WgradLaunchNote& n, const DirectJob& j, const DirectJobs* batch, int total, hipStream_t st) {
+    auto match = [&](int i) { return n.TNB == DIRECT_INST[i].TNB && n.TKB == DIRECT_INST[i].TKB && n.TA == DIRECT_INST[i].K && n.TB == n.TA; };
+    return with_inst<DIRECT_INST_N>(match, [&](auto I) -> int {
+        constexpr DirectInst t = DIRECT_INST[I];
+        if (batch) {
+            hipLaunchKernelGGL((wgrad_direct_batch_kernel<t.TNB, t.TKB, t.K, t.K>), dim3(total), dim3(256), 0, st, *batch);
+        } else {
+            hipLaunchKernelGGL((wgrad_direct_kernel<t.TNB, t.TKB, t.K, t.K>), dim3(j.nx, j.nsplit), dim3(256), 0, st, j.X, j.dY, j.rows, j.Ho,
+                               j.Wo, j.H, j.W, j.C, j.N, j.s, j.pad, j.dil, j.tiles_k, j.partial);
+        }
+        DAM_CHECK_LAUNCH();
+        return DAM_OK;
+    });
+}
+
+// The recorded direct launches of a queue, as one launch (and nothing pending afterwards, whatever the outcome).
 int launch_pending_direct(WgradQueue* q, hipStream_t st) {
     PendingDirect& p = q->pend_direct;
     const int n = p.jobs.njobs;
@@ -1202,109 +1139,63 @@ int launch_pending_direct(WgradQueue* q, hipStream_t st) {
     }
     DirectJobs jobs = p.jobs;
     jobs.njobs = n;
-    hipLaunchKernelGGL((wgrad_direct_batch_kernel<TNB, TKB, KH, KW>), dim3(total), dim3(256), 0, st, jobs);
-    DAM_CHECK_LAUNCH();
-    for (int i = 0; i < n; ++i) {
+    int rc = launch_direct_kernel(p.note, jobs.job[0], &jobs, total, st);
+    for (int i = 0; i < n && rc == DAM_OK; ++i) {
         const DirectJob& j = jobs.job[i];
-        const int rc = reduce_submit(q, j.partial, p.dw[i], j.nsplit, j.nx, TNB, TKB, KH, KW, p.n_real[i], p.k_real[i], KH, KW, 1,
-                                     j.tiles_k, st);
-        if (rc != DAM_OK) return rc;
+        rc = reduce_submit(q, j.partial, p.dw[i], j.nsplit, j.nx, p.red[i], st);
     }
-    return DAM_OK;
+    return rc;
 }
 
-template <int TNB, int TKB, int KH, int KW>
-int launch_wgrad_direct(int B, int H, int W, int C, int Ho, int Wo, int N, int s, int pad, int dil, const float* X,
-                        const float* dY, float* partial, int64_t ws_floats, float* dw, int n_real, int k_real, void* queue,
-                        hipStream_t st) {
-    constexpr int NBLK = TNB * TKB * KH * KW;
-    const int nblk = N / 16, nch = C / 16;
-    if (nblk % TNB || nch % TKB) return DAM_ERR_UNSUPPORTED;
-    if ((int64_t)B * H * W * C * 4 >= (1ll << 31) || (int64_t)B * Ho * Wo * N * 4 >= (1ll << 31)) return DAM_ERR_UNSUPPORTED;
-    const int tiles_n = nblk / TNB, tiles_k = nch / TKB, nx = tiles_n * tiles_k;
-    const int rows = B * Ho;
-    int nsplit = (int)cdiv(KH * KW == 1 ? 1024 : 768, nx);      // 3-4 workgroups per CU: the kernel lives on loads in flight
-    if (nsplit > (int)cdiv(rows, 4)) nsplit = (int)cdiv(rows, 4);
-    while (nsplit > 1 && (int64_t)nsplit * nx * NBLK * 256 > ws_floats) --nsplit;
-    if ((int64_t)nsplit * nx * NBLK * 256 > ws_floats) return DAM_ERR_WORKSPACE;
+int launch_direct(const WgradPlan& p, const WgradOperands& a, void* queue, hipStream_t st) {
     WgradQueue* q = static_cast<WgradQueue*>(queue);
     if (q && q->magic != WGRAD_QUEUE_MAGIC) return DAM_ERR_BAD_ARG;
-    if (q && q->batching) {
+    DirectJob j = p.direct;
+    j.X = a.x; j.dY = a.dy; j.partial = a.workspace;
+    if (p.note.issued == WGRAD_LAUNCH_RECORDED) {
         // record instead of launching: launches of this instantiation wait for each other until the queue is flushed (the caller
         // keeps X, dY and the slabs valid until then: the batching contract of include/dam_hip.h)
-        PendingDirect& p = q->pend_direct;
-        constexpr int sig = TNB | TKB << 4 | KH << 8 | KW << 12;
-        if (p.jobs.njobs > 0 && (p.sig != sig || p.jobs.njobs == WD_MAX_JOBS)) {
-            const int rc = p.launch(q, st);
+        PendingDirect& pd = q->pend_direct;
+        if (pd.jobs.njobs > 0 && (!same_inst(pd.note, p.note) || pd.jobs.njobs == WD_MAX_JOBS)) {
+            const int rc = launch_pending_direct(q, st);
             if (rc != DAM_OK) return rc;
         }
-        const int i = p.jobs.njobs++;
-        p.sig = sig; p.launch = &launch_pending_direct<TNB, TKB, KH, KW>;
-        DirectJob& j = p.jobs.job[i];
-        j.X = X; j.dY = dY; j.partial = partial; j.rows = rows; j.Ho = Ho; j.Wo = Wo; j.H = H; j.W = W; j.C = C; j.N = N; j.s = s;
-        j.pad = pad; j.dil = dil; j.tiles_k = tiles_k; j.nx = nx; j.nsplit = nsplit; j.wg0 = 0;
-        p.dw[i] = dw; p.n_real[i] = n_real; p.k_real[i] = k_real;
-        wgrad_last_launch = WgradLaunchNote{WGRAD_FAM_DIRECT, TNB, TKB, 0, 0, 0, 0, 0, 0, KH, KW, nx, nsplit, 0, 0, WGRAD_LAUNCH_RECORDED};
+        const int i = pd.jobs.njobs++;
+        pd.note = p.note; pd.jobs.job[i] = j; pd.dw[i] = a.dw; pd.red[i] = p.red;
+        commit(p);
         return DAM_OK;
     }
-    wgrad_last_launch = WgradLaunchNote{WGRAD_FAM_DIRECT, TNB, TKB, 0, 0, 0, 0, 0, 0, KH, KW, nx, nsplit, 0, 0,
-                                        queue ? WGRAD_REDUCTION_QUEUED : WGRAD_REDUCED_NOW};
-    hipLaunchKernelGGL((wgrad_direct_kernel<TNB, TKB, KH, KW>), dim3(nx, nsplit), dim3(256), 0, st, X, dY, rows, Ho, Wo, H, W, C,
-                       N, s, pad, dil, tiles_k, partial);
-    DAM_CHECK_LAUNCH();
-    return reduce_submit(queue, partial, dw, nsplit, nx, TNB, TKB, KH, KW, n_real, k_real, KH, KW, 1, tiles_k, st);
+    commit(p);
+    const int rc = launch_direct_kernel(p.note, j, nullptr, 0, st);
+    return rc != DAM_OK ? rc : reduce_submit(queue, a.workspace, a.dw, p.nsplit, p.nx, p.red, st);
 }
 
+bool tile_inst_is(const WgradLaunchNote& n, int i) {
+    return n.TNB == TILE_INST[i].TNB && n.TKB == TILE_INST[i].TKB && n.TA == TILE_INST[i].TA && n.TB == TILE_INST[i].TB;
+}
+// The LDS limit of the note's instantiation, raised where the launch needs more than the default.
+int tile_lds_ready(const WgradLaunchNote& n, size_t lds) {
+    return with_inst<TILE_INST_N>([&](int i) { return tile_inst_is(n, i); }, [&](auto I) -> int {
+        constexpr TileInst t = TILE_INST[I];
+        return lds <= 64 * 1024 || raise_lds_limit<&wgrad_kernel<t.TNB, t.TKB, t.TA, t.TB>>(160 * 1024) ? DAM_OK : DAM_ERR_LAUNCH;
+    });
+}
 // One launch of the tile kernel for `njobs` weight gradients of geometry g (blockIdx.z = job), then their slab reductions.
-template <int TNB, int TKB, int TA, int TB>
-int launch_wgrad_jobs(WgradGeo g, const WgradJobs& jobs, int njobs, int64_t ws_floats, float* const* dw, const int* n_real,
-                      const int* k_real, void* queue, hipStream_t st, bool note = false) {
-    constexpr int NBLK = TNB * TKB * TA * TB;
+int launch_tile_jobs(const WgradLaunchNote& n, const WgradGeo& g, size_t lds, const WgradJobs& jobs, int njobs, float* const* dw,
+                     const WgradReduce* red, void* queue, hipStream_t st) {
     const int nx = g.tiles_n * g.tiles_k * g.tap_groups;
-    size_t lds = (size_t)TKB * g.PR * g.PWT * 64 + (size_t)TNB * g.TMW * 64;
-    auto split_for = [&](int64_t slots, double fixed) {
-        // Pixel split by MAKESPAN: every CU works through ceil(workgroups / slots) workgroups of ceil(total_tiles / nsplit) tiles
-        // each (co-resident workgroups share the matrix pipe, so it is the count per CU that matters).  The first rule -- at least
-        // 512 workgroups -- gave the 9x9 / 64 -> 128 layer of the scalar models 72 x 8 = 576 workgroups of 40 tiles: a third round
-        // for a quarter of the chip (1.64 ms); 72 x 7 = 504 of 46 tiles is two rounds.  Batched jobs multiply the workgroups, not the
-        // tiles of one: three jobs need a third of the splits -- and slabs.
-        int ns_best = 1;
-        double best = 1e300;
-        // (up to 512 splits: a layer with ONE channel tile -- the scalar models' 4 -> 16 first convolution -- had 63 workgroups on
-        // 256 CUs under the former cap of 64: 170 us for 0.15 GFLOP)
-        const int hi = g.total_tiles < 512 ? g.total_tiles : 512;
-        for (int ns = 1; ns <= hi; ++ns) {
-            const int64_t wgs = (int64_t)nx * ns * njobs;
-            if ((int64_t)nx * ns * NBLK * 256 > ws_floats && ns > 1) break;
-            const double cost = (double)cdiv(wgs, slots) * ((double)cdiv(g.total_tiles, ns) + fixed);   // + fixed: per-workgroup part
-            if (cost < best * 0.999) { best = cost; ns_best = ns; }
-        }
-        return ns_best;
-    };
-    // slots: two workgroups per CU where the LDS holds two (the small-patch layers: their staging phases overlap each
-    // other -- 256 workgroups of two tiles measured slower than 512 of one on the 33 x 5 stage), one otherwise
-    if (lds < (size_t)NBLK * 1024) lds = (size_t)NBLK * 1024;
-    int nsplit = split_for(lds * 2 <= 160 * 1024 ? 512 : 256, 1.0);
-    while (nsplit > 1 && (int64_t)nsplit * nx * NBLK * 256 > ws_floats) --nsplit;
-    if ((int64_t)nsplit * nx * NBLK * 256 > ws_floats) return DAM_ERR_WORKSPACE;
-    g.nsplit = nsplit;
-    if (lds > 160 * 1024) return DAM_ERR_UNSUPPORTED;
-    if (lds > 64 * 1024 && !raise_lds_limit<&wgrad_kernel<TNB, TKB, TA, TB>>(160 * 1024)) return DAM_ERR_LAUNCH;
-    if (note)                                // (not for the recorded launches of a flush: the record belongs to the last CALL)
-        wgrad_last_launch = WgradLaunchNote{WGRAD_FAM_TILE, TNB, TKB, 0, 0, 0, 0, 0, 0, TA, TB, nx, nsplit, g.TMW, 0,
-                                            queue ? WGRAD_REDUCTION_QUEUED : WGRAD_REDUCED_NOW};
-    hipLaunchKernelGGL((wgrad_kernel<TNB, TKB, TA, TB>), dim3(nx, nsplit, njobs), dim3(256), lds, st, g, jobs);
-    DAM_CHECK_LAUNCH();
-    for (int i = 0; i < njobs; ++i) {
-        const int rc = reduce_submit(queue, jobs.partial[i], dw[i], g.nsplit, nx, TNB, TKB, TA, TB, n_real[i], k_real[i], g.KH, g.KW,
-                                     g.tap_groups, g.tiles_k, st);
-        if (rc != DAM_OK) return rc;
-    }
-    return DAM_OK;
+    int rc = with_inst<TILE_INST_N>([&](int i) { return tile_inst_is(n, i); }, [&](auto I) -> int {
+        constexpr TileInst t = TILE_INST[I];
+        hipLaunchKernelGGL((wgrad_kernel<t.TNB, t.TKB, t.TA, t.TB>), dim3(nx, g.nsplit, njobs), dim3(256), lds, st, g, jobs);
+        DAM_CHECK_LAUNCH();
+        return DAM_OK;
+    });
+    for (int i = 0; i < njobs && rc == DAM_OK; ++i) rc = reduce_submit(queue, jobs.partial[i], dw[i], g.nsplit, nx, red[i], st);
+    return rc;
 }
 
-// The recorded tile launches of a queue, as one launch (and nothing pending afterwards, whatever the outcome).
-template <int TNB, int TKB, int TA, int TB>
+// The recorded tile launches of a queue, as one launch (and nothing pending afterwards, whatever the outcome): the refusals a
+// recorded call had ahead of it -- pixel split for this number of jobs in the smallest workspace, LDS size, LDS limit -- are met here.
 int launch_pending_tile(WgradQueue* q, hipStream_t st) {
     PendingTile& p = q->pend;
     const int n = p.njobs;
@@ -1312,42 +1203,50 @@ int launch_pending_tile(WgradQueue* q, hipStream_t st) {
     if (n <= 0) return DAM_OK;
     int64_t ws = p.ws_floats[0];
     for (int i = 1; i < n; ++i) ws = p.ws_floats[i] < ws ? p.ws_floats[i] : ws;
-    return launch_wgrad_jobs<TNB, TKB, TA, TB>(p.g, p.jobs, n, ws, p.dw, p.n_real, p.k_real, q, st);
+    const int NBLK = p.note.TNB * p.note.TKB * p.note.TA * p.note.TB;
+    size_t lds = tile_lds(p.g, p.note.TNB, p.note.TKB);
+    if (lds < (size_t)NBLK * 1024) lds = (size_t)NBLK * 1024;
+    WgradGeo g = p.g;
+    g.nsplit = plan_tile_split(g, NBLK, lds, n, ws);
+    if (!g.nsplit) return DAM_ERR_WORKSPACE;
+    if (lds > 160 * 1024) return DAM_ERR_UNSUPPORTED;
+    const int rc = tile_lds_ready(p.note, lds);
+    return rc != DAM_OK ? rc : launch_tile_jobs(p.note, g, lds, p.jobs, n, p.dw, p.red, q, st);
 }
 
-template <int TNB, int TKB, int TA, int TB>
-int launch_wgrad(WgradGeo& g, const float* X, const float* dY, const float* sc, const float* sh, float* partial,
-                 int64_t ws_floats, float* dw, int n_real, int k_real, void* queue, hipStream_t st) {
-    g.tiles_n = (int)cdiv(g.nblk, TNB);
-    g.tiles_k = (int)cdiv(g.nchunks, TKB);
-    g.tap_groups = (int)cdiv(g.KH, TA);
-    g.nsplit = 0;
-    const int relu_in = g.relu_in;
-    g.relu_in = 0;                           // travels per job, not in the shared geometry
+int launch_tile(const WgradPlan& p, const WgradOperands& a, void* queue, hipStream_t st) {
     WgradQueue* q = static_cast<WgradQueue*>(queue);
     if (q && q->magic != WGRAD_QUEUE_MAGIC) return DAM_ERR_BAD_ARG;
-    if (q && q->batching) {
+    if (p.note.issued == WGRAD_LAUNCH_RECORDED) {
         // record instead of launching: jobs of the same instantiation and geometry wait for each other until the queue is
         // flushed (or another geometry arrives); the caller keeps X, dY, the affine and the slabs valid until then
-        PendingTile& p = q->pend;
-        constexpr int sig = TNB | TKB << 4 | TA << 8 | TB << 12;
-        if (p.njobs > 0 && (p.sig != sig || memcmp(&p.g, &g, sizeof(WgradGeo)) != 0 || p.njobs == WG_MAX_JOBS)) {
-            const int rc = p.launch(q, st);
+        PendingTile& pt = q->pend;
+        if (pt.njobs > 0 && (!same_inst(pt.note, p.note) || memcmp(&pt.g, &p.tile, sizeof(WgradGeo)) != 0 || pt.njobs == WG_MAX_JOBS)) {
+            const int rc = launch_pending_tile(q, st);
             if (rc != DAM_OK) return rc;
         }
-        const int i = p.njobs++;
-        p.sig = sig; p.g = g; p.launch = &launch_pending_tile<TNB, TKB, TA, TB>;
-        p.jobs.X[i] = X; p.jobs.dY[i] = dY; p.jobs.sc[i] = sc; p.jobs.sh[i] = sh; p.jobs.partial[i] = partial;
-        p.jobs.relu_in[i] = relu_in;
-        p.dw[i] = dw; p.ws_floats[i] = ws_floats; p.n_real[i] = n_real; p.k_real[i] = k_real;
-        wgrad_last_launch = WgradLaunchNote{WGRAD_FAM_TILE, TNB, TKB, 0, 0, 0, 0, 0, 0, TA, TB, g.tiles_n * g.tiles_k * g.tap_groups, 0,
-                                            g.TMW, 0, WGRAD_LAUNCH_RECORDED};
+        const int i = pt.njobs++;
+        pt.note = p.note; pt.g = p.tile;
+        pt.jobs.X[i] = a.x; pt.jobs.dY[i] = a.dy; pt.jobs.sc[i] = a.in_scale; pt.jobs.sh[i] = a.in_shift; pt.jobs.partial[i] = a.workspace;
+        pt.jobs.relu_in[i] = p.relu_in;
+        pt.dw[i] = a.dw; pt.ws_floats[i] = p.workspace_floats; pt.red[i] = p.red;
+        commit(p);
         return DAM_OK;
     }
+    const int rc = tile_lds_ready(p.note, p.lds);
+    if (rc != DAM_OK) return rc;
+    commit(p);
     WgradJobs jobs;
     memset(&jobs, 0, sizeof(jobs));
-    jobs.X[0] = X; jobs.dY[0] = dY; jobs.sc[0] = sc; jobs.sh[0] = sh; jobs.partial[0] = partial; jobs.relu_in[0] = relu_in;
-    return launch_wgrad_jobs<TNB, TKB, TA, TB>(g, jobs, 1, ws_floats, &dw, &n_real, &k_real, queue, st, true);
+    jobs.X[0] = a.x; jobs.dY[0] = a.dy; jobs.sc[0] = a.in_scale; jobs.sh[0] = a.in_shift; jobs.partial[0] = a.workspace;
+    jobs.relu_in[0] = p.relu_in;
+    return launch_tile_jobs(p.note, p.tile, p.lds, jobs, 1, &a.dw, &p.red, queue, st);
+}
+
+void note_to_ints(const WgradLaunchNote& n, int* out16) {
+    const int v[16] = {n.family, n.TNB, n.TKB, n.STEPS, n.KP, n.GPP, n.GPPD, n.HV, n.NL, n.TA, n.TB, n.nx, n.nsplit, n.spi_tmw, n.rps,
+                       n.issued};
+    for (int i = 0; i < 16; ++i) out16[i] = v[i];
 }
 
 }  // namespace
@@ -1381,23 +1280,14 @@ extern "C" int dam_wgrad_queue_pending(const void* queue) {
 extern "C" int dam_wgrad_queue_flush(void* queue, void* stream) {
     dam::WgradQueue* q = static_cast<dam::WgradQueue*>(queue);
     if (!q || q->magic != dam::WGRAD_QUEUE_MAGIC) return DAM_ERR_BAD_ARG;
-    if (q->pend.njobs > 0) {
-        const int rc = q->pend.launch(q, (hipStream_t)stream);
-        if (rc != DAM_OK) return rc;
-    }
-    if (q->pend_direct.jobs.njobs > 0) {
-        const int rc = q->pend_direct.launch(q, (hipStream_t)stream);
-        if (rc != DAM_OK) return rc;
-    }
-    return dam::reduce_flush(q->batch, (hipStream_t)stream);
+    int rc = dam::launch_pending_tile(q, (hipStream_t)stream);
+    if (rc == DAM_OK) rc = dam::launch_pending_direct(q, (hipStream_t)stream);
+    return rc != DAM_OK ? rc : dam::reduce_flush(q->batch, (hipStream_t)stream);
 }
 
 extern "C" int dam_wgrad_last_launch(int* out16_host) {
     if (!out16_host) return DAM_ERR_BAD_ARG;
-    const dam::WgradLaunchNote& n = dam::wgrad_last_launch;
-    const int v[16] = {n.family, n.TNB, n.TKB, n.STEPS, n.KP, n.GPP, n.GPPD, n.HV, n.NL, n.TA, n.TB, n.nx, n.nsplit, n.spi_tmw, n.rps,
-                       n.issued};
-    for (int i = 0; i < 16; ++i) out16_host[i] = v[i];
+    dam::note_to_ints(dam::wgrad_last_launch, out16_host);
     return DAM_OK;
 }
 
@@ -1409,119 +1299,39 @@ extern "C" int64_t dam_conv2d_wgrad_workspace_floats(int n_out, int c_in, int kh
     return a;
 }
 
+extern "C" int dam_conv2d_wgrad_plan(int B, int H, int W, int C, int in_nchw, int relu_in, int Ho, int Wo, int n_chan, int n_out, int kh,
+                                     int kw, int stride, int pad, int dil, int c_real, int has_affine, int has_shift, int queue_mode,
+                                     int64_t workspace_floats, int* out16_host) {
+    using namespace dam;
+    if (!out16_host) return DAM_ERR_BAD_ARG;
+    WgradPlan plan{};
+    const WgradRequest rq{B, H, W, C, in_nchw, relu_in, Ho, Wo, n_chan, n_out, kh, kw, stride, pad, dil, c_real, has_affine != 0,
+                          has_shift != 0, workspace_floats, queue_mode};
+    const int rc = queue_mode < 0 || queue_mode > 2 ? DAM_ERR_BAD_ARG : plan_wgrad(rq, plan);
+    note_to_ints(plan.note, out16_host);     // (all zero on any refusal)
+    return rc;
+}
+
 extern "C" int dam_conv2d_wgrad_f32(const float* x, int B, int H, int W, int C, int in_nchw, const float* in_scale,
                                     const float* in_shift, int relu_in, const float* dy, int Ho, int Wo, int n_chan,
                                     int n_out, int kh, int kw, int stride, int pad, int dil, float* dw, int c_real,
                                     float* workspace, int64_t workspace_floats, void* reduce_queue, void* stream) {
     using namespace dam;
     wgrad_last_launch = WgradLaunchNote{};
-    if (!x || !dy || !dw || !workspace || B <= 0 || H <= 0 || W <= 0 || C <= 0 || Ho <= 0 || Wo <= 0) return DAM_ERR_BAD_ARG;
-    if (c_real < 0 || c_real > C) return DAM_ERR_BAD_ARG;
-    const int k_real = c_real ? c_real : C;         // dw rows kept: the real input channels (the stem's zero-padded planes drop out)
-    if (n_chan % 16 || n_out > n_chan || (stride != 1 && stride != 2)) return DAM_ERR_UNSUPPORTED;
-    if (in_nchw ? C > 16 : C % 16) return DAM_ERR_UNSUPPORTED;
-    if (in_scale && !in_shift) return DAM_ERR_BAD_ARG;
-    if (in_nchw && in_scale) return DAM_ERR_UNSUPPORTED;        // the NCHW loader (stage_patch) applies no affine: the first layer reads raw features
+    if (!x || !dy || !dw || !workspace) return DAM_ERR_BAD_ARG;
+    // (a queue that is none -- wrong magic -- plans as one without batching and is refused by the launcher)
+    const WgradQueue* q = static_cast<const WgradQueue*>(reduce_queue);
+    const WgradRequest rq{B, H, W, C, in_nchw, relu_in, Ho, Wo, n_chan, n_out, kh, kw, stride, pad, dil, c_real, in_scale != nullptr,
+                          in_shift != nullptr, workspace_floats, !q ? 0 : q->magic == WGRAD_QUEUE_MAGIC && q->batching ? 2 : 1};
+    WgradPlan plan;
+    const int rc = plan_wgrad(rq, plan);
+    if (rc != DAM_OK) return rc;
+    const WgradOperands a{x, dy, in_scale, in_shift, workspace, dw};
     hipStream_t st = (hipStream_t)stream;
-    if (kh == 3 && kw == 3 && stride == 1 && pad == 1 && dil == 1 && !in_nchw && Ho == H && Wo == W && C == n_chan) {
-        // row-streaming kernel for the shapes of the ResNet stages; anything else takes the tile kernel below
-        int rc = DAM_ERR_UNSUPPORTED;
-#define DAM_WGR(...) launch_wgrad_rows<__VA_ARGS__>(B, H, W, C, x, dy, in_scale, in_shift, relu_in, workspace, workspace_floats, dw, n_out, k_real, reduce_queue, st)
-        // <TN, TK, steps, planes per loader wave, pieces per plane, row parts>: the shapes of the ResNet stages at 130 frames
-        // (3 s clips) and at the reference's native 216 frames
-        // (the last parameter, loader waves: four measured 53.7 -> 48.5 us on the 129x17 stage, where two workgroups then share a
-        // CU; no difference on the three wide stages -- 56.6 / 57.5 / 59.5 against 57.0 / 57.0 / 59.2 us -- and 31.8 -> 32.7 on 65x9)
-        if (C == 16) { rc = DAM_WGR(1, 1, 33, 1, 9); if (rc == DAM_ERR_UNSUPPORTED) rc = DAM_WGR(1, 1, 28, 1, 14, 2); }
-        else if (W > 80) rc = DAM_WGR(2, 1, 14, 1, 7, 2);
-        else if (W > 48) { rc = DAM_WGR(2, 1, 17, 2, 5); if (rc == DAM_ERR_UNSUPPORTED) rc = DAM_WGR(2, 1, 14, 2, 4); }
-        else if (W > 20) rc = DAM_WGR(2, 1, 9, 2, 3);
-        else if (W > 12) rc = DAM_WGR(2, 1, 5, 3, 2, 1, 4);   // 17-pixel rows (129x17 stage), four loader waves
-        else if (W > 6) rc = DAM_WGR(2, 1, 3, 2, 1);        // 9-pixel rows (65x9 stage): 40.8 -> 32.1 us; narrower: tile kernel
-#undef DAM_WGR
-        if (rc != DAM_ERR_UNSUPPORTED) return rc;
+    switch (plan.note.family) {
+        case WGRAD_FAM_ROWS: return launch_rows(plan, a, reduce_queue, st);
+        case WGRAD_FAM_ROWS_S2: return launch_rows_s2(plan, a, reduce_queue, st);
+        case WGRAD_FAM_DIRECT: return launch_direct(plan, a, reduce_queue, st);
+        default: return launch_tile(plan, a, reduce_queue, st);
     }
-#define DAM_WGD(TN_, TK_, KH_, KW_) \
-    launch_wgrad_direct<TN_, TK_, KH_, KW_>(B, H, W, C, Ho, Wo, n_chan, stride, pad, dil, x, dy, workspace, workspace_floats, dw, n_out, k_real, reduce_queue, st)
-    if (kh == 1 && kw == 1 && pad == 0 && !in_nchw && !in_scale) {
-        int rc = DAM_WGD(2, 2, 1, 1);
-        if (rc == DAM_ERR_UNSUPPORTED) rc = DAM_WGD(2, 1, 1, 1);
-        if (rc == DAM_ERR_UNSUPPORTED) rc = DAM_WGD(1, 1, 1, 1);
-        if (rc != DAM_ERR_UNSUPPORTED) return rc;
-    }
-    // strided 3x3 (the first convolution of a down-sampling block): measured 61/62/58 us against 80/78/67 us for the tile
-    // kernel; for stride-1 narrow rows (17 pixels, 96 channels) it is slower (117 vs 60 us: nine L2 reads per element)
-    if (kh == 3 && kw == 3 && !in_nchw && !in_scale && stride == 2 && pad == 1 && dil == 1) {
-        // <TN, steps, planes per loader wave, pieces per X plane, per dY plane, row parts>: the down-sampling convolutions of
-        // the ResNet stages at 130 frames (65-, 33- and 17-pixel output rows) and at the reference's native 216 (54, 27)
-#define DAM_WGR2(...) launch_wgrad_rows_s2<__VA_ARGS__>(B, H, W, C, Ho, Wo, n_chan, x, dy, workspace, workspace_floats, dw, n_out, k_real, reduce_queue, st)
-        int rc = DAM_ERR_UNSUPPORTED;
-        if (Wo > 56) rc = DAM_WGR2(2, 9, 1, 9, 5, 2);
-        else if (Wo > 34) rc = DAM_WGR2(2, 7, 1, 7, 4, 2);
-        else if (Wo > 28) rc = DAM_WGR2(2, 9, 2, 5, 3, 1);
-        else if (Wo > 18) rc = DAM_WGR2(2, 7, 2, 4, 2, 1);
-        else if (Wo > 14) rc = DAM_WGR2(2, 5, 2, 3, 2, 1);
-        // narrower rows stay on the tile kernel: slots of 3 / 2 MFMA steps are all barrier (measured 38.5 vs 38.9 us on the
-        // 65x9 stage, 31.6 vs 29.5 us on 33x5)
-#undef DAM_WGR2
-        if (rc != DAM_ERR_UNSUPPORTED) return rc;
-    }
-    if (kh == 3 && kw == 3 && !in_nchw && !in_scale && Wo >= 16 && stride == 2) {
-        int rc = DAM_WGD(2, 1, 3, 3);
-        if (rc == DAM_ERR_UNSUPPORTED) rc = DAM_WGD(1, 1, 3, 3);
-        if (rc != DAM_ERR_UNSUPPORTED) return rc;
-    }
-#undef DAM_WGD
-    WgradGeo g;
-    memset(&g, 0, sizeof(g));               // (compared bytewise when launches of one geometry are batched)
-    g.B = B; g.H = H; g.W = W; g.C = C; g.Ho = Ho; g.Wo = Wo; g.N = n_chan; g.s = stride; g.KH = kh; g.KW = kw;
-    g.off_h = -pad; g.step_h = dil; g.off_w = -pad; g.step_w = dil;
-    g.r0 = -pad; g.c0 = -pad;
-    g.PWin = (Wo - 1) * stride + (kw - 1) * dil + 1;
-    g.PWs = (int)cdiv(g.PWin, stride);
-    g.PWT = g.PWs * stride;
-    const int ta_rows = (kh == 3 && kw == 3) ? 3 : 1;               // TA of the instantiations below
-    auto set_tile = [&](int tmw_max) {
-        // pixels per tile: the image in equal parts of at most tmw_max pixels, rounded up to the 16 a step of the four waves takes
-        // (165 pixels of the 33 x 5 stage in a 256-pixel tile were 16 MFMA steps per wave for 10.3 of work: 176 -> 11)
-        const int64_t npix_ = (int64_t)Ho * Wo, parts_ = cdiv(npix_, tmw_max);
-        const int tmw = (int)(cdiv(cdiv(npix_, parts_), 16) * 16);
-        int rows_out = (tmw + Wo - 2) / Wo + 1;
-        if (rows_out > Ho) rows_out = Ho;
-        g.TMW = tmw;
-        g.PR = (rows_out - 1) * stride + (ta_rows - 1) * dil + 1;        // rows one tap group (TA kernel rows) touches
-        g.tiles_m = (int)cdiv((int64_t)Ho * Wo, tmw);
-        g.total_tiles = g.tiles_m * B;
-    };
-    auto lds_bytes = [&](int tnb, int tkb) { return (size_t)tkb * g.PR * g.PWT * 64 + (size_t)tnb * g.TMW * 64; };
-    g.nchunks = in_nchw ? 1 : C / 16;
-    g.nblk = n_chan / 16;
-    g.in_nchw = in_nchw; g.relu_in = relu_in;
-    // tile choice: 2x2 channel blocks when both sides have them and LDS allows two workgroups per CU.  48 OUTPUT channels (three blocks:
-    // the scalar models' 5x5 / 32 -> 48 layer) take a three-block tile on that side instead of two tiles of two with the fourth block
-    // empty (a quarter of the MFMAs on zeros): 167 -> 115 us.  The same on the INPUT side (7x7 / 48 -> 64
-    // as a 1x3 tile) measured 476 us against 463: 22 LDS reads per 21 MFMAs; a 2x3 tile needs 273 VGPRs.  Not instantiated.
-    int tnb = 2, tkb = 2;
-    if (kh == 5 && kw == 5 && g.nblk == 3 && g.nchunks % 2 == 0) { tnb = 3; tkb = 2; }
-    bool small = g.nchunks == 1 || g.nblk == 1;
-    set_tile(256);
-    if (!small && lds_bytes(tnb, tkb) > 72 * 1024) {
-        set_tile(128);
-        if (lds_bytes(tnb, tkb) > 72 * 1024) {
-            if (tnb == 2 && tkb == 2) small = true;
-            else { tnb = tkb = 2; set_tile(256); if (lds_bytes(2, 2) > 72 * 1024) { set_tile(128); if (lds_bytes(2, 2) > 72 * 1024) small = true; } }
-        }
-    }
-    if (small) {
-        set_tile(256);
-        if (lds_bytes(1, 1) > 72 * 1024) set_tile(128);
-    }
-#define DAM_WG(TN_, TK_, TA_, TB_) \
-    return launch_wgrad<TN_, TK_, TA_, TB_>(g, x, dy, in_scale, in_shift, workspace, workspace_floats, dw, n_out, k_real, reduce_queue, st)
-    if (kw == 3 && kh == 3) { if (small) DAM_WG(1, 1, 3, 3); else DAM_WG(2, 2, 3, 3); }
-    if (kw == 1 && kh == 1) { if (small) DAM_WG(1, 1, 1, 1); else DAM_WG(2, 2, 1, 1); }
-    if (kw == 5) { if (small) DAM_WG(1, 1, 1, 5); else if (tnb == 3) DAM_WG(3, 2, 1, 5); else DAM_WG(2, 2, 1, 5); }
-    if (kw == 7) { if (small) DAM_WG(1, 1, 1, 7); else DAM_WG(2, 2, 1, 7); }
-    if (kw == 9) { if (small) DAM_WG(1, 1, 1, 9); else DAM_WG(2, 2, 1, 9); }
-#undef DAM_WG
-    return DAM_ERR_UNSUPPORTED;
 }

@@ -437,6 +437,18 @@ def wgrad_flush(device=None):
             del q[2][:]
 
 
+def _wgrad_call(x_shape, dy_shape, n_out, kh, kw, in_nchw, c_real):
+    """-> (B, H, W, C, Ho, Wo, n_chan, c_real or C, workspace floats) of a weight-gradient call: the shape unpacking and the
+    workspace size conv2d_wgrad and conv2d_wgrad_plan share."""
+    if in_nchw:
+        B, C, H, W = x_shape
+    else:
+        B, H, W, C = x_shape
+    _, Ho, Wo, n_chan = dy_shape
+    floats = _lib.lib().dam_conv2d_wgrad_workspace_floats(n_out, C, kh, kw)
+    return B, H, W, C, Ho, Wo, n_chan, C if c_real is None else int(c_real), floats
+
+
 def conv2d_wgrad(x, dy, n_out, kh, kw, stride=1, pad=0, dil=1, in_scale=None, in_shift=None, relu_in=False,
                  in_nchw=False, out=None, c_real=None, defer=False):
     """dW in torch layout [n_out, c_real or C, kh, kw] from x (NHWC, or NCHW first layer) and dy NHWC [B,Ho,Wo,n16].
@@ -445,14 +457,8 @@ def conv2d_wgrad(x, dy, n_out, kh, kw, stride=1, pad=0, dil=1, in_scale=None, in
     one launch for every weight gradient of the backward pass (each deferred call keeps its own slab buffer until then)."""
     _lib.require_cuda(x, dy)
     _f32c(x, 'x'), _f32c(dy, 'dy')
-    if in_nchw:
-        B, C, H, W = x.shape
-    else:
-        B, H, W, C = x.shape
-    _, Ho, Wo, n_chan = dy.shape
+    B, H, W, C, Ho, Wo, n_chan, cr, floats = _wgrad_call(x.shape, dy.shape, n_out, kh, kw, in_nchw, c_real)
     L = _lib.lib()
-    floats = L.dam_conv2d_wgrad_workspace_floats(n_out, C, kh, kw)
-    cr = C if c_real is None else int(c_real)
     if out is None:
         if defer:
             raise ValueError('a deferred weight gradient needs the buffer it will be written to')
@@ -478,6 +484,13 @@ WGRAD_FAMILIES = ('none', 'rows', 'rows_s2', 'direct', 'tile')
 WgradLaunch = collections.namedtuple('WgradLaunch', 'family TNB TKB STEPS KP GPP GPPD HV NL TA TB nx nsplit spi rps TMW issued')
 
 
+def _wgrad_launch(v):
+    """The 16 ints of dam_wgrad_last_launch / dam_conv2d_wgrad_plan as a WgradLaunch."""
+    fam = WGRAD_FAMILIES[v[0]]
+    rows = fam in ('rows', 'rows_s2')
+    return WgradLaunch(fam, *v[1:13], v[13] if rows else 0, v[14] if rows else 0, v[13] if fam == 'tile' else 0, v[15])
+
+
 def wgrad_last_launch():
     """Which kernel the last conv2d_wgrad call of this thread committed to (dam_wgrad_last_launch): the family by name, the
     template parameters of the instantiation (rows_s2: GPP is GPPX; direct: TA, TB are KH, KW), the grid (nx, nsplit), strips per
@@ -486,9 +499,23 @@ def wgrad_last_launch():
     belong to the family are 0.  Host-side only."""
     v = (ctypes.c_int * 16)()
     _lib.check(_lib.lib().dam_wgrad_last_launch(v), 'dam_wgrad_last_launch')
-    fam = WGRAD_FAMILIES[v[0]]
-    rows = fam in ('rows', 'rows_s2')
-    return WgradLaunch(fam, *v[1:13], v[13] if rows else 0, v[14] if rows else 0, v[13] if fam == 'tile' else 0, v[15])
+    return _wgrad_launch(v)
+
+
+def conv2d_wgrad_plan(x_shape, dy_shape, n_out, kh, kw, stride=1, pad=0, dil=1, affine=False, relu_in=False, in_nchw=False,
+                      c_real=None, defer=False, workspace_floats=None):
+    """The WgradLaunch wgrad_last_launch() would report after conv2d_wgrad on tensors of these shapes, with in_scale and in_shift
+    given (affine) or not: host arithmetic in the library (dam_conv2d_wgrad_plan), no tensors, no GPU.  defer: the call goes to
+    this package's queue; workspace_floats: None for the workspace conv2d_wgrad passes.  Raises where the call would be refused
+    for its arguments or its workspace."""
+    B, H, W, C, Ho, Wo, n_chan, cr, floats = _wgrad_call(x_shape, dy_shape, n_out, kh, kw, in_nchw, c_real)
+    v = (ctypes.c_int * 16)()
+    _lib.check(_lib.lib().dam_conv2d_wgrad_plan(B, H, W, C, 1 if in_nchw else 0, 1 if relu_in else 0, Ho, Wo, n_chan, n_out, kh, kw,
+                                                stride, pad, dil, cr, 1 if affine else 0, 1 if affine else 0,
+                                                (2 if WGRAD_BATCH else 1) if defer else 0,
+                                                floats if workspace_floats is None else int(workspace_floats), v),
+               'dam_conv2d_wgrad_plan')
+    return _wgrad_launch(v)
 
 
 S2_ENTRIES = ('none', 'pair_fwd', 'dgrad_s2', 'pair_1x1')

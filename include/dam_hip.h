@@ -55,7 +55,7 @@ struct dam_bn_bwd_sums; /* defined in the BatchNorm section */
 /* Library / build identification ("gfx950").  DAM_ABI_VERSION is bumped whenever a signature below changes; a binding
  * compares dam_abi_version() of the library it loaded with the version it was written against and refuses a stale one
  * (deep-audio-mixer_amd/_lib.py: EXPECTED_ABI). */
-#define DAM_ABI_VERSION 31
+#define DAM_ABI_VERSION 32
 const char* dam_arch(void);
 int dam_abi_version(void);
 
@@ -414,7 +414,7 @@ int dam_wgrad_queue_set_batching(void* queue, int on);
 /* Which kernel the last dam_conv2d_wgrad_f32 call of the CALLING THREAD committed to (ABI 27): the entry point picks between four
  * kernel families with 29 instantiations by row width and channel counts and falls through to the tile kernel without
  * telling, so a test that means to exercise one instantiation asks here (as dam_conv_last_launch for the forward kernels).  A host
- * variable: reset to "none" at the entry of every call, written where the dispatcher has passed an instantiation's last refusal --
+ * variable: reset to "none" at the entry of every call, written from the call's plan where the launcher has passed its last refusal --
  * no device work, no kernel argument, nothing synchronised.  out16_host (host memory, 16 ints) receives
  *   [0] family: 0 none (no call yet, or the call failed before committing), 1 row-streaming kernel (3x3 / stride 1), 2 row-streaming
  *       kernel on column-parity planes (3x3 / stride 2), 3 direct kernel, 4 tile kernel
@@ -431,6 +431,14 @@ int dam_wgrad_queue_set_batching(void* queue, int on);
  *        tile launch has its LDS, workspace and LDS-limit refusals still ahead of it: they are returned by the call that runs it)
  * Fields foreign to the family are 0. */
 int dam_wgrad_last_launch(int* out16_host);
+/* The same answer BEFORE a call and without a GPU (ABI 32): the dispatch of dam_conv2d_wgrad_f32 is host arithmetic on its scalar
+ * arguments, on which optional operands are given (has_affine: in_scale, has_shift: in_shift) and on what the queue does with the
+ * launch (queue_mode: 0 no queue, 1 a queue without batching, 2 a batching queue).  out16_host receives the 16 ints
+ * dam_wgrad_last_launch would report after that call; returns the status the launching call would return for everything that
+ * needs no pointer and no device (DAM_ERR_BAD_ARG, DAM_ERR_UNSUPPORTED, DAM_ERR_WORKSPACE), with the 16 ints zero then. */
+int dam_conv2d_wgrad_plan(int B, int H, int W, int C, int in_nchw, int relu_in, int Ho, int Wo, int n_chan, int n_out, int kh, int kw,
+                          int stride, int pad, int dil, int c_real, int has_affine, int has_shift, int queue_mode,
+                          int64_t workspace_floats, int* out16_host);
 
 /* Diagnostic builds of the library only (libdam_hip_diag.so: dam_conv_strip.hip compiled with -DDAM_STRIP_DIAG_TAGS): the row-ring
  * convolution's loader waves tag every geometry-table entry with the tile it describes and its compute waves check the tag of every

@@ -6,6 +6,8 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import test_wgrad_kernels_gpu as wk
+
 pytestmark = pytest.mark.gpu
 TOL = 2e-5
 
@@ -139,10 +141,14 @@ def test_full_resolution_layer1(ops):
     close(ops.conv2d_wgrad(nhwc(x).cuda(), nhwc(dy).cuda(), 16, 3, 3, 1, 1, 1), want_dw, 1e-4)
 
 
-def wgrad_ran(ops, family, *inst):
+def wgrad_ran(ops, family, *inst, call=None):
     """The kernel the last conv2d_wgrad call committed to (ops.wgrad_last_launch()): rows <TNB, TKB, STEPS, HV, NL>,
-    rows_s2 <STEPS, HV>, direct <TNB, TKB, K>, tile <TNB, TKB, TA, TB>.  Every instantiation: tests/test_wgrad_kernels_gpu.py."""
+    rows_s2 <STEPS, HV>, direct <TNB, TKB, K>, tile <TNB, TKB, TA, TB>.  Every instantiation: tests/test_wgrad_kernels_gpu.py.
+    call = (x, dy, n_out, k, stride, pad, dil) of that call: its record is the plan of the same call (ops.conv2d_wgrad_plan)."""
     rec = ops.wgrad_last_launch()
+    if call is not None:
+        plan = wk.planned(ops, *call)
+        assert rec == plan, 'launched %s, planned %s' % (rec, plan)
     got = {'rows': (rec.TNB, rec.TKB, rec.STEPS, rec.HV, rec.NL), 'rows_s2': (rec.STEPS, rec.HV), 'direct': (rec.TNB, rec.TKB, rec.TA),
            'tile': (rec.TNB, rec.TKB, rec.TA, rec.TB)}.get(rec.family)
     assert (rec.family, got) == (family, inst) and rec.issued == 0, rec
@@ -168,13 +174,15 @@ def test_wgrad_row_streaming_shapes(ops, B, C, H, W):
     x = torch.randn(B, C, H, W, generator=g)
     dy = torch.randn(B, C, H, W, generator=g)
     want = torch.nn.grad.conv2d_weight(x.double(), (C, C, 3, 3), dy.double(), 1, 1)
-    got = ops.conv2d_wgrad(nhwc(x).cuda(), nhwc(dy).cuda(), C, 3, 3, 1, 1, 1)
+    xd, dyd = nhwc(x).cuda(), nhwc(dy).cuda()
+    got = ops.conv2d_wgrad(xd, dyd, C, 3, 3, 1, 1, 1)
+    call = (xd, dyd, C, 3, 1, 1, 1)
     inst = (ROW_KERNEL_16 if C == 16 else ROW_KERNEL_32).get(W)
     if inst:
-        wgrad_ran(ops, 'rows', *inst)
+        wgrad_ran(ops, 'rows', *inst, call=call)
     else:
         assert W in (213, 5), 'name the kernel that rows of %d pixels at %d channels take (ROW_KERNEL_16 / ROW_KERNEL_32)' % (W, C)
-        rec = wgrad_ran(ops, 'tile', *((1, 1, 3, 3) if C == 16 else (2, 2, 3, 3)))
+        rec = wgrad_ran(ops, 'tile', *((1, 1, 3, 3) if C == 16 else (2, 2, 3, 3)), call=call)
         assert rec.TMW == {213: 128, 5: 176}[W], rec
     assert got.shape == (C, C, 3, 3)
     close(got, want, 5e-5)
@@ -194,14 +202,16 @@ def test_wgrad_strided_row_streaming_shapes(ops, B, Ci, Co, H, W):
     Ho, Wo = (H - 1) // 2 + 1, (W - 1) // 2 + 1
     dy = torch.randn(B, Co, Ho, Wo, generator=g)
     want = torch.nn.grad.conv2d_weight(x.double(), (Co, Ci, 3, 3), dy.double(), 2, 1)
-    got = ops.conv2d_wgrad(nhwc(x).cuda(), nhwc(dy).cuda(), Co, 3, 3, 2, 1, 1)
+    xd, dyd = nhwc(x).cuda(), nhwc(dy).cuda()
+    got = ops.conv2d_wgrad(xd, dyd, Co, 3, 3, 2, 1, 1)
+    call = (xd, dyd, Co, 3, 2, 1, 1)
     if Wo < 15:
         # (33 output rows of 9 pixels: the patch of a two-block tile is past the tile kernel's 72 KB rule at either tile size)
-        wgrad_ran(ops, 'tile', *((1, 1, 3, 3) if (H, W) == (65, 17) else (2, 2, 3, 3)))
+        wgrad_ran(ops, 'tile', *((1, 1, 3, 3) if (H, W) == (65, 17) else (2, 2, 3, 3)), call=call)
     else:
         inst = {65: (9, 2), 33: (9, 1), 17: (5, 1), 54: (7, 2), 27: (7, 1)}.get(Wo)
         assert inst, 'name the stride-2 row instantiation (or other kernel) that output rows of %d pixels take' % Wo
-        wgrad_ran(ops, 'rows_s2', *inst)
+        wgrad_ran(ops, 'rows_s2', *inst, call=call)
     assert got.shape == (Co, Ci, 3, 3)
     close(got, want, 5e-5)
 
@@ -222,15 +232,17 @@ def test_wgrad_direct_kernel_shapes(ops, B, Ci, Co, H, W, k, s, p):
     Ho, Wo = (H + 2 * p - k) // s + 1, (W + 2 * p - k) // s + 1
     dy = torch.randn(B, Co, Ho, Wo, generator=g)
     want = torch.nn.grad.conv2d_weight(x.double(), (Co, Ci, k, k), dy.double(), s, p)
-    got = ops.conv2d_wgrad(nhwc(x).cuda(), nhwc(dy).cuda(), Co, k, k, s, p, 1)
+    xd, dyd = nhwc(x).cuda(), nhwc(dy).cuda()
+    got = ops.conv2d_wgrad(xd, dyd, Co, k, k, s, p, 1)
+    call = (xd, dyd, Co, k, s, p, 1)
     if s == 1:
-        wgrad_ran(ops, *(('rows', 2, 1, 5, 1, 4) if Ci == 96 else ('tile', 2, 2, 3, 3)))
+        wgrad_ran(ops, *(('rows', 2, 1, 5, 1, 4) if Ci == 96 else ('tile', 2, 2, 3, 3)), call=call)
     elif k == 3 and Wo in (33, 17):
-        wgrad_ran(ops, 'rows_s2', *{33: (9, 1), 17: (5, 1)}[Wo])
+        wgrad_ran(ops, 'rows_s2', *{33: (9, 1), 17: (5, 1)}[Wo], call=call)
     else:
         assert k == 1 or Wo in (108, 20, 23, 19), 'output rows of %d pixels: inside a stride-2 row window?' % Wo
         tn = 2 if Co // 16 % 2 == 0 else 1
-        wgrad_ran(ops, 'direct', tn, 2 if k == 1 and tn == 2 and Ci // 16 % 2 == 0 else 1, k)
+        wgrad_ran(ops, 'direct', tn, 2 if k == 1 and tn == 2 and Ci // 16 % 2 == 0 else 1, k, call=call)
     assert got.shape == (Co, Ci, k, k)
     close(got, want, 5e-5)
 

@@ -1,5 +1,6 @@
 """GPU: every instantiation of the convolution weight gradient (dam_wgrad.hip) against torch.nn.grad.conv2d_weight on the CPU in
-float64, each case asserting through ops.wgrad_last_launch() the kernel it names.
+float64, each case asserting through ops.wgrad_last_launch() the kernel it names and that
+the record equals the plan of the same call (ops.conv2d_wgrad_plan; tests/test_wgrad_plan_cpu.py plans the whole table on the CPU).
 
 dam_conv2d_wgrad_f32 picks between four kernel families -- wgrad_rows_kernel (3x3 / stride 1 / pad 1, equal channel counts),
 wgrad_rows_s2_kernel (3x3 / stride 2 / pad 1), wgrad_direct_kernel (1x1, and strided 3x3 outside the stride-2 row windows) and the
@@ -389,6 +390,15 @@ def _expected(c, form):
     return e
 
 
+def planned(ops, x, dy, n_out, k, s, p, d, defer=False, **kw):
+    """ops.conv2d_wgrad_plan of the conv2d_wgrad call just made on x and dy (before any flush), in the workspace that call was
+    given: ops' slab buffers only grow, so a call can be handed more floats than it asks for, and a pixel split may use them."""
+    dev = x.device
+    key = (dev.type, dev.index) + (('wgrad slabs', ops._wgrad_queue(dev)[1] - 1) if defer else ())
+    return ops.conv2d_wgrad_plan(tuple(x.shape), tuple(dy.shape), n_out, k, k, s, p, d, defer=defer,
+                                 workspace_floats=ops._workspaces[key].numel(), **kw)
+
+
 SEEN = {}           # (case id, form) -> WgradLaunch
 WORST = {}          # family -> (relative error, case id, form)
 
@@ -411,6 +421,9 @@ def _launch(ops, c, form, xd, dyd, scd, shd):
         with pytest.raises(RuntimeError, match='DAM_ERR_UNSUPPORTED'):
             ops.conv2d_wgrad(xd, dyd, n_out, c.k, c.k, c.s, c.p, c.d, **kw)
         rec = SEEN[(c.id, form)] = ops.wgrad_last_launch()
+        with pytest.raises(RuntimeError, match='DAM_ERR_UNSUPPORTED'):      # the plan of the same call: the same refusal
+            ops.conv2d_wgrad_plan(tuple(xd.shape), tuple(dyd.shape), n_out, c.k, c.k, c.s, c.p, c.d, affine=True, relu_in=form == 'relu',
+                                  in_nchw=True)
         want = _expected(c, form)
         assert {k: getattr(rec, k) for k in want} == want, '%s %s: recorded %s' % (c.id, form, rec)
         torch.cuda.synchronize()
@@ -418,6 +431,9 @@ def _launch(ops, c, form, xd, dyd, scd, shd):
         return None, None
     got = ops.conv2d_wgrad(xd, dyd, n_out, c.k, c.k, c.s, c.p, c.d, defer=form == 'defer', **kw)
     rec = ops.wgrad_last_launch()
+    plan = planned(ops, xd, dyd, n_out, c.k, c.s, c.p, c.d, defer=form == 'defer', affine=form in ('relu', 'affine'),
+                   relu_in=form == 'relu', in_nchw=c.nchw, c_real=c.c_real)
+    assert rec == plan, '%s %s: launched %s, planned %s' % (c.id, form, rec, plan)      # (defer: the recorded form)
     if form == 'defer':
         torch.cuda.synchronize()
         assert bool((buf == FILL).all()), '%s: written before the flush' % c.id
@@ -493,6 +509,7 @@ def test_direct_batched_jobs(ops):
         ops.conv2d_wgrad(jobs[-1][0], jobs[-1][1], co, 1, 1, 2, 0, 1, out=out, defer=True)
         rec = ops.wgrad_last_launch()
         assert {k: getattr(rec, k) for k in exp} == exp and rec.issued == 2, rec
+        assert rec == planned(ops, jobs[-1][0], jobs[-1][1], co, 1, 2, 0, 1, defer=True), rec
     ops.wgrad_flush()
     torch.cuda.synchronize()
     for i, (_, _, out, want) in enumerate(jobs):
