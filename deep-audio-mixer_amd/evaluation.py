@@ -37,8 +37,11 @@ stem by stem and window by window, relative to each window's mean over the stems
 fractional-octave band of the STFT (gainfit.fit_band_gains): 'oracle_band_gains' (the reference's EQ curve per stem),
 'oracle_band_residual_total' (what per-band gains still leave unexplained: its distance in dB from 'oracle_residual' is the
 headroom of a band-gain mixer over a gain-only one) and a '*_band_gain_error' beside every '*_gain_error' -- how far a
-variant's broadband gains sit from the band-wise optimum.
+variant's broadband gains sit from the band-wise optimum.  ``band_render=True`` makes that band-gain mixer audible: the fitted
+band gains rendered to audio (gainfit.render_band_gains), 'oracle_band_render_residual' -- what the render leaves of the
+reference, measured on the audio -- and, with ``write_wavs_to_disk``, ``{song}_oracle_band.wav`` beside the other variants.
 """
+import numbers
 import os
 from collections import OrderedDict
 from statistics import mean
@@ -168,6 +171,27 @@ class LoudnessEvaluator:
             ops.align_check_shapes((1, 1, 1), None, o['align'])
         return {'n_fft': n_fft, 'hop': hop, 'edges': edges, 'centres': centres, 'pool': pool, 'ridge': ridge, 'align': o['align']}
 
+    @staticmethod
+    def _band_render_args(band_render, band_fit):
+        """``band_render`` as the whole-song methods take it (False, True, or {'fill': 'broadband' | number}) -> None where it is
+        off, else the fill: 'broadband' or a float.  It renders what ``band_fit`` fits: ValueError without it."""
+        if not band_render:
+            return None
+        if not band_fit:
+            raise ValueError('band_render renders the gains band_fit fits: it needs band_fit')
+        given = {} if band_render is True else dict(band_render)
+        unknown = set(given) - {'fill'}
+        if unknown:
+            raise ValueError("band_render: unknown keys %s (expected 'fill')" % sorted(unknown))
+        fill = given.get('fill', 'broadband')
+        if isinstance(fill, str):
+            if fill != 'broadband':
+                raise ValueError("band_render: fill must be 'broadband' or a number, got %r" % fill)
+            return fill
+        if isinstance(fill, bool) or not isinstance(fill, numbers.Real):
+            raise ValueError("band_render: fill must be 'broadband' or a number, got %r" % (fill,))
+        return float(fill)
+
     def evaluate_spectrum_batch(self, stems, gains=None, **spectral):
         """Band powers of the stem sum (long-term average spectrum in fractional-octave bands at the evaluator's rate),
         measured as ``sum of stem * gain ramp`` where gains are given, without that sum being written.  stems as
@@ -218,7 +242,8 @@ class LoudnessEvaluator:
 
     def process_song_tracks(self, loaded_tracks: dict, reference_tracks: dict, song_name: str, n_random_samples: int = 5,
                             chunk_length: int = 2, write_wavs_to_disk=False, results_dir='./experiment',
-                            ceiling_dbtp=None, dynamics=False, limiter=None, spectral=False, gain_fit=False, band_fit=False) -> dict:
+                            ceiling_dbtp=None, dynamics=False, limiter=None, spectral=False, gain_fit=False, band_fit=False,
+                            band_render=False) -> dict:
         """evaluation.py:77-116 on stems already in memory ({name: ndarray [channels, n]} each): the loudness profile of
         ``reference_tracks`` against the profiles of ``loaded_tracks`` summed as they are ('sum_error'), normalised to the
         training set's mean loudness ('loudnorm_error'), mixed by the model ('mix_error') and scaled by random gains
@@ -261,7 +286,17 @@ class LoudnessEvaluator:
         'sum_band_gain_error', 'loudnorm_band_gain_error', 'mix_band_gain_error', 'random_band_gain_error': each variant's
         broadband gains against the band-wise optimum, the gain error over every (band, window) with the variant's curve
         repeated over the bands.  'align' is gain_fit's; where both ask for the same lag the stems are aligned once.  It needs
-        no gain_fit, changes no other key and comes to the host in the same copy.  The lengths must agree."""
+        no gain_fit, changes no other key and comes to the host in the same copy.  The lengths must agree.
+        band_render (True, or {'fill': 'broadband' | number}; needs band_fit, whose hop must then not exceed n_fft / 2): the
+        fitted band gains are rendered to audio on the band fit's stems (gainfit.render_band_gains) -- the best band-gain mix.
+        fill is the gain of the bins outside the bands and of the cells that were not fitted: 'broadband' (the default) takes the
+        broadband fit's gains (gainfit.fit_gains on the same stems with band_fit's pool and ridge; gain_fit's result where its
+        arguments are the same), a number that constant.  The stats gain, after the band_fit keys, 'oracle_band_render_residual'
+        [windows]: the share of the fit target's energy that (target - render) holds in every window, from the time-domain
+        moments of the two -- the time-domain counterpart of 'oracle_band_residual_total', in the same copy to the host.  With
+        write_wavs_to_disk the render goes to ``{song_name}_oracle_band.wav`` as the other variants do (-20 LUFS, the ceiling
+        and the limiter).  Off (the default), nothing changes."""
+        render_fill = self._band_render_args(band_render, band_fit)
         if self.d is None or self.mix_model is None or self.mean_loudness_model is None:
             raise ValueError('process_song needs the dataset, d_mean_loudness and mix_model constructor arguments')
         stems = [t for t in self.d.get_tracklist() if t != 'mix']
@@ -273,6 +308,9 @@ class LoudnessEvaluator:
             band = self._band_fit_args(band_fit)
             if np.asarray(reference_tracks[self.keys[0]]).shape[-1] != np.asarray(loaded_tracks[self.keys[0]]).shape[-1]:
                 raise ValueError('band_fit fits frame by frame: the reference mix and the stems differ in length')
+            if render_fill is not None and band['hop'] > band['n_fft'] // 2:
+                raise ValueError('band_render overlap-adds the frames: hop must not exceed n_fft / 2 (got %d for n_fft %d)'
+                                 % (band['hop'], band['n_fft']))
         if gain_fit:
             (fit_pool, fit_ridge), fit_align = self._gain_fit_args(gain_fit), self._gain_fit_align(gain_fit)
             if np.asarray(reference_tracks[self.keys[0]]).shape[-1] != np.asarray(loaded_tracks[self.keys[0]]).shape[-1]:
@@ -404,6 +442,19 @@ class LoudnessEvaluator:
                     cand.unsqueeze(2).expand(-1, -1, n_bands, -1).reshape(n_var, n_stems, n_bands * W))[0]
                 parts += [band_errors, band_gains.reshape(-1), band_residual.reshape(-1),
                           gainfit.band_residual_total(band_residual, band_target, band_status)]
+                if render_fill is not None:
+                    fill = render_fill
+                    if fill == 'broadband':
+                        if gain_fit and (fit_pool, fit_ridge, fit_align) == (band['pool'], band['ridge'], band['align']):
+                            fill = fitted
+                        else:
+                            fill = gainfit.fit_gains(band_stems, target, W, pool=band['pool'], ridge=band['ridge'])[0]
+                    rendered = gainfit.render_band_gains(band_stems, band_gains, n_fft=band['n_fft'], hop=band['hop'],
+                                                         edges=band['edges'], fill=fill)             # float32 [channels, n]
+                    # (target - render) against the target, window by window: the moments of the pair
+                    m = gainfit.moments(rendered.transpose(0, 1).unsqueeze(0), target, W)
+                    parts.append((m[:, 0, 0] - 2.0 * m[:, 0, 1] + m[:, 1, 1]) / m[:, 1, 1])
+                    write('oracle_band', rendered.unsqueeze(0))
             host = torch.cat(parts).cpu().tolist()
             at = 0
 
@@ -429,29 +480,34 @@ class LoudnessEvaluator:
                 stats['oracle_band_gains'] = {name: [per_band[b][i] for b in range(n_bands)] for i, name in enumerate(self.keys)}
                 stats['oracle_band_residual'] = [take(W) for _ in range(n_bands)]
                 stats['oracle_band_residual_total'] = take(W)
+                if render_fill is not None:
+                    stats['oracle_band_render_residual'] = take(W)
         return stats
 
     def process_song(self, base_dir: str, song_name: str, n_random_samples: int = 5, chunk_length: int = 2,
                      write_wavs_to_disk=False, results_dir='./experiment', ceiling_dbtp=None, dynamics=False, limiter=None,
-                     spectral=False, gain_fit=False, band_fit=False) -> dict:
+                     spectral=False, gain_fit=False, band_fit=False, band_render=False) -> dict:
         """evaluation.py:77-116: the reference mix from ``base_dir/manual_gain_mixes``, the stems from ``base_dir/test``."""
         from .data.dataset_utils import load_tracks_musdb18
+        self._band_render_args(band_render, band_fit)          # (before a file is read)
         reference_tracks = load_tracks_musdb18(os.path.join(base_dir, 'manual_gain_mixes'), song_name, tracklist=self.keys,
                                                sr=self.sr)
         loaded_tracks = load_tracks_musdb18(os.path.join(base_dir, 'test'), song_name, tracklist=self.keys, sr=self.sr)
         return self.process_song_tracks(loaded_tracks, reference_tracks, song_name, n_random_samples, chunk_length,
                                         write_wavs_to_disk, results_dir, ceiling_dbtp, dynamics, limiter, spectral,
                                         **({'gain_fit': gain_fit} if gain_fit else {}),
-                                        **({'band_fit': band_fit} if band_fit else {}))
+                                        **({'band_fit': band_fit} if band_fit else {}),
+                                        **({'band_render': band_render} if band_render else {}))
 
     def process_songlist(self, base_dir, songlist, n_random_samples: int = 5, chunk_length: int = 2,
                          write_wavs_to_disk=False, results_dir='./experiment', ceiling_dbtp=None, dynamics=False, limiter=None,
-                         spectral=False, gain_fit=False, band_fit=False):
+                         spectral=False, gain_fit=False, band_fit=False, band_render=False):
         """evaluation.py:118-144 without the spreadsheet: (rows, means) -- one stats dict per song and the mean of every
         error over the songs (the sheet's last row); with ``dynamics`` the four '*_st_error' keys too, with ``spectral``
         the four '*_spec_error' keys, with ``gain_fit`` the four '*_gain_error' keys (a song whose figure is NaN -- nothing
         to compare -- is left out of that mean; the mean is NaN if every song's is), with ``band_fit`` the four
-        '*_band_gain_error' keys in the same way."""
+        '*_band_gain_error' keys in the same way.  ``band_render`` is passed on to every song (its key is per window: no mean)."""
+        self._band_render_args(band_render, band_fit)
         keys = ['sum_error', 'random_error', 'loudnorm_error', 'mix_error']
         if dynamics:
             keys += ['sum_st_error', 'random_st_error', 'loudnorm_st_error', 'mix_st_error']
@@ -471,6 +527,8 @@ class LoudnessEvaluator:
                 extra['gain_fit'] = gain_fit
             if band_fit:
                 extra['band_fit'] = band_fit
+            if band_render:
+                extra['band_render'] = band_render
             rows.append(self.process_song(base_dir, song_name, n_random_samples, chunk_length, write_wavs_to_disk,
                                           results_dir, ceiling_dbtp, dynamics, **extra))
         means = {key: mean(row[key] for row in rows) for key in keys}

@@ -120,6 +120,42 @@ def band_residual_total(residual, target, status):
     return ops.gainfit_band_summary(residual, target, status)
 
 
+def render_band_gains(stems, band_gains, *, n_fft=4096, hop=None, edges, fill=1.0, out=None):
+    """The audio of per-band gains: stems as ``band_moments`` takes them; band_gains CUDA float64 [B, S, W], the layout
+    ``fit_band_gains`` returns; edges the host table the gains were fitted on; hop defaults to n_fft / 2 and must not exceed it.
+    -> CUDA float32 [channels, n]: every stem's STFT (frames and window those of the fit) scaled bin by bin with the gain of the
+    bin's band and the frame's window, summed over the stems, inverted and overlap-added (include/dam_hip.h: dam_bandmix_render)
+    in one fused pass -- no spectrum is written to memory.  fill: the gain of the bins outside every band and of the cells whose
+    fitted gain is NaN (a silent or unfitted stem): a number, or a CUDA float64 [S], [S, 1] or [S, W] tensor such as
+    ``fit_gains``' broadband gains; where that is NaN too the gain is 0.  Unit gains and unit fill give back the stems' sum;
+    a sample at least n_fft / 2 inside its window does not depend on the other windows' gains.  NOT the inverse of the fit:
+    band-wise constant gains are a filter the synthesis window truncates.  The workspace (the synthesised frames,
+    4 * channels * frames * n_fft bytes) comes from torch's caching allocator, which keeps it per device and size.  No host
+    synchronisation once the tables are resident; hipGraph-capturable then."""
+    if not torch.is_tensor(band_gains):
+        raise TypeError('render_band_gains: band_gains must be a tensor [bands, stems, windows]')
+    if torch.is_tensor(fill):
+        fill_shape = tuple(fill.shape)
+    elif isinstance(fill, (int, float)) and not isinstance(fill, bool):
+        fill_shape = ()
+    else:
+        raise TypeError('render_band_gains: fill must be a number or a tensor')
+    S, n, ch, B, W, n_fft, hop = ops.bandmix_check_shapes(tuple(stems.shape), tuple(band_gains.shape), fill_shape, n_fft, hop)
+    table = spectrum.check_edges(edges, n_fft)
+    if table.size - 1 != B:
+        raise ValueError('render_band_gains: %d bands of gains for a table of %d bands' % (B, table.size - 1))
+    ops._lib.require_cuda(stems, band_gains, fill if torch.is_tensor(fill) else None, out)
+    if torch.is_tensor(fill):
+        if fill.dtype != torch.float64:
+            raise TypeError('render_band_gains: a fill tensor must be float64')
+        fill = fill.reshape(S, -1).expand(S, W)
+    else:
+        fill = torch.full((S, W), float(fill), dtype=torch.float64, device=stems.device)
+    dev_edges = spectrum._device_edges(table, n_fft, stems.device)
+    win, tw = features._get_tables(stems.device, n_fft)
+    return ops.bandmix_render(stems, band_gains, fill, dev_edges, win, tw, n_fft, hop, out=out)
+
+
 def residual_db(residual):
     """The residual of ``solve`` (torch tensor, numpy array or number) in dB: 10 log10, -inf at 0; the same kind of array
     comes back."""

@@ -1488,6 +1488,91 @@ def gainfit_band_summary(residual, target, status, out=None):
     return out
 
 
+# ----------------------------------------------------------------------------- band-gain mixer
+def bandmix_check_shapes(stems_shape, gains_shape, fill_shape, n_fft, hop):
+    """The host-side argument rules of bandmix_render on shapes alone -> (S, n, channels, B, W, n_fft, hop); ValueError /
+    TypeError otherwise.  stems_shape [S, n, channels]; gains_shape [B, S, W]; fill_shape: () for a number, [S], [S, 1] or
+    [S, W]; hop None: n_fft / 2.  No tensor and no library is touched."""
+    if len(stems_shape) != 3:
+        raise ValueError('bandmix_render: stems must be [stems, samples, channels], got shape %s' % (tuple(stems_shape),))
+    S, n, ch = stems_shape
+    if not 1 <= S <= GAINFIT_MAX_STEMS:
+        raise ValueError('bandmix_render: 1..%d stems expected, got %d' % (GAINFIT_MAX_STEMS, S))
+    if ch not in (1, 2):
+        raise ValueError('bandmix_render: 1 or 2 channels expected, got %d' % ch)
+    if not isinstance(n_fft, numbers.Integral) or isinstance(n_fft, bool) or \
+            (hop is not None and (not isinstance(hop, numbers.Integral) or isinstance(hop, bool))):
+        raise TypeError('bandmix_render: n_fft and hop must be integers')
+    n_fft = int(n_fft)
+    hop = n_fft // 2 if hop is None else int(hop)
+    if n_fft < 64 or n_fft > 16384 or n_fft & (n_fft - 1):
+        raise ValueError('bandmix_render: n_fft must be a power of two from 64 to 16384')
+    if not 1 <= hop <= n_fft // 2:
+        raise ValueError('bandmix_render: hop must be 1 .. n_fft / 2 (the overlap-add needs every sample under two frames), got %d'
+                         % hop)
+    if n <= n_fft // 2:
+        raise ValueError('bandmix_render: reflect padding needs more than n_fft / 2 samples (got %d)' % n)
+    if 1 + n // hop > 0x7fffffff // 2:
+        raise ValueError('bandmix_render: too many frames')
+    gains_shape = tuple(gains_shape)
+    if len(gains_shape) != 3 or gains_shape[1] != S or not 1 <= gains_shape[0] <= GAINFIT_BAND_MAX_BANDS or \
+            not 1 <= gains_shape[2] <= n:
+        raise ValueError('bandmix_render: gains must be [bands, stems, windows] = [1..%d, %d, 1..%d], got shape %s'
+                         % (GAINFIT_BAND_MAX_BANDS, S, n, gains_shape))
+    B, W = gains_shape[0], gains_shape[2]
+    if tuple(fill_shape) not in ((), (S,), (S, 1), (S, W)):
+        raise ValueError('bandmix_render: fill must be a number or [S], [S, 1] or [S, W] = [%d, %d], got shape %s'
+                         % (S, W, tuple(fill_shape)))
+    first = gainfit_band_frame_windows(n, W, hop)
+    empty = [w for w in range(W) if first[w + 1] <= first[w]]
+    if empty:
+        raise ValueError('bandmix_render: window %d of %d owns no frame (%d samples, hop %d): fewer windows or a smaller hop'
+                         % (empty[0], W, n, hop))
+    return S, n, ch, B, W, n_fft, hop
+
+
+def bandmix_render(stems, gains, fill, edges, window, twiddles, n_fft, hop, out=None, workspace=None):
+    """stems: CUDA float32 / float64 [S, samples, channels] with any strides; gains: CUDA float64 [B, S, W]; fill: CUDA float64
+    [S, W]; edges: CUDA int32 [B + 1] (content unchecked here); window, twiddles: the float32 tables of features._get_tables
+    for ``n_fft`` -> the band-gain mix, float32 [channels, samples] (include/dam_hip.h: dam_bandmix_render states the
+    definition).  workspace: optional float32 tensor of dam_bandmix_workspace_bytes / 4 elements.  No host synchronisation,
+    hipGraph-capturable."""
+    _lib.require_cuda(stems, gains, fill, edges, window, twiddles, out, workspace)
+    xk = _audio_kind(stems, 'stems')
+    if gains.dtype != torch.float64 or fill.dtype != torch.float64:
+        raise TypeError('bandmix_render: float64 gains and fill expected')
+    if edges.dtype != torch.int32 or edges.dim() != 1 or not edges.is_contiguous():
+        raise TypeError('bandmix_render: edges must be a contiguous int32 [bands + 1] tensor')
+    S, n, ch, B, W, n_fft, hop = bandmix_check_shapes(stems.shape, gains.shape, fill.shape, n_fft, hop)
+    if tuple(fill.shape) != (S, W) or edges.numel() != B + 1:
+        raise ValueError('bandmix_render: fill must be [%d, %d] and edges [%d]' % (S, W, B + 1))
+    for t, what, count in ((window, 'window', n_fft), (twiddles, 'twiddles', 2 * n_fft)):
+        if t.dtype != torch.float32 or t.numel() != count or not t.is_contiguous():
+            raise ValueError('bandmix_render: %s must be a contiguous float32 tensor of %d elements' % (what, count))
+    dev = stems.device
+    if any(t.device != dev for t in (gains, fill, edges, window, twiddles)):
+        raise ValueError('bandmix_render: every tensor must be on the stems\' device')
+    gains, fill = gains.contiguous(), fill.contiguous()
+    if out is None:
+        out = torch.empty((ch, n), dtype=torch.float32, device=dev)
+    elif tuple(out.shape) != (ch, n) or out.dtype != torch.float32 or not out.is_contiguous():
+        raise ValueError('bandmix_render: out must be a contiguous float32 [%d, %d] tensor' % (ch, n))
+    L = _lib.lib()
+    need = L.dam_bandmix_workspace_bytes(n, ch, n_fft, hop)
+    if need <= 0:
+        raise ValueError('bandmix_render: the library refuses these arguments')
+    if workspace is None:
+        workspace = torch.empty(need // 4, dtype=torch.float32, device=dev)
+    elif workspace.dtype != torch.float32 or workspace.numel() * 4 < need or not workspace.is_contiguous():
+        raise ValueError('bandmix_render: workspace must be a contiguous float32 tensor of at least %d elements' % (need // 4))
+    with torch.cuda.device(dev):
+        _lib.check(L.dam_bandmix_render(_lib.ptr(stems), xk, S, ch, n, stems.stride(0), stems.stride(1), stems.stride(2),
+                                        _lib.ptr(gains), _lib.ptr(fill), _lib.ptr(edges), B, W, _lib.ptr(window),
+                                        _lib.ptr(twiddles), n_fft, hop, _lib.ptr(out), _lib.ptr(workspace),
+                                        workspace.numel() * 4, _lib.stream()), 'dam_bandmix_render')
+    return out
+
+
 # ----------------------------------------------------------------------------- alignment
 ALIGN_MAX_STEMS = 8
 ALIGN_WEIGHTINGS = {'plain': 0, 'phat': 1}      # DAM_ALIGN_PLAIN, DAM_ALIGN_PHAT

@@ -55,7 +55,7 @@ struct dam_bn_bwd_sums; /* defined in the BatchNorm section */
 /* Library / build identification ("gfx950").  DAM_ABI_VERSION is bumped whenever a signature below changes; a binding
  * compares dam_abi_version() of the library it loaded with the version it was written against and refuses a stale one
  * (deep-audio-mixer_amd/_lib.py: EXPECTED_ABI). */
-#define DAM_ABI_VERSION 32
+#define DAM_ABI_VERSION 33
 const char* dam_arch(void);
 int dam_abi_version(void);
 
@@ -1024,7 +1024,7 @@ int dam_gainfit_gain_error(const double* fit, const double* cand, int n_variants
  *   Argument errors (a NULL pointer; S outside 1 .. DAM_GAINFIT_MAX_STEMS; channels not 1 or 2; n_fft not a power of two in
  *     64 .. 16384; hop < 1; n <= n_fft/2; W outside 1 .. n; a window without a frame; B outside 1 .. dam_spectrum_max_bands();
  *     a negative slab_bytes; a non-positive count; negative pool or ridge, or a NaN ridge) return DAM_ERR_BAD_ARG before any launch.
- * Not covered: complex (phase-shifting) band gains, and rendering the fitted band gains to audio.
+ * Not covered: complex (phase-shifting) band gains.  Rendering the fitted band gains to audio is the band-gain mixer below.
  * --------------------------------------------------------------------------------- */
 #define DAM_BANDFIT_SLAB_BYTES 134217728
 int64_t dam_bandfit_tile_elements(void);
@@ -1039,6 +1039,58 @@ int dam_bandfit_solve_grouped(const double* moments, int n_groups, int n_windows
                               double* gains, double* residual, double* target, int32_t* status, void* stream);
 int dam_bandfit_summary(const double* residual, const double* target, const int32_t* status, int n_groups, int n_windows,
                              double* total, void* stream);
+
+/* ---------------------------------------------------------------------------------
+ * Band-gain mixer (ABI 33): the audio of per-stem, per-band, per-window gains -- what the band fit above fits, rendered: every
+ * stem's STFT scaled bin by bin with the gain of the bin's band and of the frame's window, the stems summed, the sum inverted
+ * and overlap-added.  One fused pass: no stem spectrum and no mix spectrum is written to memory.  Every entry is stateless,
+ * allocates nothing, does not synchronise with the host, uses no atomics and is hipGraph-capturable.  tests/_bandmix_ref.py
+ * restates the definition in numpy float64.
+ *   Inputs.  Stems s = 0 .. S-1, 1 <= S <= DAM_GAINFIT_MAX_STEMS, of `channels` (1 or 2) and n = n_samples samples, addressed
+ *     exactly as dam_bandfit_moments addresses them (element strides, float32 or float64).  gains: device float64 [B][S][W],
+ *     the layout dam_bandfit_solve_grouped writes; fill: device float64 [S][W]; edges: device int32 [B + 1] as the band fit takes
+ *     it, 1 <= B <= dam_spectrum_max_bands() (the CONTENT is the caller's to check -- gainfit.py does, on the host copy it
+ *     uploads; the kernel clamps every edge to [0, n_fft/2 + 1]); window, twiddles: the front-end's tables; n_fft a power of two
+ *     64 .. 16384; 1 <= hop <= n_fft/2 (dam_istft_f32's rule: a larger hop is DAM_ERR_UNSUPPORTED before the device is touched);
+ *     n > n_fft/2; 1 <= W <= n and every window owns a frame, as in the band fit.
+ *   Transforms and frames.  X_s[c][t][k] = the float32 STFT of channel c of stem s, exactly the band fit's U_s (a float64 sample
+ *     rounded to float32 first, reflect padding, the periodic Hann table, the imaginary parts of bins 0 and n_fft/2 taken as 0,
+ *     the same operations in the same order); T = 1 + n / hop frames; the window of frame t is the band fit's w(t).
+ *   Effective gain of stem s at bin k of a frame of window w.  The band of k is the lowest b with edges[b] <= k < edges[b+1]
+ *     (clamped edges).  In a band: e = gains[b][s][w] if that is finite, else fill[s][w] if that is finite, else 0.  Outside
+ *     every band: fill[s][w] if finite, else 0.  e is rounded to float32.  The gain is piecewise constant over a band: the model
+ *     the fit assumes.
+ *   Mix spectrum.  Y[c][t][k] = sum_s e X_s[c][t][k] in float32, in ascending s from +0, every step one FUSED multiply-add per
+ *     component: re = fmaf(e, Re X_s, re), im = fmaf(e, Im X_s, im).
+ *   Output.  y_t = irfft(Y[c][t]) (n_fft samples; the imaginary parts of bins 0 and n_fft/2 ignored), as dam_istft_f32 inverts
+ *     a frame: the real-FFT pre-twiddle, an n_fft/2-point inverse transform, the scale 1/n_fft riding on the window.
+ *     v_t[j] = (w[j] / n_fft) * y_t[j] in float32 (the frame as the workspace holds it), and with j = p + n_fft/2 - t hop:
+ *       out[c][p] = (sum over the t with 0 <= j < n_fft of v_t[j]) / (sum over the same t of w[j]^2),  0 <= p < n,
+ *     both sums in float32 in ascending t from +0, the first by additions, the second by fused multiply-adds; 0 where the
+ *     envelope is not above 1e-11 (torch.istft's threshold; with hop <= n_fft/2 it is above it everywhere).  This is
+ *     dam_istft_f32's formula with length = n.  A gather, no atomics: device float32 [channels][n].
+ *     A sample depends on its covering frames only, and a frame on its own window's gains only (bitwise): the samples at least
+ *     n_fft/2 inside window w do not change when the gains of the other windows do.
+ *   What follows (tests/test_bandmix_ref_cpu.py, in float64 to 1e-12): unit gains and unit fill give the stems' sum; gains
+ *     constant over the bands and W = 1 give sum_s g_s x_s; with W > 1 a sample p with w n/W + n_fft/2 <= p < (w+1) n/W - n_fft/2
+ *     (no margin at the two ends of the signal) is the gain-ramp mix's: only the frames that straddle a border cross-fade.
+ *   What it is NOT: the inverse of the fit.  Piecewise-constant bin gains are a circular filter whose response the synthesis
+ *     window truncates, so rendering gains and fitting the render does not give the gains back (planted random third-octave
+ *     gains came back only to 0.3); the render of FITTED gains, though, leaves of the fit's target about what the fit's own
+ *     residual says.
+ *   dam_bandmix_render: one workgroup per (frame, channel) writes v_t to the workspace, one lane per output sample gathers.
+ *     workspace: dam_bandmix_workspace_bytes(n_samples, channels, n_fft, hop) = 4 * channels * T * n_fft bytes (the synthesised
+ *     frames, nothing else), 4-byte aligned; 0 for arguments the entry refuses.  workspace_bytes below that: DAM_ERR_WORKSPACE.
+ *   Argument errors (a NULL pointer; S outside 1 .. DAM_GAINFIT_MAX_STEMS; channels not 1 or 2; n_fft not a power of two in
+ *     64 .. 16384; hop < 1; n <= n_fft/2; W outside 1 .. n; a window without a frame; B outside 1 .. dam_spectrum_max_bands())
+ *     return DAM_ERR_BAD_ARG before any launch.
+ * Not covered: gains interpolated between the band centres, complex (phase-shifting) gains.
+ * --------------------------------------------------------------------------------- */
+int64_t dam_bandmix_workspace_bytes(int64_t n_samples, int channels, int n_fft, int hop);
+int dam_bandmix_render(const void* x, int x_is_f64, int n_stems, int channels, int64_t n_samples, int64_t stem_stride,
+                       int64_t sample_stride, int64_t channel_stride, const double* gains, const double* fill,
+                       const int32_t* edges, int n_bands, int n_windows, const float* window, const float* twiddles, int n_fft,
+                       int hop, float* out, void* workspace, int64_t workspace_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------
  * Alignment (ABI 28): the time offset of every stem against a mix by block cross-correlation, and the sample shift that removes
