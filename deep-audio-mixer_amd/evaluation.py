@@ -40,6 +40,12 @@ headroom of a band-gain mixer over a gain-only one) and a '*_band_gain_error' be
 variant's broadband gains sit from the band-wise optimum.  ``band_render=True`` makes that band-gain mixer audible: the fitted
 band gains rendered to audio (gainfit.render_band_gains), 'oracle_band_render_residual' -- what the render leaves of the
 reference, measured on the audio -- and, with ``write_wavs_to_disk``, ``{song}_oracle_band.wav`` beside the other variants.
+
+``feature_distance=True`` measures the training criterion itself on the audio a variant renders: the distance between the dB
+spectrogram of "stems x the variant's gains" and the reference mix's, frame by frame and bin by bin, in the model's own
+features (spectrum.spectrogram_distance) -- '*_feat_mse' (the criterion, dB^2) and '*_feat_error' (its level-free part, the
+centred RMS in dB) beside every '*_error'.  '*_spec_error' and '*_st_error' are its two marginals: a mix that is bright in the
+verses and dull in the choruses reads fine on both and badly here.
 """
 import numbers
 import os
@@ -192,6 +198,29 @@ class LoudnessEvaluator:
             raise ValueError("band_render: fill must be 'broadband' or a number, got %r" % (fill,))
         return float(fill)
 
+    FEATURE_DISTANCE_DEFAULTS = {'n_fft': 2048, 'hop': 1024, 'fraction': 3}          # the model's own features
+
+    def _feature_distance_args(self, feature_distance):
+        """``feature_distance`` as the whole-song methods take it (True, or a dict with any of n_fft, hop, fraction) ->
+        (n_fft, hop, edges, centres): the fractional-octave table at the evaluator's rate grown by one band below and one above
+        where bins are left (spectrum.extend_edges), so that the cells cover every bin and their total is the criterion; the
+        centre of such a band is the mean frequency of its bins."""
+        given = {} if feature_distance is True else dict(feature_distance)
+        unknown = set(given) - set(self.FEATURE_DISTANCE_DEFAULTS)
+        if unknown:
+            raise ValueError('feature_distance: unknown keys %s (expected any of %s)'
+                             % (sorted(unknown), sorted(self.FEATURE_DISTANCE_DEFAULTS)))
+        o = dict(self.FEATURE_DISTANCE_DEFAULTS, **given)
+        if 'n_fft' in given and 'hop' not in given:
+            o['hop'] = None                                 # (n_fft / 2, as everywhere)
+        # (the shapes are placeholders: what is checked here is n_fft and hop)
+        n_fft, hop = ops.specdist_check_shapes((1, o['n_fft'], 1), None, (1, o['n_fft'], 1), None, o['n_fft'], o['hop'], 1)[6:8]
+        edges, centres = spectrum.band_edges(self.sr, n_fft, o['fraction'])
+        edges, low, high = spectrum.extend_edges(edges, n_fft)
+        mid = lambda a, b: 0.5 * (int(a) + int(b) - 1) * self.sr / n_fft
+        centres = ([mid(edges[0], edges[1])] if low else []) + centres.tolist() + ([mid(edges[-2], edges[-1])] if high else [])
+        return n_fft, hop, edges, centres
+
     def evaluate_spectrum_batch(self, stems, gains=None, **spectral):
         """Band powers of the stem sum (long-term average spectrum in fractional-octave bands at the evaluator's rate),
         measured as ``sum of stem * gain ramp`` where gains are given, without that sum being written.  stems as
@@ -243,7 +272,7 @@ class LoudnessEvaluator:
     def process_song_tracks(self, loaded_tracks: dict, reference_tracks: dict, song_name: str, n_random_samples: int = 5,
                             chunk_length: int = 2, write_wavs_to_disk=False, results_dir='./experiment',
                             ceiling_dbtp=None, dynamics=False, limiter=None, spectral=False, gain_fit=False, band_fit=False,
-                            band_render=False) -> dict:
+                            band_render=False, feature_distance=False) -> dict:
         """evaluation.py:77-116 on stems already in memory ({name: ndarray [channels, n]} each): the loudness profile of
         ``reference_tracks`` against the profiles of ``loaded_tracks`` summed as they are ('sum_error'), normalised to the
         training set's mean loudness ('loudnorm_error'), mixed by the model ('mix_error') and scaled by random gains
@@ -295,7 +324,16 @@ class LoudnessEvaluator:
         [windows]: the share of the fit target's energy that (target - render) holds in every window, from the time-domain
         moments of the two -- the time-domain counterpart of 'oracle_band_residual_total', in the same copy to the host.  With
         write_wavs_to_disk the render goes to ``{song_name}_oracle_band.wav`` as the other variants do (-20 LUFS, the ceiling
-        and the limiter).  Off (the default), nothing changes."""
+        and the limiter).  Off (the default), nothing changes.
+        feature_distance (True, or a dict with any of n_fft, hop, fraction; defaults 2048, 1024, 3 -- the model's features):
+        the dB-spectrogram distance of every variant's rendered stem sum from the reference stems' sum
+        (spectrum.spectrogram_distance over third-octave bands grown to cover every bin and the windows of the model's gain
+        ramp; every variant in one call, from the gains it already passes to the meter; one copy to the host).  The stats gain,
+        after every other key, 'sum_feat_error', 'loudnorm_feat_error', 'mix_feat_error', 'random_feat_error' (the mean over the
+        draws): the centred RMS of the difference in dB, which a common gain does not move; the same four as '*_feat_mse': the
+        mean squared difference in dB^2, the criterion as trained; and 'feat_profile' {'centres': [Hz], 'mix_band_rms': [bands],
+        'mix_window_rms': [windows]}, the centred RMS of the model's mix per band and per window.  Nothing else depends on it.
+        The reference mix and the stems must be of one length."""
         render_fill = self._band_render_args(band_render, band_fit)
         if self.d is None or self.mix_model is None or self.mean_loudness_model is None:
             raise ValueError('process_song needs the dataset, d_mean_loudness and mix_model constructor arguments')
@@ -315,6 +353,10 @@ class LoudnessEvaluator:
             (fit_pool, fit_ridge), fit_align = self._gain_fit_args(gain_fit), self._gain_fit_align(gain_fit)
             if np.asarray(reference_tracks[self.keys[0]]).shape[-1] != np.asarray(loaded_tracks[self.keys[0]]).shape[-1]:
                 raise ValueError('gain_fit fits sample by sample: the reference mix and the stems differ in length')
+        if feature_distance:
+            feat_n_fft, feat_hop, feat_edges, feat_centres = self._feature_distance_args(feature_distance)
+            if np.asarray(reference_tracks[self.keys[0]]).shape[-1] != np.asarray(loaded_tracks[self.keys[0]]).shape[-1]:
+                raise ValueError('feature_distance compares frame by frame: the reference mix and the stems differ in length')
         stats = {'song_name': song_name}
 
         def write(identifier, pcm, gains=None):
@@ -341,6 +383,8 @@ class LoudnessEvaluator:
             fit_target = ops.mixdown_peak_normalize(reference_pcm, torch.ones((len(self.keys), 1), dtype=torch.float64,
                                                                               device=reference_pcm.device), normalize=False)
             candidates_fit = []                             # loudnorm, then the draws: [stems] each
+        if feature_distance:                                # the reference stays resident until the distance is taken
+            feat_reference, candidates_feat = reference_pcm, []                            # loudnorm, then the draws: [stems] each
         del reference_pcm
 
         def error(profile):
@@ -368,6 +412,8 @@ class LoudnessEvaluator:
             candidates_spec.append(band_power(pcm, loudnorm_gains))
         if gain_fit or band_fit:
             candidates_fit.append(loudnorm_gains.reshape(-1))
+        if feature_distance:
+            candidates_feat.append(loudnorm_gains.reshape(-1))
         stats['mix_error'] = error(self._profile([float(v) for v in mix_lufs]))
         write('mix', pcm, mixer.gains[1])
         if dynamics:
@@ -386,6 +432,8 @@ class LoudnessEvaluator:
                 drawn_gains.append(g)
             if gain_fit or band_fit:
                 candidates_fit.append(g)
+            if feature_distance:
+                candidates_feat.append(g)
         stats['random_error'] = mean(random_errors)
         stats['smooth_gains'] = {name: list(gains[1, i]) for i, name in enumerate(self.keys)}
         if dynamics:                                        # one launch for every variant, one copy to the host
@@ -482,14 +530,35 @@ class LoudnessEvaluator:
                 stats['oracle_band_residual_total'] = take(W)
                 if render_fill is not None:
                     stats['oracle_band_render_residual'] = take(W)
+        if feature_distance:                                # every variant in one call, one summary launch, one copy to the host
+            n_stems, W = len(self.keys), mixer.n_proc
+            constant = torch.stack(candidates_feat).unsqueeze(-1).expand(-1, -1, W)        # loudnorm, draws: [.., stems, W]
+            cand = torch.cat([torch.ones((1, n_stems, W), dtype=torch.float64, device=pcm.device), constant[:1],
+                              mixer.gains[1].unsqueeze(0), constant[1:]])
+            sums, count = spectrum.spectrogram_distance(pcm.transpose(1, 2), cand, feat_reference.transpose(1, 2), None,
+                                                        n_fft=feat_n_fft, hop=feat_hop, edges=feat_edges, n_windows=W)
+            del feat_reference
+            fig = spectrum.distance_summary(sums, count)
+            host = torch.cat([fig.rms_centred, fig.mse, fig.band_rms[2], fig.window_rms[2]]).cpu().tolist()
+            n_var = cand.shape[0]
+            rms, mse = host[:n_var], host[n_var:2 * n_var]
+            stats['sum_feat_error'], stats['loudnorm_feat_error'], stats['mix_feat_error'] = rms[:3]
+            stats['random_feat_error'] = mean(rms[3:]) if n_var > 3 else float('nan')
+            stats['sum_feat_mse'], stats['loudnorm_feat_mse'], stats['mix_feat_mse'] = mse[:3]
+            stats['random_feat_mse'] = mean(mse[3:]) if n_var > 3 else float('nan')
+            n_bands = len(feat_centres)
+            stats['feat_profile'] = {'centres': feat_centres, 'mix_band_rms': host[2 * n_var:2 * n_var + n_bands],
+                                     'mix_window_rms': host[2 * n_var + n_bands:]}
         return stats
 
     def process_song(self, base_dir: str, song_name: str, n_random_samples: int = 5, chunk_length: int = 2,
                      write_wavs_to_disk=False, results_dir='./experiment', ceiling_dbtp=None, dynamics=False, limiter=None,
-                     spectral=False, gain_fit=False, band_fit=False, band_render=False) -> dict:
+                     spectral=False, gain_fit=False, band_fit=False, band_render=False, feature_distance=False) -> dict:
         """evaluation.py:77-116: the reference mix from ``base_dir/manual_gain_mixes``, the stems from ``base_dir/test``."""
         from .data.dataset_utils import load_tracks_musdb18
         self._band_render_args(band_render, band_fit)          # (before a file is read)
+        if feature_distance:
+            self._feature_distance_args(feature_distance)
         reference_tracks = load_tracks_musdb18(os.path.join(base_dir, 'manual_gain_mixes'), song_name, tracklist=self.keys,
                                                sr=self.sr)
         loaded_tracks = load_tracks_musdb18(os.path.join(base_dir, 'test'), song_name, tracklist=self.keys, sr=self.sr)
@@ -497,22 +566,28 @@ class LoudnessEvaluator:
                                         write_wavs_to_disk, results_dir, ceiling_dbtp, dynamics, limiter, spectral,
                                         **({'gain_fit': gain_fit} if gain_fit else {}),
                                         **({'band_fit': band_fit} if band_fit else {}),
-                                        **({'band_render': band_render} if band_render else {}))
+                                        **({'band_render': band_render} if band_render else {}),
+                                        **({'feature_distance': feature_distance} if feature_distance else {}))
 
     def process_songlist(self, base_dir, songlist, n_random_samples: int = 5, chunk_length: int = 2,
                          write_wavs_to_disk=False, results_dir='./experiment', ceiling_dbtp=None, dynamics=False, limiter=None,
-                         spectral=False, gain_fit=False, band_fit=False, band_render=False):
+                         spectral=False, gain_fit=False, band_fit=False, band_render=False, feature_distance=False):
         """evaluation.py:118-144 without the spreadsheet: (rows, means) -- one stats dict per song and the mean of every
         error over the songs (the sheet's last row); with ``dynamics`` the four '*_st_error' keys too, with ``spectral``
         the four '*_spec_error' keys, with ``gain_fit`` the four '*_gain_error' keys (a song whose figure is NaN -- nothing
         to compare -- is left out of that mean; the mean is NaN if every song's is), with ``band_fit`` the four
-        '*_band_gain_error' keys in the same way.  ``band_render`` is passed on to every song (its key is per window: no mean)."""
+        '*_band_gain_error' keys in the same way.  ``band_render`` is passed on to every song (its key is per window: no mean).
+        With ``feature_distance`` the four '*_feat_error' and the four '*_feat_mse' keys are averaged as the '*_spec_error' keys
+        are."""
         self._band_render_args(band_render, band_fit)
         keys = ['sum_error', 'random_error', 'loudnorm_error', 'mix_error']
         if dynamics:
             keys += ['sum_st_error', 'random_st_error', 'loudnorm_st_error', 'mix_st_error']
         if spectral:
             keys += ['sum_spec_error', 'random_spec_error', 'loudnorm_spec_error', 'mix_spec_error']
+        if feature_distance:
+            keys += ['sum_feat_error', 'random_feat_error', 'loudnorm_feat_error', 'mix_feat_error',
+                     'sum_feat_mse', 'random_feat_mse', 'loudnorm_feat_mse', 'mix_feat_mse']
         fit_keys = ['sum_gain_error', 'random_gain_error', 'loudnorm_gain_error', 'mix_gain_error'] if gain_fit else []
         if band_fit:
             fit_keys += ['sum_band_gain_error', 'random_band_gain_error', 'loudnorm_band_gain_error', 'mix_band_gain_error']
@@ -529,6 +604,8 @@ class LoudnessEvaluator:
                 extra['band_fit'] = band_fit
             if band_render:
                 extra['band_render'] = band_render
+            if feature_distance:
+                extra['feature_distance'] = feature_distance
             rows.append(self.process_song(base_dir, song_name, n_random_samples, chunk_length, write_wavs_to_disk,
                                           results_dir, ceiling_dbtp, dynamics, **extra))
         means = {key: mean(row[key] for row in rows) for key in keys}

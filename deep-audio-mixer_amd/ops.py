@@ -1573,6 +1573,145 @@ def bandmix_render(stems, gains, fill, edges, window, twiddles, n_fft, hop, out=
     return out
 
 
+# ----------------------------------------------------------------------------- spectrogram distance
+def specdist_check_shapes(stems_shape, gains_shape, ref_shape, ref_gains_shape, n_fft, hop, n_windows, n_bands=None, amin=1e-5):
+    """The host-side argument rules of specdist_sums on shapes alone -> (R, S, n, channels, S_ref, ref_channels, n_fft, hop, W);
+    ValueError / TypeError otherwise.  stems_shape [S, n, channels]; gains_shape None or [R, S, n_gains]; ref_shape
+    [S_ref, n, channels]; ref_gains_shape None or [S_ref, n_gains]; hop None: n_fft / 2.  No tensor and no library is touched."""
+    if len(stems_shape) != 3 or len(ref_shape) != 3:
+        raise ValueError('specdist_sums: stems and reference must be [stems, samples, channels], got shapes %s and %s'
+                         % (tuple(stems_shape), tuple(ref_shape)))
+    S, n, ch = stems_shape
+    S_ref, n_ref, ch_ref = ref_shape
+    if S < 1 or S_ref < 1:
+        raise ValueError('specdist_sums: at least one stem on either side expected')
+    if ch not in (1, 2) or ch_ref not in (1, 2):
+        raise ValueError('specdist_sums: 1 or 2 channels expected, got %d and %d' % (ch, ch_ref))
+    if n_ref != n:
+        raise ValueError('specdist_sums: the reference has %d samples, the stems %d: equal lengths expected' % (n_ref, n))
+    for v in (n_fft, n_windows) + (() if hop is None else (hop,)):
+        if not isinstance(v, numbers.Integral) or isinstance(v, bool):
+            raise TypeError('specdist_sums: n_fft, hop and n_windows must be integers')
+    n_fft, W = int(n_fft), int(n_windows)
+    hop = n_fft // 2 if hop is None else int(hop)
+    if n_fft < 64 or n_fft > 16384 or n_fft & (n_fft - 1):
+        raise ValueError('specdist_sums: n_fft must be a power of two from 64 to 16384')
+    if hop < 1:
+        raise ValueError('specdist_sums: hop must be positive')
+    if n <= n_fft // 2:
+        raise ValueError('specdist_sums: reflect padding needs more than n_fft / 2 samples (got %d)' % n)
+    if 1 + n // hop > 0x7fffffff // 2:
+        raise ValueError('specdist_sums: too many frames')
+    R = 1
+    if gains_shape is not None:
+        gains_shape = tuple(gains_shape)
+        if len(gains_shape) != 3 or gains_shape[1] != S or not 1 <= gains_shape[0] <= 65535 or not 1 <= gains_shape[2] <= n:
+            raise ValueError('specdist_sums: gains must be [rows, stems, n_gains] = [1..65535, %d, 1..%d], got shape %s'
+                             % (S, n, gains_shape))
+        R = gains_shape[0]
+    if ref_gains_shape is not None:
+        ref_gains_shape = tuple(ref_gains_shape)
+        if len(ref_gains_shape) != 2 or ref_gains_shape[0] != S_ref or not 1 <= ref_gains_shape[1] <= n:
+            raise ValueError('specdist_sums: ref_gains must be [stems, n_gains] = [%d, 1..%d], got shape %s'
+                             % (S_ref, n, ref_gains_shape))
+    if not 1 <= W <= n:
+        raise ValueError('specdist_sums: 1..%d windows expected, got %d' % (n, W))
+    first = gainfit_band_frame_windows(n, W, hop) if W <= 1 + n // hop else None
+    empty = [0] if first is None else [w for w in range(W) if first[w + 1] <= first[w]]
+    if empty:
+        raise ValueError('specdist_sums: window %d of %d owns no frame (%d samples, hop %d): fewer windows or a smaller hop'
+                         % (empty[0], W, n, hop))
+    if n_bands is not None and not 1 <= n_bands <= GAINFIT_BAND_MAX_BANDS:
+        raise ValueError('specdist_sums: 1..%d bands expected, got %d' % (GAINFIT_BAND_MAX_BANDS, n_bands))
+    if not isinstance(amin, numbers.Real) or isinstance(amin, bool) or not float(amin) > 0.0 or \
+            not ctypes.c_float(float(amin)).value > 0.0:
+        raise ValueError('specdist_sums: amin must be a positive float32 number')
+    return R, S, n, ch, S_ref, ch_ref, n_fft, hop, W
+
+
+def specdist_sums(stems, gains, ref_stems, ref_gains, window, twiddles, n_fft, hop, edges, n_windows, amin=1e-5, sums_out=None,
+                  count_out=None, workspace=None):
+    """stems: CUDA float32 / float64 [S, samples, channels] with any strides; gains: None (one row, the plain sum) or CUDA float64
+    [R, S, n_gains]; ref_stems: CUDA float32 / float64 [S_ref, samples, channels], the reference mix as its own stems;
+    ref_gains: None or CUDA float64 [S_ref, n_gains]; window, twiddles: the float32 tables of features._get_tables for
+    ``n_fft``; edges: CUDA int32 [B + 1] (content unchecked here, as in spectrum_band_power) -> (sums float64 [R, B, W, 2],
+    count int64 [B, W]): (sum d, sum d^2) of the dB-spectrogram difference of every row against the reference over the bins
+    of band b and the frames of window w, and the number of (frame, bin) pairs in the cell (include/dam_hip.h:
+    dam_specdist_sums states the definition and the order of the additions).  workspace: optional float64 tensor of
+    dam_specdist_workspace_bytes / 8 elements.  No host synchronisation, hipGraph-capturable."""
+    _lib.require_cuda(stems, gains, ref_stems, ref_gains, window, twiddles, edges, sums_out, count_out, workspace)
+    xk, rk = _audio_kind(stems, 'stems'), _audio_kind(ref_stems, 'ref_stems')
+    for g, what in ((gains, 'gains'), (ref_gains, 'ref_gains')):
+        if g is not None and g.dtype != torch.float64:
+            raise TypeError('specdist_sums: %s must be float64' % what)
+    if edges.dtype != torch.int32 or edges.dim() != 1 or not edges.is_contiguous():
+        raise TypeError('specdist_sums: edges must be a contiguous int32 [bands + 1] tensor')
+    B = edges.numel() - 1
+    R, S, n, ch, S_ref, ch_ref, n_fft, hop, W = specdist_check_shapes(
+        stems.shape, None if gains is None else gains.shape, ref_stems.shape, None if ref_gains is None else ref_gains.shape,
+        n_fft, hop, n_windows, B, amin)
+    for t, what, count in ((window, 'window', n_fft), (twiddles, 'twiddles', 2 * n_fft)):
+        if t.dtype != torch.float32 or t.numel() != count or not t.is_contiguous():
+            raise ValueError('specdist_sums: %s must be a contiguous float32 tensor of %d elements' % (what, count))
+    dev = stems.device
+    if any(t is not None and t.device != dev for t in (gains, ref_stems, ref_gains, edges, window, twiddles)):
+        raise ValueError('specdist_sums: every tensor must be on the stems\' device')
+    gains = None if gains is None else gains.contiguous()
+    ref_gains = None if ref_gains is None else ref_gains.contiguous()
+    outs = []
+    for o, dt, shape in ((sums_out, torch.float64, (R, B, W, 2)), (count_out, torch.int64, (B, W))):
+        if o is None:
+            o = torch.empty(shape, dtype=dt, device=dev)
+        elif o.dtype != dt or tuple(o.shape) != shape or not o.is_contiguous():
+            raise ValueError('specdist_sums: outputs must be contiguous float64 %s and int64 %s tensors'
+                             % ((R, B, W, 2), (B, W)))
+        outs.append(o)
+    L = _lib.lib()
+    need = L.dam_specdist_workspace_bytes(R, n, n_fft, hop, B, W)
+    if need <= 0:
+        raise ValueError('specdist_sums: the library refuses these arguments')
+    if workspace is None:
+        workspace = torch.empty(need // 8, dtype=torch.float64, device=dev)
+    elif workspace.dtype != torch.float64 or workspace.numel() * 8 < need or not workspace.is_contiguous() or \
+            workspace.data_ptr() % 16:
+        raise ValueError('specdist_sums: workspace must be a contiguous, 16-byte aligned float64 tensor of at least %d elements'
+                         % (need // 8))
+    with torch.cuda.device(dev):
+        _lib.check(L.dam_specdist_sums(_lib.ptr(stems), xk, R, S, ch, n, stems.stride(0), stems.stride(1), stems.stride(2),
+                                       _lib.ptr(gains), 0 if gains is None else gains.shape[2], _lib.ptr(ref_stems), rk, S_ref,
+                                       ch_ref, ref_stems.stride(0), ref_stems.stride(1), ref_stems.stride(2), _lib.ptr(ref_gains),
+                                       0 if ref_gains is None else ref_gains.shape[1], _lib.ptr(window), _lib.ptr(twiddles),
+                                       n_fft, hop, float(amin), _lib.ptr(edges), B, W, _lib.ptr(outs[0]), _lib.ptr(outs[1]),
+                                       _lib.ptr(workspace), _lib.stream()), 'dam_specdist_sums')
+    return outs[0], outs[1]
+
+
+def specdist_summary(sums, count, out=None):
+    """sums CUDA float64 [R, B, W, 2], count int64 [B, W] (specdist_sums) -> float64 [R, 1 + B + W, 3]: (mse in dB^2, bias in
+    dB, centred rms in dB) of every row as a whole (index 0), per band (1 + b) and per window (1 + B + w); NaN where the
+    count is 0 (include/dam_hip.h: dam_specdist_summary).  One launch, nothing comes to the host."""
+    _lib.require_cuda(sums, count, out)
+    if sums.dtype != torch.float64 or count.dtype != torch.int64:
+        raise TypeError('specdist_summary: float64 sums and int64 count expected')
+    if sums.dim() != 4 or sums.shape[3] != 2 or count.dim() != 2 or tuple(count.shape) != tuple(sums.shape[1:3]) or \
+            sums.shape[0] < 1 or not 1 <= sums.shape[1] <= GAINFIT_BAND_MAX_BANDS or sums.shape[2] < 1:
+        raise ValueError('specdist_summary: [rows, bands, windows, 2] with 1..%d bands and [bands, windows] expected, got %s and %s'
+                         % (GAINFIT_BAND_MAX_BANDS, tuple(sums.shape), tuple(count.shape)))
+    if count.device != sums.device:
+        raise ValueError('specdist_summary: the sums and the count must be on one device')
+    sums, count = sums.contiguous(), count.contiguous()
+    R, B, W = sums.shape[:3]
+    shape = (R, 1 + B + W, 3)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float64, device=sums.device)
+    elif out.dtype != torch.float64 or tuple(out.shape) != shape or not out.is_contiguous():
+        raise ValueError('specdist_summary: out must be a contiguous float64 %s tensor' % (shape,))
+    with torch.cuda.device(sums.device):
+        _lib.check(_lib.lib().dam_specdist_summary(_lib.ptr(sums), _lib.ptr(count), R, B, W, _lib.ptr(out), _lib.stream()),
+                   'dam_specdist_summary')
+    return out
+
+
 # ----------------------------------------------------------------------------- alignment
 ALIGN_MAX_STEMS = 8
 ALIGN_WEIGHTINGS = {'plain': 0, 'phat': 1}      # DAM_ALIGN_PLAIN, DAM_ALIGN_PHAT

@@ -11,6 +11,7 @@ the loudness error does not (evaluation.py:39-53: loudness relative to the stems
 Importable without a GPU (``band_edges`` and ``relative_levels_db`` are host arithmetic); the measuring functions need
 CUDA tensors and raise otherwise -- there is no CPU fallback.
 """
+import collections
 import math
 import numbers
 
@@ -166,3 +167,77 @@ def relative_levels_db(power):
     power = np.asarray(power, dtype=np.float64)
     with np.errstate(divide='ignore', invalid='ignore'):
         return 10.0 * np.log10(power / power.sum(axis=-1, keepdims=True))
+
+
+DistanceSummary = collections.namedtuple('DistanceSummary', ['mse', 'bias', 'rms_centred', 'band_mse', 'band_bias', 'band_rms',
+                                                             'window_mse', 'window_bias', 'window_rms'])
+
+
+def extend_edges(edges, n_fft):
+    """A band table grown by one band below (bins 0 .. edges[0]-1) and one above (edges[-1] .. n_fft/2) where bins are left
+    there, so that the cells of spectrogram_distance cover every bin exactly once -> (edges int32, has_low, has_high)."""
+    e = check_edges(edges, n_fft).tolist()
+    low, high = e[0] > 0, e[-1] < n_fft // 2 + 1
+    return np.asarray(([0] if low else []) + e + ([n_fft // 2 + 1] if high else []), dtype=np.int32), low, high
+
+
+def spectrogram_distance(stems, gains, ref_stems, ref_gains=None, *, n_fft=2048, hop=None, edges=None, n_windows=1, amin=1e-5):
+    """The distance between the dB spectrograms of R candidate mixes and of one reference mix -- the training criterion
+    (a mean squared error of amplitude_to_DB(|STFT|) features) on the audio that is rendered (include/dam_hip.h:
+    dam_specdist_sums states the definition).  stems: CUDA float32 / float64 [S, samples, channels] with any strides (planar
+    storage as ``pcm.transpose(1, 2)``, no copy); gains: None (one row, the plain sum) or CUDA float64 [S], [S, n_gains] or
+    [R, S, n_gains], as band_power_mix takes them; ref_stems [S_ref, samples, channels] and ref_gains (None, [S_ref] or
+    [S_ref, n_gains]): the reference mix as its own stems, of the same length; a finished mix is ``mix.unsqueeze(0)``.
+    edges: a host table of bin edges as band_power_mix takes it, None: one band over every bin.  n_windows: W time windows by
+    the mixer's gain-index rule (every window must own a frame).  amin: the floor of the levels, the model's 1e-5 (-100 dB).
+    -> (sums CUDA float64 [R, B, W, 2] = (sum d, sum d^2) of d = L_cand - L_ref in dB over the cell's frames and bins,
+    count CUDA int64 [B, W]).  A cell does not depend on the other rows, bands or windows (bitwise).  No mix and no
+    spectrogram is written; no host synchronisation once the tables are resident, hipGraph-capturable then."""
+    for t, what in ((stems, 'stems'), (ref_stems, 'ref_stems')):
+        if not t.is_cuda:
+            raise RuntimeError('deep_audio_mixer_amd kernels run on the GPU only (got a %s tensor); there is no CPU fallback'
+                               % t.device)
+        if t.dtype not in (torch.float32, torch.float64):
+            raise TypeError('float32 or float64 samples expected')
+        if t.dim() != 3:
+            raise ValueError('%s must be [stems, samples, channels], got shape %s' % (what, tuple(t.shape)))
+    S, S_ref = stems.shape[0], ref_stems.shape[0]
+    if gains is not None:
+        if gains.dim() == 1:
+            gains = gains.view(1, -1, 1)
+        elif gains.dim() == 2:
+            gains = gains.unsqueeze(0)
+        if gains.dim() != 3 or gains.shape[1] != S:
+            raise ValueError('gains must be [S], [S, n_gains] or [R, S, n_gains] with S = %d, got shape %s'
+                             % (S, tuple(gains.shape)))
+    if ref_gains is not None:
+        if ref_gains.dim() == 1:
+            ref_gains = ref_gains.view(-1, 1)
+        if ref_gains.dim() != 2 or ref_gains.shape[0] != S_ref:
+            raise ValueError('ref_gains must be [S_ref] or [S_ref, n_gains] with S_ref = %d, got shape %s'
+                             % (S_ref, tuple(ref_gains.shape)))
+    for g in (gains, ref_gains):
+        if g is not None:
+            if not g.is_cuda:
+                raise RuntimeError('gains must be a CUDA tensor')
+            if g.dtype != torch.float64:
+                raise TypeError('gains must be float64')
+    R, S, n, ch, S_ref, ch_ref, n_fft, hop, W = ops.specdist_check_shapes(
+        stems.shape, None if gains is None else gains.shape, ref_stems.shape, None if ref_gains is None else ref_gains.shape,
+        n_fft, hop, n_windows, None, amin)
+    if edges is None:
+        edges = np.asarray([0, n_fft // 2 + 1], dtype=np.int32)
+    dev_edges = _device_edges(edges, n_fft, stems.device)      # (checked before anything is launched)
+    win, tw = features._get_tables(stems.device, n_fft)
+    return ops.specdist_sums(stems, gains, ref_stems, ref_gains, win, tw, n_fft, hop, dev_edges, W, amin)
+
+
+def distance_summary(sums, count):
+    """sums [R, B, W, 2], count [B, W] of spectrogram_distance -> DistanceSummary of CUDA float64 tensors: mse (dB^2, the
+    criterion), bias (dB) and rms_centred = sqrt(max(0, mse - bias^2)) (dB) per row [R], per band [R, B] and per window
+    [R, W]; NaN where the count is 0.  One launch, nothing comes to the host."""
+    out = ops.specdist_summary(sums, count)
+    B, W = count.shape
+    tot, band, win = out[:, 0], out[:, 1:1 + B], out[:, 1 + B:]
+    return DistanceSummary(tot[:, 0], tot[:, 1], tot[:, 2], band[..., 0], band[..., 1], band[..., 2],
+                           win[..., 0], win[..., 1], win[..., 2])

@@ -55,7 +55,7 @@ struct dam_bn_bwd_sums; /* defined in the BatchNorm section */
 /* Library / build identification ("gfx950").  DAM_ABI_VERSION is bumped whenever a signature below changes; a binding
  * compares dam_abi_version() of the library it loaded with the version it was written against and refuses a stale one
  * (deep-audio-mixer_amd/_lib.py: EXPECTED_ABI). */
-#define DAM_ABI_VERSION 33
+#define DAM_ABI_VERSION 34
 const char* dam_arch(void);
 int dam_abi_version(void);
 
@@ -1091,6 +1091,59 @@ int dam_bandmix_render(const void* x, int x_is_f64, int n_stems, int channels, i
                        int64_t sample_stride, int64_t channel_stride, const double* gains, const double* fill,
                        const int32_t* edges, int n_bands, int n_windows, const float* window, const float* twiddles, int n_fft,
                        int hop, float* out, void* workspace, int64_t workspace_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------------
+ * Spectrogram distance (ABI 34): the frame-by-frame, bin-by-bin distance between the dB spectrogram of R candidate mixes
+ * "stems x gain ramps" and that of one reference mix -- the criterion the models are trained on (model_trainer.py:34-35, a mean
+ * squared error of amplitude_to_DB(|STFT|) features, data/dataset.py:145-155), measured on the audio that is rendered rather than
+ * on the surrogate sum_s g_s dB(X_s) the network forms.  The band spectrum above and the short-term loudness error are its two
+ * marginals (time averaged away; frequency summed away).  Neither a mix nor a spectrogram is written.  Every entry is stateless,
+ * allocates nothing, does not synchronise with the host, uses no atomics and is hipGraph-capturable.  tests/_specdist_ref.py
+ * restates the definition in numpy float64.
+ *   Mix signal.  xm exactly as dam_spectrum_band_power forms it (channel mean of every stem times its gain, gain index
+ *     min(p / (n / n_gains), n_gains-1), added in double in ascending stem order, rounded to float once; gains NULL: every gain
+ *     exactly 1).  Candidates: stems x [S][n][channels] by element strides (float32 or float64), gains device float64
+ *     [R][S][n_gains] or NULL (every row the plain sum), 1 <= R <= 65535.  Reference: its own stems ref [S_ref][n][ref_channels]
+ *     with its own strides and type, ref_gains device float64 [S_ref][ref_n_gains] or NULL.  Both have n = n_samples samples.
+ *   Frames and transform.  Those of the band spectrum: T = 1 + n / hop, frame_t[j] = xm[reflect(t*hop - n_fft/2 + j)] * w[j] in
+ *     float32, the float32 LDS FFT, bins k = 0 .. n_fft/2, the imaginary parts of bins 0 and n_fft/2 taken as 0.
+ *   Level.  p = re*re + im*im in float32 (every operation its own rounding);  L[t][k] = p <= amin*amin ? floor_db :
+ *     3.01029995663981195f * log2f(p), the front-end's power_to_db, floor_db = (float)(20 log10((double)amin)), amin*amin a
+ *     float32 product.  amin > 0; the model's is 1e-5 (floor -100 dB).  Every bin has weight 1: no c_k.
+ *   Difference.  d_r[t][k] = (double)L_cand,r[t][k] - (double)L_ref[t][k]; d^2 = d*d in double.
+ *   Cells.  Band b = bins edges[b] .. edges[b+1]-1, edges as dam_spectrum_band_power takes it (device int32 [B + 1], the CONTENT
+ *     the caller's to check, clamped to [0, n_fft/2 + 1] by the kernels, 1 <= B <= dam_spectrum_max_bands()).  Window of frame t:
+ *     the band fit's w(t) = min(min(t*hop, n-1) / (n / W), W-1), 1 <= W <= n, every window must own a frame.
+ *       sums[r][b][w] = (sum d, sum d^2) over the frames of window w and the bins of band b   device float64 [R][B][W][2]
+ *       count[b][w]   = frames of w times bins of b (geometry only)                            device int64 [B][W]
+ *   Order of the float64 additions.  Per (row, frame, band), for sum d and sum d^2 alike: lane q of 64 adds the bins edges[b] + q,
+ *     + 64, ... in ascending order from +0.0, then an xor-butterfly over the 64 partials, distances 1, 2, .. 32: one record.  A
+ *     cell adds its frames' records in ascending t from +0.0.  So a cell depends on its own frames and bins and on its row's
+ *     stems and gains only: it is bitwise reproducible and independent of R, of the other rows, of the other bands and of every
+ *     sample further than n_fft/2 outside the centres of its own frames.
+ *   dam_specdist_sums: two launches (frames: one workgroup per frame transforms the reference frame once and then every row's;
+ *     cells).  workspace: dam_specdist_workspace_bytes(R, n, n_fft, hop, B, W) = 16 R T B bytes (the records), 16-byte aligned;
+ *     0 for arguments the entry refuses.
+ *   dam_specdist_summary: one launch; out device float64 [R][1 + B + W][3] = (mse, bias, rms_centred) of the whole row (index
+ *     0), of every band (1 + b) and of every window (1 + B + w).  S1, S2, N are the sums of a figure's cells from +0.0: a band adds
+ *     its cells in ascending window, a window in ascending band, and the row adds its bands' sums in ascending band.
+ *     mse = S2 / N (dB^2, the criterion),  bias = S1 / N (dB),  rms_centred =
+ *     sqrt(max(0, mse - bias*bias)) (dB; it does not move under a common gain wherever both levels are above the floor).
+ *     N = 0: all three NaN.
+ *   Argument errors (a NULL pointer other than gains / ref_gains; R outside 1 .. 65535; no stem; channels not 1 or 2; n_fft not a
+ *     power of two in 64 .. 16384; hop < 1; n <= n_fft/2; gains with n_gains < 1 or > n; amin not above 0; B outside
+ *     1 .. dam_spectrum_max_bands(); W outside 1 .. n; a window without a frame) return DAM_ERR_BAD_ARG before any launch.
+ * Not covered: a gradient in the gains, per-channel distances, perceptual (mel / loudness-weighted) bins.
+ * --------------------------------------------------------------------------------- */
+int64_t dam_specdist_workspace_bytes(int n_rows, int64_t n_samples, int n_fft, int hop, int n_bands, int n_windows);
+int dam_specdist_sums(const void* x, int x_is_f64, int n_rows, int n_stems, int channels, int64_t n_samples,
+                      int64_t stem_stride, int64_t sample_stride, int64_t channel_stride, const double* gains, int n_gains,
+                      const void* ref, int ref_is_f64, int ref_stems, int ref_channels, int64_t ref_stem_stride,
+                      int64_t ref_sample_stride, int64_t ref_channel_stride, const double* ref_gains, int ref_n_gains,
+                      const float* window, const float* twiddles, int n_fft, int hop, float amin, const int32_t* edges,
+                      int n_bands, int n_windows, double* sums, int64_t* count, void* workspace, void* stream);
+int dam_specdist_summary(const double* sums, const int64_t* count, int n_rows, int n_bands, int n_windows, double* out,
+                         void* stream);
 
 /* ---------------------------------------------------------------------------------
  * Alignment (ABI 28): the time offset of every stem against a mix by block cross-correlation, and the sample shift that removes
