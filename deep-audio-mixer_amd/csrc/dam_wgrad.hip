@@ -305,12 +305,21 @@ struct PendingDirect {
     float* dw[WD_MAX_JOBS];
     WgradReduce red[WD_MAX_JOBS];
 };
+// stride-1 row-kernel launches of one instantiation, geometry and grid recorded, not yet launched (batching mode 2)
+struct PendingRows {
+    WgradPlan plan;                          // as planned for every job: instantiation, RowsGeo, grid, LDS bytes
+    RowsJobs jobs;                           // jobs.njobs == 0: nothing pending
+    float* dw[ROWS_MAX_JOBS];
+    WgradReduce red[ROWS_MAX_JOBS];
+};
 struct WgradQueue {
     unsigned magic;
-    int batching;                            // 1: same-geometry tile launches may wait for each other until the flush
+    int batching;                            // 1: tile launches of one geometry and direct launches wait for each other until the flush;
+                                             // 2: so do the row kernel's launches of the next call
     ReduceBatch batch;
     PendingTile pend;
     PendingDirect pend_direct;
+    PendingRows pend_rows;
 };
 constexpr unsigned WGRAD_QUEUE_MAGIC = 0x57475251u;     // "WGRQ"
 
@@ -392,10 +401,7 @@ template <int D> __device__ __forceinline__ int rw_mod(int v) { return D == 10 ?
 // begins ~7 k clocks after the first when all CUs start at once); the narrow stages' few planes per slot do not need eight loaders,
 // and at eight waves per workgroup two workgroups really are co-resident on a CU (107 registers x 16 waves).
 template <int TNB, int TKB, int STEPS, int KP, int GPP, int HV, int NL>
-__global__ __launch_bounds__(256 + 64 * NL) void wgrad_rows_kernel(const RowsGeo g, const float* __restrict__ X,
-                                                                const float* __restrict__ dY, const float* __restrict__ in_scale,
-                                                                const float* __restrict__ in_shift, int relu_in,
-                                                                float* __restrict__ partial) {
+__global__ __launch_bounds__(256 + 64 * NL) void wgrad_rows_kernel(const RowsGeo g, const RowsJobs jobs) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     constexpr int NBLK = TNB * TKB * 9;
     constexpr int RPS = 4 / HV, RW_NRX = 2 * RPS + 2, RW_NRD = 2 * RPS;     // rows per slot; ring rows (in use + being written)
@@ -418,7 +424,7 @@ __global__ __launch_bounds__(256 + 64 * NL) void wgrad_rows_kernel(const RowsGeo
     const int img = by / g.spi, sidx = by - img * g.spi;
     const int r_begin = (int)(((long long)sidx * g.H) / g.spi), r_end = (int)(((long long)(sidx + 1) * g.H) / g.spi);
     const int n_slots = (r_end - r_begin + RPS - 1) / RPS;
-    const int n_slots2 = (n_slots + 1) & ~1;
+    const int n_slots2 = n_slots > 0 ? (n_slots + 1) & ~1 : 2;       // (>= 2: the loaders' last pair of slots stands outside their loop)
     const int ROWB = g.P4 * 64;
     const int XPLANE = RW_NRX * ROWB, DPLANE = RW_NRD * ROWB;
     const int XBASE = RW_GUARD, DBASE = XBASE + TKB * XPLANE;
@@ -442,9 +448,38 @@ __global__ __launch_bounds__(256 + 64 * NL) void wgrad_rows_kernel(const RowsGeo
             *reinterpret_cast<float4*>(smem + lds_bytes - RW_TAIL + e) = make_float4(0.f, 0.f, 0.f, 0.f);                  \
     } while (0)
 
-    v4f acc[NBLK];
-#pragma unroll
-    for (int i = 0; i < NBLK; ++i) acc[i] = (v4f){0.f, 0.f, 0.f, 0.f};
+    // Jobs: the weight gradients of one launch (one geometry, one grid: jobs.njobs of them, see launch_pending_rows).  The workgroup
+    // keeps its (tile, strip) and walks them in order: waves started, lane offsets and column masks computed once; per job the
+    // accumulators start at zero and the combine below leaves one slab in the job's buffer -- arithmetic, strips and slot order of
+    // a job are those of a launch of its own, so its slabs are bitwise the same.  A job boundary costs the slab write-out, not a
+    // launch, a wave start and a cold ring: the loaders ask for the next job's first rows (registers only) during the current
+    // job's last two slots and commit them once the combine's scratch -- it aliases the ring base -- has been read out.  The
+    // scratch runs over padding cells and the front guard, so DAM_RW_ZERO runs per job (a few hundred 16-byte stores).  Both roles
+    // carry the job loop themselves (and the combine's barriers): the loaders' register sets must not be live in the MFMA stream.
+    const int njobs = jobs.njobs;
+    const size_t img_off = (size_t)img * g.H * g.W * g.C;
+#define DAM_RW_BARRIER() asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory")
+    // one slab per workgroup and job out of the combine's scratch; MORE_: another job follows -- its first rows go where the
+    // scratch is, so every wave's reads of it must have returned (the stores may still be on their way)
+#ifdef DAM_WGR_STAMPS
+#define DAM_RW_WRITEOUT(PARTIAL_, MORE_)                                                                                   \
+    do {                                                                                                                   \
+        float4* out_ = reinterpret_cast<float4*>(PARTIAL_) + ((size_t)by * gridDim.x + bx) * NBLK * 64;                    \
+        DAM_WSTAMP(8);                                                                                                     \
+        if (lane == 0 && (wave == 0 || wave == 4)) {                                                                       \
+            unsigned long long* sp = reinterpret_cast<unsigned long long*>(out_) + (wave >> 2) * 32;                       \
+            for (int i = 0; i < 32; ++i) sp[i] = stamp_v[i];                                                               \
+        }                                                                                                                  \
+        if (MORE_) DAM_RW_BARRIER();                                                                                       \
+    } while (0)
+#else
+#define DAM_RW_WRITEOUT(PARTIAL_, MORE_)                                                                                   \
+    do {                                                                                                                   \
+        float4* out_ = reinterpret_cast<float4*>(PARTIAL_) + ((size_t)by * gridDim.x + bx) * NBLK * 64;                    \
+        for (int e = tid; e < NBLK * 64; e += (256 + 64 * NL)) out_[e] = reinterpret_cast<const float4*>(smem)[e];         \
+        if (MORE_) DAM_RW_BARRIER();                                                                                       \
+    } while (0)
+#endif
 #ifdef DAM_WGR_STAMPS
     unsigned long long stamp_v[32];
     int stamp_n = 0;
@@ -467,31 +502,19 @@ __global__ __launch_bounds__(256 + 64 * NL) void wgrad_rows_kernel(const RowsGeo
             cmask[gi] = __ballot(ok);
         }
         const int img_bytes = g.H * g.W * g.C * 4;
-        const __amdgpu_buffer_rsrc_t xrsrc =
-            __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(X) + (size_t)img * g.H * g.W * g.C, 0, img_bytes, 0x00020000);
-        const __amdgpu_buffer_rsrc_t drsrc =
-            __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(dY) + (size_t)img * g.H * g.W * g.C, 0, img_bytes, 0x00020000);
         const int lane16 = lane * 16;
         const v4f zero4 = {0.f, 0.f, 0.f, 0.f};
-        const float relu_lo = relu_in ? 0.f : -__builtin_inff();
-        const v4f relu_lo4 = {relu_lo, relu_lo, relu_lo, relu_lo};
-        // fused input affine on the X planes (the producer's BatchNorm + ReLU): a lane holds channel quad (lane & 3) of a cell
-        const bool has_aff = in_scale != nullptr;
-        v4f scq[TKB], shq[TKB];
-#pragma unroll
-        for (int kb = 0; kb < TKB; ++kb) {
-            const int ch = (tk * TKB + kb) * 16 + (lane & 3) * 4;
-            scq[kb] = has_aff ? *reinterpret_cast<const v4f*>(in_scale + ch) : (v4f){1.f, 1.f, 1.f, 1.f};
-            shq[kb] = has_aff ? *reinterpret_cast<const v4f*>(in_shift + ch) : (v4f){0.f, 0.f, 0.f, 0.f};
-        }
         v4f lv[KP][GPP];
         int dst[KP];               // scalar: LDS byte offset of the plane | 1 << 30 (row outside the image: zeros), -1 = none
         int aff[KP], aff2[KP];     // scalar: chunk index kb of an X plane that gets the input affine, -1 other X, -2 dY
         const int rowstride = g.W * g.C * 4;
         // X rows xr0 .. xr0+nx-1 (in-channel chunks of this tile) then dY rows dr0 .. dr0+nd-1 (out-channel blocks), one
         // plane = one (row, 16 channels); loader wave cwl takes planes cwl, cwl+4, ...  Loads are unconditional (clamped).
-#define DAM_RW_REQUEST(XR0_, NX_, DR0_, ND_, LV_, DST_, KP_, AFF_)                                                  \
+        // XP_ / DP_: this image of the job's X / dY; HA_: that job has an input affine.
+#define DAM_RW_REQUEST(XP_, DP_, HA_, XR0_, NX_, DR0_, ND_, LV_, DST_, KP_, AFF_)                                         \
     do {                                                                                                                   \
+        const __amdgpu_buffer_rsrc_t xrsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(XP_), 0, img_bytes, 0x00020000); \
+        const __amdgpu_buffer_rsrc_t drsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(DP_), 0, img_bytes, 0x00020000); \
         _Pragma("unroll") for (int k = 0; k < KP_; ++k) {                                                                  \
             const int pl_ = cwl + NL * k;                                                                          \
             const int nxp_ = (NX_) * TKB;                                                                                  \
@@ -515,7 +538,7 @@ __global__ __launch_bounds__(256 + 64 * NL) void wgrad_rows_kernel(const RowsGeo
                     LV_[k][gi] = __builtin_bit_cast(v4f, __builtin_amdgcn_raw_buffer_load_b128(drsrc, loffb[gi], soff_, 0)); \
             }                                                                                                              \
             DST_[k] = need_ ? (ldsoff_ | (inimg_ ? 0 : 1 << 30)) : -1;                                                     \
-            AFF_[k] = (isx_ && has_aff) ? c_ : (isx_ ? -1 : -2);                                                           \
+            AFF_[k] = (isx_ && (HA_)) ? c_ : (isx_ ? -1 : -2);                                                             \
         }                                                                                                                  \
     } while (0)
 #define DAM_RW_WRITE(ADDR_, DATA_, GI_)                                                                                    \
@@ -542,43 +565,85 @@ __global__ __launch_bounds__(256 + 64 * NL) void wgrad_rows_kernel(const RowsGeo
             }                                                                                                              \
         }                                                                                                                  \
     } while (0)
-        // rows of slot 0: X rows r_begin-1 .. r_begin+RPS, dY rows r_begin .. r_begin+RPS-1: both rounds requested up front
         constexpr int KPB = (2 * TKB + NL - 1) / NL;
-        v4f lvb[KPB][GPP], lv2[KP][GPP];
-        int dstb[KPB], dst2[KP], affb[KPB];
+        static_assert(KPB <= KP, "the second round of slot 0 fits a register set");
+        v4f lv2[KP][GPP];
+        int dst2[KP];
         DAM_WSTAMP(9);                                                         // setup done
-        DAM_RW_REQUEST(r_begin - 1, RPS, r_begin, RPS, lv, dst, KP, aff);
-        DAM_RW_REQUEST(r_begin + RPS - 1, 2, r_begin, 0, lvb, dstb, KPB, affb);
+        // rows of slot 0 of a job: X rows r_begin-1 .. r_begin+RPS, dY rows r_begin .. r_begin+RPS-1, both rounds up front: the
+        // first RPS X rows and the dY rows in set lv, the other two X rows in the first KPB planes of set lv2
+#define DAM_RW_SLOT0_A(XP_, DP_, HA_) DAM_RW_REQUEST(XP_, DP_, HA_, r_begin - 1, RPS, r_begin, RPS, lv, dst, KP, aff)
+#define DAM_RW_SLOT0_B(XP_, DP_, HA_) DAM_RW_REQUEST(XP_, DP_, HA_, r_begin + RPS - 1, 2, r_begin, 0, lv2, dst2, KPB, aff2)
+        // the first job's (a later job's are requested inside the job in front of it)
+        DAM_RW_SLOT0_A(jobs.job[0].X + img_off, jobs.job[0].dY + img_off, jobs.job[0].in_scale != nullptr);
+        DAM_RW_SLOT0_B(jobs.job[0].X + img_off, jobs.job[0].dY + img_off, jobs.job[0].in_scale != nullptr);
         DAM_WSTAMP(10);                                                        // first rows requested
-        DAM_RW_ZERO();
-        DAM_WSTAMP(11);                                                        // padding cells cleared
-        DAM_RW_COMMIT(lv, dst, KP, aff);
-        DAM_RW_COMMIT(lvb, dstb, KPB, affb);
-        DAM_WSTAMP(12);                                                        // first rows written (their loads have landed)
-        // the compute waves start slot 0 HERE; the requests for slots 1 and 2 follow (in front of this barrier they held the
-        // first MFMA back by 5-8 k clocks: with three slots of rows wanted by 256 CUs at once the request queue backs up)
-        asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-        // steady state, two slots ahead (HBM latency under this load is about one slot): slot s writes the rows slot s+1
-        // adds (X rows r_begin+RPS(s+1)+1 .. +RPS, dY rows r_begin+RPS(s+1) .. +RPS-1; requested during slot s-1) and
-        // requests those of slot s+3.  Two register sets alternate; slots come in pairs so that no load sits inside a
-        // conditional.
-#define DAM_RW_SLOT(T_, LV_, DST_, AFF_) DAM_RW_REQUEST(r_begin + RPS * (T_) + 1, RPS, r_begin + RPS * (T_), RPS, LV_, DST_, KP, AFF_)
-        DAM_WSTAMP(2);
-        DAM_RW_SLOT(1, lv, dst, aff);
-        DAM_RW_SLOT(2, lv2, dst2, aff2);
-        for (int s = 0; s < n_slots2; s += 2) {
+        for (int job = 0; job < njobs; ++job) {
+            const RowsJob& J = jobs.job[job];
+            const bool more = job + 1 < njobs;
+            const float* const Xc = J.X + img_off;
+            const float* const Dc = J.dY + img_off;
+            const float relu_lo = J.relu_in ? 0.f : -__builtin_inff();
+            const v4f relu_lo4 = {relu_lo, relu_lo, relu_lo, relu_lo};
+            // fused input affine on the X planes (the producer's BatchNorm + ReLU): a lane holds channel quad (lane & 3) of a cell
+            const bool has_aff = J.in_scale != nullptr;
+            v4f scq[TKB], shq[TKB];
+#pragma unroll
+            for (int kb = 0; kb < TKB; ++kb) {
+                const int ch = (tk * TKB + kb) * 16 + (lane & 3) * 4;
+                scq[kb] = has_aff ? *reinterpret_cast<const v4f*>(J.in_scale + ch) : (v4f){1.f, 1.f, 1.f, 1.f};
+                shq[kb] = has_aff ? *reinterpret_cast<const v4f*>(J.in_shift + ch) : (v4f){0.f, 0.f, 0.f, 0.f};
+            }
+            DAM_RW_ZERO();
+            DAM_WSTAMP(11);                                                    // padding cells cleared
             DAM_RW_COMMIT(lv, dst, KP, aff);
-            DAM_RW_SLOT(s + 3, lv, dst, aff);
+            DAM_RW_COMMIT(lv2, dst2, KPB, aff2);
+            DAM_WSTAMP(12);                                                    // first rows written (their loads have landed)
+            // the compute waves start slot 0 HERE; the requests for slots 1 and 2 follow (in front of this barrier they held the
+            // first MFMA back by 5-8 k clocks: with three slots of rows wanted by 256 CUs at once the request queue backs up)
+            DAM_RW_BARRIER();
+            // steady state, two slots ahead (HBM latency under this load is about one slot): slot s writes the rows slot s+1
+            // adds (X rows r_begin+RPS(s+1)+1 .. +RPS, dY rows r_begin+RPS(s+1) .. +RPS-1; requested during slot s-1) and
+            // requests those of slot s+3.  Two register sets alternate; slots come in pairs so that no steady-state load sits
+            // inside a conditional.  The last pair stands apart: it has nothing left to ask for of its own job, so each set, once
+            // committed, takes its round of the NEXT job's slot 0 where there is one (registers only: the ring is the current
+            // job's until the combine is over).
+#define DAM_RW_SLOT(T_, LV_, DST_, AFF_) \
+    DAM_RW_REQUEST(Xc, Dc, has_aff, r_begin + RPS * (T_) + 1, RPS, r_begin + RPS * (T_), RPS, LV_, DST_, KP, AFF_)
+            DAM_WSTAMP(2);
+            DAM_RW_SLOT(1, lv, dst, aff);
+            DAM_RW_SLOT(2, lv2, dst2, aff2);
+            for (int s = 0; s + 2 < n_slots2; s += 2) {
+                DAM_RW_COMMIT(lv, dst, KP, aff);
+                DAM_RW_SLOT(s + 3, lv, dst, aff);
+                DAM_WSTAMP(5);
+                DAM_RW_BARRIER();
+                DAM_WSTAMP(7);
+                DAM_RW_COMMIT(lv2, dst2, KP, aff2);
+                DAM_RW_SLOT(s + 4, lv2, dst2, aff2);
+                DAM_WSTAMP(5);
+                DAM_RW_BARRIER();
+                DAM_WSTAMP(7);
+            }
+            const RowsJob& Jn = jobs.job[more ? job + 1 : job];
+            DAM_RW_COMMIT(lv, dst, KP, aff);
+            if (more) DAM_RW_SLOT0_A(Jn.X + img_off, Jn.dY + img_off, Jn.in_scale != nullptr);
             DAM_WSTAMP(5);
-            asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+            DAM_RW_BARRIER();
             DAM_WSTAMP(7);
             DAM_RW_COMMIT(lv2, dst2, KP, aff2);
-            DAM_RW_SLOT(s + 4, lv2, dst2, aff2);
+            if (more) DAM_RW_SLOT0_B(Jn.X + img_off, Jn.dY + img_off, Jn.in_scale != nullptr);
             DAM_WSTAMP(5);
-            asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+            DAM_RW_BARRIER();
             DAM_WSTAMP(7);
-        }
 #undef DAM_RW_SLOT
+            // the combine of the compute waves (below): its barriers, then this wave's share of the slab
+#pragma unroll
+            for (int w = 0; w < 4; ++w) DAM_RW_BARRIER();
+            DAM_RW_WRITEOUT(J.partial, more);
+        }
+#undef DAM_RW_SLOT0_A
+#undef DAM_RW_SLOT0_B
 #undef DAM_RW_REQUEST
 #undef DAM_RW_WRITE
 #undef DAM_RW_COMMIT
@@ -586,9 +651,6 @@ __global__ __launch_bounds__(256 + 64 * NL) void wgrad_rows_kernel(const RowsGeo
         // ================================ compute waves ================================
         const int cw = wave;
         const int lane_b = kq * 64 + j * 4;       // lane group kq owns cell 4t + kq of step t, lane j channel j of the cell
-        DAM_RW_ZERO();
-        asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");       // rows of slot 0 are in LDS, padding cleared
-        DAM_WSTAMP(2);
         // operand reads of step t + 1 against the MFMAs of step t: one read behind each of the first MFMAs (as a burst in front
         // of them the launch is 1.3-1.6 us slower: the pipe drains while seven reads issue).  MFMAs between two operand reads:
         // 2 measured -1.1 us on the four-loader 129x17 kernel, +0.5 us on the others
@@ -636,55 +698,55 @@ __global__ __launch_bounds__(256 + 64 * NL) void wgrad_rows_kernel(const RowsGeo
             DAM_RW_SCHED();                                                                                                \
         }                                                                                                                  \
     } while (0)
-        for (int s = 0; s < n_slots2; ++s) {
-            const int rows_here = r_end - (r_begin + RPS * s);                // rows of this slot (<= 0: none)
-            // a strip's last row: every fourth step per wave.  Only for the one-block tile: with 18 accumulator blocks a second
-            // copy of the MFMA stream -- unrolled, rolled, or the same copy with an early exit (which halves its speed) -- makes
-            // the register allocator spill (168 registers at three waves per SIMD)
-            if (HV == 1 && TNB * TKB == 1 && rows_here == 1) {
-                DAM_RW_ROW(4, 0, cw * 256, cw);
-            } else {
-                const int rw = cw / HV, half = cw - rw * HV;                  // row of the slot, part of the row
-                if (rw < rows_here) DAM_RW_ROW(1, rw, half * STEPS * 256, 0);
+        for (int job = 0; job < njobs; ++job) {
+            v4f acc[NBLK];
+#pragma unroll
+            for (int i = 0; i < NBLK; ++i) acc[i] = (v4f){0.f, 0.f, 0.f, 0.f};
+            DAM_RW_ZERO();
+            DAM_RW_BARRIER();                                                     // rows of slot 0 are in LDS, padding cleared
+            DAM_WSTAMP(2);
+            for (int s = 0; s < n_slots2; ++s) {
+                const int rows_here = r_end - (r_begin + RPS * s);                // rows of this slot (<= 0: none)
+                // a strip's last row: every fourth step per wave.  Only for the one-block tile: with 18 accumulator blocks a second
+                // copy of the MFMA stream -- unrolled, rolled, or the same copy with an early exit (which halves its speed) -- makes
+                // the register allocator spill (168 registers at three waves per SIMD)
+                if (HV == 1 && TNB * TKB == 1 && rows_here == 1) {
+                    DAM_RW_ROW(4, 0, cw * 256, cw);
+                } else {
+                    const int rw = cw / HV, half = cw - rw * HV;                  // row of the slot, part of the row
+                    if (rw < rows_here) DAM_RW_ROW(1, rw, half * STEPS * 256, 0);
+                }
+                DAM_WSTAMP(5);
+                DAM_RW_BARRIER();
+                DAM_WSTAMP(7);
             }
-            DAM_WSTAMP(5);
-            asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-            DAM_WSTAMP(7);
+            // combine the 4 compute waves through LDS (sequential adds: fixed order), one slab per workgroup and job; the last
+            // slot's barrier is behind every wave's ring reads
+            float* red = reinterpret_cast<float*>(smem);
+            for (int w = 0; w < 4; ++w) {
+                if (cw == w) {
+#pragma unroll
+                    for (int i = 0; i < NBLK; ++i) {
+                        float4* d4 = reinterpret_cast<float4*>(red + (i * 64 + lane) * 4);
+                        if (w == 0) {
+                            *d4 = make_float4(acc[i].x, acc[i].y, acc[i].z, acc[i].w);
+                        } else {
+                            float4 o = *d4;
+                            o.x += acc[i].x; o.y += acc[i].y; o.z += acc[i].z; o.w += acc[i].w;
+                            *d4 = o;
+                        }
+                    }
+                }
+                DAM_RW_BARRIER();
+            }
+            DAM_RW_WRITEOUT(jobs.job[job].partial, job + 1 < njobs);
         }
     }
 #undef DAM_RW_ROW
 #undef DAM_RW_LOAD
 #undef DAM_RW_SCHED
-
-    // combine the 4 compute waves through LDS (sequential adds: fixed order), one slab per workgroup
-    __syncthreads();
-    float* red = reinterpret_cast<float*>(smem);
-    for (int w = 0; w < 4; ++w) {
-        if (wave == w) {
-#pragma unroll
-            for (int i = 0; i < NBLK; ++i) {
-                float4* d4 = reinterpret_cast<float4*>(red + (i * 64 + lane) * 4);
-                if (w == 0) {
-                    *d4 = make_float4(acc[i].x, acc[i].y, acc[i].z, acc[i].w);
-                } else {
-                    float4 o = *d4;
-                    o.x += acc[i].x; o.y += acc[i].y; o.z += acc[i].z; o.w += acc[i].w;
-                    *d4 = o;
-                }
-            }
-        }
-        __syncthreads();
-    }
-    float4* out = reinterpret_cast<float4*>(partial) + ((size_t)by * gridDim.x + bx) * NBLK * 64;
-#ifdef DAM_WGR_STAMPS
-    DAM_WSTAMP(8);
-    if (lane == 0 && (wave == 0 || wave == 4)) {
-        unsigned long long* sp = reinterpret_cast<unsigned long long*>(out) + (wave >> 2) * 32;
-        for (int i = 0; i < 32; ++i) sp[i] = stamp_v[i];
-    }
-#else
-    for (int e = tid; e < NBLK * 64; e += (256 + 64 * NL)) out[e] = reinterpret_cast<const float4*>(red)[e];
-#endif
+#undef DAM_RW_WRITEOUT
+#undef DAM_RW_BARRIER
 }
 
 #undef DAM_RW_ZERO
@@ -1063,21 +1125,70 @@ bool same_inst(const WgradLaunchNote& a, const WgradLaunchNote& b) { return a.TN
 // The one write of the record: where a launcher has passed its last refusal, before it launches (or records the launch).
 void commit(const WgradPlan& p) { wgrad_last_launch = p.note; }
 
-int launch_rows(const WgradPlan& p, const WgradOperands& a, void* queue, hipStream_t st) {
-    const WgradLaunchNote& n = p.note;
-    auto match = [&](int i) {
-        const RowsInst& t = ROWS_INST[i];
-        return n.TNB == t.TNB && n.TKB == t.TKB && n.STEPS == t.STEPS && n.KP == t.KP && n.GPP == t.GPP && n.HV == t.HV && n.NL == t.NL;
-    };
-    return with_inst<ROWS_INST_N>(match, [&](auto I) -> int {
+bool rows_inst_is(const WgradLaunchNote& n, int i) {
+    const RowsInst& t = ROWS_INST[i];
+    return n.TNB == t.TNB && n.TKB == t.TKB && n.STEPS == t.STEPS && n.KP == t.KP && n.GPP == t.GPP && n.HV == t.HV && n.NL == t.NL;
+}
+// The LDS limit of the note's row instantiation, raised.
+int rows_lds_ready(const WgradLaunchNote& n) {
+    return with_inst<ROWS_INST_N>([&](int i) { return rows_inst_is(n, i); }, [&](auto I) -> int {
         constexpr RowsInst t = ROWS_INST[I];
-        if (!raise_lds_limit<&wgrad_rows_kernel<t.TNB, t.TKB, t.STEPS, t.KP, t.GPP, t.HV, t.NL>>(160 * 1024)) return DAM_ERR_LAUNCH;
-        commit(p);
-        hipLaunchKernelGGL((wgrad_rows_kernel<t.TNB, t.TKB, t.STEPS, t.KP, t.GPP, t.HV, t.NL>), dim3(p.nx, p.nsplit), dim3(256 + 64 * t.NL),
-                           p.lds, st, p.rows, a.x, a.dy, a.in_scale, a.in_shift, p.relu_in, a.workspace);
-        DAM_CHECK_LAUNCH();
-        return reduce_submit(queue, a.workspace, a.dw, p.nsplit, p.nx, p.red, st);
+        return raise_lds_limit<&wgrad_rows_kernel<t.TNB, t.TKB, t.STEPS, t.KP, t.GPP, t.HV, t.NL>>(160 * 1024) ? DAM_OK : DAM_ERR_LAUNCH;
     });
+}
+// One launch of the row kernel for the jobs of the table (plan p: instantiation, geometry and grid of every one).
+int launch_rows_jobs(const WgradPlan& p, const RowsJobs& jobs, hipStream_t st) {
+    return with_inst<ROWS_INST_N>([&](int i) { return rows_inst_is(p.note, i); }, [&](auto I) -> int {
+        constexpr RowsInst t = ROWS_INST[I];
+        hipLaunchKernelGGL((wgrad_rows_kernel<t.TNB, t.TKB, t.STEPS, t.KP, t.GPP, t.HV, t.NL>), dim3(p.nx, p.nsplit), dim3(256 + 64 * t.NL),
+                           p.lds, st, p.rows, jobs);
+        DAM_CHECK_LAUNCH();
+        return DAM_OK;
+    });
+}
+
+// The recorded row launches of a queue, as one launch (and nothing pending afterwards, whatever the outcome), then their reductions.
+int launch_pending_rows(WgradQueue* q, hipStream_t st) {
+    PendingRows& p = q->pend_rows;
+    const int n = p.jobs.njobs;
+    p.jobs.njobs = 0;
+    if (n <= 0) return DAM_OK;
+    RowsJobs jobs = p.jobs;
+    jobs.njobs = n;
+    int rc = launch_rows_jobs(p.plan, jobs, st);
+    for (int i = 0; i < n && rc == DAM_OK; ++i) rc = reduce_submit(q, jobs.job[i].partial, p.dw[i], p.plan.nsplit, p.plan.nx, p.red[i], st);
+    return rc;
+}
+
+int launch_rows(const WgradPlan& p, const WgradOperands& a, void* queue, hipStream_t st) {
+    WgradQueue* q = static_cast<WgradQueue*>(queue);
+    if (q && q->magic != WGRAD_QUEUE_MAGIC) return DAM_ERR_BAD_ARG;
+    const int rc = rows_lds_ready(p.note);
+    if (rc != DAM_OK) return rc;
+    const RowsJob j{a.x, a.dy, a.in_scale, a.in_shift, a.workspace, p.relu_in, 0};
+    if (p.note.issued == WGRAD_LAUNCH_RECORDED) {
+        // record instead of launching: jobs of one instantiation, geometry and grid wait for each other until the queue is flushed,
+        // another kind arrives or the table is full; the caller keeps X, dY, the affine and the slabs valid until then
+        PendingRows& pr = q->pend_rows;
+        const WgradLaunchNote& o = pr.plan.note;
+        const bool same = o.TNB == p.note.TNB && o.TKB == p.note.TKB && o.STEPS == p.note.STEPS && o.KP == p.note.KP && o.GPP == p.note.GPP &&
+                          o.HV == p.note.HV && o.NL == p.note.NL && memcmp(&pr.plan.rows, &p.rows, sizeof(RowsGeo)) == 0 &&
+                          pr.plan.nx == p.nx && pr.plan.nsplit == p.nsplit && pr.plan.lds == p.lds;
+        if (pr.jobs.njobs > 0 && (pr.jobs.njobs == ROWS_MAX_JOBS || !same)) {
+            const int rc2 = launch_pending_rows(q, st);
+            if (rc2 != DAM_OK) return rc2;
+        }
+        const int i = pr.jobs.njobs++;
+        pr.plan = p; pr.jobs.job[i] = j; pr.dw[i] = a.dw; pr.red[i] = p.red;
+        commit(p);
+        return DAM_OK;
+    }
+    commit(p);
+    RowsJobs jobs;
+    memset(&jobs, 0, sizeof(jobs));
+    jobs.job[0] = j; jobs.njobs = 1;
+    const int rc1 = launch_rows_jobs(p, jobs, st);
+    return rc1 != DAM_OK ? rc1 : reduce_submit(queue, a.workspace, a.dw, p.nsplit, p.nx, p.red, st);
 }
 
 int launch_rows_s2(const WgradPlan& p, const WgradOperands& a, void* queue, hipStream_t st) {
@@ -1267,20 +1378,26 @@ extern "C" int dam_wgrad_queue_init(void* queue) {
 extern "C" int dam_wgrad_queue_set_batching(void* queue, int on) {
     dam::WgradQueue* q = static_cast<dam::WgradQueue*>(queue);
     if (!q || q->magic != dam::WGRAD_QUEUE_MAGIC) return DAM_ERR_BAD_ARG;
-    if (q->pend.njobs > 0 || q->pend_direct.jobs.njobs > 0) return DAM_ERR_BAD_ARG;          // flush first
-    q->batching = on ? 1 : 0;
+    if (on < 0 || on > 2) return DAM_ERR_BAD_ARG;
+    // between the two batching modes the queue may hold recorded launches (the mode says what becomes of the NEXT call; what is
+    // recorded runs at the flush either way); switching batching off or on needs an empty queue
+    const bool pending = q->pend.njobs > 0 || q->pend_direct.jobs.njobs > 0 || q->pend_rows.jobs.njobs > 0;
+    if (pending && (on == 0 || q->batching == 0)) return DAM_ERR_BAD_ARG;                      // flush first
+    q->batching = on;
     return DAM_OK;
 }
 
 extern "C" int dam_wgrad_queue_pending(const void* queue) {
     const dam::WgradQueue* q = static_cast<const dam::WgradQueue*>(queue);
-    return q && q->magic == dam::WGRAD_QUEUE_MAGIC ? q->batch.njobs + q->pend.njobs + q->pend_direct.jobs.njobs : -1;
+    return q && q->magic == dam::WGRAD_QUEUE_MAGIC ? q->batch.njobs + q->pend.njobs + q->pend_direct.jobs.njobs + q->pend_rows.jobs.njobs
+                                                   : -1;
 }
 
 extern "C" int dam_wgrad_queue_flush(void* queue, void* stream) {
     dam::WgradQueue* q = static_cast<dam::WgradQueue*>(queue);
     if (!q || q->magic != dam::WGRAD_QUEUE_MAGIC) return DAM_ERR_BAD_ARG;
-    int rc = dam::launch_pending_tile(q, (hipStream_t)stream);
+    int rc = dam::launch_pending_rows(q, (hipStream_t)stream);
+    if (rc == DAM_OK) rc = dam::launch_pending_tile(q, (hipStream_t)stream);
     if (rc == DAM_OK) rc = dam::launch_pending_direct(q, (hipStream_t)stream);
     return rc != DAM_OK ? rc : dam::reduce_flush(q->batch, (hipStream_t)stream);
 }
@@ -1307,7 +1424,7 @@ extern "C" int dam_conv2d_wgrad_plan(int B, int H, int W, int C, int in_nchw, in
     WgradPlan plan{};
     const WgradRequest rq{B, H, W, C, in_nchw, relu_in, Ho, Wo, n_chan, n_out, kh, kw, stride, pad, dil, c_real, has_affine != 0,
                           has_shift != 0, workspace_floats, queue_mode};
-    const int rc = queue_mode < 0 || queue_mode > 2 ? DAM_ERR_BAD_ARG : plan_wgrad(rq, plan);
+    const int rc = !wgrad_queue_mode_ok(queue_mode) ? DAM_ERR_BAD_ARG : plan_wgrad(rq, plan);
     note_to_ints(plan.note, out16_host);     // (all zero on any refusal)
     return rc;
 }
@@ -1322,7 +1439,8 @@ extern "C" int dam_conv2d_wgrad_f32(const float* x, int B, int H, int W, int C, 
     // (a queue that is none -- wrong magic -- plans as one without batching and is refused by the launcher)
     const WgradQueue* q = static_cast<const WgradQueue*>(reduce_queue);
     const WgradRequest rq{B, H, W, C, in_nchw, relu_in, Ho, Wo, n_chan, n_out, kh, kw, stride, pad, dil, c_real, in_scale != nullptr,
-                          in_shift != nullptr, workspace_floats, !q ? 0 : q->magic == WGRAD_QUEUE_MAGIC && q->batching ? 2 : 1};
+                          in_shift != nullptr, workspace_floats,
+                          !q ? 0 : q->magic != WGRAD_QUEUE_MAGIC || !q->batching ? 1 : q->batching == 2 ? 4 : 2};
     WgradPlan plan;
     const int rc = plan_wgrad(rq, plan);
     if (rc != DAM_OK) return rc;

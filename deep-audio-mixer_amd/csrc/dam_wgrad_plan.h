@@ -9,7 +9,8 @@
 namespace dam {
 
 // Everything the decision depends on: the scalar arguments of dam_conv2d_wgrad_f32, which optional operands are present, and what
-// the caller's queue does with the launch (0 no queue, 1 queue without batching, 2 batching queue).
+// the caller's queue does with the launch (0 no queue, 1 queue without batching, 2 batching queue, 4 batching queue that records
+// the stride-1 row kernel's launches too; 3 is no mode).
 struct WgradRequest {
     int B, H, W, C, in_nchw, relu_in, Ho, Wo, n_chan, n_out, kh, kw, stride, pad, dil, c_real;
     bool affine, shift;      // in_scale / in_shift given
@@ -60,6 +61,18 @@ struct DirectJob {
     int rows, Ho, Wo, H, W, C, N, s, pad, dil, tiles_k;
     int nx, nsplit, wg0;                     // the job's (nx, nsplit) grid and its first workgroup in the flat launch
 };
+// Stride-1 row kernel: the operands of one weight gradient, and the job table of one launch (a kernel argument).  All jobs of a
+// launch share one RowsGeo and one grid; a workgroup keeps its (tile, strip) and walks the jobs in order.
+struct RowsJob {
+    const float *X, *dY, *in_scale, *in_shift;
+    float* partial;
+    int relu_in, pad_;
+};
+constexpr int ROWS_MAX_JOBS = 8;             // stem + layer1 of a ResNet18 are five of one geometry; 8 x 48 B of kernel arguments
+struct RowsJobs {
+    RowsJob job[ROWS_MAX_JOBS];
+    int njobs;
+};
 constexpr int RW_LOADERS = 8;                 // loader waves (waves 4..11)
 constexpr int RW_THREADS = 256 + 64 * RW_LOADERS, RW_GUARD = 64, RW_TAIL = 1280;   // (tail: the step-split last slot prefetches up to 1 KB past a row)
 
@@ -95,6 +108,17 @@ constexpr RowsInst ROWS_INST[ROWS_INST_N] = {
     {2, 1, 5, 3, 2, 1, 4},   // 17-pixel rows (129x17 stage), four loader waves
     {2, 1, 3, 2, 1, 1, 8},   // 9-pixel rows (65x9 stage): 40.8 -> 32.1 us; narrower: tile kernel
 };
+// The instantiations whose launches a queue in mode 4 records and runs as one launch of up to ROWS_MAX_JOBS jobs (launch_pending_rows):
+// those whose one batched launch measured shorter than its launches alone (DESIGN.md section 4.3 has the ladder).
+constexpr bool ROWS_BATCHED[ROWS_INST_N] = {true, false, false, true, false, true, true, true};
+inline bool rows_batched(const RowsInst& t) {
+    for (int i = 0; i < ROWS_INST_N; ++i) {
+        const RowsInst& u = ROWS_INST[i];
+        if (u.TNB == t.TNB && u.TKB == t.TKB && u.STEPS == t.STEPS && u.KP == t.KP && u.GPP == t.GPP && u.HV == t.HV && u.NL == t.NL)
+            return ROWS_BATCHED[i];
+    }
+    return false;
+}
 // stride-2 row kernel <TN, steps, planes per loader wave, pieces per X plane, per dY plane, row parts>: the down-sampling
 // convolutions of the ResNet stages at 130 frames (65-, 33- and 17-pixel output rows) and at the reference's native 216 (54, 27)
 struct RowsS2Inst { int TNB, STEPS, KP, GPPX, GPPD, HV; };
@@ -113,8 +137,9 @@ constexpr TileInst TILE_INST[TILE_INST_N] = {{1, 1, 3, 3}, {2, 2, 3, 3}, {1, 1, 
 // ------------------------------------------------------------------------------------------------------------------ planners
 // One per family: DAM_OK and the plan, DAM_ERR_UNSUPPORTED (the layer does not fit the family) or DAM_ERR_WORKSPACE.
 inline int wgrad_issue(const WgradRequest& rq, bool recordable) {
-    return recordable && rq.queue_mode == 2 ? WGRAD_LAUNCH_RECORDED : rq.queue_mode ? WGRAD_REDUCTION_QUEUED : WGRAD_REDUCED_NOW;
+    return recordable && rq.queue_mode >= 2 ? WGRAD_LAUNCH_RECORDED : rq.queue_mode ? WGRAD_REDUCTION_QUEUED : WGRAD_REDUCED_NOW;
 }
+inline bool wgrad_queue_mode_ok(int m) { return m == 0 || m == 1 || m == 2 || m == 4; }
 
 // Strips of the two row kernels: `rows` output rows per image in spi nearly equal parts; false: the workspace holds not even one.
 inline bool plan_strips(int B, int rows, int RPS, int nx, int NBLK, size_t lds, int64_t ws_floats, int& spi_out, int& rps_out) {
@@ -155,7 +180,7 @@ inline int plan_rows(const WgradRequest& rq, const RowsInst& t, WgradPlan& p) {
     if (!plan_strips(rq.B, rq.H, RPS, nx, NBLK, lds, rq.workspace_floats, g.spi, g.rps)) return DAM_ERR_WORKSPACE;
     p.rows = g; p.nx = nx; p.nsplit = rq.B * g.spi; p.lds = lds;
     p.note = WgradLaunchNote{WGRAD_FAM_ROWS, t.TNB, t.TKB, t.STEPS, t.KP, t.GPP, 0, t.HV, t.NL, 0, 0, nx, p.nsplit, g.spi, g.rps,
-                             wgrad_issue(rq, false)};
+                             wgrad_issue(rq, rq.queue_mode == 4 && rows_batched(t))};
     p.red = WgradReduce{t.TNB, t.TKB, 3, 3, rq.n_out, 0, 3, 3, 1, g.tiles_k};
     return DAM_OK;
 }

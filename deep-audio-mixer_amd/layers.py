@@ -12,6 +12,14 @@ import torch.nn as nn
 
 from . import ops
 
+# The slotted 3x3 weight gradients of a stage (one geometry: stem + layer1 five, the other stages three each) wait for each other
+# and run as one launch of the row kernel (ops.conv2d_wgrad(batch_rows=True)).  What a recorded job reads until ops.wgrad_flush():
+# its x -- a saved activation or conv output, never written again --, its dy -- the fresh dx of a BatchNorm backward
+# (ops.bn_backward / bn_backward_pair allocate it; nothing accumulates into it: data gradients accumulate into the tensors
+# the dgrad kernels return) -- and the forward's BatchNorm scale and shift (written by the NEXT forward's statistics, after
+# the flush).  Tests switch it off to compare.
+WGRAD_ROWS_BATCH = True
+
 
 def _slot(p):
     """The parameter's slice of a flat gradient buffer, if an optimizer bound one (optim.Adam.bind_grad_slots): the
@@ -88,7 +96,7 @@ class ConvSpec:
         # before the optimizer, so its slab reduction joins the one launch of ops.wgrad_flush().  (On a second stream beside
         # the backward chain it measured slower: C3 5.57 -> 5.96 ms, profiles/r02_side_stream_trace_summary.txt)
         return ops.conv2d_wgrad(x, dy, self.cout, self.k, self.k, self.stride, self.pad, self.dil,
-                                in_nchw=self.in_nchw, out=out, defer=out is not None, **aff)
+                                in_nchw=self.in_nchw, out=out, defer=out is not None, batch_rows=WGRAD_ROWS_BATCH, **aff)
 
     def dgrad(self, dy, w, hw, **kw):
         return ops.conv2d_dgrad(dy, self.packed(w, transpose=True), self.cin, hw[0], hw[1], self.k, self.k,
@@ -111,7 +119,8 @@ class _Nhwc16Spec(ConvSpec):
 
     def wgrad(self, x, dy, in_affine=None, out=None):
         # only the real input planes are written ([cout, cin, 3, 3] = conv1.weight's shape): the zero-padded ones drop out
-        return ops.conv2d_wgrad(x, dy, self.cout, 3, 3, 1, 1, 1, out=out, c_real=self.parent.cin, defer=out is not None)
+        return ops.conv2d_wgrad(x, dy, self.cout, 3, 3, 1, 1, 1, out=out, c_real=self.parent.cin, defer=out is not None,
+                                batch_rows=WGRAD_ROWS_BATCH)
 
 
 class WeightPacker:

@@ -450,11 +450,15 @@ def _wgrad_call(x_shape, dy_shape, n_out, kh, kw, in_nchw, c_real):
 
 
 def conv2d_wgrad(x, dy, n_out, kh, kw, stride=1, pad=0, dil=1, in_scale=None, in_shift=None, relu_in=False,
-                 in_nchw=False, out=None, c_real=None, defer=False):
+                 in_nchw=False, out=None, c_real=None, defer=False, batch_rows=False):
     """dW in torch layout [n_out, c_real or C, kh, kw] from x (NHWC, or NCHW first layer) and dy NHWC [B,Ho,Wo,n16].
     out: where to write it (e.g. the parameter's slice of a flat gradient buffer).
     defer (needs out): only the slab kernel runs now; the reduction into `out` is recorded and happens in wgrad_flush(),
-    one launch for every weight gradient of the backward pass (each deferred call keeps its own slab buffer until then)."""
+    one launch for every weight gradient of the backward pass (each deferred call keeps its own slab buffer until then).
+    batch_rows (with defer): a call that takes the stride-1 row kernel is recorded as well and runs with the other recorded
+    calls of its instantiation and geometry as ONE launch -- when another kind arrives, when the job table is full or at
+    wgrad_flush() (dam_wgrad_queue_set_batching mode 2).  x, dy and the affine must then stay UNMODIFIED until the flush (the
+    queue keeps them alive, it cannot keep them from being written in place).  Without it such a call is launched at once."""
     _lib.require_cuda(x, dy)
     _f32c(x, 'x'), _f32c(dy, 'dy')
     B, H, W, C, Ho, Wo, n_chan, cr, floats = _wgrad_call(x.shape, dy.shape, n_out, kh, kw, in_nchw, c_real)
@@ -471,6 +475,8 @@ def conv2d_wgrad(x, dy, n_out, kh, kw, stride=1, pad=0, dil=1, in_scale=None, in
         q[1] += 1
         q[2].append((x, dy, in_scale, in_shift))
         queue = ctypes.addressof(q[0])
+        if WGRAD_BATCH:        # the mode is that of the NEXT call: row launches wait for each other only where the caller asked
+            _lib.check(L.dam_wgrad_queue_set_batching(queue, 2 if batch_rows else 1), 'dam_wgrad_queue_set_batching')
     else:
         ws, queue = _workspace(x.device, floats), None
     _lib.check(L.dam_conv2d_wgrad_f32(_lib.ptr(x), B, H, W, C, 1 if in_nchw else 0, _lib.ptr(in_scale),
@@ -495,7 +501,7 @@ def wgrad_last_launch():
     """Which kernel the last conv2d_wgrad call of this thread committed to (dam_wgrad_last_launch): the family by name, the
     template parameters of the instantiation (rows_s2: GPP is GPPX; direct: TA, TB are KH, KW), the grid (nx, nsplit), strips per
     image and rows per strip (row kernels) or pixels per tile (tile kernel), and how it was issued (0 launched and reduced now,
-    1 launched with the reduction queued, 2 the launch itself recorded for a batched launch at the flush); fields that do not
+    1 launched with the reduction queued, 2 the launch itself recorded for a batched launch at the flush or earlier); fields that do not
     belong to the family are 0.  Host-side only."""
     v = (ctypes.c_int * 16)()
     _lib.check(_lib.lib().dam_wgrad_last_launch(v), 'dam_wgrad_last_launch')
@@ -503,16 +509,16 @@ def wgrad_last_launch():
 
 
 def conv2d_wgrad_plan(x_shape, dy_shape, n_out, kh, kw, stride=1, pad=0, dil=1, affine=False, relu_in=False, in_nchw=False,
-                      c_real=None, defer=False, workspace_floats=None):
+                      c_real=None, defer=False, workspace_floats=None, batch_rows=False):
     """The WgradLaunch wgrad_last_launch() would report after conv2d_wgrad on tensors of these shapes, with in_scale and in_shift
     given (affine) or not: host arithmetic in the library (dam_conv2d_wgrad_plan), no tensors, no GPU.  defer: the call goes to
-    this package's queue; workspace_floats: None for the workspace conv2d_wgrad passes.  Raises where the call would be refused
+    this package's queue (batch_rows: as in conv2d_wgrad); workspace_floats: None for the workspace conv2d_wgrad passes.  Raises where the call would be refused
     for its arguments or its workspace."""
     B, H, W, C, Ho, Wo, n_chan, cr, floats = _wgrad_call(x_shape, dy_shape, n_out, kh, kw, in_nchw, c_real)
     v = (ctypes.c_int * 16)()
     _lib.check(_lib.lib().dam_conv2d_wgrad_plan(B, H, W, C, 1 if in_nchw else 0, 1 if relu_in else 0, Ho, Wo, n_chan, n_out, kh, kw,
                                                 stride, pad, dil, cr, 1 if affine else 0, 1 if affine else 0,
-                                                (2 if WGRAD_BATCH else 1) if defer else 0,
+                                                ((4 if batch_rows else 2) if WGRAD_BATCH else 1) if defer else 0,
                                                 floats if workspace_floats is None else int(workspace_floats), v),
                'dam_conv2d_wgrad_plan')
     return _wgrad_launch(v)

@@ -55,7 +55,7 @@ struct dam_bn_bwd_sums; /* defined in the BatchNorm section */
 /* Library / build identification ("gfx950").  DAM_ABI_VERSION is bumped whenever a signature below changes; a binding
  * compares dam_abi_version() of the library it loaded with the version it was written against and refuses a stale one
  * (deep-audio-mixer_amd/_lib.py: EXPECTED_ABI). */
-#define DAM_ABI_VERSION 34
+#define DAM_ABI_VERSION 35
 const char* dam_arch(void);
 int dam_abi_version(void);
 
@@ -408,7 +408,15 @@ int dam_wgrad_queue_flush(void* queue, void* stream);
  * to 8 of one instantiation with whatever geometries, as one flat launch whose jobs share the chip (each a fraction of the pixel
  * splits it would take alone).  Off by default.
  *   Contract while on: x, dy, in_scale / in_shift of a queued call must stay valid and unmodified until the flush as well
- *   (not only its workspace and dw).  Switching needs an empty queue (DAM_ERR_BAD_ARG otherwise). */
+ *   (not only its workspace and dw).  Switching needs an empty queue (DAM_ERR_BAD_ARG otherwise).
+ * on = 2 (ABI 35): as 1, and a call that takes the stride-1 ROW kernel is recorded too where its instantiation is in the batching
+ * table (dam_wgrad_plan.h: ROWS_BATCHED).  The 3x3 convolutions of a ResNet stage have one geometry (stem + layer1: five, the other
+ * stages three each); recorded, up to 8 of one instantiation, geometry and grid run as ONE launch whose workgroups keep their tile and
+ * strip and walk the jobs in order, the loader waves asking for the next job's first rows while the current job's last slots are
+ * multiplied: a job boundary costs a slab write-out instead of a launch, a wave start and a cold ring.  The slabs are bitwise those of
+ * launches of their own.  Recorded row launches run when another instantiation or geometry arrives, when the table is full, or at
+ * the flush.  The mode says what becomes of the NEXT call, so 1 <-> 2 may be switched with launches recorded (a caller that batches
+ * only some of its calls); to or from 0 still needs an empty queue.  Any other value: DAM_ERR_BAD_ARG. */
 int dam_wgrad_queue_set_batching(void* queue, int on);
 
 /* Which kernel the last dam_conv2d_wgrad_f32 call of the CALLING THREAD committed to (ABI 27): the entry point picks between four
@@ -433,7 +441,8 @@ int dam_wgrad_queue_set_batching(void* queue, int on);
 int dam_wgrad_last_launch(int* out16_host);
 /* The same answer BEFORE a call and without a GPU (ABI 32): the dispatch of dam_conv2d_wgrad_f32 is host arithmetic on its scalar
  * arguments, on which optional operands are given (has_affine: in_scale, has_shift: in_shift) and on what the queue does with the
- * launch (queue_mode: 0 no queue, 1 a queue without batching, 2 a batching queue).  out16_host receives the 16 ints
+ * launch (queue_mode: 0 no queue, 1 a queue without batching, 2 a batching queue, 4 a batching queue in mode 2: row launches
+ * recorded too; 3 is no mode: DAM_ERR_BAD_ARG).  out16_host receives the 16 ints
  * dam_wgrad_last_launch would report after that call; returns the status the launching call would return for everything that
  * needs no pointer and no device (DAM_ERR_BAD_ARG, DAM_ERR_UNSUPPORTED, DAM_ERR_WORKSPACE), with the 16 ints zero then. */
 int dam_conv2d_wgrad_plan(int B, int H, int W, int C, int in_nchw, int relu_in, int Ho, int Wo, int n_chan, int n_out, int kh, int kw,
