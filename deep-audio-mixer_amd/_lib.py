@@ -12,7 +12,7 @@ LIB_PATH = os.environ.get('DAM_LIB_PATH') or os.path.join(_HERE, 'libdam_hip.so'
 # include/dam_hip.h: bumped whenever a C signature changes (together with dam_abi_version() in csrc/dam_api.hip and
 # DAM_ABI_VERSION in the header).  libdam_hip.so is git-ignored and travels prebuilt: a stale one would read device pointers
 # as streams, so lib() refuses it instead of launching.
-EXPECTED_ABI = 35
+EXPECTED_ABI = 36
 
 _STATUS = {0: 'DAM_OK', -1: 'DAM_ERR_BAD_ARG', -2: 'DAM_ERR_UNSUPPORTED', -3: 'DAM_ERR_LAUNCH',
            -4: 'DAM_ERR_WORKSPACE'}
@@ -45,7 +45,7 @@ SIGNATURES = {
     'dam_conv_pack_weights_f32': (c_i, [c_p, c_i, c_i, c_i, c_i, c_i, c_p, c_p]),
     'dam_conv_pack_weights_multi_f32': (c_i, [c_p, c_i, c_i64, c_p]),
     'dam_conv2d_tapgrid_f32': (c_i, [c_p, c_i, c_i, c_i, c_i, c_i, c_p, c_i, c_i, c_p, c_p, c_p, c_i, c_i, c_p] +
-                               [c_i] * 17 + [c_p, c_p, c_p, c_p, c_p, c_p, c_i64, c_p, c_p]),
+                               [c_i] * 17 + [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i64, c_p, c_p]),
     'dam_conv_batch_bytes': (c_i64, []),
     'dam_conv_batch_init': (c_i, [c_p]),
     'dam_conv_batch_flush': (c_i, [c_p, c_p]),
@@ -77,6 +77,7 @@ SIGNATURES = {
     'dam_bn_stats_pair_f32': (c_i, [c_p, c_p, c_i64, c_i, c_p, c_p, c_p, c_p]),
     'dam_bn_pair_workspace_floats': (c_i64, [c_i]),
     'dam_bn_backward_pair_f32': (c_i, [c_p, c_p, c_p, c_i64, c_i, c_i] + [c_p] * 16),
+    'dam_bn_backward_finalize_f32': (c_i, [c_p, c_i, c_i64, c_i, c_p, c_p, c_p, c_i, c_p, c_p, c_p, c_p]),
     'dam_bn_backward_f32': (c_i, [c_p, c_p, c_p, c_i64, c_i, c_p, c_p, c_p, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_p]),
     'dam_channel_sum_f32': (c_i, [c_p, c_i64, c_i, c_i, c_p, c_p, c_p]),
     'dam_dropout_tick': (c_i, [c_p, c_i64, c_p, c_p]),
@@ -159,6 +160,11 @@ class BnFin(ctypes.Structure):
     """struct dam_bn_fin (include/dam_hip.h): device pointers of one BatchNorm's finalize (pair and finalize-apply entry points)."""
     _fields_ = [('gamma', c_p), ('beta', c_p), ('running_mean', c_p), ('running_var', c_p), ('num_batches_tracked', c_p),
                 ('momentum', c_f), ('eps', c_f), ('save_mean', c_p), ('save_invstd', c_p), ('scale', c_p), ('shift', c_p)]
+
+
+class BnBwdIn(ctypes.Structure):
+    """struct dam_bn_bwd_in (include/dam_hip.h): BatchNorm-backward apply in a data gradient's row loaders."""
+    _fields_ = [('c', c_p), ('coef', c_p), ('mask_scale', c_p), ('mask_shift', c_p), ('mask_bits', c_p), ('dc', c_p)]
 
 
 class BnBwdSums(ctypes.Structure):

@@ -637,6 +637,50 @@ __global__ __launch_bounds__(FA_THREADS) void bn_fin_apply_kernel(const float* _
     });
 }
 
+// The backward merge of one channel slice: records [parts][C][1 + NB] -> tab [NB][3][CS] = c1, c2, c3 of every side, and (where
+// `write_grads`) dgamma / dbeta.  One body for the fused launch's prologue and the finalize-only launch: the same sums in the
+// same order, so the two give the same bits.  The caller synchronises before it reads tab.
+template <int NB>
+__device__ __forceinline__ void bn_bwd_merge_slice(const float* __restrict__ partial, int parts, int C, int CS, int slice, double count,
+                                                   int training, const BnBwdSides<NB>& sd, double* red, float* tab, bool write_grads) {
+    constexpr int NR = 1 + NB;
+    const int tid = threadIdx.x;
+    const int cl = tid % CS, ch = slice * CS + cl;
+    float gam[NB], inv[NB], mu[NB];
+#pragma unroll
+    for (int s = 0; s < NB; ++s) { gam[s] = sd.s[s].gamma[ch]; inv[s] = sd.s[s].invstd[ch]; mu[s] = sd.s[s].mean[ch]; }
+    double acc[NR];
+    fa_slice_sums<NR, NR>(partial, parts, C, ch, CS, red, acc, [](const float (&r)[NR], double (&v)[NR]) {
+#pragma unroll
+        for (int k = 0; k < NR; ++k) v[k] = (double)r[k];
+    });
+    if (tid < CS) {
+#pragma unroll
+        for (int s = 0; s < NB; ++s) {
+            const double s1 = acc[0], s2 = acc[1 + s];
+            const double g = (double)gam[s] * inv[s];
+            double c2 = 0, c3 = 0;
+            if (training) { c2 = -g * inv[s] * s2 / count; c3 = -g * s1 / count - c2 * mu[s]; }
+            float* t = tab + 3 * s * CS;
+            t[cl] = (float)g; t[CS + cl] = (float)c2; t[2 * CS + cl] = (float)c3;
+            if (write_grads) { sd.s[s].dbeta[ch] = (float)s1; sd.s[s].dgamma[ch] = (float)s2; }
+        }
+    }
+}
+
+// Finalize only: one workgroup per channel slice runs the fused launch's merge and leaves coef [3][C] = c1, c2, c3 for a consumer
+// that applies dx = c1 dz + c2 x + c3 itself (the strip kernel's row loaders, dam_conv_strip.hip: BNF).
+__global__ __launch_bounds__(FA_THREADS) void bn_bwd_fin_only_kernel(const float* __restrict__ partial, int parts, int C, int CS,
+                                                                      double count, int training, const BnBwdSides<1> sd,
+                                                                      float* __restrict__ coef) {
+    __shared__ double red[FA_THREADS * 2];
+    __shared__ __attribute__((aligned(16))) float tab[3 * 32];
+    bn_bwd_merge_slice<1>(partial, parts, C, CS, blockIdx.x, count, training, sd, red, tab, true);
+    __syncthreads();
+    const int tid = threadIdx.x;
+    if (tid < 3 * CS) coef[(tid / CS) * C + blockIdx.x * CS + tid % CS] = tab[tid];
+}
+
 // Backward: records [parts][C][1 + NB] = (sum dz, sum dz * xhat of every side) -> dgamma / dbeta (range 0 writes them) and
 // dx = c1 dz + c2 x + c3 per side.
 template <int MASK, int NB>
@@ -670,30 +714,8 @@ __global__ __launch_bounds__(FA_THREADS) void bn_bwd_fin_apply_kernel(const floa
     load(FaSet<0>{}, lo + tp);
     float4 msc = zero4(), msh = zero4();
     if (MASK == 2) { msc = reinterpret_cast<const float4*>(mscale)[cq]; msh = reinterpret_cast<const float4*>(mshift)[cq]; }
-    {
-        const int cl = tid % CS, ch = slice * CS + cl;
-        float gam[NB], inv[NB], mu[NB];
-#pragma unroll
-        for (int s = 0; s < NB; ++s) { gam[s] = sd.s[s].gamma[ch]; inv[s] = sd.s[s].invstd[ch]; mu[s] = sd.s[s].mean[ch]; }
-        double acc[NR];
-        fa_slice_sums<NR, NR>(partial, parts, C, ch, CS, red, acc, [](const float (&r)[NR], double (&v)[NR]) {
-#pragma unroll
-            for (int k = 0; k < NR; ++k) v[k] = (double)r[k];
-        });
-        if (tid < CS) {
-#pragma unroll
-            for (int s = 0; s < NB; ++s) {
-                const double s1 = acc[0], s2 = acc[1 + s];
-                const double g = (double)gam[s] * inv[s];
-                double c2 = 0, c3 = 0;
-                if (training) { c2 = -g * inv[s] * s2 / count; c3 = -g * s1 / count - c2 * mu[s]; }
-                float* t = tab + 3 * s * CS;
-                t[cl] = (float)g; t[CS + cl] = (float)c2; t[2 * CS + cl] = (float)c3;
-                if (blockIdx.x == 0) { sd.s[s].dbeta[ch] = (float)s1; sd.s[s].dgamma[ch] = (float)s2; }
-            }
-        }
-        __syncthreads();
-    }
+    bn_bwd_merge_slice<NB>(partial, parts, C, CS, slice, count, training, sd, red, tab, blockIdx.x == 0);
+    __syncthreads();
     float4 k[NB][3];
 #pragma unroll
     for (int i = 0; i < 3 * NB; ++i) k[i / 3][i % 3] = *reinterpret_cast<const float4*>(tab + i * CS + tq * 4);
@@ -946,6 +968,28 @@ extern "C" int dam_bn_backward_f32(const float* dy, const float* y_mask, const f
                            C, (const float*)coef, mask_scale, mask_shift, dx);
     });
     if (!known) return DAM_ERR_BAD_ARG;
+    DAM_CHECK_LAUNCH();
+    return DAM_OK;
+}
+
+// The finalize of dam_bn_backward_f32(partials_given = parts) without its apply: the same merge (inside the fused launch's table
+// limit that launch's own, beyond it bn_bwd_finalize_kernel as there), the coefficients to `coef`.
+extern "C" int dam_bn_backward_finalize_f32(const float* partial, int parts, int64_t n_pixels, int C, const float* gamma,
+                                            const float* save_mean, const float* save_invstd, int training, float* dgamma,
+                                            float* dbeta, float* coef, void* stream) {
+    if (!partial || !gamma || !save_mean || !save_invstd || !dgamma || !dbeta || !coef || n_pixels <= 0) return DAM_ERR_BAD_ARG;
+    if (parts <= 0 || parts > BN_MAX_PARTS) return DAM_ERR_BAD_ARG;
+    if (C % 16 || C > 1024) return DAM_ERR_UNSUPPORTED;
+    hipStream_t st = (hipStream_t)stream;
+    if (fa_table_ok(C, parts, 2)) {
+        const FaPlan f = fa_plan(n_pixels, C);
+        const BnBwdSides<1> sd{{{nullptr, gamma, save_mean, save_invstd, nullptr, dgamma, dbeta}}};
+        hipLaunchKernelGGL(bn_bwd_fin_only_kernel, dim3(f.nslices), dim3(FA_THREADS), 0, st, partial, parts, C, f.cs, (double)n_pixels,
+                           training, sd, coef);
+    } else {
+        hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3(C), dim3(64), 0, st, partial, parts, C, (double)n_pixels, gamma, save_mean,
+                           save_invstd, training, dgamma, dbeta, coef);
+    }
     DAM_CHECK_LAUNCH();
     return DAM_OK;
 }

@@ -822,11 +822,12 @@ void request_operands(ConvRequest& rq, unsigned has, int64_t workspace_floats) {
     rq.workspace = has & DAM_CONV_HAS_WORKSPACE; rq.batch = has & DAM_CONV_HAS_BATCH;
     rq.bn_bwd = has & DAM_CONV_HAS_BN_BWD; rq.bwd_mask_bits = has & DAM_CONV_HAS_BWD_MASK_BITS;
     rq.bwd_res_mask_bits = has & DAM_CONV_HAS_BWD_RES_MASK_BITS; rq.bwd_mask_scale = has & DAM_CONV_HAS_BWD_MASK_SCALE;
+    rq.bn_in = has & DAM_CONV_HAS_BN_IN; rq.bn_in_bits = has & DAM_CONV_HAS_BN_IN_BITS;
     rq.workspace_floats = workspace_floats;
 }
 
 void note_ints(const ConvLaunchNote& n, int* out16) {
-    const int v[16] = {n.family, n.MB, n.NB, n.NCH, n.T33, n.LW, n.EPI, n.SO, n.PU, n.STATS, n.KS, n.ksplit, n.ranges, 0, 0, 0};
+    const int v[16] = {n.family, n.MB, n.NB, n.NCH, n.T33, n.LW, n.EPI, n.SO, n.PU, n.STATS, n.KS, n.ksplit, n.ranges, n.BNF, 0, 0};
     for (int i = 0; i < 16; ++i) out16[i] = v[i];
 }
 
@@ -867,12 +868,14 @@ extern "C" int dam_conv2d_tapgrid_f32(const float* x, int B, int H, int W, int C
                                       int out_stride, int out_off_h, int out_off_w, int in_stride, int nA, int nB,
                                       int off_h, int step_h, int off_w, int step_w, int wt_base, int wt_sa, int wt_sb,
                                       const float* res, const float* res_mask, float* bn_partial, int* bn_parts_host,
-                                      const dam_bn_bwd_sums* bn_bwd, float* workspace, int64_t workspace_floats,
-                                      void* batch, void* stream) {
+                                      const dam_bn_bwd_sums* bn_bwd, const dam_bn_bwd_in* bn_in, float* workspace,
+                                      int64_t workspace_floats, void* batch, void* stream) {
     using namespace dam;
     conv_last_launch = ConvLaunchNote{};
     if (bn_parts_host) *bn_parts_host = 0;
     if (!x || !w_packed || !y) return DAM_ERR_BAD_ARG;
+    const dam_bn_bwd_in* f = bn_in && bn_in->c ? bn_in : nullptr;
+    if (f && (!f->coef || !f->dc || !f->mask_scale != !f->mask_shift || !f->mask_bits == !f->mask_scale)) return DAM_ERR_BAD_ARG;
     const dam_bn_bwd_sums* s = bn_bwd && bn_bwd->x ? bn_bwd : nullptr;
     if (s && (!bn_parts_host || !s->mean || !s->invstd || !s->mask_scale != !s->mask_shift)) return DAM_ERR_BAD_ARG;
     ConvRequest rq{B, H, W, C, in_nchw, k_chunks, n_out, relu_in, relu_out, OHt, OWt, Ho, Wo, out_stride, out_off_h, out_off_w, in_stride,
@@ -881,12 +884,15 @@ extern "C" int dam_conv2d_tapgrid_f32(const float* x, int B, int H, int W, int C
                          (res ? DAM_CONV_HAS_RES : 0) | (res_mask ? DAM_CONV_HAS_RES_MASK : 0) | (bn_partial ? DAM_CONV_HAS_BN_PARTIAL : 0) |
                          (workspace ? DAM_CONV_HAS_WORKSPACE : 0) | (batch ? DAM_CONV_HAS_BATCH : 0) | (s ? DAM_CONV_HAS_BN_BWD : 0) |
                          (s && s->mask_bits ? DAM_CONV_HAS_BWD_MASK_BITS : 0) | (s && s->res_mask_bits ? DAM_CONV_HAS_BWD_RES_MASK_BITS : 0) |
-                         (s && s->mask_scale ? DAM_CONV_HAS_BWD_MASK_SCALE : 0), workspace_floats);
+                         (s && s->mask_scale ? DAM_CONV_HAS_BWD_MASK_SCALE : 0) | (f ? DAM_CONV_HAS_BN_IN : 0) |
+                         (f && f->mask_bits ? DAM_CONV_HAS_BN_IN_BITS : 0), workspace_floats);
     ConvPlan plan;
     int rc = plan_conv(rq, plan);
     if (rc != DAM_OK) return rc;
+    if (f && !plan.note.BNF) return DAM_ERR_UNSUPPORTED;      // no kernel applies the BatchNorm backward for this layer: ask the plan first
     const ConvOperands a{x, w_packed, bias, in_scale, in_shift, res, res_mask, y, bn_partial, workspace,
-                         s ? BnBwdEpi{s->x, s->mean, s->invstd, s->mask_scale, s->mask_shift, s->res_mask_bits, s->mask_bits} : BnBwdEpi{}};
+                         s ? BnBwdEpi{s->x, s->mean, s->invstd, s->mask_scale, s->mask_shift, s->res_mask_bits, s->mask_bits} : BnBwdEpi{},
+                         f ? BnBwdIn{f->c, f->coef, f->mask_scale, f->mask_shift, f->mask_bits, f->dc} : BnBwdIn{}};
     rc = launch_plan(plan, a, batch, (hipStream_t)stream);
     if (rc != DAM_OK) return rc;
     conv_last_launch = plan.note;

@@ -38,6 +38,17 @@ struct BnBwdEpi {
     const unsigned char* mask_bits;  // the BatchNorm's own ReLU mask as sign bytes instead of mscale / mshift (relu(bn(x) + shortcut))
 };
 
+// BatchNorm-backward APPLY fused into a data gradient's row loaders (strip kernel, template parameter BNF): the launch's input is
+// dy, the gradient reaching relu(bn(c)) [+ shortcut]; the loaders form  dc = a * (dy * mask) + b * c + k  per channel, feed it to
+// the convolution and store it to `dc` (every element once).  coef = [3][C]: a, b, k from dam_bn_backward_finalize_f32.
+struct BnBwdIn {
+    const float* c;          // null: off
+    const float* coef;
+    const float* mscale; const float* mshift;      // mask = fma(c, mscale, mshift) > 0, or
+    const unsigned char* mask_bits;                // ... the sign bytes of bn_apply
+    float* dc;
+};
+
 struct StripGeo {
     int NR;                  // ring rows (power of two)
     int RH;                  // input rows touched by one output row
@@ -55,6 +66,7 @@ enum ConvFamily { CONV_FAM_NONE = 0, CONV_FAM_STRIP = 1, CONV_FAM_PIPE = 2, CONV
                   CONV_FAM_TILE_BATCH = 5, CONV_FAM_1X1 = 6 };
 struct ConvLaunchNote {
     int family, MB, NB, NCH, T33, LW, EPI, SO, PU, STATS, KS, ksplit, ranges;
+    int BNF;                 // strip: BatchNorm-backward apply in the row loaders, 2 affine mask / 3 sign bytes (BnBwdIn); 0 none
 };
 extern thread_local ConvLaunchNote conv_last_launch;     // dam_conv.hip
 

@@ -12,6 +12,7 @@ struct ConvRequest {
         nA, nB, off_h, step_h, off_w, step_w, wt_base, wt_sa, wt_sb;
     bool bias, in_scale, in_shift, res, res_mask, bn_partial, workspace, batch;
     bool bn_bwd, bwd_mask_bits, bwd_res_mask_bits, bwd_mask_scale;      // dam_bn_bwd_sums: x, mask_bits, res_mask_bits, mask_scale given
+    bool bn_in, bn_in_bits;                                             // dam_bn_bwd_in: given, its mask as sign bytes
     int64_t workspace_floats;
 };
 
@@ -51,6 +52,7 @@ struct ConvOperands {
     const float *x, *w_packed, *bias, *in_scale, *in_shift, *res, *res_mask;
     float *y, *bn_partial, *workspace;
     BnBwdEpi bwd;
+    BnBwdIn bin;
 };
 
 // Launch what the plan says: the table from template parameters to instantiation; DAM_OK or DAM_ERR_LAUNCH.

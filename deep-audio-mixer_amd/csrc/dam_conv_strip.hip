@@ -12,8 +12,10 @@
 //     SIMD hosts one wave of each group, so its matrix pipe always has exactly one MFMA stream;
 //   * a streaming MFMA wave owns its SIMD's vector issue port, so everything wave-uniform runs on the scalar ALU: loader
 //     waves 8-11 work in whole (row, chunk) planes (scalar plane arithmetic, per-lane column pattern computed once,
-//     buffer_load + EXEC-masked ds_write: no VALU per piece; optional fused input affine = 8 VALU per piece), two slots
-//     ahead in two register sets; pixel geometry by s_mul_hi; outputs through buffer_store;
+//     buffer_load + EXEC-masked ds_write: no VALU per piece; optional fused input affine = 8 VALU per piece; optional fused
+//     BatchNorm-backward apply of the 16-channel data gradients = a second (third) input stream, 16-17 VALU and a dc store
+//     per piece, template parameter BNF), two slots ahead in two register sets; pixel geometry by s_mul_hi; outputs
+//     through buffer_store;
 //   * 3x3 / stride 1: compile-time item grid, operands = register + immediate, two-deep software pipeline; weights are LDS
 //     resident in canonical [3a+b][chunk][nb][lane] order, so compute waves issue no vector-memory loads in the loop;
 //   * one raw s_barrier per slot; compute waves do not drain their output stores at it;
@@ -32,6 +34,7 @@ namespace {
 typedef float v4f __attribute__((ext_vector_type(4)));
 typedef int v4i __attribute__((ext_vector_type(4)));
 typedef float v2f __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ v4f zero4x() { return (v4f){0.f, 0.f, 0.f, 0.f}; }
 
 // Diagnostic build only (-DDAM_STRIP_DIAG_TAGS, libdam_hip_diag.so; tests/test_strip_diag_gpu.py): every geometry-table entry the
 // loader waves of the self-overlapped form write carries the index of the tile it describes, and every compute wave checks, for
@@ -141,13 +144,21 @@ __device__ __forceinline__ void rows_commit(unsigned char* smem, const float4 (&
 // pinned between the MFMAs with sched_group_barrier), so what the write-out does is compile time: with EPI == 0, SO = 1 raw
 // store, 2 raw + BatchNorm partial statistics, 3 + bias, max(., floor) [folded inference convolution], 4 as 3 + residual,
 // 5 + residual * (mask > 0); with EPI >= 1 the sums epilogues as above (SO = 1).
-template <int MB, int NB, int NCH, bool T33, bool LW, int EPI, int SO>
+// BNF: the BatchNorm-backward APPLY in front of this data gradient runs in the row loaders (BnBwdIn; 16 channels, ordinary rows,
+// self-overlapped form with a sums epilogue only).  X is then dy, the gradient reaching relu(bn(c)): for every piece a loader
+// requests, it requests the matching piece of c as well (BNF 3: and of the sign bytes), forms  dc = a * (dy * mask) + (b * c + k)
+// -- bn_bwd_fin_apply_kernel's expression, operation by operation -- and writes dc into the ring where the raw piece went.
+// BNF 2: mask = fma(c, mscale, mshift) > 0 (the forward's own expression), BNF 3: mask from the sign bytes.  The pieces of the
+// pixels this workgroup COMPUTES also go to global memory (the weight gradient reads dc later): the store's buffer resource
+// covers exactly the workgroup's pixel range, so halo rows and the foreign part of a shared first / last row fail the range
+// check -- every dc element has one writer, no VALU spent on ownership.  a, b, k come from dam_bn_backward_finalize_f32.
+template <int MB, int NB, int NCH, bool T33, bool LW, int EPI, int SO, int BNF>
 __global__ __launch_bounds__(SO ? 512 : STRIP_THREADS, 1) void conv_strip_kernel(const ConvGeo g, const StripGeo sg, const float* __restrict__ X,
                                                          const float4* __restrict__ Wp, const float* __restrict__ bias,
                                                          float* __restrict__ Y, const float* __restrict__ res,
                                                          const float* __restrict__ res_mask, float* __restrict__ stats,
                                                          const float* __restrict__ in_scale, const float* __restrict__ in_shift,
-                                                         const BnBwdEpi bwd) {
+                                                         const BnBwdEpi bwd, const BnBwdIn bin) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);     // wave-uniform: role tests and loader arithmetic on the scalar ALU
@@ -237,10 +248,46 @@ __global__ __launch_bounds__(SO ? 512 : STRIP_THREADS, 1) void conv_strip_kernel
     // buffer addressing: scalar resource (this image) + scalar plane offset + per-lane column offset, no VALU
     const __amdgpu_buffer_rsrc_t xrsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(ximg), 0, g.H * g.W * g.C * 4, 0x00020000);
     const int lane16 = lane * 16 + hsel * 1024;
+    // BNF: c (and the sign bytes) through resources of their own with the SAME offsets (bytes: offsets >> 4, one byte per channel
+    // quad); per-lane constants of the lane's channel quad, fetched once; the dc store's resource = the pixels [p_lo, p_hi) this
+    // workgroup computes, its per-lane offsets = the load's, out of every range for lanes that hold no real column
+    constexpr bool FUSE = BNF != 0;
+    static_assert(!FUSE || (NCH == 1 && !LW && SO != 0 && EPI != 0 && T33), "fused BatchNorm-backward apply: 16-channel SO sums shapes");
+    constexpr int GPF = FUSE ? GPP : 1, GPB = BNF == 3 ? GPP : 1;
+    const int img_bytes_i = g.H * g.W * g.C * 4;
+    const int dc_lo = FUSE ? t_begin * TM * 64 : 0;
+    const int dc_span = FUSE ? ((t_end * TM < HoWo ? t_end * TM : HoWo) - t_begin * TM) * 64 : 0;
+    const __amdgpu_buffer_rsrc_t fcrsrc = __builtin_amdgcn_make_buffer_rsrc(
+        const_cast<char*>(reinterpret_cast<const char*>(bin.c)) + (FUSE ? (size_t)img * img_bytes_i : 0), 0, FUSE ? img_bytes_i : 0, 0x00020000);
+    const __amdgpu_buffer_rsrc_t fbrsrc = __builtin_amdgcn_make_buffer_rsrc(
+        const_cast<char*>(reinterpret_cast<const char*>(bin.mask_bits)) + (BNF == 3 ? (size_t)img * (img_bytes_i >> 4) : 0), 0,
+        BNF == 3 ? (img_bytes_i >> 4) : 0, 0x00020000);
+    const __amdgpu_buffer_rsrc_t fdrsrc = __builtin_amdgcn_make_buffer_rsrc(
+        reinterpret_cast<char*>(bin.dc) + (FUSE ? (size_t)img * img_bytes_i + dc_lo : 0), 0, dc_span, 0x00020000);
+    int loffq[GPB], loffs[GPF];
+    v4f fk1 = zero4x(), fk2 = zero4x(), fk3 = zero4x(), fms = zero4x(), fmh = zero4x();
+    if constexpr (FUSE) {
+#pragma unroll
+        for (int gu = 0; gu < GPP; ++gu) {
+            loffs[gu] = ((cmask[gu] >> lane) & 1) ? loffb[gu] : 0x40000000;
+            if constexpr (BNF == 3) loffq[gu] = loffb[gu] >> 4;
+        }
+        const int qo = (lane & 3) * 4;
+        fk1 = *reinterpret_cast<const v4f*>(bin.coef + qo);
+        fk2 = *reinterpret_cast<const v4f*>(bin.coef + g.C + qo);
+        fk3 = *reinterpret_cast<const v4f*>(bin.coef + 2 * g.C + qo);
+        if constexpr (BNF == 2) {
+            fms = *reinterpret_cast<const v4f*>(bin.mscale + qo);
+            fmh = *reinterpret_cast<const v4f*>(bin.mshift + qo);
+        }
+    }
     const v4f zero4 = {0.f, 0.f, 0.f, 0.f};
     const float relu_lo = relu_in ? 0.f : -__builtin_inff();       // (a run-time `if (relu_in)` became four v_cndmask per piece on the loaders)
     const v4f relu_lo4 = {relu_lo, relu_lo, relu_lo, relu_lo};
     v4f lvA[KP][GPP], lvB[KP][GPP];
+    v4f lvAc[FUSE ? KP : 1][GPF], lvBc[FUSE ? KP : 1][GPF];       // BNF: the pieces of c, the sign bytes, the dc store's scalar offset
+    int lvAm[BNF == 3 ? KP : 1][GPB], lvBm[BNF == 3 ? KP : 1][GPB];
+    int lvAo[FUSE ? KP : 1], lvBo[FUSE ? KP : 1];
     int dstA[KP], dstB[KP];                          // scalar: ring byte offset of the plane | 1 << 30 if the row is
     int ccA[KP], ccB[KP];                            // outside the tensor (zeros are written), -1 = nothing to write; chunk
 #pragma unroll
@@ -248,6 +295,17 @@ __global__ __launch_bounds__(SO ? 512 : STRIP_THREADS, 1) void conv_strip_kernel
     const int chs = NCH == 1 ? 0 : 1;
     int loaded_hi;
     { int lo; tile_rows(t_begin, lo, loaded_hi); }
+    // BNF: the pieces of c (and the sign bytes) that belong to the pieces of dy just requested, same offsets
+#define DAM_STRIP_REQUEST_BN(LV_, SOFF_)                                                                                   \
+    do {                                                                                                                   \
+        if constexpr (FUSE) {                                                                                              \
+            _Pragma("unroll") for (int gi = 0; gi < GPP; ++gi) {                                                           \
+                LV_##c[k][gi] = __builtin_bit_cast(v4f, __builtin_amdgcn_raw_buffer_load_b128(fcrsrc, loffb[gi], (SOFF_), 0)); \
+                if constexpr (BNF == 3) LV_##m[k][gi] = (int)__builtin_amdgcn_raw_buffer_load_b8(fbrsrc, loffq[gi], (SOFF_) >> 4, 0); \
+            }                                                                                                              \
+            LV_##o[k] = (SOFF_) - dc_lo;                                                                                   \
+        }                                                                                                                  \
+    } while (0)
 #define DAM_STRIP_REQUEST(K_, LV_, DST_, CC_)                                                                                \
     do {                                                                                                                   \
         int first_ = 0, planes_ = 0;                                                                                       \
@@ -265,6 +323,7 @@ __global__ __launch_bounds__(SO ? 512 : STRIP_THREADS, 1) void conv_strip_kernel
             const int soff_ = ((rowok_ ? ih_ : 0) * g.W * g.C + (used_ ? cc_ : 0) * 16) * 4;                               \
             _Pragma("unroll") for (int gi = 0; gi < GPP; ++gi)                                                             \
                 LV_[k][gi] = __builtin_bit_cast(v4f, __builtin_amdgcn_raw_buffer_load_b128(xrsrc, loffb[gi], soff_, 0));   \
+            DAM_STRIP_REQUEST_BN(LV_, soff_);                                                                              \
             DST_[k] = used_ ? ((cc_ * CHB + ((ih_ + sg.ring_off) & (sg.NR - 1)) * RB) | (rowok_ ? 0 : 1 << 30)) : -1;     \
             CC_[k] = cc_;                                                                                                  \
         }                                                                                                                  \
@@ -279,7 +338,25 @@ __global__ __launch_bounds__(SO ? 512 : STRIP_THREADS, 1) void conv_strip_kernel
             if (DST_[k] >= 0) {                                                                                            \
                 const int va_ = lane16 + (DST_[k] & 0x3fffffff);                                                           \
                 if (!(DST_[k] >> 30)) {                                                                                    \
-                    if (has_aff) {             /* 8 VALU per piece (4 fma + 4 max), ~40 per loader wave and slot */        \
+                    if constexpr (FUSE) {      /* 16-17 VALU per piece: mask, 8 fma, the store's offset */                 \
+                        _Pragma("unroll") for (int gi = 0; gi < GPP; ++gi) {                                               \
+                            const v4f d_ = LV_[k][gi], c_ = LV_##c[k][gi];                                                 \
+                            v4f g_;                                                                                        \
+                            if constexpr (BNF == 2) {                                                                      \
+                                const v4f m_ = __builtin_elementwise_fma(c_, fms, fmh);                                    \
+                                g_.x = m_.x > 0.f ? d_.x : 0.f; g_.y = m_.y > 0.f ? d_.y : 0.f;                            \
+                                g_.z = m_.z > 0.f ? d_.z : 0.f; g_.w = m_.w > 0.f ? d_.w : 0.f;                            \
+                            } else {                                                                                       \
+                                const int b_ = LV_##m[BNF == 3 ? k : 0][BNF == 3 ? gi : 0];                                \
+                                g_.x = (b_ & 1) ? d_.x : 0.f; g_.y = (b_ & 2) ? d_.y : 0.f;                                \
+                                g_.z = (b_ & 4) ? d_.z : 0.f; g_.w = (b_ & 8) ? d_.w : 0.f;                                \
+                            }                                                                                              \
+                            const v4f o_ = __builtin_elementwise_fma(fk1, g_, __builtin_elementwise_fma(fk2, c_, fk3));    \
+                            DAM_STRIP_WRITE(va_, o_, gi);                                                                  \
+                            /* whole byte offset in the vector register, soffset 0: see SO_UNIT */                          \
+                            __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(v4i, o_), fdrsrc, loffs[gi] + LV_##o[k], 0, 0); \
+                        }                                                                                                  \
+                    } else if (has_aff) {             /* 8 VALU per piece (4 fma + 4 max), ~40 per loader wave and slot */        \
                         const v4f sc_ = (NCH > 1 && CC_[k] > 0) ? scq[NCH - 1] : scq[0];                                   \
                         const v4f sh_ = (NCH > 1 && CC_[k] > 0) ? shq[NCH - 1] : shq[0];                                   \
                         _Pragma("unroll") for (int gi = 0; gi < GPP; ++gi) {                                               \
@@ -309,6 +386,7 @@ __global__ __launch_bounds__(SO ? 512 : STRIP_THREADS, 1) void conv_strip_kernel
             const int soff_ = ((rowok_ ? ih_ : 0) * g.W * g.C + (used_ ? cc_ : 0) * 16) * 4;                               \
             _Pragma("unroll") for (int gi = 0; gi < GPP; ++gi)                                                             \
                 LV_[k][gi] = __builtin_bit_cast(v4f, __builtin_amdgcn_raw_buffer_load_b128(xrsrc, loffb[gi], soff_, 0));   \
+            DAM_STRIP_REQUEST_BN(LV_, soff_);                                                                              \
             DST_[k] = used_ ? ((cc_ * CHB + ((ih_ + sg.ring_off) & (sg.NR - 1)) * RB) | (rowok_ ? 0 : 1 << 30)) : -1;     \
             CC_[k] = cc_;                                                                                                  \
         }                                                                                                                  \
@@ -338,6 +416,8 @@ __global__ __launch_bounds__(SO ? 512 : STRIP_THREADS, 1) void conv_strip_kernel
     }
     DAM_STAMP(9);
     v4f lv0[SO ? KP0 : 1][SO ? GPP : 1];
+    v4f lv0c[FUSE ? KP0 : 1][GPF];
+    int lv0m[BNF == 3 ? KP0 : 1][GPB], lv0o[FUSE ? KP0 : 1];
     int dst0[KP0], cc0[KP0];
     if constexpr (SO != 0) {
         // rows of the first tile: whole planes over all waves (the per-piece path of the ping-pong form costs 3.4-5 k cycles
@@ -348,8 +428,10 @@ __global__ __launch_bounds__(SO ? 512 : STRIP_THREADS, 1) void conv_strip_kernel
 #ifdef DAM_STRIP_ONE_SET       // experiment: ONE register set, the rows of tile s+2 are requested in slot s (one slot ahead, not two)
             DAM_STRIP_REQUEST(1, lvA, dstA, ccA);
 #else
+            // (BNF: a set is 2.25 times as many registers -- dy, c, sign bytes -- and three sets in flight do not fit: tile 2's
+            // rows are requested once the first tile's set has been written, still a slot before they are needed)
             DAM_STRIP_REQUEST(1, lvB, dstB, ccB);
-            DAM_STRIP_REQUEST(2, lvA, dstA, ccA);
+            if constexpr (!FUSE) DAM_STRIP_REQUEST(2, lvA, dstA, ccA);
 #endif
         }
     } else {
@@ -370,6 +452,9 @@ __global__ __launch_bounds__(SO ? 512 : STRIP_THREADS, 1) void conv_strip_kernel
     DAM_STAMP(2);
     if constexpr (SO != 0) {
         DAM_STRIP_COMMIT_N(KP0, lv0, dst0, cc0);
+        if constexpr (FUSE) {
+            if (grp == LGRP) DAM_STRIP_REQUEST(2, lvA, dstA, ccA);
+        }
     } else {
         rows_commit<NCH>(smem, lv, ldst, laff, has_aff, scq, shq, relu_in);
         for (int base = (NT / 64) * STRIP_PU; base < total0; base += (NT / 64) * STRIP_PU) {
@@ -405,6 +490,17 @@ __global__ __launch_bounds__(SO ? 512 : STRIP_THREADS, 1) void conv_strip_kernel
     // 1 and 2 in the prologue are register loads from the read-only input: they write no LDS, so their being early changes when
     // data travels, not what any wave reads -- the ring writes (commits) of tile sigma + 1 stay in slot sigma, where the host's
     // ring sizing (StripGeo::NR: the rows of two consecutive tiles never alias) covers them exactly as in the ping-pong form.
+    // THE LONGER LOADER SLOT OF THE FUSED FORMS (BNF) changes none of this.  The bound never used how long a loader's slot takes: it
+    // rests on (a) one barrier per slot executed by all eight waves, (b) every wave draining its LDS traffic in front of it, (c) which
+    // tile's entry a wave touches in slot sigma.  A fused loader adds, per piece, register loads of c (and the sign bytes) from
+    // read-only inputs, 16-17 VALU instructions and one global store to dc, a tensor no wave of the launch reads: no LDS access that
+    // was not there, no barrier, no table entry.  Its ds_writes of tile sigma + 1's rows still wait (s_waitcnt vmcnt) for their
+    // loads and are still drained in front of slot sigma's barrier, so a slow loader lengthens the slot for all eight waves and
+    // cannot let one run ahead: concurrent table accesses stay {sigma + 2} written, {sigma + 1} (+ {0} in slot 0) read.  The one
+    // change in ORDER is in the prologue: a fused loader requests tile 2's rows after the first tile's set is written (three sets
+    // of dy + c + bytes do not fit the registers), i.e. between P1 and P2 instead of in front of P1 -- register loads again, committed
+    // in slot 1 as before.  The dc stores are not drained at the slot barriers (nothing in the launch reads them); they complete
+    // before the kernel ends like the compute waves' output stores.
     // tests/test_strip_diag_gpu.py runs the layer1 / layer2 shapes of the C3 step through a build that checks this on the device.
     const int tab_base = CHB * g.nchunks + 9 * g.nchunks * NB * 1024;
 #ifdef DAM_STRIP_DIAG_TAGS
@@ -482,6 +578,7 @@ __global__ __launch_bounds__(SO ? 512 : STRIP_THREADS, 1) void conv_strip_kernel
         }
         }
 #undef DAM_STRIP_REQUEST
+#undef DAM_STRIP_REQUEST_BN
 #undef DAM_STRIP_REQUEST0
 #undef DAM_STRIP_WRITE
 #undef DAM_STRIP_COMMIT
@@ -1141,17 +1238,17 @@ __global__ __launch_bounds__(SO ? 512 : STRIP_THREADS, 1) void conv_strip_kernel
 
 }  // namespace
 
-template <int MB, int NB, int NCH, bool T33, bool LW, int EPI, int SO>
+template <int MB, int NB, int NCH, bool T33, bool LW, int EPI, int SO, int BNF = 0>
 static int launch_strip_as(const ConvLaunchPlan& p, const ConvOperands& a, hipStream_t st) {
-    if (p.lds > 64 * 1024 && !raise_lds_limit<&conv_strip_kernel<MB, NB, NCH, T33, LW, EPI, SO>>(160 * 1024)) return DAM_ERR_LAUNCH;
+    if (p.lds > 64 * 1024 && !raise_lds_limit<&conv_strip_kernel<MB, NB, NCH, T33, LW, EPI, SO, BNF>>(160 * 1024)) return DAM_ERR_LAUNCH;
     // the sums epilogue reads the BatchNorm's input through the residual operand, a real residual's mask as sign bytes
     const bool sums = p.stats == 2;
     const float* res = sums && !a.res ? a.bwd.x : a.res;
     const float* res_mask = sums && a.res ? reinterpret_cast<const float*>(a.bwd.res_bits) : a.res_mask;
     dim3 grid((unsigned)p.sg.strips, (unsigned)cdiv(p.g.N / 16, NB), (unsigned)p.g.B);
-    hipLaunchKernelGGL((conv_strip_kernel<MB, NB, NCH, T33, LW, EPI, SO>), grid, dim3(SO ? 512 : STRIP_THREADS), p.lds, st, p.g, p.sg, a.x,
+    hipLaunchKernelGGL((conv_strip_kernel<MB, NB, NCH, T33, LW, EPI, SO, BNF>), grid, dim3(SO ? 512 : STRIP_THREADS), p.lds, st, p.g, p.sg, a.x,
                        reinterpret_cast<const float4*>(a.w_packed), a.bias, a.y, res, res_mask, p.stats ? a.bn_partial : nullptr, a.in_scale,
-                       a.in_shift, sums ? a.bwd : BnBwdEpi{});
+                       a.in_shift, sums ? a.bwd : BnBwdEpi{}, BNF ? a.bin : BnBwdIn{});
     DAM_CHECK_LAUNCH();
     return DAM_OK;
 }
@@ -1159,6 +1256,14 @@ static int launch_strip_as(const ConvLaunchPlan& p, const ConvOperands& a, hipSt
 // Every instantiation of conv_strip_kernel, by the plan's note <MB, NB, NCH, T33, LW, EPI, SO> (plan_strip names no other).
 int launch_strip(const ConvLaunchPlan& p, const ConvOperands& a, hipStream_t st) {
     const ConvLaunchNote& n = p.note;
+    // the BatchNorm-backward apply in the row loaders (BNF): the 16-channel sums shapes of the self-overlapped form -- the table of
+    // adopted instantiations is strip_bn_fused() below
+#define DAM_STRIP_FUSED(E_, F_)                                                                                               \
+    if (n.MB == 4 && n.NB == 1 && n.NCH == 1 && n.T33 && !n.LW && n.EPI == E_ && n.SO == 1 && n.BNF == F_)                     \
+        return launch_strip_as<4, 1, 1, true, false, E_, 1, F_>(p, a, st)
+    DAM_STRIP_FUSED(1, 3); DAM_STRIP_FUSED(2, 2); DAM_STRIP_FUSED(3, 2);
+#undef DAM_STRIP_FUSED
+    if (n.BNF) return DAM_ERR_UNSUPPORTED;
 #define DAM_STRIP_INST(M_, N_, C_, T_, L_, E_, S_)                                                                             \
     if (n.MB == M_ && n.NB == N_ && n.NCH == C_ && n.T33 == T_ && n.LW == L_ && n.EPI == E_ && n.SO == S_)                     \
         return launch_strip_as<M_, N_, C_, T_, L_, E_, S_>(p, a, st)
@@ -1181,6 +1286,16 @@ int launch_strip(const ConvLaunchPlan& p, const ConvOperands& a, hipStream_t st)
 #undef DAM_STRIP_PAIR
 #undef DAM_STRIP_INST
     return DAM_ERR_UNSUPPORTED;
+}
+
+// The fused BatchNorm-backward apply (template parameter BNF) that a self-overlapped 16-channel sums launch with epilogue `epi`
+// takes when the call supplies a BnBwdIn with the mask as sign bytes (`bits`) or as (scale, shift); 0: none, the apply stays a
+// launch of its own.  One line per ADOPTED instantiation (profiles/r08_strip_bnfused_ladder.txt): EPI 1 follows a block's bn2
+// (sign bytes), EPI 2 / 3 its bn1 (affine mask).
+static int strip_bn_fused(int epi, bool bits) {
+    if (epi == 1 && bits) return 3;
+    if ((epi == 2 || epi == 3) && !bits) return 2;
+    return 0;
 }
 
 // The strip kernel's eligibility, tile, ring and strip count, and which instantiation writes the result out.  stats: 0 none,
@@ -1282,7 +1397,14 @@ int plan_strip(const ConvRequest& rq, const ConvGeo& g_in, int stats, ConvLaunch
         if (sums && !(t33 && (tile16 || (tile32 && !res)))) return DAM_ERR_UNSUPPORTED;
         if (wide && !(tile16 || tile32)) return DAM_ERR_UNSUPPORTED;
     }
-    p.note = ConvLaunchNote{CONV_FAM_STRIP, MB, NB, g.nchunks, t33, wide, g.epi_bwd, so, 0, 0, 0, 1, 1};
+    // BatchNorm-backward apply in the loaders: exactly the full-resolution 16-channel stage's data gradients -- 16 channels in and
+    // out, 3x3 / stride 1 / pad 1 (dx has dy's pixel grid), 130-pixel rows, nothing else on the loader side
+    int bnf = 0;
+    if (rq.bn_in && so == 1 && sums && tile16 && g.C == 16 && g.N == 16 && g.W == 130 && g.H == g.Ho && g.W == g.Wo && g.os == 1 &&
+        g.oo_h == 0 && g.oo_w == 0 && g.OHt == g.Ho && g.OWt == g.Wo && g.off_h + g.step_h == 0 && g.off_w + g.step_w == 0 &&
+        !rq.in_scale && !bias)
+        bnf = strip_bn_fused(g.epi_bwd, rq.bn_in_bits);
+    p.note = ConvLaunchNote{CONV_FAM_STRIP, MB, NB, g.nchunks, t33, wide, g.epi_bwd, so, 0, 0, 0, 1, 1, bnf};
     p.g = g; p.sg = sg; p.lds = lds; p.stats = stats;
     if (stats) *records = sg.strips * g.B;
     return DAM_OK;

@@ -311,6 +311,24 @@ class DropoutFn(torch.autograd.Function):
         return ops.dropout_apply(dy, ctx.p, ctx.seed, snap), None
 
 
+def _bn_bwd_dgrad(spec, w, hw, dy, c, gamma, mean, invstd, training, partials, dgamma, dbeta, mask_affine, mask_bits, wgrad, **kw):
+    """Backward of relu(bn(c)) [+ shortcut] (gradient dy, mask as mask_affine or mask_bits), the weight gradient wgrad(dc) of the
+    convolution that produced c, and the data gradient spec.dgrad(dc, w, hw, **kw) of the convolution in front of it
+    -> (dgamma, dbeta, wgrad's result, dgrad's result).  Where the plan names a kernel that applies the BatchNorm backward in its
+    row loaders (ConvLaunch.BNF: the sums came from an epilogue, 16-channel full-resolution layers), the finalize-only launch
+    and that kernel run and dc comes back from the data gradient; everywhere else bn_backward, then the two gradients."""
+    if (partials is not None and spec.stride == 1 and kw.get('bn_bwd') is not None and
+            ops.conv2d_dgrad_plan(dy.shape, spec.cin, hw[0], hw[1], spec.k, spec.k, 1, spec.pad, spec.dil,
+                                  bn_in=(True, True, mask_affine, mask_bits), **kw).BNF):
+        coef, dg, db = ops.bn_backward_finalize(partials, c, gamma, mean, invstd, training, dgamma=dgamma, dbeta=dbeta)
+        dx, sums, dc = spec.dgrad(dy, w, hw, bn_in=(c, coef, mask_affine, mask_bits), **kw)
+        return dg, db, wgrad(dc), (dx, sums)
+    dc, dg, db = ops.bn_backward(dy, None, c, gamma, mean, invstd, training, mask_affine=mask_affine, dgamma=dgamma, dbeta=dbeta,
+                                 mask_bits=mask_bits, partials=partials)
+    dw = wgrad(dc)
+    return dg, db, dw, spec.dgrad(dc, w, hw, **kw)
+
+
 class BasicBlockFn(torch.autograd.Function):
     """models/model_resnet.py:23-28: relu(bn2(conv2(relu(bn1(conv1(x))))) + shortcut(x))."""
 
@@ -375,13 +393,30 @@ class BasicBlockFn(torch.autograd.Function):
         s_w1, s_g1, s_b1, s_w2, s_g2, s_b2, s_ws, s_gs, s_bs = ctx.slots
         keep = lambda grad, slot: None if slot is not None else grad      # slotted gradients are already in place
         wview = lambda slot, w: None if slot is None else slot.view(w.shape)
+        wgrad2 = lambda dc2: blk.spec2.wgrad(c1, dc2, in_affine=(sc1, sh1), out=wview(s_w2, w2))
+        wgrad1 = lambda dc1: blk.spec1.wgrad(x, dc1, out=wview(s_w1, w1))
+        up = ctx.upstream
+        if not ctx.has_sc and ops.DGRAD_BN_SUMS and up is not None and up.c.shape == x.shape:
+            # identity block behind a relu(bn(c)) whose producer left its record: every BatchNorm backward of the block sits in front
+            # of a data gradient that takes the next BatchNorm's sums in its epilogue -- bn2 in front of conv2's (the gradient
+            # reaching relu(bn1(c1)): bn1's sums), bn1 in front of conv1's + identity shortcut (the gradient of the block input: the
+            # upstream BatchNorm's sums).  _bn_bwd_dgrad runs each pair as the plan says: apply launch + data gradient, or the
+            # finalize-only launch + the data gradient that applies the BatchNorm in its loaders.
+            sums2 = ctx.up_self.take(dout) if ctx.up_self is not None else None      # left by the next block's data gradient
+            dg2, db2, dw2, (da1, sums) = _bn_bwd_dgrad(blk.spec2, w2, (c1.shape[1], c1.shape[2]), dout, c2, g2, m2, i2, tr, sums2,
+                                                       s_g2, s_b2, None, bits, wgrad2, bn_bwd=(c1, m1, i1, sc1, sh1))
+            dg1, db1, dw1, (dx, sums_up) = _bn_bwd_dgrad(blk.spec1, w1, hw, da1, c1, g1, m1, i1, tr, sums, s_g1, s_b1, (sc1, sh1), None,
+                                                         wgrad1, res=dout, res_mask=out, res_mask_bits=bits, bn_bwd=up.request())
+            up.offer(sums_up, dx)
+            return (dx, keep(dw1, s_w1), keep(dg1, s_g1), keep(db1, s_b1), keep(dw2, s_w2), keep(dg2, s_g2), keep(db2, s_b2),
+                    None, None, None, None, None)
         if ctx.has_sc:      # bn2 and the shortcut's BatchNorm see the same dout through the same mask: one pass for both
             (dc2, dg2, db2), (dcs, dgs, dbs) = ops.bn_backward_pair(dout, None, (c2, g2, m2, i2, s_g2, s_b2),
                                                                     (cs, gsc, ms, is_, s_gs, s_bs), tr, mask_bits=bits)
         else:
             sums2 = ctx.up_self.take(dout) if ctx.up_self is not None else None      # left by the next block's data gradient
             dc2, dg2, db2 = ops.bn_backward(dout, None, c2, g2, m2, i2, tr, dgamma=s_g2, dbeta=s_b2, mask_bits=bits, partials=sums2)
-        dw2 = blk.spec2.wgrad(c1, dc2, in_affine=(sc1, sh1), out=wview(s_w2, w2))
+        dw2 = wgrad2(dc2)
         # conv2's data gradient IS the gradient reaching relu(bn1(c1)): where the kernel can, bn1's two backward sums come out
         # of its epilogue (sums = (records, count)) and bn_backward only finalizes and applies
         sums = None
@@ -391,7 +426,7 @@ class BasicBlockFn(torch.autograd.Function):
             da1 = blk.spec2.dgrad(dc2, w2, (c1.shape[1], c1.shape[2]))
         dc1, dg1, db1 = ops.bn_backward(da1, None, c1, g1, m1, i1, tr, mask_affine=(sc1, sh1),   # mask = (bn1(c1) > 0)
                                         dgamma=s_g1, dbeta=s_b1, partials=sums)
-        dw1 = blk.spec1.wgrad(x, dc1, out=wview(s_w1, w1))
+        dw1 = wgrad1(dc1)
         first = (keep(dw1, s_w1), keep(dg1, s_g1), keep(db1, s_b1), keep(dw2, s_w2), keep(dg2, s_g2), keep(db2, s_b2))
         if ctx.has_sc:
             dws = blk.spec_sc.wgrad(x, dcs, out=wview(s_ws, wsc))
@@ -410,12 +445,8 @@ class BasicBlockFn(torch.autograd.Function):
                 dx = blk.spec1.dgrad(dc1, w1, hw)
                 blk.spec_sc.dgrad(dcs, wsc, hw, accumulate_into=dx)
             return (dx,) + first + (keep(dws, s_ws), keep(dgs, s_gs), keep(dbs, s_bs), None, None)
-        up = ctx.upstream
-        if up is not None and ops.DGRAD_BN_SUMS and up.c.shape == x.shape:
-            dx, sums = blk.spec1.dgrad(dc1, w1, hw, res=dout, res_mask=out, res_mask_bits=bits, bn_bwd=up.request())
-            up.offer(sums, dx)
-        else:
-            dx = blk.spec1.dgrad(dc1, w1, hw, res=dout, res_mask=out)      # + dout * (out > 0): identity shortcut
+        # (an identity block with an upstream record returned above)
+        dx = blk.spec1.dgrad(dc1, w1, hw, res=dout, res_mask=out)      # + dout * (out > 0): identity shortcut
         return (dx,) + first + (None, None, None, None, None)
 
 

@@ -64,7 +64,8 @@ TapGrid = collections.namedtuple('TapGrid', 'B H W C in_nchw k_chunks n_out OHt 
                                             'off_h step_h off_w step_w wt_base wt_sa wt_sb')
 # dam_conv2d_tapgrid_plan's `operands` bits (include/dam_hip.h: DAM_CONV_HAS_*)
 _HAS = dict(bias=0x001, in_scale=0x002, in_shift=0x004, res=0x008, res_mask=0x010, bn_partial=0x020, bn_bwd=0x040,
-            bwd_mask_bits=0x080, bwd_res_mask_bits=0x100, bwd_mask_scale=0x200, workspace=0x400, batch=0x800)
+            bwd_mask_bits=0x080, bwd_res_mask_bits=0x100, bwd_mask_scale=0x200, workspace=0x400, batch=0x800, bn_in=0x1000,
+            bn_in_bits=0x2000)
 
 
 def _given(v):
@@ -106,7 +107,7 @@ def _splitk_floats(g):
 
 
 def _tapgrid(g, x, wp, y, bias=None, in_scale=None, in_shift=None, relu_in=False, res=None, res_mask=None, bn_partial=None,
-             relu_out=False, batch=None, bn_bwd=None):
+             relu_out=False, batch=None, bn_bwd=None, bn_in=None):
     """dam_conv2d_tapgrid_f32 on the tap grid g -> the record count left in bn_partial."""
     parts = ctypes.c_int(0)
     ws = _workspace(y.device, _splitk_floats(g))
@@ -114,7 +115,7 @@ def _tapgrid(g, x, wp, y, bias=None, in_scale=None, in_shift=None, relu_in=False
         _lib.ptr(x), *g[:5], _lib.ptr(wp), g.k_chunks, g.n_out, _lib.ptr(bias), _lib.ptr(in_scale), _lib.ptr(in_shift),
         1 if relu_in else 0, 1 if relu_out else 0, _lib.ptr(y), *g[7:], _lib.ptr(res), _lib.ptr(res_mask), _lib.ptr(bn_partial),
         ctypes.byref(parts) if bn_partial is not None else None, ctypes.byref(bn_bwd) if bn_bwd is not None else None,
-        _lib.ptr(ws), ws.numel(), ctypes.addressof(batch) if batch is not None else None, _lib.stream())
+        ctypes.byref(bn_in) if bn_in is not None else None, _lib.ptr(ws), ws.numel(), ctypes.addressof(batch) if batch is not None else None, _lib.stream())
     _lib.check(st, 'dam_conv2d_tapgrid_f32')
     return parts.value
 
@@ -129,7 +130,7 @@ def _tapgrid_plan(g, relu_in=False, relu_out=False, **given):
     st = _lib.lib().dam_conv2d_tapgrid_plan(*g[:7], 1 if relu_in else 0, 1 if relu_out else 0, *g[7:], has, _splitk_floats(g),
                                             rec, ctypes.byref(parts))
     _lib.check(st, 'dam_conv2d_tapgrid_plan')
-    return ConvLaunch(CONV_FAMILIES[rec[0]], *rec[1:13]), parts.value
+    return ConvLaunch(CONV_FAMILIES[rec[0]], *rec[1:14]), parts.value
 
 
 def conv2d_fwd(x, wp, n_out, kh, kw, stride=1, pad=0, dil=1, bias=None, in_scale=None, in_shift=None,
@@ -161,7 +162,7 @@ def conv2d_fwd(x, wp, n_out, kh, kw, stride=1, pad=0, dil=1, bias=None, in_scale
 
 
 CONV_FAMILIES = ('none', 'strip', 'pipe', 'pipe_ranges', 'tile', 'tile_batch', '1x1')
-ConvLaunch = collections.namedtuple('ConvLaunch', 'family MB NB NCH T33 LW EPI SO PU STATS KS ksplit ranges')
+ConvLaunch = collections.namedtuple('ConvLaunch', 'family MB NB NCH T33 LW EPI SO PU STATS KS ksplit ranges BNF')
 
 
 def conv_last_launch():
@@ -169,7 +170,7 @@ def conv_last_launch():
     the template parameters of the instantiation; fields that do not belong to the family are 0.  Host-side only."""
     v = (ctypes.c_int * 16)()
     _lib.check(_lib.lib().dam_conv_last_launch(v), 'dam_conv_last_launch')
-    return ConvLaunch(CONV_FAMILIES[v[0]], *v[1:13])
+    return ConvLaunch(CONV_FAMILIES[v[0]], *v[1:14])
 
 
 def conv2d_fwd_plan(x_shape, n_out, kh, kw, stride=1, pad=0, dil=1, bias=None, in_scale=None, in_shift=None, relu_in=False,
@@ -183,9 +184,11 @@ def conv2d_fwd_plan(x_shape, n_out, kh, kw, stride=1, pad=0, dil=1, bias=None, i
     return (rec, n) if parts else rec
 
 
-def _dgrad_operands(res, res_mask, bn_bwd, res_mask_bits):
+def _dgrad_operands(res, res_mask, bn_bwd, res_mask_bits, bn_in=None):
     """Which optional operands a stride-1 conv2d_dgrad hands to the tap-grid call (keys of _HAS)."""
     given = dict(res=res, res_mask=res_mask)
+    if bn_in is not None:
+        given.update(bn_in=True, bn_in_bits=bn_in[3])
     if bn_bwd is not None:
         given.update(bn_partial=True, bn_bwd=True, bwd_mask_scale=bn_bwd[3], bwd_mask_bits=bn_bwd[5] if len(bn_bwd) > 5 else None,
                      bwd_res_mask_bits=res_mask_bits)
@@ -193,16 +196,17 @@ def _dgrad_operands(res, res_mask, bn_bwd, res_mask_bits):
 
 
 def conv2d_dgrad_plan(dy_shape, n_in, H, W, kh, kw, stride=1, pad=0, dil=1, res=None, res_mask=None, accumulate_into=None,
-                      bn_bwd=None, res_mask_bits=None, parts=False):
+                      bn_bwd=None, res_mask_bits=None, parts=False, bn_in=None):
     """What a stride-1 conv2d_dgrad would launch for a gradient of dy_shape, as conv_last_launch() would report it (see
-    conv2d_fwd_plan).  bn_bwd: the tuple conv2d_dgrad takes, its entries True (or tensors) / None.  parts=True: -> (ConvLaunch,
-    record count of the sums; 0 = conv2d_dgrad returns no partials)."""
+    conv2d_fwd_plan).  bn_bwd, bn_in: the tuples conv2d_dgrad takes, their entries True (or tensors) / None; with bn_in the
+    record's BNF says whether a kernel applies that BatchNorm's backward in its loaders (0: conv2d_dgrad(bn_in=) would raise).
+    parts=True: -> (ConvLaunch, record count of the sums; 0 = conv2d_dgrad returns no partials)."""
     if stride != 1:
         raise ValueError('conv2d_dgrad_plan: stride-1 data gradients only')
     if _given(accumulate_into):
         res, res_mask = True, None
     rec, n = _tapgrid_plan(_dgrad_grid(tuple(dy_shape), n_in, H, W, kh, kw, 1, pad, dil),
-                           **_dgrad_operands(res, res_mask, bn_bwd, res_mask_bits))
+                           **_dgrad_operands(res, res_mask, bn_bwd, res_mask_bits, bn_in))
     return (rec, n) if parts else rec
 
 
@@ -218,7 +222,7 @@ def _dgrad_axis(parity, pad, dil, k, stride):
 
 
 def conv2d_dgrad(dy, wpt, n_in, H, W, kh, kw, stride=1, pad=0, dil=1, res=None, res_mask=None, accumulate_into=None,
-                 bn_bwd=None, res_mask_bits=None, pair_1x1=None, _s2_sums=None, out=None, records=None):
+                 bn_bwd=None, res_mask_bits=None, pair_1x1=None, _s2_sums=None, out=None, records=None, bn_in=None):
     """dy: NHWC [B,Ho,Wo,Cout]; wpt packed with transpose=True.  Returns dx NHWC [B,H,W,n_in16]
     (+ res * (res_mask > 0) if given).  With accumulate_into=dx0 the result is added to dx0 in place.
     bn_bwd=(x, save_mean, save_invstd, mask_scale, mask_shift[, mask_bits]) (stride 1; 3x3 / stride 2 / pad 1 with the mask_bits
@@ -227,6 +231,10 @@ def conv2d_dgrad(dy, wpt, n_in, H, W, kh, kw, stride=1, pad=0, dil=1, res=None, 
     (dx, partials) where partials = (records, count) for bn_backward(partials=) when the launch could also take that
     BatchNorm's two backward sums from its epilogue, else None (stride 1; with a residual only when its mask is also given
     as the sign bytes of bn_apply, res_mask_bits -- the float res_mask serves the launches that cannot use them).
+    bn_in=(c, coef, mask_affine, mask_bits) (with bn_bwd at stride 1, where conv2d_dgrad_plan reports BNF): dy is the gradient
+    reaching relu(bn(c)) [+ shortcut] with the mask as mask_affine=(scale, shift) or as sign bytes, coef from
+    bn_backward_finalize; the launch applies that BatchNorm's backward in its loaders and returns (dx, partials, dc), dc being
+    what bn_backward would have returned as dx.
     out: the result tensor to write (contiguous float32 [B,H,W,n_in16] on dy's device) instead of a fresh one.
     records (the strided bn_bwd form only): the record buffer to write (contiguous float32, at least
     dam_bn_workspace_floats(n_in16) elements, on dy's device) instead of a fresh one."""
@@ -243,6 +251,8 @@ def conv2d_dgrad(dy, wpt, n_in, H, W, kh, kw, stride=1, pad=0, dil=1, res=None, 
             raise ValueError('out and accumulate_into exclude each other')
         if out.dtype != torch.float32 or not out.is_contiguous() or tuple(out.shape) != want or out.device != dy.device:
             raise ValueError('out must be a contiguous float32 tensor of shape %s on %s' % (want, dy.device))
+    if bn_in is not None and (bn_bwd is None or stride != 1):
+        raise ValueError('bn_in: with bn_bwd at stride 1 only')
     if bn_bwd is not None and stride == 2:
         # the strided form: the upstream BatchNorm is a residual block's bn2 (mask = the sign bytes of the block output); only the
         # one-launch kernels of the thin stages take its sums, (dx, None) otherwise
@@ -276,8 +286,20 @@ def conv2d_dgrad(dy, wpt, n_in, H, W, kh, kw, stride=1, pad=0, dil=1, res=None, 
         rec = torch.empty(_lib.lib().dam_bn_workspace_floats(n16), dtype=torch.float32, device=dy.device)
         epi = _lib.BnBwdSums(_lib.ptr(xb), _lib.ptr(mean), _lib.ptr(invstd), _lib.ptr(msc), _lib.ptr(msh), _lib.ptr(res_mask_bits),
                              _lib.ptr(up_bits))
+        fin = dc = None
+        if bn_in is not None:
+            c, coef, aff, bits = bn_in
+            _lib.require_cuda(c, coef)
+            _f32c(c, 'c'), _f32c(coef, 'coef')
+            if c.shape != dy.shape or (aff is None) == (bits is None):
+                raise ValueError('bn_in: c has the shape of dy; the mask as (scale, shift) or as sign bytes')
+            dc = torch.empty_like(c)
+            fin = _lib.BnBwdIn(_lib.ptr(c), _lib.ptr(coef), _lib.ptr(aff[0]) if aff else None, _lib.ptr(aff[1]) if aff else None,
+                               _lib.ptr(bits), _lib.ptr(dc))
         parts = _tapgrid(_dgrad_grid(dy.shape, n_in, H, W, kh, kw, 1, pad, dil), dy, wpt, dx, res=res, res_mask=res_mask,
-                         bn_partial=rec, bn_bwd=epi)
+                         bn_partial=rec, bn_bwd=epi, bn_in=fin)
+        if bn_in is not None:
+            return dx, ((rec, parts) if parts > 0 else None), dc
         return dx, ((rec, parts) if parts > 0 else None)
     _f32c(dy, 'dy'), _f32c(res, 'res'), _f32c(res_mask, 'res_mask')
     B, Ho, Wo, Co = dy.shape
@@ -756,6 +778,24 @@ def bn_backward(dy, y_mask, x, gamma, save_mean, save_invstd, training=True, mas
                                               _lib.ptr(dgamma), _lib.ptr(dbeta), _lib.ptr(ws), given, _lib.stream()),
                'dam_bn_backward_f32')
     return dx, dgamma, dbeta
+
+
+def bn_backward_finalize(partials, x, gamma, save_mean, save_invstd, training=True, dgamma=None, dbeta=None):
+    """The finalize of bn_backward(partials=) on its own: -> (coef [3, C], dgamma, dbeta), dgamma / dbeta bitwise bn_backward's;
+    coef is what conv2d_dgrad(bn_in=) applies in its loaders (x: the BatchNorm's input, for its shape only)."""
+    _lib.require_cuda(x, gamma)
+    C = x.shape[-1]
+    if dgamma is None:
+        dgamma = torch.empty(C, dtype=torch.float32, device=x.device)
+    if dbeta is None:
+        dbeta = torch.empty(C, dtype=torch.float32, device=x.device)
+    coef = torch.empty((3, C), dtype=torch.float32, device=x.device)
+    ws, given = partials
+    _lib.check(_lib.lib().dam_bn_backward_finalize_f32(_lib.ptr(ws), given, x.numel() // C, C, _lib.ptr(gamma), _lib.ptr(save_mean),
+                                                       _lib.ptr(save_invstd), 1 if training else 0, _lib.ptr(dgamma),
+                                                       _lib.ptr(dbeta), _lib.ptr(coef), _lib.stream()),
+               'dam_bn_backward_finalize_f32')
+    return coef, dgamma, dbeta
 
 
 def channel_sum(x, n_real, out=None):

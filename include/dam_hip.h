@@ -51,11 +51,12 @@ typedef enum dam_pcm_dtype { DAM_PCM_F32 = 0, DAM_PCM_F64 = 1, DAM_PCM_S16 = 2, 
  * launch behind an 8 us gap per step (profiles/r05_C3_step_timeline.txt, the last line).  n >= 1, counter + offset >= 0. */
 #define DAM_PCM_ROTATE 0x200
 struct dam_bn_bwd_sums; /* defined in the BatchNorm section */
+struct dam_bn_bwd_in;
 
 /* Library / build identification ("gfx950").  DAM_ABI_VERSION is bumped whenever a signature below changes; a binding
  * compares dam_abi_version() of the library it loaded with the version it was written against and refuses a stale one
  * (deep-audio-mixer_amd/_lib.py: EXPECTED_ABI). */
-#define DAM_ABI_VERSION 35
+#define DAM_ABI_VERSION 36
 const char* dam_arch(void);
 int dam_abi_version(void);
 
@@ -235,6 +236,10 @@ int dam_conv_pack_weights_multi_f32(const int64_t* desc_dev, int n_tensors, int6
  * bn_bwd (optional, see dam_bn_bwd_sums below; needs bn_partial; with res only if res_mask_bits is set there): the launch is a data gradient whose
  * output dy feeds the backward pass of y = relu(bn(x)); if it can, it also writes that pass's two per-channel sums as records
  * [*bn_parts_host][n_out][2] into bn_partial (then hand them to dam_bn_backward_f32 as partials_given); 0 records = not produced.
+ * bn_in (optional, ABI 36; see dam_bn_bwd_in below): x is the gradient dy that reaches relu(bn(c)); the launch applies that
+ * BatchNorm's backward (dc = a * (dy * mask) + b * c + k, coefficients from dam_bn_backward_finalize_f32) in its row loaders,
+ * convolves dc and stores it to bn_in->dc -- bitwise dam_bn_backward_f32(partials_given) followed by this call on its dx.  Only
+ * for the layers the plan names (out16[13] != 0, see dam_conv2d_tapgrid_plan); DAM_ERR_UNSUPPORTED for every other.
  * workspace (optional): scratch for split-K over the input channels (used for small-spatial, wide layers; at most
  * 8 * B*OHt*OWt*n_out floats are used, fewer if less is given); partial slabs are summed in a fixed order.
  * Which kernel a call gets (1x1 direct, row-ring strip, loader-wave pipe, pipe on column ranges, tile) is decided by host
@@ -246,8 +251,8 @@ int dam_conv2d_tapgrid_f32(const float* x, int B, int H, int W, int C, int in_nc
                            int out_stride, int out_off_h, int out_off_w, int in_stride, int nA, int nB,
                            int off_h, int step_h, int off_w, int step_w, int wt_base, int wt_sa, int wt_sb,
                            const float* res, const float* res_mask, float* bn_partial, int* bn_parts_host,
-                           const struct dam_bn_bwd_sums* bn_bwd, float* workspace, int64_t workspace_floats,
-                           void* batch, void* stream);
+                           const struct dam_bn_bwd_sums* bn_bwd, const struct dam_bn_bwd_in* bn_in, float* workspace,
+                           int64_t workspace_floats, void* batch, void* stream);
 
 /* Two single-tap operators into the same output pixels in ONE launch:
  *   y[b, oh*out_stride+out_off_h, ow*out_stride+out_off_w, :] = W1p[tap1] . x1[b, oh, ow, :] + W2p[tap2] . x2[b, oh, ow, :]
@@ -347,6 +352,8 @@ int dam_conv_batch_flush(void* batch, void* stream);
 #define DAM_CONV_HAS_BWD_MASK_SCALE 0x200u     /* mask_scale and mask_shift */
 #define DAM_CONV_HAS_WORKSPACE 0x400u
 #define DAM_CONV_HAS_BATCH 0x800u
+#define DAM_CONV_HAS_BN_IN 0x1000u             /* bn_in (ABI 36) */
+#define DAM_CONV_HAS_BN_IN_BITS 0x2000u        /* ... with its mask as sign bytes (else mask_scale / mask_shift) */
 int dam_conv2d_tapgrid_plan(int B, int H, int W, int C, int in_nchw, int k_chunks, int n_out, int relu_in, int relu_out,
                             int OHt, int OWt, int Ho, int Wo, int out_stride, int out_off_h, int out_off_w, int in_stride,
                             int nA, int nB, int off_h, int step_h, int off_w, int step_w, int wt_base, int wt_sa, int wt_sb,
@@ -364,7 +371,9 @@ int dam_conv2d_tapgrid_plan(int B, int H, int W, int C, int in_nchw, int k_chunk
  *   [8] PU  [9] STATS [10] KS      pipe: items per loader thread, statistics mode, K split over the wave pairs
  *   [11] ksplit                    tile: split-K factor (> 1: splitk_reduce_kernel wrote the result)
  *   [12] ranges                    column ranges launched (family 3; the tile fields are those of the last range), else 1
- *   [13..15] 0 */
+ *   [13] BNF                       strip: the BatchNorm-backward apply of bn_in ran in the row loaders, 2 = mask from (scale, shift),
+ *                                  3 = from sign bytes; 0 = not fused (a call WITH bn_in then returns DAM_ERR_UNSUPPORTED)
+ *   [14..15] 0 */
 int dam_conv_last_launch(int* out16_host);
 
 /* Weight gradient of the same convolutions (autograd of nn.Conv2d reached from loss.backward(),
@@ -487,6 +496,14 @@ typedef struct dam_bn_bwd_sums {
     const uint8_t* mask_bits;
 } dam_bn_bwd_sums;
 
+/* BatchNorm-backward apply in a data gradient's row loaders (dam_conv2d_tapgrid_f32's bn_in, ABI 36): the call's x is dy, the
+ * gradient reaching y = relu(bn(c)) [+ shortcut]; mask as in dam_bn_backward_f32: (c*mask_scale + mask_shift > 0) or the sign
+ * bytes of dam_bn_apply_f32 (exactly one form).  coef: [3][C] from dam_bn_backward_finalize_f32.  dc (shape of c) receives what
+ * dam_bn_backward_f32 would have written to dx.  Host struct of device pointers. */
+typedef struct dam_bn_bwd_in {
+    const float* c; const float* coef; const float* mask_scale; const float* mask_shift; const uint8_t* mask_bits; float* dc;
+} dam_bn_bwd_in;
+
 /* Training-mode statistics of x: save_mean, save_invstd = 1/sqrt(biased var + eps), the fused affine
  * scale = gamma*invstd, shift = beta - mean*scale, and torch's running-stat update
  * (running = (1-momentum)*running + momentum*stat, unbiased variance; ++*num_batches_tracked).
@@ -552,6 +569,13 @@ int dam_bn_backward_f32(const float* dy, const float* y_mask, const float* x, in
                         const float* gamma, const float* save_mean, const float* save_invstd, int training,
                         const float* mask_scale, const float* mask_shift, const uint8_t* mask_bits, float* dx,
                         float* dgamma, float* dbeta, float* workspace, int partials_given, void* stream);
+
+/* The finalize of dam_bn_backward_f32(partials_given = parts) on its own (ABI 36): merges the records [parts][C][2] with the
+ * arithmetic that call uses, writes dgamma / dbeta (bitwise that call's) and coef = [3][C]: dx = coef[0] * dz + coef[1] * x + coef[2]
+ * per channel -- for a consumer that applies it itself (dam_conv2d_tapgrid_f32's bn_in).  One small launch. */
+int dam_bn_backward_finalize_f32(const float* partial, int parts, int64_t n_pixels, int C, const float* gamma,
+                                 const float* save_mean, const float* save_invstd, int training, float* dgamma, float* dbeta,
+                                 float* coef, void* stream);
 
 /* The same for TWO BatchNorms that share dy and the mask (exactly one of y_mask / mask_bits) -- a residual block's bn2 and the BatchNorm of its shortcut
  * convolution, both fed by the gradient of relu(bn2(..) + bn_sc(..)) (models/model_resnet.py:23-28): dy and the mask are
