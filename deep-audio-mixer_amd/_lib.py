@@ -12,7 +12,7 @@ LIB_PATH = os.environ.get('DAM_LIB_PATH') or os.path.join(_HERE, 'libdam_hip.so'
 # include/dam_hip.h: bumped whenever a C signature changes (together with dam_abi_version() in csrc/dam_api.hip and
 # DAM_ABI_VERSION in the header).  libdam_hip.so is git-ignored and travels prebuilt: a stale one would read device pointers
 # as streams, so lib() refuses it instead of launching.
-EXPECTED_ABI = 36
+EXPECTED_ABI = 37
 
 _STATUS = {0: 'DAM_OK', -1: 'DAM_ERR_BAD_ARG', -2: 'DAM_ERR_UNSUPPORTED', -3: 'DAM_ERR_LAUNCH',
            -4: 'DAM_ERR_WORKSPACE'}
@@ -62,6 +62,9 @@ SIGNATURES = {
     'dam_wgrad_last_launch': (c_i, [c_p]),
     'dam_conv2d_wgrad_plan': (c_i, [c_i] * 19 + [c_i64, c_p]),
     'dam_s2_last_launch': (c_i, [c_p]),
+    'dam_conv_s2_pair_fwd_plan': (c_i, [c_i] * 8 + [c_p]),
+    'dam_dgrad_s2_3x3_plan': (c_i, [c_i] * 11 + [c_p]),
+    'dam_conv1x1_pair_plan': (c_i, [c_i] * 10 + [c_p]),
     'dam_bn_workspace_floats': (c_i64, [c_i]),
     'dam_bn_stats_f32': (c_i, [c_p, c_i64, c_i, c_p, c_p, c_p, c_p, c_p, c_f, c_f, c_p, c_p, c_p, c_p, c_p, c_p]),
     'dam_bn_finalize_f32': (c_i, [c_p, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_f, c_f, c_p, c_p, c_p, c_p, c_p]),

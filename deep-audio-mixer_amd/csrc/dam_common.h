@@ -116,24 +116,4 @@ static inline int device_cus() {
     return n;
 }
 
-// What the last call of this thread to one of the down-sampling block's entry points (dam_conv_s2_pair_fwd_f32,
-// dam_dgrad_s2_3x3_f32, dam_conv1x1_pair_f32) committed to (dam_s2_last_launch, include/dam_hip.h): a host variable cleared at
-// the top of each of the three, written once the launch is made, read by tests that must know which instantiation they exercised.
-enum S2Entry { S2_ENTRY_NONE = 0, S2_ENTRY_PAIR_FWD = 1, S2_ENTRY_DGRAD = 2, S2_ENTRY_PAIR_1X1 = 3 };
-enum S2Family { S2_FAM_NONE = 0, S2_FAM_RESIDENT = 1, S2_FAM_STREAM_LDS = 2, S2_FAM_STREAM = 3, S2_FAM_PAIR_1X1 = 4 };
-struct S2LaunchNote {
-    int entry, family, NB, NCH, MB, WAVES, pair, sums, workgroups, units, rounds, n_xcd, records;
-};
-extern thread_local S2LaunchNote s2_last_launch;       // (defined in dam_conv_s2.hip)
-// The unit walk of the two persistent kernels (conv_s2_pair_kernel, dgrad_s2_kernel) in host arithmetic: every XCD takes one
-// contiguous share `per_xcd` of the units, its wave w of workgroup g starts at unit w * wg_per_xcd + g of the share and steps by
-// wg_per_xcd * WAVES.  -> the largest number of units any wave takes (the first wave of XCD 0, whose share is never cut short).
-static inline int s2_resident_rounds(int64_t units, int64_t wgs, int waves, int* n_xcd_out) {
-    const int n_xcd = (wgs & 7) == 0 ? 8 : 1;
-    const int64_t wg_per_xcd = wgs / n_xcd, per_xcd = (units + n_xcd - 1) / n_xcd;
-    const int64_t share = per_xcd < units ? per_xcd : units, ustride = wg_per_xcd * waves;
-    if (n_xcd_out) *n_xcd_out = n_xcd;
-    return ustride > 0 ? (int)cdiv(share, ustride) : 0;
-}
-
 }  // namespace dam

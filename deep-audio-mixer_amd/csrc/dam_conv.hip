@@ -25,6 +25,7 @@
 #include "dam_common.h"
 #include "dam_conv_plan.h"
 #include "dam_conv_stage.h"
+#include "dam_s2_plan.h"
 
 namespace dam {
 
@@ -559,6 +560,32 @@ int launch_1x1(const ConvLaunchPlan& p, const ConvOperands& a, hipStream_t st) {
     return DAM_ERR_UNSUPPORTED;
 }
 
+// Operands of one dam_conv1x1_pair_f32 call, as it got them.
+struct Pair1x1Operands {
+    const float *x1, *w1;
+    int tap1;
+    const float *x2, *w2;
+    int tap2;
+    float* y;
+};
+
+// Every instantiation of conv1x1_pair_kernel, by <NB, R, BOTH> (the note carries R as WAVES, BOTH as pair).
+int launch_pair_1x1(const S2Plan& p, const Pair1x1Operands& a, int B, int H, int W, int C, int n_out, int OHt, int OWt, int out_stride,
+                    int out_off_h, int out_off_w, hipStream_t st) {
+#define DAM_PAIR_CASE(NB_, R_, BOTH_)                                                                                         \
+    if (p.note.NB == NB_ && p.note.WAVES == R_ && (p.note.pair != 0) == BOTH_) {                                              \
+        hipLaunchKernelGGL((conv1x1_pair_kernel<NB_, R_, BOTH_>), dim3(p.grid_x, p.grid_y), dim3(p.threads), 0, st, a.x1,     \
+                           reinterpret_cast<const float4*>(a.w1), a.tap1, a.x2, reinterpret_cast<const float4*>(a.w2), a.tap2, B, H, W, C, \
+                           n_out, a.y, OHt, OWt, out_stride, out_off_h, out_off_w, p.segs, (int)p.units);                     \
+        DAM_CHECK_LAUNCH();                                                                                                   \
+        return DAM_OK;                                                                                                        \
+    }
+    DAM_PAIR_CASE(2, 2, true) DAM_PAIR_CASE(2, 4, true) DAM_PAIR_CASE(2, 4, false)
+    DAM_PAIR_CASE(1, 2, true) DAM_PAIR_CASE(1, 4, true) DAM_PAIR_CASE(1, 8, false)
+#undef DAM_PAIR_CASE
+    return DAM_ERR_UNSUPPORTED;
+}
+
 }  // namespace
 }  // namespace dam
 
@@ -567,36 +594,24 @@ extern "C" int dam_conv1x1_pair_f32(const float* x1, const float* w1_packed, int
                                     int out_off_h, int out_off_w, void* stream) {
     using namespace dam;
     s2_last_launch = S2LaunchNote{};
-    if (!x1 || !w1_packed || !x2 || !w2_packed || !y || B <= 0 || H <= 0 || W <= 0 || tap1 < 0 || tap2 < 0 || out_stride < 1)
-        return DAM_ERR_BAD_ARG;
-    if (C % 16 || n_out % 16 || C <= 0 || n_out <= 0) return DAM_ERR_UNSUPPORTED;
-    if ((H - 1) * out_stride + out_off_h >= OHt || (W - 1) * out_stride + out_off_w >= OWt || out_off_h < 0 || out_off_w < 0)
-        return DAM_ERR_BAD_ARG;
-    if ((int64_t)B * H * W * C * 4 >= (1ll << 31)) return DAM_ERR_UNSUPPORTED;
-    const int segs = (int)cdiv(W, 16);
-    const int64_t units = (int64_t)B * H * segs;
-    if (units >= (1ll << 30)) return DAM_ERR_UNSUPPORTED;
-    const int nblk = n_out / 16, nch = C / 16;
-    hipStream_t st = (hipStream_t)stream;
-#define DAM_PAIR_GO(NB_, R_, BOTH_)                                                                                           \
-    do {                                                                                                                      \
-        hipLaunchKernelGGL((conv1x1_pair_kernel<NB_, R_, BOTH_>), dim3((unsigned)cdiv(units, 4), (unsigned)(nblk / NB_)), dim3(256), 0, st, \
-                           x1, reinterpret_cast<const float4*>(w1_packed), tap1, x2, reinterpret_cast<const float4*>(w2_packed), tap2, B, \
-                           H, W, C, n_out, y, OHt, OWt, out_stride, out_off_h, out_off_w, segs, (int)units);                      \
-        note_nb = NB_; note_r = R_; note_both = BOTH_;                                                                        \
-    } while (0)
-    int note_nb = 0, note_r = 0, note_both = 0;
-    if (nblk % 2 == 0) {
-        if (nch <= 2) DAM_PAIR_GO(2, 2, true); else if (nch <= 4) DAM_PAIR_GO(2, 4, true); else DAM_PAIR_GO(2, 4, false);
-    } else {
-        if (nch <= 2) DAM_PAIR_GO(1, 2, true); else if (nch <= 4) DAM_PAIR_GO(1, 4, true); else DAM_PAIR_GO(1, 8, false);
-    }
-#undef DAM_PAIR_GO
-    DAM_CHECK_LAUNCH();
-    // a wave takes exactly one (image, row, 16-pixel segment) unit of NB channel blocks
-    s2_last_launch = S2LaunchNote{S2_ENTRY_PAIR_1X1, S2_FAM_PAIR_1X1, note_nb, nch, 0, note_r, note_both, 0,
-                                  (int)(cdiv(units, 4) * (nblk / note_nb)), (int)units, 1, 1, 0};
-    return DAM_OK;
+    if (!x1 || !w1_packed || !x2 || !w2_packed || !y || tap1 < 0 || tap2 < 0) return DAM_ERR_BAD_ARG;
+    S2Plan plan;
+    int rc = plan_pair_1x1(B, H, W, C, n_out, OHt, OWt, out_stride, out_off_h, out_off_w, plan);
+    if (rc != DAM_OK) return rc;
+    rc = launch_pair_1x1(plan, Pair1x1Operands{x1, w1_packed, tap1, x2, w2_packed, tap2, y}, B, H, W, C, n_out, OHt, OWt, out_stride,
+                         out_off_h, out_off_w, (hipStream_t)stream);
+    if (rc == DAM_OK) s2_last_launch = plan.note;
+    return rc;
+}
+
+extern "C" int dam_conv1x1_pair_plan(int B, int H, int W, int C, int n_out, int OHt, int OWt, int out_stride, int out_off_h,
+                                     int out_off_w, int* out16_host) {
+    using namespace dam;
+    if (!out16_host) return DAM_ERR_BAD_ARG;
+    S2Plan plan;
+    const int rc = plan_pair_1x1(B, H, W, C, n_out, OHt, OWt, out_stride, out_off_h, out_off_w, plan);
+    s2_note_to_ints(plan.note, out16_host);      // (all zero on any refusal)
+    return rc;
 }
 
 extern "C" int64_t dam_conv_batch_bytes(void) { return (int64_t)sizeof(dam::ConvBatch); }

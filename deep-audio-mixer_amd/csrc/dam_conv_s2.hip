@@ -14,7 +14,7 @@
 // operand sets: the next chunk's (or next unit's) nine loads are in flight under the current MFMAs.  Statistics: every lane
 // keeps shifted sums (pivot = its first value) of the 4 * NB channels it owns across all its units, the sixteen pixel lanes are
 // merged once at the end (Chan), then the four waves: one record per workgroup -- no pass over c1 / cs.
-#include "dam_common.h"
+#include "dam_s2_plan.h"
 
 namespace dam {
 
@@ -260,56 +260,38 @@ __global__ __launch_bounds__(64 * WAVES) void conv_s2_pair_kernel(const float* _
     }
 }
 
-template <int NB, int NCH, int WAVES>
-int launch_conv_s2_pair(const float* x, const float* wp, const float* wp2, int B, int H, int W, float* y, float* ys, float* p1,
-                        float* p2, int* parts_host, hipStream_t st) {
-    const int Hd = (H + 1) / 2, Wd = (W + 1) / 2;
-    const int64_t px = (int64_t)B * Hd * Wd, xb = (int64_t)B * H * W * NCH * 64;
-    if (px >= (1ll << 26) || xb >= (1ll << 31)) return DAM_ERR_UNSUPPORTED;      // byte offsets of the range-checked loads
-    const int64_t units = cdiv(px, 16);
-    const size_t lds = (size_t)10 * NCH * NB * 1024;
-    const int cus = device_cus();
-    // Workgroups per CU by makespan, as in dam_dgrad_s2.hip: n resident waves per SIMD share its MFMA pipe; more waves hide the operand
-    // latency better, which decides while the costs are within ~15 %.  One statistics record per workgroup, <= BN_RECORDS_MAX.
-    const bool stats = p1 != nullptr;
-    static PerDevice<int> occ[2];       // resident workgroups per CU of this instantiation (registers and LDS; asked once per device)
-    int& oc = occ[stats ? 1 : 0]();
+// Device pointers of one call, as dam_conv_s2_pair_fwd_f32 got them.
+struct PairFwdOperands {
+    const float *x, *wp, *wp2;
+    float *y, *ys, *p1, *p2;
+};
+
+// Every instantiation of conv_s2_pair_kernel, by the plan's note: F_<NB, NCH, STATS, WAVES>(...).
+#define DAM_CS2_INST(N_, F_, ...)                                                                                              \
+    ((N_).NB == 2 && (N_).NCH == 1 && (N_).WAVES == 4 ? ((N_).sums ? F_<2, 1, true, 4>(__VA_ARGS__) : F_<2, 1, false, 4>(__VA_ARGS__)) \
+     : (N_).NB == 4 && (N_).NCH == 2 && (N_).WAVES == 8 ? ((N_).sums ? F_<4, 2, true, 8>(__VA_ARGS__) : F_<4, 2, false, 8>(__VA_ARGS__)) \
+     : DAM_ERR_UNSUPPORTED)
+
+// Resident workgroups per CU of one instantiation (registers and LDS; asked once per device).
+template <int NB, int NCH, bool STATS, int WAVES>
+int conv_s2_pair_per_cu(size_t lds) {
+    static PerDevice<int> occ;
+    int& oc = occ();
     if (!oc) {
         int n = 0;
-        const hipError_t e = stats ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, conv_s2_pair_kernel<NB, NCH, true, WAVES>, 64 * WAVES, lds)
-                                   : hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, conv_s2_pair_kernel<NB, NCH, false, WAVES>, 64 * WAVES, lds);
+        const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, conv_s2_pair_kernel<NB, NCH, STATS, WAVES>, 64 * WAVES, lds);
         oc = (e == hipSuccess && n >= 1) ? n : 1;
     }
-    int max_per_cu = oc;
-    if (max_per_cu > 3) max_per_cu = 3;
-    if (WAVES == 8) max_per_cu = 1;
-    if (max_per_cu < 1) max_per_cu = 1;
-    while (max_per_cu > 1 && (int64_t)cus * max_per_cu > BN_RECORDS_MAX) --max_per_cu;
-    if ((int64_t)cus > BN_RECORDS_MAX) return DAM_ERR_UNSUPPORTED;
-    int per_cu = 1;
-    int64_t best = 0;
-    for (int n = 1; n <= max_per_cu; ++n) {
-        const int64_t cost = cdiv(units, (int64_t)WAVES * cus * n) * n * 100;
-        if (n == 1 || cost * 100 <= best * 115) { best = n == 1 ? cost : (cost < best ? cost : best); per_cu = n; }
-    }
-    int64_t wgs = (int64_t)cus * per_cu;
-    if (wgs > cdiv(units, WAVES)) wgs = cdiv(units, WAVES);
-    if (parts_host) *parts_host = stats ? (int)wgs : 0;
-    if (lds > 64 * 1024 && !(stats ? raise_lds_limit<&conv_s2_pair_kernel<NB, NCH, true, WAVES>>(160 * 1024)
-                                   : raise_lds_limit<&conv_s2_pair_kernel<NB, NCH, false, WAVES>>(160 * 1024))) return DAM_ERR_LAUNCH;
-    if (stats)
-        hipLaunchKernelGGL((conv_s2_pair_kernel<NB, NCH, true, WAVES>), dim3((unsigned)wgs), dim3(64 * WAVES), lds, st, x, (unsigned)xb,
-                           reinterpret_cast<const float4*>(wp), reinterpret_cast<const float4*>(wp2), Hd, Wd, H, W, y, ys, p1, p2, (int)px,
-                           (int)units);
-    else
-        hipLaunchKernelGGL((conv_s2_pair_kernel<NB, NCH, false, WAVES>), dim3((unsigned)wgs), dim3(64 * WAVES), lds, st, x, (unsigned)xb,
-                           reinterpret_cast<const float4*>(wp), reinterpret_cast<const float4*>(wp2), Hd, Wd, H, W, y, ys, p1, p2, (int)px,
-                           (int)units);
+    return oc;
+}
+
+template <int NB, int NCH, bool STATS, int WAVES>
+int launch_conv_s2_pair_as(const S2Plan& p, const PairFwdOperands& a, int Hd, int Wd, int H, int W, hipStream_t st) {
+    if (p.lds > 64 * 1024 && !raise_lds_limit<&conv_s2_pair_kernel<NB, NCH, STATS, WAVES>>(160 * 1024)) return DAM_ERR_LAUNCH;
+    hipLaunchKernelGGL((conv_s2_pair_kernel<NB, NCH, STATS, WAVES>), dim3(p.grid_x), dim3(p.threads), p.lds, st, a.x, (unsigned)p.xb,
+                       reinterpret_cast<const float4*>(a.wp), reinterpret_cast<const float4*>(a.wp2), Hd, Wd, H, W, a.y, a.ys, a.p1, a.p2,
+                       (int)p.px, (int)p.units);
     DAM_CHECK_LAUNCH();
-    int n_xcd = 1;
-    const int rounds = s2_resident_rounds(units, wgs, WAVES, &n_xcd);
-    s2_last_launch = S2LaunchNote{S2_ENTRY_PAIR_FWD, S2_FAM_RESIDENT, NB, NCH, 1, WAVES, 1, stats ? 1 : 0, (int)wgs, (int)units, rounds, n_xcd,
-                                  stats ? (int)wgs : 0};
     return DAM_OK;
 }
 
@@ -496,27 +478,32 @@ __global__ __launch_bounds__(256) void conv_s2_pair_stream_kernel(const float* _
     }
 }
 
-int launch_conv_s2_pair_stream(const float* x, const float* wp, const float* wp2, int B, int H, int W, int Ci, int Co, float* y, float* ys,
-                               float* p1, float* p2, int* parts_host, hipStream_t st) {
-    const int Hd = (H + 1) / 2, Wd = (W + 1) / 2, NCH = Ci / 16, NB = Co / 16;
-    const int64_t px = (int64_t)B * Hd * Wd, xb = (int64_t)B * H * W * Ci * 4;
-    const int64_t groups = cdiv(px, 64);             // one pixel block of 16 per wave
-    if (px >= (1ll << 26) || xb >= (1ll << 31) || groups * NB >= (1ll << 31) || (int64_t)9 * Ci * Co * 4 >= (1ll << 31)) return DAM_ERR_UNSUPPORTED;
-    const bool stats = p1 != nullptr;
-    if (stats && groups > BN_RECORDS_MAX) return DAM_ERR_UNSUPPORTED;      // (one record per group of 64 pixels)
-    if (parts_host) *parts_host = stats ? (int)groups : 0;
-    const dim3 grid((unsigned)(cdiv(groups, 8) * 8 * NB)), block(256);        // whole rounds of eight groups (one per XCD)
-#define DAM_CS2S_GO(ST_)                                                                                                        \
-    hipLaunchKernelGGL((conv_s2_pair_stream_kernel<ST_>), grid, block, 0, st, x, (unsigned)xb, reinterpret_cast<const float4*>(wp), \
-                       reinterpret_cast<const float4*>(wp2), Hd, Wd, H, W, NCH, NB, y, ys, p1, p2, (int)px)
-    if (stats) DAM_CS2S_GO(true); else DAM_CS2S_GO(false);
+int launch_conv_s2_pair_stream(const S2Plan& p, const PairFwdOperands& a, int Hd, int Wd, int H, int W, hipStream_t st) {
+    const dim3 grid(p.grid_x), block(p.threads);
+#define DAM_CS2S_GO(ST_)                                                                                                          \
+    hipLaunchKernelGGL((conv_s2_pair_stream_kernel<ST_>), grid, block, 0, st, a.x, (unsigned)p.xb, reinterpret_cast<const float4*>(a.wp), \
+                       reinterpret_cast<const float4*>(a.wp2), Hd, Wd, H, W, p.note.NCH, p.note.NB, a.y, a.ys, a.p1, a.p2, (int)p.px)
+    if (p.note.sums) DAM_CS2S_GO(true); else DAM_CS2S_GO(false);
 #undef DAM_CS2S_GO
     DAM_CHECK_LAUNCH();
-    // a wave takes exactly one (16 pixels, 16 channels) unit; group g of 64 pixels runs on XCD g % 8
-    s2_last_launch = S2LaunchNote{S2_ENTRY_PAIR_FWD, S2_FAM_STREAM_LDS, NB, NCH, 1, 4, 1, stats ? 1 : 0, (int)grid.x, (int)(cdiv(px, 16) * NB), 1, 8,
-                                  stats ? (int)groups : 0};
     return DAM_OK;
 }
+
+int launch_conv_s2_pair(const S2Plan& p, const PairFwdOperands& a, int H, int W, hipStream_t st) {
+    const int Hd = (H + 1) / 2, Wd = (W + 1) / 2;
+    if (p.note.family == S2_FAM_STREAM_LDS) return launch_conv_s2_pair_stream(p, a, Hd, Wd, H, W, st);
+    return DAM_CS2_INST(p.note, launch_conv_s2_pair_as, p, a, Hd, Wd, H, W, st);
+}
+
+// The two facts the plan takes from the device: what the caller gave (> 0), else the current device's -- the occupancy of the
+// persistent instantiation the channel counts name.
+S2Device conv_s2_pair_device(int Ci, int Co, bool stats, int cus, int resident_per_cu) {
+    S2LaunchNote inst{};
+    if (resident_per_cu <= 0)
+        resident_per_cu = s2_pair_fwd_resident(Ci, Co, stats, inst) ? DAM_CS2_INST(inst, conv_s2_pair_per_cu, s2_resident_lds(inst)) : 1;
+    return S2Device{cus > 0 ? cus : device_cus(), resident_per_cu};
+}
+#undef DAM_CS2_INST
 
 }  // namespace
 }  // namespace dam
@@ -527,23 +514,29 @@ extern "C" int dam_conv_s2_pair_fwd_f32(const float* x, const float* w_packed, c
                                         void* stream) {
     using namespace dam;
     s2_last_launch = S2LaunchNote{};
-    if (!x || !w_packed || !wsc_packed || !y || !ysc || B <= 0 || H <= 0 || W <= 0) return DAM_ERR_BAD_ARG;
-    if ((partial != nullptr) != (partial_sc != nullptr)) return DAM_ERR_BAD_ARG;
-    if (partial && !parts_host) return DAM_ERR_BAD_ARG;
-    hipStream_t st = (hipStream_t)stream;
-    if (Ci == 16 && Co == 32) return launch_conv_s2_pair<2, 1, 4>(x, w_packed, wsc_packed, B, H, W, y, ysc, partial, partial_sc, parts_host, st);
-    if (Ci == 32 && Co == 64) return launch_conv_s2_pair<4, 2, 8>(x, w_packed, wsc_packed, B, H, W, y, ysc, partial, partial_sc, parts_host, st);
-    // the wide blocks: weight fragments streamed from L2 (an even chunk count: the two register sets alternate)
-    if (Ci % 32 == 0 && Co % 16 == 0)
-        return launch_conv_s2_pair_stream(x, w_packed, wsc_packed, B, H, W, Ci, Co, y, ysc, partial, partial_sc, parts_host, st);
-    return DAM_ERR_UNSUPPORTED;
+    if (!x || !w_packed || !wsc_packed || !y || !ysc) return DAM_ERR_BAD_ARG;
+    if ((partial != nullptr) != (partial_sc != nullptr) || (partial && !parts_host)) return DAM_ERR_BAD_ARG;
+    const bool stats = partial != nullptr;
+    S2Plan plan;
+    int rc = plan_s2_pair_fwd(B, H, W, Ci, Co, stats, conv_s2_pair_device(Ci, Co, stats, 0, 0), plan);
+    if (rc != DAM_OK) return rc;
+    if (parts_host) *parts_host = plan.note.records;
+    rc = launch_conv_s2_pair(plan, PairFwdOperands{x, w_packed, wsc_packed, y, ysc, partial, partial_sc}, H, W, (hipStream_t)stream);
+    if (rc == DAM_OK) s2_last_launch = plan.note;
+    return rc;
+}
+
+extern "C" int dam_conv_s2_pair_fwd_plan(int B, int H, int W, int Ci, int Co, int stats, int cus, int resident_per_cu, int* out16_host) {
+    using namespace dam;
+    if (!out16_host) return DAM_ERR_BAD_ARG;
+    S2Plan plan;
+    const int rc = plan_s2_pair_fwd(B, H, W, Ci, Co, stats != 0, conv_s2_pair_device(Ci, Co, stats != 0, cus, resident_per_cu), plan);
+    s2_note_to_ints(plan.note, out16_host);      // (all zero on any refusal)
+    return rc;
 }
 
 extern "C" int dam_s2_last_launch(int* out16_host) {
     if (!out16_host) return DAM_ERR_BAD_ARG;
-    const dam::S2LaunchNote& n = dam::s2_last_launch;
-    const int v[16] = {n.entry, n.family, n.NB, n.NCH, n.MB, n.WAVES, n.pair, n.sums, n.workgroups, n.units, n.rounds, n.n_xcd, n.records,
-                       0, 0, 0};
-    for (int i = 0; i < 16; ++i) out16_host[i] = v[i];
+    dam::s2_note_to_ints(dam::s2_last_launch, out16_host);
     return DAM_OK;
 }

@@ -19,7 +19,7 @@
 //   dgrad_s2_stream_kernel  the wide blocks (image 240 KB ... 1.3 MB): one (pixel block, channel block) unit per wave, the weight
 //                           fragments go straight from L2 into the MFMA operand.
 // DESIGN.md section 4.2a has the measurements; profiles/r04_s2_kernels_ab.txt the steps that led here.
-#include "dam_common.h"
+#include "dam_s2_plan.h"
 
 namespace dam {
 namespace {
@@ -261,58 +261,42 @@ __global__ __launch_bounds__(64 * WAVES) void dgrad_s2_kernel(const float* __res
 #undef DAM_S2_CHUNK
 }
 
-template <int NB, int NCH, int MB, int WAVES>
-int launch_dgrad_s2(const float* dc, const float* wpt, const float* ds, const float* wpt2, int B, int Hd, int Wd, float* dx, int H,
-                    int W, const S2Sums& sums, int* parts_host, hipStream_t st) {
-    // Units are 16 * MB pixels of the FLATTENED [B * Hd * Wd] index space (a unit per row segment left the last segment of every row
-    // nearly empty: Wd = 33 -> half the MFMAs on padding), each lane finds its row / column by division.
-    const int64_t px = (int64_t)B * Hd * Wd;
-    if (px >= (1ll << 30)) return DAM_ERR_UNSUPPORTED;
-    const int64_t units = cdiv(px, 16 * MB);
-    const size_t lds = (size_t)(9 + (ds ? 1 : 0)) * NCH * NB * 1024;
-    const int cus = device_cus();
-    // resident workgroups per CU of THIS instantiation (registers and LDS; asked once): a grid beyond it would run a second, partial round
-    static PerDevice<int> occ[2][2];
-    int& oc = occ[ds ? 1 : 0][sums.u ? 1 : 0]();
+// Device pointers of one call, as dam_dgrad_s2_3x3_f32 got them (ds, wpt2 null without a pair term; sums.u null without sums).
+struct DgradS2Operands {
+    const float *dc, *wpt, *ds, *wpt2;
+    float* dx;
+    S2Sums sums;
+};
+
+// Every instantiation of dgrad_s2_kernel, by the plan's note: F_<NB, NCH, MB, PAIR, WAVES, SUMS>(...).
+#define DAM_S2_FLAGS(N_, F_, NB_, NCH_, MB_, WAVES_, ...)                                                                      \
+    ((N_).pair ? ((N_).sums ? F_<NB_, NCH_, MB_, true, WAVES_, true>(__VA_ARGS__) : F_<NB_, NCH_, MB_, true, WAVES_, false>(__VA_ARGS__)) \
+               : ((N_).sums ? F_<NB_, NCH_, MB_, false, WAVES_, true>(__VA_ARGS__) : F_<NB_, NCH_, MB_, false, WAVES_, false>(__VA_ARGS__)))
+#define DAM_S2_INST(N_, F_, ...)                                                                                               \
+    ((N_).NB == 1 && (N_).NCH == 2 && (N_).MB == 2 && (N_).WAVES == 4 ? DAM_S2_FLAGS(N_, F_, 1, 2, 2, 4, __VA_ARGS__)           \
+     : (N_).NB == 2 && (N_).NCH == 4 && (N_).MB == 1 && (N_).WAVES == 8 ? DAM_S2_FLAGS(N_, F_, 2, 4, 1, 8, __VA_ARGS__)         \
+     : DAM_ERR_UNSUPPORTED)
+
+// Resident workgroups per CU of one instantiation (registers and LDS; asked once per device).
+template <int NB, int NCH, int MB, bool PAIR, int WAVES, bool SUMS>
+int dgrad_s2_per_cu(size_t lds) {
+    static PerDevice<int> occ;
+    int& oc = occ();
     if (!oc) {
         int n = 0;
-        hipError_t e;
-        if (ds) e = sums.u ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, dgrad_s2_kernel<NB, NCH, MB, true, WAVES, true>, 64 * WAVES, lds)
-                           : hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, dgrad_s2_kernel<NB, NCH, MB, true, WAVES, false>, 64 * WAVES, lds);
-        else e = sums.u ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, dgrad_s2_kernel<NB, NCH, MB, false, WAVES, true>, 64 * WAVES, lds)
-                        : hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, dgrad_s2_kernel<NB, NCH, MB, false, WAVES, false>, 64 * WAVES, lds);
+        const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, dgrad_s2_kernel<NB, NCH, MB, PAIR, WAVES, SUMS>, 64 * WAVES, lds);
         oc = (e == hipSuccess && n >= 1) ? n : 1;
     }
-    int max_per_cu = oc;
-    if (max_per_cu > 3) max_per_cu = 3;
-    if (WAVES == 8) max_per_cu = 1;
-    // Workgroups per CU by makespan: n resident waves per SIMD share its MFMA pipe, so a SIMD's time is (units per wave) * n unit
-    // times; more waves hide the operand latency better, which decides when the costs are within ~15 %.
-    int per_cu = 1;
-    int64_t best = 0;
-    for (int n = 1; n <= max_per_cu; ++n) {
-        const int64_t cost = cdiv(units, (int64_t)WAVES * cus * n) * n * 100;
-        if (n == 1 || cost * 100 <= best * 115) { best = n == 1 ? cost : (cost < best ? cost : best); per_cu = n; }
-    }
-    int64_t wgs = (int64_t)cus * per_cu;
-    if (wgs > cdiv(units, WAVES)) wgs = cdiv(units, WAVES);
-    if (sums.u && wgs > BN_BWD_RECORDS_MAX) return DAM_ERR_UNSUPPORTED;
-#define DAM_S2_GO(PAIR_, SUMS_)                                                                                                   \
-    do {                                                                                                                          \
-        if (lds > 64 * 1024 && !raise_lds_limit<&dgrad_s2_kernel<NB, NCH, MB, PAIR_, WAVES, SUMS_>>(160 * 1024)) return DAM_ERR_LAUNCH; \
-        hipLaunchKernelGGL((dgrad_s2_kernel<NB, NCH, MB, PAIR_, WAVES, SUMS_>), dim3((unsigned)wgs), dim3(64 * WAVES), lds, st, dc, \
-                           reinterpret_cast<const float4*>(wpt), ds, reinterpret_cast<const float4*>(wpt2), B, Hd, Wd, dx, H, W,      \
-                           (int)px, (int)units, sums);                                                                            \
-    } while (0)
-    if (ds) { if (sums.u) DAM_S2_GO(true, true); else DAM_S2_GO(true, false); }
-    else { if (sums.u) DAM_S2_GO(false, true); else DAM_S2_GO(false, false); }
-#undef DAM_S2_GO
-    if (parts_host) *parts_host = sums.u ? (int)wgs : 0;
+    return oc;
+}
+
+template <int NB, int NCH, int MB, bool PAIR, int WAVES, bool SUMS>
+int launch_dgrad_s2_as(const S2Plan& p, const DgradS2Operands& a, int B, int Hd, int Wd, int H, int W, hipStream_t st) {
+    if (p.lds > 64 * 1024 && !raise_lds_limit<&dgrad_s2_kernel<NB, NCH, MB, PAIR, WAVES, SUMS>>(160 * 1024)) return DAM_ERR_LAUNCH;
+    hipLaunchKernelGGL((dgrad_s2_kernel<NB, NCH, MB, PAIR, WAVES, SUMS>), dim3(p.grid_x), dim3(p.threads), p.lds, st, a.dc,
+                       reinterpret_cast<const float4*>(a.wpt), a.ds, reinterpret_cast<const float4*>(a.wpt2), B, Hd, Wd, a.dx, H, W,
+                       (int)p.px, (int)p.units, a.sums);
     DAM_CHECK_LAUNCH();
-    int n_xcd = 1;
-    const int rounds = s2_resident_rounds(units, wgs, WAVES, &n_xcd);
-    s2_last_launch = S2LaunchNote{S2_ENTRY_DGRAD, S2_FAM_RESIDENT, NB, NCH, MB, WAVES, ds ? 1 : 0, sums.u ? 1 : 0, (int)wgs, (int)units, rounds,
-                                  n_xcd, sums.u ? (int)wgs : 0};
     return DAM_OK;
 }
 
@@ -529,37 +513,40 @@ __global__ __launch_bounds__(256) void dgrad_s2_stream_lds_kernel(const float* _
     }
 }
 
-int launch_dgrad_s2_stream(const float* dc, const float* wpt, const float* ds, const float* wpt2, int B, int Hd, int Wd, int Co, int Ci,
-                           float* dx, int H, int W, hipStream_t st) {
-    const int64_t px = (int64_t)B * Hd * Wd;
-    const int NCH = Co / 16, NB = Ci / 16;
-    const int MB = cdiv(px, 16) * NB >= 8 * 1024 ? 2 : 1;                  // two pixel blocks per wave once the chip is full
-    const int64_t units = cdiv(px, 16 * MB) * NB;
-    if (px >= (1ll << 26) || units >= (1ll << 30)) return DAM_ERR_UNSUPPORTED;
-    if (MB == 1) {
-        const dim3 grid_l((unsigned)(cdiv(cdiv(px, 64), 8) * 8 * NB)), block_l(256);      // whole rounds of eight groups (one per XCD)
-        if (ds)
-            hipLaunchKernelGGL((dgrad_s2_stream_lds_kernel<true>), grid_l, block_l, 0, st, dc, reinterpret_cast<const float4*>(wpt), ds,
-                               reinterpret_cast<const float4*>(wpt2), Hd, Wd, dx, H, W, (int)px, NCH, NB);
-        else
-            hipLaunchKernelGGL((dgrad_s2_stream_lds_kernel<false>), grid_l, block_l, 0, st, dc, reinterpret_cast<const float4*>(wpt),
-                               (const float*)nullptr, (const float4*)nullptr, Hd, Wd, dx, H, W, (int)px, NCH, NB);
-        DAM_CHECK_LAUNCH();
-        // a wave takes exactly one unit; group g of 64 pixels runs on XCD g % 8
-        s2_last_launch = S2LaunchNote{S2_ENTRY_DGRAD, S2_FAM_STREAM_LDS, NB, NCH, 1, 4, ds ? 1 : 0, 0, (int)grid_l.x, (int)units, 1, 8, 0};
-        return DAM_OK;
+// The two streaming kernels, by the plan's family.
+int launch_dgrad_s2_stream(const S2Plan& p, const DgradS2Operands& a, int Hd, int Wd, int H, int W, hipStream_t st) {
+    const dim3 grid(p.grid_x), block(p.threads);
+    const float4 *wpt = reinterpret_cast<const float4*>(a.wpt), *wpt2 = reinterpret_cast<const float4*>(a.wpt2);
+    const int px = (int)p.px, NCH = p.note.NCH, NB = p.note.NB;
+    if (p.note.family == S2_FAM_STREAM_LDS) {
+        if (p.note.pair) hipLaunchKernelGGL((dgrad_s2_stream_lds_kernel<true>), grid, block, 0, st, a.dc, wpt, a.ds, wpt2, Hd, Wd, a.dx, H, W, px, NCH, NB);
+        else hipLaunchKernelGGL((dgrad_s2_stream_lds_kernel<false>), grid, block, 0, st, a.dc, wpt, (const float*)nullptr, (const float4*)nullptr,
+                                Hd, Wd, a.dx, H, W, px, NCH, NB);
+    } else {
+        if (p.note.pair) hipLaunchKernelGGL((dgrad_s2_stream_kernel<true>), grid, block, 0, st, a.dc, wpt, a.ds, wpt2, Hd, Wd, a.dx, H, W, px, NCH, NB,
+                                            (int)p.units);
+        else hipLaunchKernelGGL((dgrad_s2_stream_kernel<false>), grid, block, 0, st, a.dc, wpt, (const float*)nullptr, (const float4*)nullptr,
+                                Hd, Wd, a.dx, H, W, px, NCH, NB, (int)p.units);
     }
-    const dim3 grid((unsigned)cdiv(units, 4)), block(256);
-    if (ds)
-        hipLaunchKernelGGL((dgrad_s2_stream_kernel<true>), grid, block, 0, st, dc, reinterpret_cast<const float4*>(wpt), ds,
-                           reinterpret_cast<const float4*>(wpt2), Hd, Wd, dx, H, W, (int)px, NCH, NB, (int)units);
-    else
-        hipLaunchKernelGGL((dgrad_s2_stream_kernel<false>), grid, block, 0, st, dc, reinterpret_cast<const float4*>(wpt),
-                           (const float*)nullptr, (const float4*)nullptr, Hd, Wd, dx, H, W, (int)px, NCH, NB, (int)units);
     DAM_CHECK_LAUNCH();
-    s2_last_launch = S2LaunchNote{S2_ENTRY_DGRAD, S2_FAM_STREAM, NB, NCH, 2, 4, ds ? 1 : 0, 0, (int)grid.x, (int)units, 1, 1, 0};
     return DAM_OK;
 }
+
+int launch_dgrad_s2(const S2Plan& p, const DgradS2Operands& a, int B, int Hd, int Wd, int H, int W, hipStream_t st) {
+    if (p.note.family != S2_FAM_RESIDENT) return launch_dgrad_s2_stream(p, a, Hd, Wd, H, W, st);
+    return DAM_S2_INST(p.note, launch_dgrad_s2_as, p, a, B, Hd, Wd, H, W, st);
+}
+
+// The two facts the plan takes from the device: what the caller gave (> 0), else the current device's -- the occupancy of the
+// persistent instantiation the channel counts and the operand flags name.
+S2Device dgrad_s2_device(int Co, int Ci, bool pair, bool sums, int cus, int resident_per_cu) {
+    S2LaunchNote inst{};
+    if (resident_per_cu <= 0)
+        resident_per_cu = s2_dgrad_resident(Co, Ci, pair, sums, inst) ? DAM_S2_INST(inst, dgrad_s2_per_cu, s2_resident_lds(inst)) : 1;
+    return S2Device{cus > 0 ? cus : device_cus(), resident_per_cu};
+}
+#undef DAM_S2_INST
+#undef DAM_S2_FLAGS
 
 }  // namespace
 }  // namespace dam
@@ -570,20 +557,30 @@ extern "C" int dam_dgrad_s2_3x3_f32(const float* dy, const float* w_packed_t, co
                                     float* bn_partial, int* bn_parts_host, void* stream) {
     using namespace dam;
     s2_last_launch = S2LaunchNote{};
-    if (!dy || !w_packed_t || !dx || B <= 0 || Hd <= 0 || Wd <= 0 || H <= 0 || W <= 0) return DAM_ERR_BAD_ARG;
-    if ((dy_pair != nullptr) != (w_pair_packed_t != nullptr)) return DAM_ERR_BAD_ARG;
-    if (Hd != (H + 1) / 2 || Wd != (W + 1) / 2) return DAM_ERR_BAD_ARG;             // 3x3 / stride 2 / pad 1 geometry
-    if ((int64_t)B * Hd * Wd * Co * 4 >= (1ll << 31)) return DAM_ERR_UNSUPPORTED;   // byte offsets of the range-checked loads
-    hipStream_t st = (hipStream_t)stream;
+    if (!dy || !w_packed_t || !dx || (dy_pair != nullptr) != (w_pair_packed_t != nullptr)) return DAM_ERR_BAD_ARG;
     if (bn_parts_host) *bn_parts_host = 0;
     // the upstream BatchNorm's backward sums (mask as sign bytes only): taken by the persistent kernels, "not produced" elsewhere
     S2Sums sums{nullptr, nullptr, nullptr, nullptr, nullptr};
     if (bn_bwd && bn_bwd->x && bn_bwd->mask_bits && bn_bwd->mean && bn_bwd->invstd && bn_partial && bn_parts_host)
         sums = S2Sums{bn_bwd->x, bn_bwd->mask_bits, bn_bwd->mean, bn_bwd->invstd, bn_partial};
-    if (Co == 32 && Ci == 16) return launch_dgrad_s2<1, 2, 2, 4>(dy, w_packed_t, dy_pair, w_pair_packed_t, B, Hd, Wd, dx, H, W, sums, bn_parts_host, st);
-    if (Co == 64 && Ci == 32) return launch_dgrad_s2<2, 4, 1, 8>(dy, w_packed_t, dy_pair, w_pair_packed_t, B, Hd, Wd, dx, H, W, sums, bn_parts_host, st);
-    // wider layers: the weight image streams from L2 (even chunk count: the two register sets alternate)
-    if (Co % 32 == 0 && Ci % 16 == 0 && (int64_t)9 * Co * Ci * 4 < (1ll << 31))
-        return launch_dgrad_s2_stream(dy, w_packed_t, dy_pair, w_pair_packed_t, B, Hd, Wd, Co, Ci, dx, H, W, st);
-    return DAM_ERR_UNSUPPORTED;
+    const bool pair = dy_pair != nullptr, want_sums = sums.u != nullptr;
+    S2Plan plan;
+    int rc = plan_dgrad_s2(B, Hd, Wd, Co, Ci, H, W, pair, want_sums, dgrad_s2_device(Co, Ci, pair, want_sums, 0, 0), plan);
+    if (rc != DAM_OK) return rc;
+    rc = launch_dgrad_s2(plan, DgradS2Operands{dy, w_packed_t, dy_pair, w_pair_packed_t, dx, sums}, B, Hd, Wd, H, W, (hipStream_t)stream);
+    if (rc != DAM_OK) return rc;
+    if (bn_parts_host) *bn_parts_host = plan.note.records;
+    s2_last_launch = plan.note;
+    return DAM_OK;
+}
+
+extern "C" int dam_dgrad_s2_3x3_plan(int B, int Hd, int Wd, int Co, int Ci, int H, int W, int pair, int sums, int cus, int resident_per_cu,
+                                     int* out16_host) {
+    using namespace dam;
+    if (!out16_host) return DAM_ERR_BAD_ARG;
+    S2Plan plan;
+    const int rc = plan_dgrad_s2(B, Hd, Wd, Co, Ci, H, W, pair != 0, sums != 0,
+                                 dgrad_s2_device(Co, Ci, pair != 0, sums != 0, cus, resident_per_cu), plan);
+    s2_note_to_ints(plan.note, out16_host);      // (all zero on any refusal)
+    return rc;
 }

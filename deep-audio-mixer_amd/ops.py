@@ -558,7 +558,45 @@ def s2_last_launch():
     'none' after a call that was refused.  Host-side only."""
     v = (ctypes.c_int * 16)()
     _lib.check(_lib.lib().dam_s2_last_launch(v), 'dam_s2_last_launch')
+    return _s2_launch(v)
+
+
+def _s2_launch(v):
     return S2Launch(S2_ENTRIES[v[0]], S2_FAMILIES[v[1]], *v[2:13])
+
+
+def _s2_plan(name, *scalars):
+    """A plan entry of the down-sampling block's kernels -> S2Launch.  A refusal (DAM_ERR_UNSUPPORTED) is an answer -- the 'none'
+    record: the caller falls back; bad arguments raise."""
+    v = (ctypes.c_int * 16)()
+    st = getattr(_lib.lib(), name)(*[int(s) for s in scalars], v)
+    if st != -2:
+        _lib.check(st, name)
+    return _s2_launch(v)
+
+
+def conv_s2_pair_fwd_plan(x_shape, n_out, stats=True, cus=0, resident=0):
+    """The S2Launch s2_last_launch() would report after conv_s2_pair_fwd on an NHWC x of this shape ('none': the call returns None):
+    host arithmetic in the library (dam_conv_s2_pair_fwd_plan), no tensors.  cus, resident: the device's CU count and the
+    workgroups of the persistent kernel a CU holds; both given, no GPU is asked; 0: the current device's, as the call takes them."""
+    B, H, W, C = x_shape
+    return _s2_plan('dam_conv_s2_pair_fwd_plan', B, H, W, C, (n_out + 15) // 16 * 16, bool(stats), cus, resident)
+
+
+def conv2d_dgrad_s2_plan(dy_shape, n_in, H, W, pair=False, sums=False, cus=0, resident=0):
+    """The S2Launch the one-launch 3x3 / stride-2 / pad-1 data gradient (dam_dgrad_s2_3x3_f32, the first thing a strided
+    conv2d_dgrad tries) would leave for a gradient of dy_shape, with pair_1x1 (pair) and the strided bn_bwd form (sums) given or
+    not; 'none': refused, conv2d_dgrad runs the parity classes (+ conv1x1_pair_plan's launch).  cus, resident: as
+    conv_s2_pair_fwd_plan."""
+    B, Hd, Wd, Co = dy_shape
+    return _s2_plan('dam_dgrad_s2_3x3_plan', B, Hd, Wd, Co, (n_in + 15) // 16 * 16, H, W, bool(pair), bool(sums), cus, resident)
+
+
+def conv1x1_pair_plan(dy_shape, n_in, H, W, stride=2, off_h=0, off_w=0):
+    """The S2Launch of the 1x1 pair launch (dam_conv1x1_pair_f32) that carries parity class (0, 0) of a strided conv2d_dgrad with
+    pair_1x1: two single-tap operators on gradients of dy_shape into the pixels (off + stride * i) of a [B, H, W, n_in16] dx."""
+    B, Ho, Wo, Co = dy_shape
+    return _s2_plan('dam_conv1x1_pair_plan', B, Ho, Wo, Co, (n_in + 15) // 16 * 16, H, W, stride, off_h, off_w)
 
 
 def nchw_to_nhwc16(x):

@@ -56,7 +56,7 @@ struct dam_bn_bwd_in;
 /* Library / build identification ("gfx950").  DAM_ABI_VERSION is bumped whenever a signature below changes; a binding
  * compares dam_abi_version() of the library it loaded with the version it was written against and refuses a stale one
  * (deep-audio-mixer_amd/_lib.py: EXPECTED_ABI). */
-#define DAM_ABI_VERSION 36
+#define DAM_ABI_VERSION 37
 const char* dam_arch(void);
 int dam_abi_version(void);
 
@@ -295,8 +295,10 @@ int dam_conv_s2_pair_fwd_f32(const float* x, const float* w_packed, const float*
 
 /* Which kernel the last call of the CALLING THREAD to one of the three entry points above (dam_conv1x1_pair_f32,
  * dam_dgrad_s2_3x3_f32, dam_conv_s2_pair_fwd_f32) launched (ABI 31): each picks between kernels and template instantiations by
- * channel counts, pixel count, the device's CU count and an occupancy answer without telling, so a test that means to exercise one
- * instantiation, or the unit loop of a persistent kernel, asks here (as dam_wgrad_last_launch for the weight gradient).  A host
+ * channel counts, pixel count, the device's CU count and an occupancy answer -- a plan made by host arithmetic before the launch,
+ * which the three plan entries below give out without launching (ABI 37).  The record is that plan's note, copied: a test that means
+ * to exercise one instantiation, or the unit loop of a persistent kernel, asks here (as dam_wgrad_last_launch for the weight
+ * gradient) and may compare with the plan of the same call.  A host
  * variable: reset to "none" at the entry of every call of the three, written after the launch was made -- no device work, no kernel
  * argument, nothing synchronised; the choice of kernel is unchanged.  out16_host (host memory, 16 ints) receives
  *   [0] entry: 0 none (no call yet, or the call was refused or failed), 1 dam_conv_s2_pair_fwd_f32, 2 dam_dgrad_s2_3x3_f32,
@@ -321,6 +323,21 @@ int dam_conv_s2_pair_fwd_f32(const float* x, const float* w_packed, const float*
  *   [12] records                   the count stored in *parts_host / *bn_parts_host
  *   [13..15] 0 */
 int dam_s2_last_launch(int* out16_host);
+
+/* The same answer BEFORE a call (ABI 37): one plan entry per entry point above, with its scalar arguments and its operand flags
+ * (stats: partial / partial_sc given; pair: dy_pair given; sums: bn_bwd / bn_partial / bn_parts_host given).  out16_host receives
+ * the 16 ints dam_s2_last_launch would hold after that call; the status is the one the call would return for these arguments
+ * (DAM_OK, DAM_ERR_BAD_ARG, DAM_ERR_UNSUPPORTED: the caller's fall-back), and after anything but DAM_OK out16_host is all zero, the
+ * "none" record.  cus, resident_per_cu: the only two facts the decision takes from the device -- its CU count, and how many
+ * workgroups of the persistent kernel the channel counts name one CU holds (the runtime's occupancy answer).  Both > 0: host
+ * arithmetic only, on a machine without a GPU too.  0 for either: taken from the calling thread's current device exactly as the
+ * launching entry takes it, so the record of a call equals the plan of the same call.  dam_conv1x1_pair_f32 asks the device
+ * nothing. */
+int dam_conv_s2_pair_fwd_plan(int B, int H, int W, int Ci, int Co, int stats, int cus, int resident_per_cu, int* out16_host);
+int dam_dgrad_s2_3x3_plan(int B, int Hd, int Wd, int Co, int Ci, int H, int W, int pair, int sums, int cus, int resident_per_cu,
+                          int* out16_host);
+int dam_conv1x1_pair_plan(int B, int H, int W, int C, int n_out, int OHt, int OWt, int out_stride, int out_off_h, int out_off_w,
+                          int* out16_host);
 
 /* Sibling launches in one.  The parity classes of a strided data gradient are up to four small launches over the same
  * tensors, weights and tile that differ only in their tap grid.  With a batch (caller-owned HOST memory of

@@ -2,14 +2,16 @@
 (dam_conv_s2_pair_fwd_f32, dam_dgrad_s2_3x3_f32, dam_conv1x1_pair_f32) against F.conv2d / torch.nn.grad.conv2d_input on the CPU in
 float64, each case asserting through ops.s2_last_launch() the launch it names.
 
-Each entry point picks its kernel without telling -- by channel counts (persistent kernels with the packed weights resident
-in LDS for 16 <-> 32 and 32 <-> 64 channels, streaming kernels for the wide layers), by pixel count (two pixel blocks per wave of the
-streaming data gradient from cdiv(px, 16) * NB >= 8192), by the CU count, an occupancy answer and a makespan rule (the grid of a
-persistent kernel, and with it how often a wave goes round its unit loop and whether the units are dealt to eight XCDs) -- and
-ops.conv2d_dgrad falls from dam_dgrad_s2_3x3_f32 to the parity classes + dam_conv1x1_pair_f32 when that refuses.  So every row of
-the table NAMES the launch it means, the helper asserts the whole record (_record: instantiation, grid, units, rounds, n_xcd,
-records -- host arithmetic from the shape, checked in test_table_conditions) before it looks at a number, and test_coverage
-asserts that the union of the records covers REQUIRED.
+Each entry point picks its kernel by a plan (csrc/dam_s2_plan.h) -- by channel counts (persistent kernels with the packed weights
+resident in LDS for 16 <-> 32 and 32 <-> 64 channels, streaming kernels for the wide layers), by pixel count (two pixel blocks per
+wave of the streaming data gradient from cdiv(px, 16) * NB >= 8192), by the CU count, an occupancy answer and a makespan rule (the
+grid of a persistent kernel, and with it how often a wave goes round its unit loop and whether the units are dealt to eight XCDs) --
+and ops.conv2d_dgrad falls from dam_dgrad_s2_3x3_f32 to the parity classes + dam_conv1x1_pair_f32 when that refuses.  The plan can be
+asked without launching (ops.conv_s2_pair_fwd_plan, ops.conv2d_dgrad_s2_plan, ops.conv1x1_pair_plan; tests/test_s2_plan_cpu.py
+holds the dispatch table on a machine without a GPU).  Every row of the table NAMES the launch it means, the helper asserts the
+whole record (_record: instantiation, grid, units, rounds, n_xcd, records -- host arithmetic from the shape, an independent second
+derivation, checked in test_table_conditions) and that the record equals the plan of the same call on this device (_plan) before
+it looks at a number, and test_coverage asserts that the union of the records covers REQUIRED.
 
 Reference: F.conv2d / torch.nn.grad.conv2d_input (+ the shortcut term) on the CPU in float64, at most 1.25 GFLOP per case
 (the block of test_retreat_block_forward: 1.8 for its two 3x3 convolutions).  Every
@@ -68,13 +70,10 @@ Findings on dispatch, settled with the launch record (tests/test_conv_gpu.py):
     retreating; the block test uses (2, 657, 400), 2057 groups.  Loud, not silent: left as it is.
   * No case exposed a wrong number.
 
-Unreachable (named instead of dropped):
-  * wgs > BN_BWD_RECORDS_MAX (1024) in launch_dgrad_s2: at most 3 workgroups per CU, 768 on 256 CUs.
-  * cus * per_cu > BN_RECORDS_MAX / cus > BN_RECORDS_MAX in launch_conv_s2_pair: the same 768.
-  * the 2 GiB byte-offset and 2^26 / 2^30 pixel and unit refusals of the three entry points: the float64 reference alone would
-    take minutes.
-  * n_xcd 1 together with rounds >= 2: a grid that is no multiple of 8 is cdiv(units, WAVES) workgroups (fewer than the chip
-    offers), i.e. one unit per wave; on a device whose CU count is no multiple of 8 it would be reachable.
+Unreachable here (named instead of dropped):
+  * the refusals that need a shape no float64 reference can follow or a device this one is not -- the record limits of the two
+    persistent kernels, the 2 GiB byte-offset and 2^26 / 2^30 pixel refusals, n_xcd 1 together with rounds >= 2 (a CU count that
+    is no multiple of 8) -- are planned in tests/test_s2_plan_cpu.py, where CU count and occupancy are arguments.
   * DAM_ERR_LAUNCH of raise_lds_limit: the runtime grants 160 KB on this device.
 
 Mutations, each compiled into a scratch copy of the library and run once against this file (numbers only: no store address,
@@ -387,11 +386,29 @@ def _note(fam, what, err, c, form):
         WORST[(fam, what)] = (err, c.id, form)
 
 
+def _plan(ops, c, form, **device):
+    """The plan of the launch whose record (c, form) leaves, from the plan entry of the entry point that leaves it.  device:
+    cus=, resident= (tests/test_s2_plan_cpu.py: no GPU asked); neither: the current device's, as the launching entry takes them."""
+    if c.kind == 'fwd':
+        return ops.conv_s2_pair_fwd_plan((c.B, c.H, c.W, c.Ci), c.Co, stats=form == 'stats', **device)
+    Hd, Wd, _ = _geo(c)
+    dy_shape, pair = (c.B, Hd, Wd, c.Co), 'pair' in form
+    if not c.patch:                                     # (patch: dam_dgrad_s2_3x3_f32 is not asked)
+        one = ops.conv2d_dgrad_s2_plan(dy_shape, c.Ci, c.H, c.W, pair=pair, sums='sums' in form, **device)
+        if c.family != 'pair_1x1':
+            return one
+        assert one.entry == 'none', '%s %s: dam_dgrad_s2_3x3_f32 would take a row named pair_1x1: %s' % (c.id, form, one)
+    # the parity classes: class (0, 0) rides in the 1x1 pair launch where there is a shortcut term, else none of the three entries runs
+    return ops.conv1x1_pair_plan(dy_shape, c.Ci, c.H, c.W) if pair else ops.S2Launch('none', 'none', *([0] * 11))
+
+
 def _assert_record(ops, c, form):
     rec = ops.s2_last_launch()._asdict()
     want = _record(c, form)
     SEEN[(c.id, form)] = rec
     assert rec == want, '%s %s: launched %s, the row names %s' % (c.id, form, rec, want)
+    plan = _plan(ops, c, form)._asdict()
+    assert rec == plan, '%s %s: launched %s, the plan of the same call is %s' % (c.id, form, rec, plan)
     return rec
 
 
@@ -641,6 +658,7 @@ def test_retreat_forward_stream_statistics_past_the_record_limit(ops):
     bufs = [_guarded((c.B, Hd, Wd, c.Co)), _guarded((c.B, Hd, Wd, c.Co)), _guarded((n_rec,)), _guarded((n_rec,))]
     got = ops.conv_s2_pair_fwd(xd, wp, wps, c.Co, out=(bufs[0][1], bufs[1][1]), records=(bufs[2][1], bufs[3][1]))
     assert got is None and ops.s2_last_launch().entry == 'none', (got, ops.s2_last_launch())
+    assert ops.s2_last_launch() == _plan(ops, c, 'stats')             # the refusal is the plan's
     torch.cuda.synchronize()
     for buf, _ in bufs:
         assert bool((buf == FILL).all()), 'a refused call wrote'
@@ -680,6 +698,7 @@ def test_retreat_block_forward_takes_the_separate_launches(ops):
         out = blk(x.cuda())
         want = ref(x.permute(0, 3, 1, 2).double())
     assert ops.s2_last_launch().entry == 'none', ops.s2_last_launch()
+    assert ops.s2_last_launch() == ops.conv_s2_pair_fwd_plan((2, 657, 400, 32), 16)
     err = float((out.permute(0, 3, 1, 2).double().cpu() - want).norm() / want.norm())
     print('block forward: %.2e of the norm' % err)
     assert err <= TOL_BLOCK, err
