@@ -12,7 +12,7 @@ LIB_PATH = os.environ.get('DAM_LIB_PATH') or os.path.join(_HERE, 'libdam_hip.so'
 # include/dam_hip.h: bumped whenever a C signature changes (together with dam_abi_version() in csrc/dam_api.hip and
 # DAM_ABI_VERSION in the header).  libdam_hip.so is git-ignored and travels prebuilt: a stale one would read device pointers
 # as streams, so lib() refuses it instead of launching.
-EXPECTED_ABI = 37
+EXPECTED_ABI = 38
 
 _STATUS = {0: 'DAM_OK', -1: 'DAM_ERR_BAD_ARG', -2: 'DAM_ERR_UNSUPPORTED', -3: 'DAM_ERR_LAUNCH',
            -4: 'DAM_ERR_WORKSPACE'}
@@ -121,6 +121,12 @@ SIGNATURES = {
     'dam_limiter_max_hold': (c_i, []),
     'dam_limiter_workspace_bytes': (c_i64, [c_i, c_i64]),
     'dam_limiter_apply': (c_i, [c_p, c_i, c_i, c_i64, c_i, c_i64, c_i64, c_i64, c_p, c_d, c_i, c_i, c_p, c_i, c_p, c_p, c_p, c_p]),
+    'dam_compressor_chunk_samples': (c_i64, []),
+    'dam_compressor_tile_samples': (c_i64, []),
+    'dam_compressor_max_time_samples': (c_i64, []),
+    'dam_compressor_workspace_bytes': (c_i64, [c_i, c_i64]),
+    'dam_compressor_apply': (c_i, [c_p, c_i, c_i, c_i64, c_i, c_i64, c_i64, c_i64, c_p, c_d, c_d, c_d, c_d, c_d, c_d, c_d, c_p, c_i,
+                                   c_p, c_p, c_p, c_p, c_p]),
     'dam_loudness_window_power': (c_i, [c_p, c_i, c_i, c_i, c_i, c_p, c_p, c_p]),
     'dam_loudness_curve_stats': (c_i, [c_p, c_i, c_i, c_p, c_p]),
     'dam_loudness_profile_error': (c_i, [c_p, c_p, c_i, c_i, c_i, c_p, c_p, c_p]),

@@ -12,7 +12,8 @@ device from the same resident PCM by the mixer's own master tail (inference_util
 variant's gains, batched meter, gain to -20 LUFS, PCM encoder with that gain -- and written as
 ``{song_name}_{identifier}.wav`` (evaluation.py:58-66); with ``ceiling_dbtp`` that gain is first clamped so that the file's
 true peak stays under the ceiling (dam_true_peak_batch of the resident sum) instead of being hard-clipped by the encoder.
-``limiter`` turns down only the peaks over the ceiling instead (dam_limiter_apply), so the file keeps its loudness.
+``limiter`` turns down only the peaks over the ceiling instead (dam_limiter_apply), so the file keeps its loudness;
+``compressor`` puts the feed-forward compressor (dam_compressor_apply) in front of either.
 The reference's spreadsheet (openpyxl) stays out: ``process_songlist`` returns the rows and the means instead of writing
 ./stats.xlsx.
 
@@ -248,21 +249,24 @@ class LoudnessEvaluator:
         return pcm
 
     def write_sum_to_target(self, pcm, gains, path, target_lufs: float = -20.0, subtype='PCM_16', ceiling_dbtp=None,
-                            limiter=None):
+                            limiter=None, compressor=None):
         """evaluation.py:58-66 with its ``sf.write``, for stems resident on the device: pcm CUDA [stems, channels, n],
         gains None, CUDA float64 [stems] (a constant per stem) or [stems, n_gains] (a gain ramp).  The float64 stem sum is
         measured, the gain to ``target_lufs`` stays on the device and is applied inside the encoder; the host receives the
         file's sample bytes.  ceiling_dbtp: the gain is clamped on the device to ``ceiling / true peak of the sum`` first, so
         a sum whose -20 LUFS rendering would exceed the ceiling is written quieter instead of clipped.  limiter (None, True
         or {'lookahead_ms', 'hold_ms'}, as inference_utils.MasterChain takes it): only the peaks over the ceiling (-1 dBTP if
-        none is given) are turned down, the rest of the file stays at ``target_lufs``.  Returns the clipped-sample count."""
+        none is given) are turned down, the rest of the file stays at ``target_lufs``.  compressor (None, True or a dict with keys of
+        MasterChain.COMPRESSOR_DEFAULTS): the sum at ``target_lufs`` is compressed and brought to ``target_lufs`` again first.
+        Returns the clipped-sample count."""
         from .data.dataset_utils import write_wav_bytes
         n_stems, channels, n = pcm.shape
         if gains is None:
             gains = torch.ones((n_stems, 1), dtype=torch.float64, device=pcm.device)
         # built per call, not cached: excerpt lengths vary
         chain = inference_utils.MasterChain(channels, n, pcm.device, 'loudness', sr=self.sr, target_lufs=target_lufs,
-                                            ceiling_dbtp=ceiling_dbtp, encode=subtype, limiter=limiter)
+                                            ceiling_dbtp=ceiling_dbtp, encode=subtype, limiter=limiter,
+                                            compressor=compressor)
         chain.render(pcm, gains.view(n_stems, -1))
         payload = staging.pipe_for(pcm.device).download(chain.enc)
         clipped = int(chain.clip.sum().item())
@@ -272,7 +276,7 @@ class LoudnessEvaluator:
     def process_song_tracks(self, loaded_tracks: dict, reference_tracks: dict, song_name: str, n_random_samples: int = 5,
                             chunk_length: int = 2, write_wavs_to_disk=False, results_dir='./experiment',
                             ceiling_dbtp=None, dynamics=False, limiter=None, spectral=False, gain_fit=False, band_fit=False,
-                            band_render=False, feature_distance=False) -> dict:
+                            band_render=False, feature_distance=False, compressor=None) -> dict:
         """evaluation.py:77-116 on stems already in memory ({name: ndarray [channels, n]} each): the loudness profile of
         ``reference_tracks`` against the profiles of ``loaded_tracks`` summed as they are ('sum_error'), normalised to the
         training set's mean loudness ('loudnorm_error'), mixed by the model ('mix_error') and scaled by random gains
@@ -280,7 +284,8 @@ class LoudnessEvaluator:
         stats dict plus 'smooth_gains' {name: list}, the gains the mix variant used.  write_wavs_to_disk: every variant's
         stem sum at -20 LUFS goes to ``results_dir/{song_name}_{identifier}.wav`` (reference, sum, loudnorm, mix,
         random_0 ...; 16-bit), each held under ``ceiling_dbtp`` dBTP if that is given, by the look-ahead ``limiter`` if one is
-        asked for (write_sum_to_target); the stats and the order of the random draws depend on none of the three.
+        asked for, behind the ``compressor`` if one is asked for (write_sum_to_target); the stats and the order of the random
+        draws depend on none of the four.
         dynamics: the stats gain 'sum_st_error', 'loudnorm_st_error', 'mix_st_error' and
         'random_st_error' -- every variant's error taken per short-term window instead of per song, from the gains the
         variant already passes to the meter -- and 'lra' {name: LU}, the loudness range of each reference stem; the other
@@ -363,7 +368,7 @@ class LoudnessEvaluator:
             if write_wavs_to_disk:
                 os.makedirs(results_dir, exist_ok=True)
                 self.write_sum_to_target(pcm, gains, os.path.join(results_dir, '{}_{}.wav'.format(song_name, identifier)),
-                                         ceiling_dbtp=ceiling_dbtp, limiter=limiter)
+                                         ceiling_dbtp=ceiling_dbtp, limiter=limiter, compressor=compressor)
 
         reference_pcm = self._upload(reference_tracks)
         reference = OrderedDict(zip(self.keys, self.evaluate_loudness_batch(reference_pcm)))
@@ -553,7 +558,8 @@ class LoudnessEvaluator:
 
     def process_song(self, base_dir: str, song_name: str, n_random_samples: int = 5, chunk_length: int = 2,
                      write_wavs_to_disk=False, results_dir='./experiment', ceiling_dbtp=None, dynamics=False, limiter=None,
-                     spectral=False, gain_fit=False, band_fit=False, band_render=False, feature_distance=False) -> dict:
+                     spectral=False, gain_fit=False, band_fit=False, band_render=False, feature_distance=False,
+                     compressor=None) -> dict:
         """evaluation.py:77-116: the reference mix from ``base_dir/manual_gain_mixes``, the stems from ``base_dir/test``."""
         from .data.dataset_utils import load_tracks_musdb18
         self._band_render_args(band_render, band_fit)          # (before a file is read)
@@ -567,11 +573,13 @@ class LoudnessEvaluator:
                                         **({'gain_fit': gain_fit} if gain_fit else {}),
                                         **({'band_fit': band_fit} if band_fit else {}),
                                         **({'band_render': band_render} if band_render else {}),
-                                        **({'feature_distance': feature_distance} if feature_distance else {}))
+                                        **({'feature_distance': feature_distance} if feature_distance else {}),
+                                        **({'compressor': compressor} if compressor else {}))
 
     def process_songlist(self, base_dir, songlist, n_random_samples: int = 5, chunk_length: int = 2,
                          write_wavs_to_disk=False, results_dir='./experiment', ceiling_dbtp=None, dynamics=False, limiter=None,
-                         spectral=False, gain_fit=False, band_fit=False, band_render=False, feature_distance=False):
+                         spectral=False, gain_fit=False, band_fit=False, band_render=False, feature_distance=False,
+                         compressor=None):
         """evaluation.py:118-144 without the spreadsheet: (rows, means) -- one stats dict per song and the mean of every
         error over the songs (the sheet's last row); with ``dynamics`` the four '*_st_error' keys too, with ``spectral``
         the four '*_spec_error' keys, with ``gain_fit`` the four '*_gain_error' keys (a song whose figure is NaN -- nothing
@@ -606,6 +614,8 @@ class LoudnessEvaluator:
                 extra['band_render'] = band_render
             if feature_distance:
                 extra['feature_distance'] = feature_distance
+            if compressor:
+                extra['compressor'] = compressor
             rows.append(self.process_song(base_dir, song_name, n_random_samples, chunk_length, write_wavs_to_disk,
                                           results_dir, ceiling_dbtp, dynamics, **extra))
         means = {key: mean(row[key] for row in rows) for key in keys}

@@ -68,7 +68,8 @@ def predict_chunk_gains(model, pcm, n_stems, n_chunks, chunk_samples, window_siz
 class MasterChain:
     """The master tail, the ONE implementation of it (SongMixer kind 'master' captures it into the song's graph,
     evaluation.LoudnessEvaluator.write_sum_to_target runs it eagerly; a new output stage goes here): stem sum -> BS.1770
-    measurement -> target gain -> look-ahead limiter -> true-peak clamp -> gain apply or PCM encode.  It owns every buffer
+    measurement -> target gain -> (compressor -> measurement -> target gain) -> look-ahead limiter -> true-peak clamp -> gain
+    apply or PCM encode.  It owns every buffer
     those steps need, allocated once and only where the configuration uses it, so a captured ``render`` holds stable pointers.
 
     normalize: True / False -- the sum, peak-normalised per channel or not (the callers' librosa.util.normalize);
@@ -80,9 +81,15 @@ class MasterChain:
     none, True: the defaults, or {'lookahead_ms': 5.0, 'hold_ms': 20.0}): the sum at the target gain goes through the
     look-ahead true-peak limiter (dam_limiter_apply, ceiling -1.0 dBTP unless ``ceiling_dbtp`` says otherwise) into a float64
     limited master; the true-peak clamp then measures THAT and is the residual trim, a few 1e-5 dB, that makes the ceiling
-    exact."""
+    exact.  compressor (with 'loudness'; None / False: none, True: COMPRESSOR_DEFAULTS, or a dict with some of its keys): the
+    sum at the target gain goes through the feed-forward compressor (dam_compressor_apply, the target gain as its
+    ``pre_gain``: the threshold is in dBFS of the song AT ``target_lufs`` and means the same for a quiet and a loud song) into
+    a float64 buffer of its own, which is measured and brought to ``target_lufs`` again -- the make-up gain is that second
+    measurement, not a parameter.  The limiter, the clamp and the encoder then see the compressed signal where they saw the
+    sum."""
 
     LIMITER_DEFAULTS = {'lookahead_ms': 5.0, 'hold_ms': 20.0}
+    COMPRESSOR_DEFAULTS = {'threshold_db': -12.0, 'ratio': 2.0, 'knee_db': 6.0, 'attack_ms': 10.0, 'release_ms': 100.0}
 
     @staticmethod
     def rules(normalize, ceiling_dbtp, encode):
@@ -115,10 +122,30 @@ class MasterChain:
             raise ValueError('limiter times must be positive, got %r' % (limiter,))
         return times, -1.0 if ceiling is None else ceiling
 
+    @staticmethod
+    def compressor_rules(compressor, normalize):
+        """What ``compressor`` may be, given what ``rules`` returned -> None or (threshold_db, ratio, knee_db, attack_ms,
+        release_ms); ValueError otherwise."""
+        if compressor is None or compressor is False:
+            return None
+        if compressor is True:
+            compressor = {}
+        if not isinstance(compressor, dict) or set(compressor) - set(MasterChain.COMPRESSOR_DEFAULTS):
+            raise ValueError('compressor must be None, a bool or a dict with keys of %s, got %r'
+                             % (sorted(MasterChain.COMPRESSOR_DEFAULTS), compressor))
+        if normalize != 'loudness':
+            raise ValueError("compressor needs normalize 'loudness'")
+        shape = tuple(float(compressor.get(k, v)) for k, v in MasterChain.COMPRESSOR_DEFAULTS.items())
+        _, ratio, knee, attack, release = shape
+        if not (ratio >= 1.0 and knee >= 0.0 and attack > 0.0 and release > 0.0 and all(v == v for v in shape)):
+            raise ValueError('compressor needs ratio >= 1, knee_db >= 0 and positive times, got %r' % (compressor,))
+        return shape
+
     def __init__(self, channels, n_samples, device, normalize=True, out_dtype=torch.float64, sr=44100, target_lufs=-20.0,
-                 ceiling_dbtp=None, encode=None, dither_seed=None, limiter=None):
+                 ceiling_dbtp=None, encode=None, dither_seed=None, limiter=None, compressor=None):
         self.normalize, self.ceiling = self.rules(normalize, ceiling_dbtp, encode)
         self.limiter, self.ceiling = self.limiter_rules(limiter, self.normalize, self.ceiling)
+        self.compressor = self.compressor_rules(compressor, self.normalize)
         self.encode, self.dither_seed = encode, dither_seed
         scaled = self.normalize in ('loudness', 'true_peak')             # the float64 sum times one measured gain
         f64 = dict(dtype=torch.float64, device=device)
@@ -155,6 +182,21 @@ class MasterChain:
             self.n_limited = torch.empty(1, dtype=torch.int64, device=device)
             self.limited_lufs = torch.empty(1, **f64)
             self.limiter_ws = torch.empty(ops._lib.lib().dam_limiter_workspace_bytes(1, n_samples) // 8, **f64)
+        if self.compressor is not None:
+            # the curve and the constants the kernel takes (ValueError beyond its caps), the gain to the target the compressor
+            # works at, the compressed sum, its statistics, its loudness and the kernel's workspace
+            threshold, ratio, knee, attack, release = self.compressor
+            self.comp_args = (threshold, ratio, knee) + ops.compressor_constants(threshold, knee, attack, release, sr)
+            longest = ops.compressor_geometry()[2]
+            if max(attack, release) * 1e-3 * sr > longest:
+                raise ValueError('compressor: %g / %g ms of attack / release at %d Hz exceed the cap of %d samples'
+                                 % (attack, release, sr, longest))
+            self.comp_gain = torch.empty(1, **f64)
+            self.compressed = torch.empty((channels, n_samples), **f64)
+            self.comp_max = torch.empty(1, **f64)
+            self.comp_over = torch.empty(1, dtype=torch.int64, device=device)
+            self.compressed_lufs = torch.empty(1, **f64)
+            self.comp_ws = torch.empty(ops._lib.lib().dam_compressor_workspace_bytes(1, n_samples) // 8, **f64)
         self.sum = self.mix if scaled else self.out
         self.ws = torch.empty(ops._lib.lib().dam_mixdown_workspace_elems(channels), dtype=self.sum.dtype, device=device)
 
@@ -163,13 +205,22 @@ class MasterChain:
         synchronisation and no branch on a tensor's value: capturable."""
         scaled = self.master_gain is not None
         ops.mixdown_peak_normalize(pcm, gains, normalize=not scaled and self.normalize, out=self.sum, workspace=self.ws)
+        source = self.sum                          # what master_gain scales
         if self.normalize == 'loudness':
             self.meter.integrated_loudness_batch(self.mix.t().unsqueeze(0), out=self.lufs)
-            loudness.target_gains_device(self.lufs, self.target, out=self.master_gain if self.ceiling is None else self.free_gain)
-        source = self.sum                          # what master_gain scales
+            lufs = self.lufs
+            if self.compressor is not None:
+                # the sum at the target gain, compressed; what follows measures and scales THAT: the second target gain is
+                # the make-up
+                loudness.target_gains_device(self.lufs, self.target, out=self.comp_gain)
+                ops.compressor_apply(self.mix.t().unsqueeze(0), *self.comp_args, pre_gain=self.comp_gain, out=self.compressed,
+                                     max_reduction_out=self.comp_max, n_over_out=self.comp_over, workspace=self.comp_ws)
+                source, lufs = self.compressed, self.compressed_lufs
+                self.meter.integrated_loudness_batch(source.t().unsqueeze(0), out=lufs)
+            loudness.target_gains_device(lufs, self.target, out=self.master_gain if self.ceiling is None else self.free_gain)
         if self.limiter is not None:
             # the sum at the target gain, its peaks turned down; the clamp below measures the result: master_gain is the trim
-            ops.limiter_apply(self.mix.t().unsqueeze(0), self.ceiling, self.lookahead, self.hold, pre_gain=self.free_gain,
+            ops.limiter_apply(source.t().unsqueeze(0), self.ceiling, self.lookahead, self.hold, pre_gain=self.free_gain,
                               out=self.limited, min_gain_out=self.min_gain, n_limited_out=self.n_limited,
                               workspace=self.limiter_ws)
             source = self.limited
@@ -212,6 +263,20 @@ class MasterChain:
                             'loudness_lufs': float(self.limited_lufs.cpu()[0]) + trim_db})
         return out
 
+    def compression(self):
+        """What the compressor did in the last render of a chain with one, from the device scalars the graph wrote:
+        {'max_reduction_db': the largest gain reduction (0.0: untouched), 'over_share': the share of samples above the knee's
+        start, 'makeup_db': the gain that brought the compressed signal back to the target, 'loudness_lufs': BS.1770 of the
+        compressed signal at that gain (before any limiter or ceiling: peaks() tells what those did)}."""
+        if self.compressor is None:
+            raise ValueError('this master chain was built without a compressor')
+        gain = float((self.master_gain if self.ceiling is None else self.free_gain).cpu()[0])
+        with np.errstate(divide='ignore', invalid='ignore'):
+            makeup_db = float(20.0 * np.log10(gain))
+        return {'max_reduction_db': float(self.comp_max.cpu()[0]),
+                'over_share': int(self.comp_over.cpu()[0]) / self.compressed.shape[1], 'makeup_db': makeup_db,
+                'loudness_lufs': float(self.compressed_lufs.cpu()[0]) + makeup_db}
+
 
 class SongMixer:
     """Static device buffers and the captured hipGraph of one song geometry: (model, stems, channels, samples, dtype,
@@ -219,9 +284,9 @@ class SongMixer:
 
     def __init__(self, model, n_stems, channels, n_samples, dtype, chunk_samples, kind, normalize=True,
                  out_dtype=torch.float64, use_graph=True, hop_length=1024, sr=44100, target_lufs=-20.0, encode=None,
-                 dither_seed=None, ceiling_dbtp=None, limiter=None):
-        """normalize, out_dtype, sr, target_lufs, encode, dither_seed, ceiling_dbtp, limiter: what MasterChain takes, for kind
-        'master' (the other kinds accept neither ``encode`` nor a ceiling nor a limiter).  With ``encode`` the master is
+                 dither_seed=None, ceiling_dbtp=None, limiter=None, compressor=None):
+        """normalize, out_dtype, sr, target_lufs, encode, dither_seed, ceiling_dbtp, limiter, compressor: what MasterChain takes,
+        for kind 'master' (the other kinds accept neither ``encode`` nor a ceiling nor a limiter nor a compressor).  With ``encode`` the master is
         quantised by the last node of the same graph and ``run`` returns its sample bytes and the clipped-sample count;
         ``peaks()`` reports the true-peak measurement of the last run."""
         if kind not in ('stems', 'master', 'spectral', 'loudness'):
@@ -230,6 +295,9 @@ class SongMixer:
         self.limiter, self.ceiling = MasterChain.limiter_rules(limiter, self.normalize, self.ceiling)
         if kind != 'master' and (encode is not None or self.ceiling is not None or self.limiter is not None):
             raise ValueError("encode, ceiling_dbtp and limiter need kind='master'")
+        self.compressor = MasterChain.compressor_rules(compressor, self.normalize)
+        if kind != 'master' and self.compressor is not None:
+            raise ValueError("compressor needs kind='master'")
         self.encode = encode
         self.model, self.kind = model, kind
         self.dev = next(model.parameters()).device
@@ -260,7 +328,7 @@ class SongMixer:
             self.out = torch.empty(n_stems, dtype=torch.float64, device=dev)                       # LUFS of every mixed stem
         else:
             self.chain = MasterChain(channels, n_samples, dev, self.normalize, out_dtype, sr, target_lufs, self.ceiling, encode,
-                                     dither_seed, limiter)
+                                     dither_seed, limiter, compressor)
             if encode is not None:
                 self.enc, self.clip = self.chain.enc, self.chain.clip
             if self.chain.out is not None:                     # (no float master is kept beside an encoded, gain-scaled one)
@@ -346,12 +414,18 @@ class SongMixer:
             raise ValueError('this mixer was built without ceiling_dbtp')
         return self.chain.peaks()
 
+    def compression(self):
+        """MasterChain.compression() of the last run."""
+        if self.kind != 'master':
+            raise ValueError('this mixer was built without a compressor')
+        return self.chain.compression()
+
 
 _mixers = {}
 
 
 def _mixer(model, stems, loaded_tracks, chunk_length, sr, kind, normalize, out_dtype, hop_length=1024, target_lufs=-20.0,
-           encode=None, dither_seed=None, ceiling_dbtp=None, limiter=None):
+           encode=None, dither_seed=None, ceiling_dbtp=None, limiter=None, compressor=None):
     first = np.asarray(loaded_tracks[stems[0]])
     if first.ndim != 2:
         raise ValueError('loaded_tracks[track] must be [channels, n] arrays')
@@ -361,16 +435,17 @@ def _mixer(model, stems, loaded_tracks, chunk_length, sr, kind, normalize, out_d
         normalize = bool(normalize)            # the callers' ``if normalize:`` (inference.ipynb cells 9/11)
     normalize, ceiling_dbtp = MasterChain.rules(normalize, ceiling_dbtp, encode)
     times, ceiling_dbtp = MasterChain.limiter_rules(limiter, normalize, ceiling_dbtp)
+    shape = MasterChain.compressor_rules(compressor, normalize)
     if normalize != 'loudness':
         target_lufs = None                     # (not part of such a mixer: one key whatever the caller passed)
     key = (id(model), len(stems), ch, n, dt, chunk_length * sr, kind, normalize, out_dtype, hop_length, sr, target_lufs,
-           encode, dither_seed if encode is not None else None, ceiling_dbtp, times)
+           encode, dither_seed if encode is not None else None, ceiling_dbtp, times, shape)
     m = _mixers.get(key)
     if m is None:
         _mixers.clear()                        # one geometry at a time: a song's buffers are hundreds of MB
         m = SongMixer(model, len(stems), ch, n, dt, chunk_length * sr, kind, normalize, out_dtype, hop_length=hop_length, sr=sr,
                       target_lufs=-20.0 if target_lufs is None else target_lufs, encode=encode, dither_seed=dither_seed,
-                      ceiling_dbtp=ceiling_dbtp, limiter=limiter)
+                      ceiling_dbtp=ceiling_dbtp, limiter=limiter, compressor=compressor)
         _mixers[key] = m
     np_dt = np.float32 if dt == torch.float32 else np.float64
     return m, [np.asarray(loaded_tracks[t], dtype=np_dt) for t in stems]
@@ -403,7 +478,7 @@ def mix_song_loudness(dataset, model, loaded_tracks: dict, chunk_length=1, sr=44
 
 
 def mix_song_to_master(dataset, model, loaded_tracks: dict, chunk_length=1, sr=44100, normalize=True, dtype=np.float64,
-                       target_lufs=-20.0, ceiling_dbtp=None, limiter=None):
+                       target_lufs=-20.0, ceiling_dbtp=None, limiter=None, compressor=None):
     """mix_song_smooth followed by what every caller of the reference does next (inference.ipynb cells 9/11,
     evaluation.py:59-66): ``track_sum = np.sum(list(mixed_tracks.values()), axis=0)`` and, if ``normalize``,
     ``librosa.util.normalize(track_sum, axis=1)`` -- fused into one pass over the song on the GPU (the per-stem mixed
@@ -414,27 +489,31 @@ def mix_song_to_master(dataset, model, loaded_tracks: dict, chunk_length=1, sr=4
     that its true peak sits at ``ceiling_dbtp`` (default -1.0), one gain for all channels.  ``limiter`` (with 'loudness';
     True or {'lookahead_ms', 'hold_ms'}): only the peaks over the ceiling (-1.0 dBTP unless given) are turned down, by a gain
     that dips ahead of each and ramps back after it, so the master stays near ``target_lufs``; SongMixer.peaks() reports the
-    largest reduction, the share of samples touched and the loudness reached.
+    largest reduction, the share of samples touched and the loudness reached.  ``compressor`` (with 'loudness'; True or a dict
+    with keys of MasterChain.COMPRESSOR_DEFAULTS): the sum at ``target_lufs`` is compressed (threshold in dBFS at that
+    loudness, one gain for all channels, attack and release) and brought to ``target_lufs`` again before the limiter and the
+    ceiling; SongMixer.compression() reports the largest reduction, the share of samples over the knee and the make-up gain.
     Returns (mix ndarray[channels, n], raw_gains, smooth_gains)."""
     out_dt = torch.float32 if np.dtype(dtype) == np.float32 else torch.float64
     _, _, out, raw_gains, smooth_gains = _mix_song(dataset, model, loaded_tracks, chunk_length, sr, 'master', normalize, out_dt,
-                                                   target_lufs=target_lufs, ceiling_dbtp=ceiling_dbtp, limiter=limiter)
+                                                   target_lufs=target_lufs, ceiling_dbtp=ceiling_dbtp, limiter=limiter,
+                                                   compressor=compressor)
     return out, raw_gains, smooth_gains
 
 
 def mix_song_to_wav(dataset, model, loaded_tracks: dict, path, chunk_length=1, sr=44100, normalize=True, subtype='PCM_16',
-                    target_lufs=-20.0, dither_seed=None, ceiling_dbtp=None, limiter=None):
+                    target_lufs=-20.0, dither_seed=None, ceiling_dbtp=None, limiter=None, compressor=None):
     """mix_song_to_master followed by the callers' ``sf.write(path, master.T, sr)`` (inference.ipynb cells 9/11;
     evaluation.py:59-66 with ``normalize='loudness'``): the float64 master is quantised to ``subtype`` by the last node of
     the song's graph (ops.pcm_encode, TPDF dither if ``dither_seed`` is given), so the host receives the file's sample
     bytes -- a quarter of the float64 master for 'PCM_16' -- and writes them behind a WAV header.  The samples are those
     tests/_pcm_ref.py's quantiser makes of mix_song_to_master(..., dtype=float64).  ``ceiling_dbtp`` / ``normalize='true_peak'``
-    and ``limiter`` as there: with a ceiling below 0 dBTP the encoder has nothing to clip.
+    ``limiter`` and ``compressor`` as there: with a ceiling below 0 dBTP the encoder has nothing to clip.
     Returns (clipped sample count, raw_gains, smooth_gains); warns (RuntimeWarning) when samples had to be clipped."""
     from .data.dataset_utils import write_wav_bytes
     m, _, (payload, clipped), raw_gains, smooth_gains = _mix_song(
         dataset, model, loaded_tracks, chunk_length, sr, 'master', normalize, torch.float64, target_lufs=target_lufs,
-        encode=subtype, dither_seed=dither_seed, ceiling_dbtp=ceiling_dbtp, limiter=limiter)
+        encode=subtype, dither_seed=dither_seed, ceiling_dbtp=ceiling_dbtp, limiter=limiter, compressor=compressor)
     write_wav_bytes(path, payload, sr, m.channels, subtype, m.n, clipped)
     return clipped, raw_gains, smooth_gains
 

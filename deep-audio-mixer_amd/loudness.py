@@ -28,6 +28,7 @@ Peaks -- ``pyln.normalize.peak`` and the true peak (BS.1770 Annex 2 / EBU R128: 
     tp = true_peak_batch(pcm.transpose(1, 2))            # [N, channels] linear, CUDA float64, no synchronisation
     limit_gains_device(gain, tp, -1.0)                   # gain = min(gain, ceiling / max over channels), on the device
     out, info = limit_true_peak(data, 44100, -1.0)       # look-ahead limiter: only the peaks are turned down
+    out, info = compress(data, 44100, -12.0, ratio=2.0)  # compressor with attack and release: the dynamics are changed
 
 The interpolator is this package's own 49-tap windowed sinc (include/dam_hip.h); parity with libebur128 is not claimed.
 
@@ -449,6 +450,43 @@ def limit_true_peak(data, rate, ceiling_dbtp=-1.0, lookahead_ms=5.0, hold_ms=20.
     limited = out[0].t().cpu().numpy().reshape(tuple(data.shape))
     return limited, {'max_reduction_db': float(20.0 * np.log10(min_gain.item())),
                      'limited_share': n_limited.item() / x.shape[0], 'lookahead_samples': L, 'hold_samples': H}
+
+
+def compress_device(data, rate, threshold_db=-12.0, ratio=2.0, knee_db=6.0, attack_ms=10.0, release_ms=100.0, makeup_db=0.0,
+                    pre_gain=None, out_dtype=None, reduction_out=None):
+    """Feed-forward compressor on the device: data CUDA float32/float64 [N, samples, channels] with any strides (N tracks,
+    the channels of each compressed with one gain), pre_gain an optional CUDA float64 [N] applied first -- the threshold is
+    in dBFS of ``data * pre_gain``.  Above ``threshold_db`` the level rises by 1/``ratio`` dB per dB (``float('inf')``: not
+    at all), through a quadratic knee ``knee_db`` wide; the reduction follows the curve with ``attack_ms`` and decays with
+    ``release_ms`` (dam_compressor_apply: include/dam_hip.h states the definition).  Returns (compressed planar [N,
+    channels, samples], float64 unless out_dtype is given; max_reduction CUDA float64 [N] in dB; n_over CUDA int64 [N], the
+    samples above the knee's start).  reduction_out: optional CUDA float64 [N, samples] for the gain-reduction curve in dB.
+    Where nothing has reached the knee yet the samples pass bit for bit (times the make-up).  No host synchronisation."""
+    from . import ops
+    if not torch.is_tensor(data):
+        raise ValueError('Data must be of type torch.Tensor.')
+    _lib.require_cuda(data, pre_gain)
+    if data.dtype not in (torch.float32, torch.float64):
+        raise ValueError('Data must be floating point.')
+    if data.dim() != 3:
+        raise ValueError('Audio must be [tracks, samples, channels].')
+    constants = ops.compressor_constants(threshold_db, knee_db, attack_ms, release_ms, rate, makeup_db)
+    return ops.compressor_apply(data, threshold_db, ratio, knee_db, *constants, pre_gain=pre_gain, out_dtype=out_dtype,
+                                reduction_out=reduction_out)
+
+
+def compress(data, rate, threshold_db=-12.0, ratio=2.0, knee_db=6.0, attack_ms=10.0, release_ms=100.0, makeup_db=0.0):
+    """One [samples] or [samples, channels] array (numpy or torch) through the compressor, in the style of limit_true_peak:
+    returns (compressed, info) with ``compressed`` a numpy array of data's shape and dtype and info = {'max_reduction_db':
+    the largest gain reduction in dB (0.0: untouched), 'over_share': the share of samples above the knee's start,
+    'reduction_db': the gain-reduction curve, numpy float64 [samples]}."""
+    x = _as_device_2d(data)
+    reduction = torch.empty((1, x.shape[0]), dtype=torch.float64, device=x.device)
+    out, max_reduction, n_over = compress_device(x.unsqueeze(0), rate, threshold_db, ratio, knee_db, attack_ms, release_ms,
+                                                 makeup_db, out_dtype=x.dtype, reduction_out=reduction)
+    compressed = out[0].t().cpu().numpy().reshape(tuple(data.shape))
+    return compressed, {'max_reduction_db': float(max_reduction.item()), 'over_share': n_over.item() / x.shape[0],
+                        'reduction_db': reduction[0].cpu().numpy()}
 
 
 def gated_loudness(z):

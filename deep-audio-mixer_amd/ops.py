@@ -1199,6 +1199,83 @@ def limiter_apply(data, ceiling_db, lookahead, hold, pre_gain=None, out=None, ou
     return out, min_gain_out, n_limited_out
 
 
+# ----------------------------------------------------------------------------- compressor with attack and release
+def compressor_geometry():
+    """(samples of one chunk, samples one workgroup owns, largest time constant in samples) of dam_compressor_apply, asked of
+    the library.  The chunk length is part of the kernel's definition: it fixes the order of every rounding."""
+    L = _lib.lib()
+    return L.dam_compressor_chunk_samples(), L.dam_compressor_tile_samples(), L.dam_compressor_max_time_samples()
+
+
+def compressor_constants(threshold_db, knee_db, attack_ms, release_ms, sr, makeup_db=0.0):
+    """The four float64 constants dam_compressor_apply takes, computed once, here, so that the kernel and a reference use
+    bit-identical values: (knee_start = 10^((T - W/2)/20), alpha_attack = exp(-1 / (attack_ms * 1e-3 * sr)), alpha_release
+    likewise, makeup = 10^(makeup_db/20)).  Needs no GPU."""
+    import math
+    threshold_db, knee_db, attack_ms, release_ms, sr = (float(v) for v in (threshold_db, knee_db, attack_ms, release_ms, sr))
+    if not (knee_db >= 0.0 and attack_ms > 0.0 and release_ms > 0.0 and sr > 0.0):
+        raise ValueError('compressor_constants: knee_db >= 0 and positive times and rate expected, got %r'
+                         % ((knee_db, attack_ms, release_ms, sr),))
+    return (10.0 ** ((threshold_db - 0.5 * knee_db) / 20.0), math.exp(-1.0 / (attack_ms * 1e-3 * sr)),
+            math.exp(-1.0 / (release_ms * 1e-3 * sr)), 10.0 ** (float(makeup_db) / 20.0))
+
+
+def compressor_apply(data, threshold_db, ratio, knee_db, knee_start, alpha_attack, alpha_release, makeup=1.0, pre_gain=None,
+                     out=None, out_dtype=None, reduction_out=None, max_reduction_out=None, n_over_out=None, workspace=None):
+    """data: CUDA float32 / float64 [N, samples, channels] with any strides (planar [N, channels, n] storage is passed as
+    ``pcm.transpose(1, 2)``, no copy): N row sets, the channels of each compressed with one gain (include/dam_hip.h:
+    dam_compressor_apply states the definition).  threshold_db, ratio (>= 1, ``float('inf')`` allowed), knee_db (>= 0): the
+    static curve; knee_start, alpha_attack, alpha_release, makeup: ``compressor_constants(...)`` of the same threshold and
+    knee (ValueError where the library refuses them).  pre_gain: optional CUDA float64 [N], multiplied in first.
+    reduction_out: optional CUDA float64 [N, samples] that receives the gain-reduction curve in dB.  Returns (out planar
+    [N, channels, samples] of ``out_dtype`` (float64 unless given), max_reduction float64 [N] in dB, n_over int64 [N]).
+    workspace: optional float64 tensor of dam_compressor_workspace_bytes / 8 elements.  No host synchronisation,
+    hipGraph-capturable."""
+    _lib.require_cuda(data, pre_gain, out, reduction_out, max_reduction_out, n_over_out, workspace)
+    xk = _audio_kind(data, 'data')
+    if data.dim() != 3:
+        raise ValueError('compressor_apply: [row sets, samples, channels] expected, got shape %s' % (tuple(data.shape),))
+    N, n, ch = data.shape
+    if N < 1 or n < 1 or ch < 1 or N > 65535:
+        raise ValueError('compressor_apply: 1..65535 row sets and at least one sample and channel expected, got %s'
+                         % (tuple(data.shape),))
+    if pre_gain is not None and (pre_gain.dtype != torch.float64 or pre_gain.numel() != N or not pre_gain.is_contiguous()):
+        raise ValueError('compressor_apply: pre_gain must be a contiguous float64 tensor of %d elements' % N)
+    L = _lib.lib()
+    dev = data.device
+    if out is None:
+        out = torch.empty((N, ch, n), dtype=out_dtype or torch.float64, device=dev)
+    elif out.numel() != N * ch * n or not out.is_contiguous():
+        raise ValueError('compressor_apply: out must be a contiguous tensor of %d x %d x %d elements' % (N, ch, n))
+    ok = _audio_kind(out, 'out')
+    if reduction_out is not None and (reduction_out.dtype != torch.float64 or reduction_out.numel() != N * n
+                                      or not reduction_out.is_contiguous()):
+        raise ValueError('compressor_apply: reduction_out must be a contiguous float64 tensor of %d x %d elements' % (N, n))
+    if max_reduction_out is None:
+        max_reduction_out = torch.empty(N, dtype=torch.float64, device=dev)
+    if n_over_out is None:
+        n_over_out = torch.empty(N, dtype=torch.int64, device=dev)
+    for o, dt in ((max_reduction_out, torch.float64), (n_over_out, torch.int64)):
+        if o.dtype != dt or o.numel() != N or not o.is_contiguous():
+            raise ValueError('compressor_apply: max_reduction_out / n_over_out must be contiguous float64 / int64 tensors of %d' % N)
+    need = L.dam_compressor_workspace_bytes(N, n) // 8
+    if workspace is None:
+        workspace = torch.empty(need, dtype=torch.float64, device=dev)
+    elif workspace.dtype != torch.float64 or workspace.numel() < need or not workspace.is_contiguous():
+        raise ValueError('compressor_apply: workspace must be a contiguous float64 tensor of at least %d elements' % need)
+    with torch.cuda.device(dev):
+        rc = L.dam_compressor_apply(_lib.ptr(data), xk, N, n, ch, data.stride(0), data.stride(1), data.stride(2),
+                                    _lib.ptr(pre_gain), float(threshold_db), float(ratio), float(knee_db), float(knee_start),
+                                    float(alpha_attack), float(alpha_release), float(makeup), _lib.ptr(out), ok,
+                                    _lib.ptr(reduction_out), _lib.ptr(max_reduction_out), _lib.ptr(n_over_out),
+                                    _lib.ptr(workspace), _lib.stream())
+    if rc == -1:                                       # DAM_ERR_BAD_ARG: everything else was checked above
+        raise ValueError('compressor_apply: the library refuses threshold %r dB, ratio %r, knee %r dB with knee_start %r, alphas '
+                         '%r / %r, makeup %r' % (threshold_db, ratio, knee_db, knee_start, alpha_attack, alpha_release, makeup))
+    _lib.check(rc, 'dam_compressor_apply')
+    return out, max_reduction_out, n_over_out
+
+
 # ----------------------------------------------------------------------------- band spectrum and spectral balance
 def spectrum_geometry():
     """(frames one workgroup owns, largest number of bands) of dam_spectrum_band_power, asked of the library."""

@@ -56,7 +56,7 @@ struct dam_bn_bwd_in;
 /* Library / build identification ("gfx950").  DAM_ABI_VERSION is bumped whenever a signature below changes; a binding
  * compares dam_abi_version() of the library it loaded with the version it was written against and refuses a stale one
  * (deep-audio-mixer_amd/_lib.py: EXPECTED_ABI). */
-#define DAM_ABI_VERSION 37
+#define DAM_ABI_VERSION 38
 const char* dam_arch(void);
 int dam_abi_version(void);
 
@@ -853,6 +853,62 @@ int64_t dam_limiter_workspace_bytes(int n_sets, int64_t n_samples);
 int dam_limiter_apply(const void* x, int x_is_f64, int n_sets, int64_t n_samples, int channels, int64_t set_stride,
                       int64_t sample_stride, int64_t channel_stride, const double* pre_gain, double ceiling_lin, int lookahead,
                       int hold, void* out, int out_is_f64, double* min_gain, int64_t* n_limited, void* workspace, void* stream);
+
+/* ---------------------------------------------------------------------------------
+ * Feed-forward compressor with attack and release: the dynamics stage of a mixer, per stem or on the bus before the
+ * limiter.  It is the recurrence the limiter above leaves out.  Everything is float64.
+ *   Per row set (the 1 .. C channels of one track, compressed with ONE gain: stereo link): rows x[c][i], i in [0, n), the
+ *   scalar s = pre_gain[set] (1 if pre_gain is NULL), threshold T dB, ratio R >= 1 (+inf allowed), knee width W >= 0 dB,
+ *   slope = 1 - 1/R, knee_start = 10^((T - W/2)/20), aA = exp(-1 / (attack_ms * 1e-3 * rate)), aR likewise from release_ms,
+ *   M = 10^(makeup_db/20).  knee_start, aA, aR and M are computed ONCE by the caller (ops.compressor_constants) and cross
+ *   this interface as doubles, so that a reference uses bit-identical constants.
+ *     1. xs[c][i] = (double)x[c][i] * s                                              (one rounding)
+ *     2. detector  d[i] = max_c |xs[c][i]|
+ *     3. static curve, the gain reduction c[i] >= 0 in dB:
+ *          d[i] <= knee_start:  c[i] = 0, exactly, no logarithm taken;
+ *          else o = 20 log10(d[i]) - T and
+ *            W > 0 and o < W/2:  c = slope * (t * t) / (2 W),  t = max(o + W/2, 0);
+ *            otherwise:          c = slope * max(o, 0).
+ *     4. ballistics, the decoupled smooth peak detector of Giannoulis, Massberg and Reiss (JAES 2012) on the reduction:
+ *          p[i] = max(c[i], aR * p[i-1])                      p[-1] = 0     (release: peak hold with exponential decay)
+ *          q[i] = fma(aA, q[i-1], (1 - aA) * p[i])            q[-1] = 0     (attack: one pole on p; 1 - aA rounded once)
+ *     5. g[i] = exp(-(q[i] * K)) * M,  K = 0.11512925464970228 (ln 10 / 20);   out[c][i] = xs[c][i] * g[i], rounded once to
+ *        the output type.
+ *     6. max_reduction = max_i q[i] (dB, >= 0);  n_over = #{i : d[i] > knee_start} (an exact integer).
+ *     7. reduction[i] = q[i], only where a pointer is given: the gain-reduction curve, for plotting and metering.
+ *   Parallel form.  Both recurrences are scans over closed families of maps: y -> max(c, a y) composes as
+ *   (c2, a2) o (c1, a1) = (max(c2, a2 c1), a2 a1) with identity (0, 1) (c, y >= 0); y -> A y + B composes as
+ *   (B2, A2) o (B1, A1) = (fma(A2, B1, B2), A2 A1).  A row is cut into chunks of K = dam_compressor_chunk_samples() samples:
+ *   every chunk is walked from a zero state, the chunk maps (end state, a^K with a^K formed by K - 1 multiplications) are
+ *   composed per tile of dam_compressor_tile_samples() samples (a shuffle scan over 64 chunks, the four 64-chunk totals
+ *   left to right) and the tile totals left to right along the row (256 at a time, the same scan, with a carried state),
+ *   and the chunks are walked again from their true entry states -- first p, then q on the true p.  The order of every
+ *   combination is a function of the position in the row only; K is therefore part of the definition of the rounding, and
+ *   the result agrees with the sequential definition to a few roundings per effective step (tests/test_compressor_gpu.py
+ *   derives the bound).  Bitwise properties: a row set does not depend on the other row sets of the call, on its strides or
+ *   on the launch geometry; out[..][:m+1] and q[:m+1] depend on x[..][:m+1] only; where no sample so far exceeded knee_start,
+ *   q == 0.0 and out == xs * M bit for bit; permuting the channels permutes out and leaves q alone.
+ *   dam_compressor_apply: n_sets row sets in one set of launches, addressed and laid out as dam_limiter_apply's (x by
+ *     element strides, float32 or float64; out planar [n_sets][channels][n_samples], float32 or float64, not overlapping
+ *     x; pre_gain device float64 [n_sets] or NULL).  reduction (device float64 [n_sets][n_samples]), max_reduction (device
+ *     float64 [n_sets]) and n_over (device int64 [n_sets]) may each be NULL.  workspace:
+ *     dam_compressor_workspace_bytes(n_sets, n_samples) bytes, 8-byte aligned (c per sample, four doubles per chunk, eight
+ *     per tile).  Stateless, allocates nothing, does not synchronise, no atomics, hipGraph-capturable.  Returns
+ *     DAM_ERR_BAD_ARG without a launch for: NULL x / out / workspace; n_sets outside 1 .. 65535; n_samples < 1;
+ *     channels < 1; R < 1 or NaN; W < 0 or not finite; a knee_start that is not positive or whose 20 log10 differs from
+ *     T - W/2 by more than 1e-9 dB; an alpha outside (0, 1) or of a time constant above
+ *     dam_compressor_max_time_samples() = 2^17 samples; a makeup that is not positive and finite.  Non-finite samples or
+ *     gains are outside the contract.
+ * --------------------------------------------------------------------------------- */
+int64_t dam_compressor_chunk_samples(void);
+int64_t dam_compressor_tile_samples(void);
+int64_t dam_compressor_max_time_samples(void);
+int64_t dam_compressor_workspace_bytes(int n_sets, int64_t n_samples);
+int dam_compressor_apply(const void* x, int x_is_f64, int n_sets, int64_t n_samples, int channels, int64_t set_stride,
+                         int64_t sample_stride, int64_t channel_stride, const double* pre_gain, double threshold_db, double ratio,
+                         double knee_db, double knee_start, double alpha_attack, double alpha_release, double makeup_lin,
+                         void* out, int out_is_f64, double* reduction, double* max_reduction, int64_t* n_over, void* workspace,
+                         void* stream);
 
 /* ---------------------------------------------------------------------------------
  * Loudness over time: momentary (400 ms) and short-term (3 s) loudness as EBU R128 names them, the loudness range of
