@@ -12,7 +12,7 @@ LIB_PATH = os.environ.get('DAM_LIB_PATH') or os.path.join(_HERE, 'libdam_hip.so'
 # include/dam_hip.h: bumped whenever a C signature changes (together with dam_abi_version() in csrc/dam_api.hip and
 # DAM_ABI_VERSION in the header).  libdam_hip.so is git-ignored and travels prebuilt: a stale one would read device pointers
 # as streams, so lib() refuses it instead of launching.
-EXPECTED_ABI = 38
+EXPECTED_ABI = 39
 
 _STATUS = {0: 'DAM_OK', -1: 'DAM_ERR_BAD_ARG', -2: 'DAM_ERR_UNSUPPORTED', -3: 'DAM_ERR_LAUNCH',
            -4: 'DAM_ERR_WORKSPACE'}
@@ -154,6 +154,9 @@ SIGNATURES = {
     'dam_specdist_sums': (c_i, [c_p, c_i, c_i, c_i, c_i, c_i64, c_i64, c_i64, c_i64, c_p, c_i, c_p, c_i, c_i, c_i, c_i64, c_i64,
                                 c_i64, c_p, c_i, c_p, c_p, c_i, c_i, c_f, c_p, c_i, c_i, c_p, c_p, c_p, c_p]),
     'dam_specdist_summary': (c_i, [c_p, c_p, c_i, c_i, c_i, c_p, c_p]),
+    'dam_specgrad_workspace_bytes': (c_i64, [c_i, c_i, c_i, c_i64, c_i, c_i, c_i]),
+    'dam_specgrad': (c_i, [c_p, c_i, c_i, c_i, c_i, c_i, c_i64, c_i64, c_i64, c_i64, c_i64, c_p, c_i, c_p, c_i, c_i, c_i, c_i64,
+                           c_i64, c_i64, c_i64, c_p, c_i, c_p, c_p, c_i, c_i, c_f, c_p, c_p, c_p, c_p]),
     'dam_align_max_lag': (c_i, []),
     'dam_align_frames_per_block': (c_i, []),
     'dam_align_fft_size': (c_i, [c_i]),

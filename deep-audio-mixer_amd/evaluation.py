@@ -207,10 +207,11 @@ class LoudnessEvaluator:
         where bins are left (spectrum.extend_edges), so that the cells cover every bin and their total is the criterion; the
         centre of such a band is the mean frequency of its bins."""
         given = {} if feature_distance is True else dict(feature_distance)
+        given.pop('sensitivity', None)                      # (a switch, not a parameter of the features: _feature_sensitivity)
         unknown = set(given) - set(self.FEATURE_DISTANCE_DEFAULTS)
         if unknown:
             raise ValueError('feature_distance: unknown keys %s (expected any of %s)'
-                             % (sorted(unknown), sorted(self.FEATURE_DISTANCE_DEFAULTS)))
+                             % (sorted(unknown), sorted(self.FEATURE_DISTANCE_DEFAULTS) + ['sensitivity']))
         o = dict(self.FEATURE_DISTANCE_DEFAULTS, **given)
         if 'n_fft' in given and 'hop' not in given:
             o['hop'] = None                                 # (n_fft / 2, as everywhere)
@@ -221,6 +222,11 @@ class LoudnessEvaluator:
         mid = lambda a, b: 0.5 * (int(a) + int(b) - 1) * self.sr / n_fft
         centres = ([mid(edges[0], edges[1])] if low else []) + centres.tolist() + ([mid(edges[-2], edges[-1])] if high else [])
         return n_fft, hop, edges, centres
+
+    @staticmethod
+    def _feature_sensitivity(feature_distance):
+        """Does ``feature_distance`` ask for the '*_feat_sens' keys ({'sensitivity': True, ...})?"""
+        return feature_distance is not True and bool(dict(feature_distance).get('sensitivity', False))
 
     def evaluate_spectrum_batch(self, stems, gains=None, **spectral):
         """Band powers of the stem sum (long-term average spectrum in fractional-octave bands at the evaluator's rate),
@@ -338,7 +344,10 @@ class LoudnessEvaluator:
         draws): the centred RMS of the difference in dB, which a common gain does not move; the same four as '*_feat_mse': the
         mean squared difference in dB^2, the criterion as trained; and 'feat_profile' {'centres': [Hz], 'mix_band_rms': [bands],
         'mix_window_rms': [windows]}, the centred RMS of the model's mix per band and per window.  Nothing else depends on it.
-        The reference mix and the stems must be of one length."""
+        The reference mix and the stems must be of one length.  With 'sensitivity': True in the dict, after those keys,
+        'sum_feat_sens', 'loudnorm_feat_sens', 'mix_feat_sens', 'random_feat_sens' (the mean over the draws) [stems][windows]:
+        the change of the variant's '*_feat_mse' in dB^2 per dB of that stem in that gain window (one fused
+        spectrum.spectrogram_distance_grad call, every variant a row; a window must hold at least n_fft samples)."""
         render_fill = self._band_render_args(band_render, band_fit)
         if self.d is None or self.mix_model is None or self.mean_loudness_model is None:
             raise ValueError('process_song needs the dataset, d_mean_loudness and mix_model constructor arguments')
@@ -542,7 +551,6 @@ class LoudnessEvaluator:
                               mixer.gains[1].unsqueeze(0), constant[1:]])
             sums, count = spectrum.spectrogram_distance(pcm.transpose(1, 2), cand, feat_reference.transpose(1, 2), None,
                                                         n_fft=feat_n_fft, hop=feat_hop, edges=feat_edges, n_windows=W)
-            del feat_reference
             fig = spectrum.distance_summary(sums, count)
             host = torch.cat([fig.rms_centred, fig.mse, fig.band_rms[2], fig.window_rms[2]]).cpu().tolist()
             n_var = cand.shape[0]
@@ -554,6 +562,14 @@ class LoudnessEvaluator:
             n_bands = len(feat_centres)
             stats['feat_profile'] = {'centres': feat_centres, 'mix_band_rms': host[2 * n_var:2 * n_var + n_bands],
                                      'mix_window_rms': host[2 * n_var + n_bands:]}
+            if self._feature_sensitivity(feature_distance):  # one fused call: every variant a row, the gain windows the nodes
+                grad_mse = spectrum.spectrogram_distance_grad(pcm.transpose(1, 2), cand, feat_reference.transpose(1, 2), None,
+                                                              n_fft=feat_n_fft, hop=feat_hop)[2]
+                sens = spectrum.gain_sensitivity_db(cand, grad_mse).cpu()                   # [variants, stems, W]
+                stats['sum_feat_sens'], stats['loudnorm_feat_sens'], stats['mix_feat_sens'] = sens[:3].tolist()
+                stats['random_feat_sens'] = (sens[3:].mean(dim=0) if n_var > 3 else
+                                             torch.full((n_stems, W), float('nan'), dtype=torch.float64)).tolist()
+            del feat_reference
         return stats
 
     def process_song(self, base_dir: str, song_name: str, n_random_samples: int = 5, chunk_length: int = 2,

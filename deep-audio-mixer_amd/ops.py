@@ -1873,6 +1873,91 @@ def specdist_summary(sums, count, out=None):
     return out
 
 
+# ----------------------------------------------------------------------------- spectrogram distance: gradient in the gains
+def specgrad_check_shapes(stems_shape, gains_shape, ref_shape, ref_gains_shape, n_fft, hop, amin=1e-5):
+    """The host-side argument rules of specgrad on shapes alone -> (clips, R, S, n, channels, S_ref, ref_channels, n_fft, hop,
+    n_gains); ValueError / TypeError otherwise.  stems_shape [clips, S, n, channels]; gains_shape None or [clips, R, S, n_gains];
+    ref_shape [clips, S_ref, n, channels]; ref_gains_shape None or [clips, S_ref, n_gains]; hop None: n_fft / 2.  n_gains comes
+    back as 1 for gains_shape None.  A frame may touch two gain segments at most: n_gains == 1 or n // n_gains >= n_fft.  No
+    tensor and no library is touched."""
+    if len(stems_shape) != 4 or len(ref_shape) != 4:
+        raise ValueError('specgrad: stems and reference must be [clips, stems, samples, channels], got shapes %s and %s'
+                         % (tuple(stems_shape), tuple(ref_shape)))
+    clips = stems_shape[0]
+    if not 1 <= clips <= 65535 or ref_shape[0] != clips:
+        raise ValueError('specgrad: 1..65535 clips on both sides expected, got %d and %d' % (clips, ref_shape[0]))
+    if gains_shape is not None:
+        gains_shape = tuple(gains_shape)
+        if len(gains_shape) != 4 or gains_shape[0] != clips:
+            raise ValueError('specgrad: gains must be [clips, rows, stems, n_gains] with %d clips, got shape %s' % (clips, gains_shape))
+    if ref_gains_shape is not None:
+        ref_gains_shape = tuple(ref_gains_shape)
+        if len(ref_gains_shape) != 3 or ref_gains_shape[0] != clips:
+            raise ValueError('specgrad: ref_gains must be [clips, stems, n_gains] with %d clips, got shape %s'
+                             % (clips, ref_gains_shape))
+    # the per-clip rules are the distance's (one window: every geometry has a frame)
+    R, S, n, ch, S_ref, ch_ref, n_fft, hop, _ = specdist_check_shapes(
+        tuple(stems_shape)[1:], None if gains_shape is None else gains_shape[1:], tuple(ref_shape)[1:],
+        None if ref_gains_shape is None else ref_gains_shape[1:], n_fft, hop, 1, None, amin)
+    G = 1 if gains_shape is None else gains_shape[3]
+    if G > 1 and n // G < n_fft:
+        raise ValueError('specgrad: unsupported gain ramp: %d samples per gain node, fewer than n_fft = %d (a frame may touch two '
+                         'gain segments at most)' % (n // G, n_fft))
+    return clips, R, S, n, ch, S_ref, ch_ref, n_fft, hop, G
+
+
+def specgrad(stems, gains, ref_stems, ref_gains, window, twiddles, n_fft, hop, amin=1e-5, value_out=None, grad_out=None,
+             workspace=None):
+    """stems: CUDA float32 / float64 [clips, S, samples, channels] with any strides; gains: None (one row, every gain 1) or CUDA
+    float64 [clips, R, S, n_gains]; ref_stems: CUDA float32 / float64 [clips, S_ref, samples, channels]; ref_gains: None or CUDA
+    float64 [clips, S_ref, n_gains]; window, twiddles: the float32 tables of features._get_tables for ``n_fft`` ->
+    (value float64 [clips, R, 2] = (sum d, sum d^2) over every frame and bin, grad float64 [clips, R, S, n_gains] = the gradient
+    of sum d^2 in the gains; n_gains 1 for gains None) (include/dam_hip.h: dam_specgrad states the definition and the order of
+    the additions).  workspace: optional float64 tensor of dam_specgrad_workspace_bytes / 8 elements.  No host
+    synchronisation, hipGraph-capturable."""
+    _lib.require_cuda(stems, gains, ref_stems, ref_gains, window, twiddles, value_out, grad_out, workspace)
+    xk, rk = _audio_kind(stems, 'stems'), _audio_kind(ref_stems, 'ref_stems')
+    for g, what in ((gains, 'gains'), (ref_gains, 'ref_gains')):
+        if g is not None and g.dtype != torch.float64:
+            raise TypeError('specgrad: %s must be float64' % what)
+    clips, R, S, n, ch, S_ref, ch_ref, n_fft, hop, G = specgrad_check_shapes(
+        stems.shape, None if gains is None else gains.shape, ref_stems.shape, None if ref_gains is None else ref_gains.shape,
+        n_fft, hop, amin)
+    for t, what, count in ((window, 'window', n_fft), (twiddles, 'twiddles', 2 * n_fft)):
+        if t.dtype != torch.float32 or t.numel() != count or not t.is_contiguous():
+            raise ValueError('specgrad: %s must be a contiguous float32 tensor of %d elements' % (what, count))
+    dev = stems.device
+    if any(t is not None and t.device != dev for t in (gains, ref_stems, ref_gains, window, twiddles)):
+        raise ValueError('specgrad: every tensor must be on the stems\' device')
+    gains = None if gains is None else gains.contiguous()
+    ref_gains = None if ref_gains is None else ref_gains.contiguous()
+    outs = []
+    for o, shape in ((value_out, (clips, R, 2)), (grad_out, (clips, R, S, G))):
+        if o is None:
+            o = torch.empty(shape, dtype=torch.float64, device=dev)
+        elif o.dtype != torch.float64 or tuple(o.shape) != shape or not o.is_contiguous():
+            raise ValueError('specgrad: outputs must be contiguous float64 %s and %s tensors' % ((clips, R, 2), (clips, R, S, G)))
+        outs.append(o)
+    L = _lib.lib()
+    need = L.dam_specgrad_workspace_bytes(clips, R, S, n, n_fft, hop, 0 if gains is None else G)
+    if need <= 0:
+        raise ValueError('specgrad: the library refuses these arguments')
+    if workspace is None:
+        workspace = torch.empty(need // 8, dtype=torch.float64, device=dev)
+    elif workspace.dtype != torch.float64 or workspace.numel() * 8 < need or not workspace.is_contiguous() or \
+            workspace.data_ptr() % 16:
+        raise ValueError('specgrad: workspace must be a contiguous, 16-byte aligned float64 tensor of at least %d elements'
+                         % (need // 8))
+    with torch.cuda.device(dev):
+        _lib.check(L.dam_specgrad(_lib.ptr(stems), xk, clips, R, S, ch, n, stems.stride(0), stems.stride(1), stems.stride(2),
+                                  stems.stride(3), _lib.ptr(gains), 0 if gains is None else G, _lib.ptr(ref_stems), rk, S_ref,
+                                  ch_ref, ref_stems.stride(0), ref_stems.stride(1), ref_stems.stride(2), ref_stems.stride(3),
+                                  _lib.ptr(ref_gains), 0 if ref_gains is None else ref_gains.shape[2], _lib.ptr(window),
+                                  _lib.ptr(twiddles), n_fft, hop, float(amin), _lib.ptr(outs[0]), _lib.ptr(outs[1]),
+                                  _lib.ptr(workspace), _lib.stream()), 'dam_specgrad')
+    return outs[0], outs[1]
+
+
 # ----------------------------------------------------------------------------- alignment
 ALIGN_MAX_STEMS = 8
 ALIGN_WEIGHTINGS = {'plain': 0, 'phat': 1}      # DAM_ALIGN_PLAIN, DAM_ALIGN_PHAT

@@ -241,3 +241,98 @@ def distance_summary(sums, count):
     tot, band, win = out[:, 0], out[:, 1:1 + B], out[:, 1 + B:]
     return DistanceSummary(tot[:, 0], tot[:, 1], tot[:, 2], band[..., 0], band[..., 1], band[..., 2],
                            win[..., 0], win[..., 1], win[..., 2])
+
+
+def _grad_args(stems, gains, ref_stems, ref_gains):
+    """The tensors of spectrogram_distance_grad with the clip axis in front -> (stems, gains, ref_stems, ref_gains, clipped):
+    clipped says whether the caller gave the axis."""
+    for t, what in ((stems, 'stems'), (ref_stems, 'ref_stems')):
+        if not t.is_cuda:
+            raise RuntimeError('deep_audio_mixer_amd kernels run on the GPU only (got a %s tensor); there is no CPU fallback'
+                               % t.device)
+        if t.dtype not in (torch.float32, torch.float64):
+            raise TypeError('float32 or float64 samples expected')
+    if stems.dim() not in (3, 4) or ref_stems.dim() != stems.dim():
+        raise ValueError('stems and ref_stems must both be [S, samples, channels] or [clips, S, samples, channels], got shapes '
+                         '%s and %s' % (tuple(stems.shape), tuple(ref_stems.shape)))
+    clipped = stems.dim() == 4
+    if not clipped:
+        stems, ref_stems = stems.unsqueeze(0), ref_stems.unsqueeze(0)
+        gains = None if gains is None else gains.unsqueeze(0)
+        ref_gains = None if ref_gains is None else ref_gains.unsqueeze(0)
+    clips, S, S_ref = stems.shape[0], stems.shape[1], ref_stems.shape[1]
+    if gains is not None:
+        if gains.dim() == 2:
+            gains = gains.view(clips, 1, -1, 1)
+        elif gains.dim() == 3:
+            gains = gains.unsqueeze(1)
+        if gains.dim() != 4 or gains.shape[0] != clips or gains.shape[2] != S:
+            raise ValueError('gains must be [S], [S, n_gains] or [R, S, n_gains] with S = %d (behind the clip axis where the stems '
+                             'have one), got shape %s' % (S, tuple(gains.shape)))
+    if ref_gains is not None:
+        if ref_gains.dim() == 2:
+            ref_gains = ref_gains.unsqueeze(-1)
+        if ref_gains.dim() != 3 or ref_gains.shape[0] != clips or ref_gains.shape[1] != S_ref:
+            raise ValueError('ref_gains must be [S_ref] or [S_ref, n_gains] with S_ref = %d (behind the clip axis where the stems '
+                             'have one), got shape %s' % (S_ref, tuple(ref_gains.shape)))
+    for g in (gains, ref_gains):
+        if g is not None:
+            if not g.is_cuda:
+                raise RuntimeError('gains must be a CUDA tensor')
+            if g.dtype != torch.float64:
+                raise TypeError('gains must be float64')
+    return stems, gains, ref_stems, ref_gains, clipped
+
+
+def spectrogram_distance_grad(stems, gains, ref_stems, ref_gains=None, *, n_fft=2048, hop=None, amin=1e-5):
+    """The criterion of spectrogram_distance over every bin and frame, and its gradient in the gains, in one fused device pass
+    (include/dam_hip.h: dam_specgrad states the definition).  stems: CUDA float32 / float64 [S, samples, channels] or
+    [clips, S, samples, channels] with any strides; gains: None (one row, every gain 1), CUDA float64 [S], [S, n_gains] or
+    [R, S, n_gains], behind a clip axis where the stems have one; ref_stems and ref_gains as spectrogram_distance takes them,
+    with the same clip axis.  n_gains == 1 or samples // n_gains >= n_fft (a frame may touch two gain segments at most).
+    -> (mse [clips?, R] in dB^2, bias [clips?, R] in dB, grad_mse [clips?, R, S, n_gains] in dB^2 per unit of linear gain), CUDA
+    float64: mse = S2 / N, bias = S1 / N, grad_mse = grad / N, N = frames * (n_fft / 2 + 1).  A row does not depend on the other
+    rows or clips (bitwise).  No host synchronisation once the tables are resident, hipGraph-capturable then."""
+    stems, gains, ref_stems, ref_gains, clipped = _grad_args(stems, gains, ref_stems, ref_gains)
+    n_fft, hop = ops.specgrad_check_shapes(stems.shape, None if gains is None else gains.shape, ref_stems.shape,
+                                           None if ref_gains is None else ref_gains.shape, n_fft, hop, amin)[7:9]
+    win, tw = features._get_tables(stems.device, n_fft)
+    value, grad = ops.specgrad(stems, gains, ref_stems, ref_gains, win, tw, n_fft, hop, amin)
+    n_pairs = float((1 + stems.shape[2] // hop) * (n_fft // 2 + 1))
+    mse, bias, grad_mse = value[..., 1] / n_pairs, value[..., 0] / n_pairs, grad / n_pairs
+    return (mse, bias, grad_mse) if clipped else (mse[0], bias[0], grad_mse[0])
+
+
+class _RenderedSpectrogramMSE(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, gains, stems, ref_stems, ref_gains, kw):
+        mse, _, grad_mse = spectrogram_distance_grad(stems, gains, ref_stems, ref_gains, **kw)
+        ctx.save_for_backward(grad_mse.reshape(mse.shape + (stems.shape[-3], -1)))
+        ctx.gains_shape = gains.shape
+        return mse
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        grad_mse, = ctx.saved_tensors
+        return (grad_out[..., None, None] * grad_mse).reshape(ctx.gains_shape), None, None, None, None
+
+
+def rendered_spectrogram_mse(stems, gains, ref_stems, ref_gains=None, **kw):
+    """The training criterion on the rendered audio as a differentiable loss: spectrogram_distance_grad's mse [clips?, R], with
+    a backward that hands ``grad_out[..., None, None] * grad_mse`` to ``gains`` (nothing flows to the stems or the reference).
+    gains: CUDA float64, as spectrogram_distance_grad takes them and not None; from a model's dB output through
+    ``(10 ** (db / 20)).double()``.  Keywords n_fft, hop, amin.  The levels are float32: torch.autograd.gradcheck's finite
+    differences are not meaningful on it."""
+    if gains is None:
+        raise ValueError('rendered_spectrogram_mse: gains expected (there is nothing to differentiate without them)')
+    if not gains.is_cuda:
+        raise RuntimeError('gains must be a CUDA tensor')
+    if gains.dtype != torch.float64:
+        raise TypeError('gains must be float64')
+    return _RenderedSpectrogramMSE.apply(gains, stems, ref_stems, ref_gains, kw)
+
+
+def gain_sensitivity_db(gains, grad_mse):
+    """gains and grad_mse (spectrogram_distance_grad) of one shape -> g * grad_mse * ln 10 / 20: the change of the criterion in
+    dB^2 per dB of that stem in that window (d mse / d (20 log10 g)); the same kind of array comes back."""
+    return gains * grad_mse * (math.log(10.0) / 20.0)

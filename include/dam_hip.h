@@ -56,7 +56,7 @@ struct dam_bn_bwd_in;
 /* Library / build identification ("gfx950").  DAM_ABI_VERSION is bumped whenever a signature below changes; a binding
  * compares dam_abi_version() of the library it loaded with the version it was written against and refuses a stale one
  * (deep-audio-mixer_amd/_lib.py: EXPECTED_ABI). */
-#define DAM_ABI_VERSION 38
+#define DAM_ABI_VERSION 39
 const char* dam_arch(void);
 int dam_abi_version(void);
 
@@ -1239,7 +1239,7 @@ int dam_bandmix_render(const void* x, int x_is_f64, int n_stems, int channels, i
  *   Argument errors (a NULL pointer other than gains / ref_gains; R outside 1 .. 65535; no stem; channels not 1 or 2; n_fft not a
  *     power of two in 64 .. 16384; hop < 1; n <= n_fft/2; gains with n_gains < 1 or > n; amin not above 0; B outside
  *     1 .. dam_spectrum_max_bands(); W outside 1 .. n; a window without a frame) return DAM_ERR_BAD_ARG before any launch.
- * Not covered: a gradient in the gains, per-channel distances, perceptual (mel / loudness-weighted) bins.
+ * Not covered: per-channel distances, perceptual (mel / loudness-weighted) bins.
  * --------------------------------------------------------------------------------- */
 int64_t dam_specdist_workspace_bytes(int n_rows, int64_t n_samples, int n_fft, int hop, int n_bands, int n_windows);
 int dam_specdist_sums(const void* x, int x_is_f64, int n_rows, int n_stems, int channels, int64_t n_samples,
@@ -1250,6 +1250,59 @@ int dam_specdist_sums(const void* x, int x_is_f64, int n_rows, int n_stems, int 
                       int n_bands, int n_windows, double* sums, int64_t* count, void* workspace, void* stream);
 int dam_specdist_summary(const double* sums, const int64_t* count, int n_rows, int n_bands, int n_windows, double* out,
                          void* stream);
+
+/* ---------------------------------------------------------------------------------
+ * Spectrogram distance: gradient (ABI 39): the gradient in the gains of the criterion above with one band over every bin --
+ * what turns the figure into a loss for the gains a model put out, and what tells which stem pulls it in which window.  The
+ * entry is stateless, allocates nothing, does not synchronise with the host, uses no atomics and is hipGraph-capturable.
+ * tests/_specgrad_ref.py restates the definition in numpy float64.
+ *   Clips.  n_clips independent problems in one call, 1 <= n_clips <= 65535: clip c has its stems at x + c * x_clip_stride and
+ *     its reference at ref + c * ref_clip_stride (element strides), gains device float64 [n_clips][R][S][n_gains] or NULL (every
+ *     gain exactly 1, R rows alike; the gradient is still defined), ref_gains device float64 [n_clips][S_ref][ref_n_gains] or
+ *     NULL.  Everything else is addressed and typed as dam_specdist_sums takes it.
+ *   Forward.  Mix signal, frames, transform, level and difference d_r[t][k] are dam_specdist_sums', operation for operation.
+ *     Objective, per clip and row:  J_r = sum_t sum_{k = 0 .. n_fft/2} d_r[t][k]^2  (S2); the entry also returns S1 = sum d.
+ *   Gradient.  dJ/dg[r][s][j] = sum_t sum_i z_t[i] * m_s[q(t,i)] * [gain_index(q(t,i)) == j],  q(t,i) = reflect(t*hop - n_fft/2 + i),
+ *     m_s the stem's channel mean in double (((double)l + (double)r) * 0.5, or the single channel), gain_index(p) =
+ *     min(p / (n / n_gains), n_gains-1);  z_t[i] = w[i] * y_t[i],  y_t[i] = Re sum_{k = 0 .. n_fft/2} u_k e^{+2 pi i ik / n_fft},
+ *     u_k = (40 / ln 10) d_k X_k / p_k, and u_k = 0 where the candidate's p_k <= amin*amin (a floored level has no derivative;
+ *     a floored REFERENCE bin still contributes its d).  The imaginary parts of X at DC and Nyquist are 0, as in the forward.
+ *     The rounding of the mix signal to float is treated as the identity.
+ *     Form the kernel uses: u_k = c_k X_k in float32 with c_k = (float)((40 / ln 10) d_k / (double)p_k);  y = half the
+ *     UNNORMALISED inverse real transform (the float32 LDS FFT of dam_istft, its pre-twiddle included) of v, v_0 = 2 u_0,
+ *     v_{n_fft/2} = 2 u_{n_fft/2}, v_k = u_k otherwise;  z_t[i] = w[i] * (0.5f * irfft_unnormalised(v)[i]) in float32; the
+ *     products (double)z_t[i] * m_s[q] and their sums are float64.
+ *   Gain segments.  With n_gains == 1 (or gains NULL) or n / n_gains >= n_fft a frame touches at most two gain segments:
+ *     a(t) = gain_index(clamp(t*hop - n_fft/2, 0, n-1)) and a(t) + 1 (reflected samples fall in segment 0 and in the last one).
+ *     Any other n_gains: DAM_ERR_UNSUPPORTED before a launch.
+ *   Order of the float64 additions.  Per (clip, row, frame, stem) and per segment a(t), a(t)+1: lane l of 256 adds its positions
+ *     i = l, l + 256, ... in ascending order from +0.0, then an xor-butterfly over the 64 lanes of a wave, distances 1, 2, .. 32,
+ *     then the four waves as ((w0 + w1) + w2) + w3: one record.  (sum d, sum d^2) of a frame: lane l adds its bins l, l + 256,
+ *     ... < n_fft/2 in ascending order from +0.0, lane 0 then bin n_fft/2; butterfly and waves as above.  grad[c][r][s][j] adds
+ *     the records of the frames that touch node j in ascending t from +0.0: first t with t*hop + n_fft/2 - 1 >= j (n / n_gains)
+ *     (j > 0) up to the last t with t*hop - n_fft/2 < (j + 1)(n / n_gains) (j < n_gains - 1); value[c][r] = (S1, S2) adds every
+ *     frame's in ascending t from +0.0.  So an entry of grad depends on its own clip, its row's gains and the frames that touch
+ *     its node only: it is bitwise reproducible and independent of R, of the other rows, of the other clips and of every sample
+ *     that none of its node's frames covers.  S2 is dam_specdist_sums' sum d^2 over one band and one window in another order
+ *     of addition: equal within rounding of the sums, not bit for bit.
+ *   dam_specgrad: two launches (frames: one workgroup per (frame, clip) transforms the reference frame once and then, per row,
+ *     the candidate frame forward and u backward; reduce).  value device float64 [n_clips][R][2] = (S1, S2); grad device
+ *     float64 [n_clips][R][S][max(n_gains, 1)] (n_gains = 0 with gains NULL).  workspace:
+ *     dam_specgrad_workspace_bytes(n_clips, R, S, n, n_fft, hop, n_gains) = 16 n_clips R T (S + 1) bytes (the records), 16-byte
+ *     aligned; 0 for arguments the entry refuses.
+ *   Argument errors (a NULL pointer other than gains / ref_gains; n_clips or R outside 1 .. 65535; no stem; channels not 1 or 2;
+ *     n_fft not a power of two in 64 .. 16384; hop < 1; n <= n_fft/2; gains with n_gains < 1 or > n; amin not above 0) return
+ *     DAM_ERR_BAD_ARG before any launch; outputs and workspace are untouched then, and for DAM_ERR_UNSUPPORTED alike.
+ * Not covered: band or window weights in the objective, per-sample gain ramps (n / n_gains < n_fft), gradients in the stems or
+ * in the reference, and a fitter on this gradient (records why).
+ * --------------------------------------------------------------------------------- */
+int64_t dam_specgrad_workspace_bytes(int n_clips, int n_rows, int n_stems, int64_t n_samples, int n_fft, int hop, int n_gains);
+int dam_specgrad(const void* x, int x_is_f64, int n_clips, int n_rows, int n_stems, int channels, int64_t n_samples,
+                 int64_t x_clip_stride, int64_t stem_stride, int64_t sample_stride, int64_t channel_stride, const double* gains,
+                 int n_gains, const void* ref, int ref_is_f64, int ref_stems, int ref_channels, int64_t ref_clip_stride,
+                 int64_t ref_stem_stride, int64_t ref_sample_stride, int64_t ref_channel_stride, const double* ref_gains,
+                 int ref_n_gains, const float* window, const float* twiddles, int n_fft, int hop, float amin, double* value,
+                 double* grad, void* workspace, void* stream);
 
 /* ---------------------------------------------------------------------------------
  * Alignment (ABI 28): the time offset of every stem against a mix by block cross-correlation, and the sample shift that removes
